@@ -12,6 +12,10 @@ log utility, reward 'avg', episode length 100 (reset kernel every 100 steps, ins
 random actions pre-generated on the device.  N>1: the env axis is sharded, 65 536 envs per GPU (weak scaling),
 global env ids keep the draws independent of the GPU count; no collective on the data path.
 Prints ONE JSON line on rank 0.
+
+A plain run does only what the headline figure needs: set-up, warm-up, the K timed steps, the line.  `--full` adds every
+secondary figure (the other BASELINE configurations, the measured stream rate, the steady-state and sustained legs, the
+observation hand-off probe, the CPU baseline).  `--dump-outputs DIR` writes what the last timed step returned as DIR/<name>.npy.
 """
 import argparse
 import json
@@ -643,6 +647,27 @@ def valu_bound(ent, kernel_ms):
             'peak': f'{SIMDS} SIMDs x {CLOCK_GHZ} GHz / {CYCLES_PER_VALU} cycles per wave64 VALU instruction'}
 
 
+DUMP_BYTES = 64 * 10**6        # --dump-outputs: at most this many bytes of .npy data in all
+PREWARM_S = 1.0                # seconds of pre-warm launches of a run without --full, in place of the secondary configurations (see main)
+
+
+def dump_outputs(outdir, outputs, E, seed=0):
+    """outputs: name -> device tensor with the env axis first.  Written as float32 (integer tensors as float64: exact), whole when all
+    of them fit in DUMP_BYTES, else the same fixed, seeded sample of env rows (sorted) from every one of them."""
+    import torch
+    dt = {n: np.float64 if not t.is_floating_point() else np.float32 for n, t in outputs.items()}
+    per_env = sum(t.numel() // E * np.dtype(dt[n]).itemsize for n, t in outputs.items())
+    n_env = min(E, DUMP_BYTES // per_env)
+    rows = None
+    if n_env < E:
+        rows = torch.from_numpy(np.sort(np.random.default_rng(seed).choice(E, n_env, replace=False)))
+    os.makedirs(outdir, exist_ok=True)
+    for name, t in outputs.items():
+        a = t if rows is None else t.index_select(0, rows.to(t.device))
+        np.save(os.path.join(outdir, name + '.npy'), a.cpu().numpy().astype(dt[name]))
+    return n_env
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--gpus', type=int, default=1)
@@ -701,7 +726,16 @@ def main():
                          "peer in one batch (the direct all-gather spelled out)")
     ap.add_argument('--sustained-launches', type=int, default=40000,
                     help='N = 1, default workload: back-to-back headline launches of the sustained leg (also.sustained; blocks of 1 000, HIP events); 0 = skip')
+    ap.add_argument('--full', action='store_true',
+                    help='also measure every secondary figure (also.*, roofline.measured_stream / steady_state, the observation hand-off probe, '
+                         'cpu_baseline); the --no-* options above switch single ones off again.  Without it a run measures the headline only')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='after the timed steps, write what the last of them returned (observations, rewards, per-env / per-UE metrics) '
+                         f'as DIR/<name>.npy, float32 (int32 compact records as float64); above {DUMP_BYTES // 10**6} MB in all, the same '
+                         'fixed, seeded sample of envs from every array')
     args = ap.parse_args()
+    if not args.full:                          # the secondary figures are --full's (the steady-state leg and the hand-off probe are gated below)
+        args.no_also = args.no_stream = args.no_cpu_baseline = True
     if args.predict:
         pr = predict(steps=args.steps if args.steps != 1000 else 20, fragment=args.fragment)
         print(predict_table(pr))
@@ -970,6 +1004,21 @@ def main():
     also_first = None
     if not args.no_also and default_workload and not args.also_after:
         also_first = measure_also(torch, BatchedMobileEnv, scenarios, build_from_scenario, dev)
+    # Without --full, PREWARM_S seconds of headline launches stand in for the secondary launches (`also`) that preceded the pre-warm when they
+    # ran in every line: the timed region starts from the same warm state as before.  Then the env is re-seeded with its own seed, so that the
+    # episodes from here on -- and every output of the timed steps -- do not depend on how many launches that took.
+    prewarm_s = PREWARM_S if not args.full and args.prewarm > 0 else 0.0
+    if prewarm_s:
+        t_pw = time.perf_counter()
+        while time.perf_counter() - t_pw < prewarm_s:
+            env.reset()
+            for i in range(L):
+                if packed_main is not None:
+                    env.step_compact(pool[i & 15], packed_main, env.reward)
+                else:
+                    env.step(pool[i & 15])
+            torch.cuda.synchronize(dev)         # the clock then counts GPU time, not how far ahead the host has queued
+        env.seed(env.seed_value)
     if args.prewarm > 0:                        # >= 300 untimed launches of the headline kernel itself (no hand-off, no events)
         tp = 0
         while tp < args.prewarm:
@@ -1001,6 +1050,17 @@ def main():
     drain()
     fence(closing=True)
     elapsed = time.perf_counter() - t0
+    if args.dump_outputs and rank == 0:         # what the last timed step returned, before anything else steps this env
+        if packed_main is not None:
+            last = {'obs_compact': packed_main, 'reward': env.reward}
+        elif frag_bufs is not None:
+            fb, f = frag_bufs[((t_env - 1) // F) & 1], (t_env - 1) % F
+            last = {'obs_compact': fb['packed'][f]} if args.compact else {'obs': fb['obs'][f]}
+            last['reward'] = fb['reward'][f]
+        else:
+            last = {'obs': env.obs, 'reward': env.reward}
+        last.update(sum_utility=env.sum_utility, ue_dr=env.ue_dr, ue_utility=env.ue_utility)      # info's metrics (log_metrics=True)
+        dump_outputs(args.dump_outputs, last, E)
     elapsed_ranks, placements = [elapsed], [placement]
     if use_dist:
         # every rank's own clock over the same bracket: `value` uses the MAX (the contract), the line also shows min / max / all, so
@@ -1098,7 +1158,7 @@ def main():
                 'env_steps_per_s_with_obs_handoff': world * E * F / (both_ms * 1e-3)}
 
     obs_probe = None
-    if use_dist and args.gather != 'obs' and not args.no_gather:
+    if args.full and use_dist and args.gather != 'obs' and not args.no_gather:
         try:                                   # a side measurement: it must never cost the headline line
             obs_probe = probe_obs_handoff()
             if codec is not None:                  # the same hand-off with the lossless compact record (pack kernel included)
@@ -1133,7 +1193,7 @@ def main():
     # launch over 300 launches on a cold MI355X, tools/kprobe.py): with the driver's --steps 20 the timed region lies inside
     # that transient.  The steady state is reported NEXT to it, never instead of it: >= 300 further launches untimed, then 200 timed.
     steady_ms, steady_clk, sustained = None, None, None
-    if world == 1 and not T and frag_bufs is None and gather is None:
+    if args.full and world == 1 and not T and frag_bufs is None and gather is None:
         t = run(max(0, 300 - K), t_env)
         sp2 = []
         ev_pool.extend(torch.cuda.Event(enable_timing=True) for _ in range(2 * (200 // L + 3)))
@@ -1203,6 +1263,7 @@ def main():
                                       f'all-gather of per-env rewards + sum_utility ({4 * E * (env.reward.numel() // E + 1) * world / 1e6:.1f} MB received per rank) every {G} steps, async, '
                                       f'{gather_stats["collectives"]} collective(s) inside the timed region'),
                        'prewarm': (('secondary configurations (`also`), then ' if also_first is not None else '') +
+                                   (f'{prewarm_s:g} s of untimed launches of the headline kernel, a re-seed, ' if prewarm_s else '') +
                                    f'{args.prewarm} untimed launches of the headline kernel, then the {W} warm-up steps -- on every rank, identical at every N '
                                    '(methodology: rounds 1-2 entered the timed region cold, round 3 after `also` at N = 1 only; `--prewarm 0 --also-after` = the round-2 order)')},
             'roofline': {'bound': 'hbm', 'achieved': achieved, 'peak': HBM_PEAK_GBS, 'unit': 'GB/s',

@@ -112,3 +112,30 @@ def test_predict_prints_the_1_to_8_gpu_curve_without_a_gpu():
     for l in table[2:]:
         assert l in design, 'DESIGN.md section 7 does not hold the table `bench.py --predict` prints'
     assert bench.predict(steps=1000)['rows'][3]['weak_speedup'] > rows[8]['weak_speedup']     # a longer timed region dilutes the bracket
+
+
+def test_dump_outputs_keeps_the_same_seeded_sample_of_envs_under_the_cap(tmp_path, monkeypatch):
+    """--dump-outputs: whole arrays when they fit, else the same fixed, seeded env rows of every array; at most DUMP_BYTES in all;
+    float32, integer words as float64 (exact)."""
+    import numpy as np
+    import torch
+    E, U = 1000, 4
+    g = torch.Generator().manual_seed(3)
+    outs = {'obs': torch.rand((E, U, 5), generator=g), 'reward': torch.rand((E, U), generator=g),
+            'obs_compact': torch.randint(-2**31, 2**31 - 1, (E, 7), generator=g, dtype=torch.int32)}
+    assert bench.dump_outputs(str(tmp_path / 'all'), outs, E) == E
+    for name, t in outs.items():
+        a = np.load(tmp_path / 'all' / f'{name}.npy')
+        assert a.dtype == (np.float32 if t.is_floating_point() else np.float64) and np.array_equal(a, t.numpy())
+    per_env = 4 * U * 5 + 4 * U + 8 * 7
+    monkeypatch.setattr(bench, 'DUMP_BYTES', 300 * per_env + 5)
+    for d in ('a', 'b'):
+        assert bench.dump_outputs(str(tmp_path / d), outs, E) == 300
+    total = sum(os.path.getsize(p) - 128 for p in (tmp_path / 'a').iterdir())          # .npy header: 128 bytes
+    assert total <= bench.DUMP_BYTES
+    obs, rew = np.load(tmp_path / 'a' / 'obs.npy'), np.load(tmp_path / 'a' / 'reward.npy')
+    rows = [int(np.flatnonzero((outs['reward'].numpy() == r).all(axis=1))[0]) for r in rew]
+    assert len(set(rows)) == 300 and rows == sorted(rows)                                  # one sample, in env order, shared by the arrays
+    assert np.array_equal(obs, outs['obs'].numpy()[rows]) and np.array_equal(np.load(tmp_path / 'a' / 'obs_compact.npy'), outs['obs_compact'].numpy()[rows])
+    for name in outs:
+        assert np.array_equal(np.load(tmp_path / 'a' / f'{name}.npy'), np.load(tmp_path / 'b' / f'{name}.npy'))

@@ -40,7 +40,7 @@ def _run(cmd):
 
 @pytest.mark.parametrize('mode', ['obs', 'summary'])
 def test_bench_handoff_over_rccl_single_rank(mode):
-    rc, out, j = _run([sys.executable, 'bench.py', '--gpus', '1', '--force-dist', '--gather', mode, '--fragment', '5'] + COMMON)
+    rc, out, j = _run([sys.executable, 'bench.py', '--gpus', '1', '--force-dist', '--full', '--gather', mode, '--fragment', '5'] + COMMON)
     assert rc == 0 and j is not None, out[-3000:]
     h = j['handoff']
     assert h['mode'] == mode and h['backend'] == 'rccl' and h['rccl_ranks'] == 1 and h['overlapped_on_side_stream']
@@ -73,7 +73,7 @@ def test_bench_spawns_its_own_ranks_n2_gloo_same_device():
     device) -- everything else is the N > 1 control flow: global env ids per rank, RolloutGather fragments, the MAX-reduce of the
     elapsed time, the multi-GPU BASELINE splits in `also`, ONE JSON line from rank 0."""
     env_clean = {k: v for k, v in os.environ.items() if k not in ('WORLD_SIZE', 'RANK', 'LOCAL_RANK', 'MASTER_ADDR', 'MASTER_PORT')}
-    cmd = [sys.executable, 'bench.py', '--gpus', '2', '--backend', 'gloo', '--same-device', '--gather', 'obs', '--fragment', '5',
+    cmd = [sys.executable, 'bench.py', '--gpus', '2', '--full', '--backend', 'gloo', '--same-device', '--gather', 'obs', '--fragment', '5',
            '--envs', '2048', '--steps', '20', '--warmup', '10', '--no-cpu-baseline', '--no-stream', '--eps-length', '10']
     r = subprocess.run(cmd, cwd=REPO, env=env_clean, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=900)
     lines = [l for l in r.stdout.splitlines() if l.strip()]
@@ -97,7 +97,7 @@ def test_driver_form_n2_has_a_collective_inside_the_timed_region():
     counted where it is issued, and every rank runs the same pre-warm at every N.  Two self-spawned ranks on one device (gloo: RCCL
     refuses two ranks on one GPU), default workload, secondary configurations on -- the driver's command line otherwise."""
     env_clean = {k: v for k, v in os.environ.items() if k not in ('WORLD_SIZE', 'RANK', 'LOCAL_RANK', 'MASTER_ADDR', 'MASTER_PORT')}
-    cmd = [sys.executable, 'bench.py', '--gpus', '2', '--steps', '20', '--warmup', '5', '--backend', 'gloo', '--same-device']
+    cmd = [sys.executable, 'bench.py', '--gpus', '2', '--steps', '20', '--warmup', '5', '--full', '--backend', 'gloo', '--same-device']
     r = subprocess.run(cmd, cwd=REPO, env=env_clean, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=1200)
     lines = [l for l in r.stdout.splitlines() if l.strip()]
     assert r.returncode == 0 and lines, (r.stdout[-2000:], r.stderr[-3000:])
@@ -129,7 +129,7 @@ def test_single_rank_rccl_driver_form_counts_its_collectives():
 
 def test_bench_spawns_its_own_ranks_summary_mode_probe():
     env_clean = {k: v for k, v in os.environ.items() if k not in ('WORLD_SIZE', 'RANK', 'LOCAL_RANK', 'MASTER_ADDR', 'MASTER_PORT')}
-    cmd = [sys.executable, 'bench.py', '--gpus', '2', '--backend', 'gloo', '--same-device', '--fragment', '5', '--no-also'] + COMMON
+    cmd = [sys.executable, 'bench.py', '--gpus', '2', '--full', '--backend', 'gloo', '--same-device', '--fragment', '5', '--no-also'] + COMMON
     r = subprocess.run(cmd, cwd=REPO, env=env_clean, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=900)
     assert r.returncode == 0, (r.stdout[-2000:], r.stderr[-3000:])
     j = json.loads([l for l in r.stdout.splitlines() if l.strip()][-1])
@@ -234,7 +234,7 @@ def test_driver_form_n8_gloo_same_device():
     rollout hand-off throughput next to the summary's at top level; and the whole run well inside the driver's patience."""
     import time
     env_clean = {k: v for k, v in os.environ.items() if k not in ('WORLD_SIZE', 'RANK', 'LOCAL_RANK', 'MASTER_ADDR', 'MASTER_PORT')}
-    cmd = [sys.executable, 'bench.py', '--gpus', '8', '--steps', '20', '--warmup', '5', '--backend', 'gloo', '--same-device', '--envs', '256']    # (small: 24 gloo all-gathers of 8 fragments each go through loopback TCP)
+    cmd = [sys.executable, 'bench.py', '--gpus', '8', '--steps', '20', '--warmup', '5', '--full', '--backend', 'gloo', '--same-device', '--envs', '256']    # (small: 24 gloo all-gathers of 8 fragments each go through loopback TCP)
     t0 = time.time()
     r = subprocess.run(cmd, cwd=REPO, env=env_clean, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=900)
     wall = time.time() - t0
