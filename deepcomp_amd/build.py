@@ -160,6 +160,5 @@ if __name__ == '__main__':
     ap = argparse.ArgumentParser()
     ap.add_argument('--force', action='store_true')
     ap.add_argument('--jobs', type=int, default=None)
-    ap.add_argument('--no-dpp', action='store_true', help='build the __shfl_xor fallback reductions (debug)')
     a = ap.parse_args()
-    print(build(force=a.force, jobs=a.jobs, extra_flags=['-DDCOMP_NO_DPP'] if a.no_dpp else []))
+    print(build(force=a.force, jobs=a.jobs))

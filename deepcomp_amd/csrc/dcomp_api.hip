@@ -66,7 +66,6 @@ struct dcomp_env {
     bool fused_long;           // ... for rollouts of >= 4 steps at ANY batch size (small central rows: see dcomp_create)
     int upad, grid;
     int wide_pad_lds = 0;      // step_kernel_wide: extra dynamic LDS per workgroup = fewer resident workgroups per CU (see dcomp_create)
-    int wide_grid = 0;         // step_kernel_wide is persistent: workgroups launched (<= what the GPU holds at once), each walks grid / wide_grid slots
     int tight_g, tight_gpw, tight_magic, tight_grid;   // step_kernel's tight packing of non-power-of-two UE lists (0 = off)
     int cap, cur_ue;            // slots per env; UEs currently listed
     uint32_t n_removed, n_arrived;   // this episode (Philox draw words)
@@ -369,14 +368,7 @@ extern "C" int dcomp_create_v(int32_t abi_version, size_t cfg_size, size_t state
         }
     }
     if (!env->big && env->kern.step_wide && !kp.any_maxcap && !getenv("DCOMP_NO_WIDE")) {
-        env->kern.step = env->kern.step_wide;
-        // persistent launch: as many workgroups as are resident at once (LDS-bound: 4 per CU at B = 32), never more than there are slots
-        int per_cu = 0, cus = 0;
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, reinterpret_cast<const void *>(env->kern.step_wide), DCOMP_BLOCK, 0) != hipSuccess || per_cu < 1) per_cu = 4;
-        if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, cfg->device) != hipSuccess || cus < 1) cus = 256;
-        long cap = DCOMP_WIDE_PERSIST ? (long)per_cu * cus : (long)env->grid;      // (one workgroup per slot unless the persistent experiment is built)
-        if (const char *e = getenv("DCOMP_WIDE_GRID")) cap = (DCOMP_WIDE_PERSIST && atol(e) > 0) ? atol(e) : env->grid;
-        env->wide_grid = (int)(cap < env->grid ? cap : env->grid);
+        env->kern.step = env->kern.step_wide;                                                       // one workgroup per slot
         // Batches whose observation rows are >= 1 GB per step -- four times the Infinity Cache: every byte goes out at the sustained HBM
         // write rate -- run with TWO workgroups per CU instead of the four the kernel's 39.8 KB of LDS allow (24 000 B of unused dynamic
         // LDS per workgroup): 16 384 x 128 x 32 252-272 -> 251 us, 32 768 envs 517 -> 477 us (0.60 -> 0.65 of the HBM peak), repeatably;
@@ -490,11 +482,10 @@ static void launch_step(dcomp_env *env, KParams &kp, void *stream)
         hipLaunchKernelGGL(k, dim3(env->tight_grid), dim3(DCOMP_BLOCK), 0, (hipStream_t)stream, kp);
         return;
     }
-    const bool wide = env->wide_grid && env->kern.step == env->kern.step_wide;
-    const int grid = wide ? env->wide_grid : env->grid;
+    const bool wide = env->kern.step == env->kern.step_wide;
     // (the occupancy cap is for launches that stream GBs of ROWS; with the compact record a launch is bound by its arithmetic and wants
     // every wave it can get: 32 768 x 128 x 32 236 us with four workgroups per CU, 369 us with two)
-    hipLaunchKernelGGL(env->kern.step, dim3(grid), dim3(DCOMP_BLOCK), wide && !kp.obs_compact ? env->wide_pad_lds : 0, (hipStream_t)stream, kp);
+    hipLaunchKernelGGL(env->kern.step, dim3(env->grid), dim3(DCOMP_BLOCK), wide && !kp.obs_compact ? env->wide_pad_lds : 0, (hipStream_t)stream, kp);
 }
 
 static int check_horizon(const dcomp_env *env, int steps)

@@ -24,20 +24,10 @@
 //   * envs wider than a wavefront combine per-wave partial sums in wave order.
 // LDS per wavefront: 2.6 KB of per-lane slots + the tables -- the kernel is bound by registers (no per-B arrays), not by LDS; 513 ... 1 024 UE
 // slots no longer limit the station count.  UE arrival / departure (DYN): slots shift inside the env's lane group exactly as in dcomp_dyn.h.
-// The compact record (dcomp_out.obs_compact; two set words per UE above 32 stations) is written here too.  Not here: the fused rollout
-// (dcomp_rollout_ex launches one step per launch) and the in-step policy.
+// The compact record (dcomp_out.obs_compact; two set words per UE above 32 stations) is written here too, and so are the fused rollout
+// (ROLL: a stretch of an episode in one launch) and the in-step heuristic policy (POL).
 #pragma once
 #include "dcomp_device.h"
-
-#ifndef DCOMP_BIG_RUNROLL
-#define DCOMP_BIG_RUNROLL 2   // UE rows of the observation loop in flight per wavefront
-#endif
-#ifndef DCOMP_BIG_NT
-#define DCOMP_BIG_NT 0        // 1: non-temporal row stores (partial lines: measured slower in round 5, R5.7)
-#endif
-#ifndef DCOMP_BIG_ABL
-#define DCOMP_BIG_ABL 0       // timing-only ablation (results WRONG): 1 max-cap winner, 2 utility aggregates, 4 rows, 8 row pairs, 16 sharing aggregates, 32 move, 64 sparse share loops
-#endif
 
 namespace dcomp {
 
@@ -85,11 +75,7 @@ __device__ __forceinline__ void big_pair(double px, double py, const double2 bp,
 // partial line does not wait in the L2 for its other half (round 5, 8 192 x 32 x 64: 134 us non-temporal, 81 us plain).
 __device__ __forceinline__ void big_store(float *ptr, float v)
 {
-#if DCOMP_BIG_NT
-    stream_store(ptr, v);
-#else
     *ptr = v;
-#endif
 }
 // The observation rows leave through BUFFER stores: resource = the env's rows (uniform, four SGPRs), scalar offset = the row / the block of the row,
 // vector offset = the lane's station (loop-invariant).  As plain global stores every row cost ten 64-bit vector adds on per-lane pointers (one
@@ -444,7 +430,6 @@ __global__ __launch_bounds__(big_block(UPAD)) void big_kernel(const KParams p, c
         return n < 0 ? 0 : (n > PL ? PL : n);
     };
     auto sharing_aggregates = [&](double qx, double qy, float ewma_v) {
-        if (DCOMP_BIG_ABL & 16) return;
         // Both aggregates are built by the UE lanes themselves, each walking the few bits of its OWN connection set (round 6, second pass: the
         // station lanes used to scan every row -- 40 rows x 13 instructions per pass at 10 x 40 central, 47 of its 130 us):
         //  * the COUNT n_b: `ds_add_f32 1.0` per connected station -- sums of ones below 2^24 are exact, so the order is irrelevant;
@@ -508,7 +493,7 @@ __global__ __launch_bounds__(big_block(UPAD)) void big_kernel(const KParams p, c
             }
             __syncthreads();
         }
-        if (any_maxcap && !(DCOMP_BIG_ABL & 1)) {
+        if (any_maxcap) {
             // station.py:183-187: the UE with the highest FP64 rate is served; equal rates -> the oldest connection, then the lowest UE index
             // (dcomp_device.h shared_rates has the derivation: nearest UE, contenders within 1e-7, the collapsing FP64 key).  Owner threads.
             __syncthreads();
@@ -560,30 +545,28 @@ __global__ __launch_bounds__(big_block(UPAD)) void big_kernel(const KParams p, c
         sharing_aggregates(px, py, ewma);
         // 3. move (base.py:447 -> user.py:159-173); the old position stays for the pre-move rates below
         const double ox = px, oy = py;
-        if (alive && !(DCOMP_BIG_ABL & 32)) {
+        if (alive) {
             move_ue<false>(p, env, uidw, p.episode, px, py, mv, vrange);
             if (px < 0.0 || py < 0.0 || px > (double)p.map_w || py > (double)p.map_h) atomicOr(p.flags, DCOMP_FLAG_OUTSIDE_MAP);
         }
         // 4. this UE's pre-move shares (station.py:152-202), and for each: does the connection survive at the new position (user.py:175-188)?
         //    EWMA from the STALE rates of what stays (user.py:148-157).
         float curr_pre = 0.f, stale = 0.f;
-        if (!(DCOMP_BIG_ABL & 64)) {
-            const float inv_ewma = fast_rcp(ewma + EPS);
-            for (unsigned long long m = conn; m; m &= m - 1ull) {
-                const int b = __ffsll((long long)m) - 1, q = env_local * B + b;
-                const double2 bp = bs_s[b];
-                bool ir;
-                float l;
-                big_pair(ox, oy, bp, p, ir, l);
-                const float out = big_share(mode_s[b], big_rate(l), agg_n[q], agg_s[q], inv_ewma, mc_win[q] == (uint32_t)u);
-                curr_pre += out;
-                const double dx = bp.x - px, dy = bp.y - py;
-                const double dsq = __builtin_fma(dy, dy, dx * dx);
-                bool stays = dsq < p.dt2;
-                if ((float)dsq == p.dt2f || p.dsq_exact) stays = in_range_exact(px, py, bp.x, bp.y, p.dt2);
-                if (stays) stale += out;
-                else conn &= ~(1ull << b);
-            }
+        const float inv_ewma_pre = fast_rcp(ewma + EPS);
+        for (unsigned long long m = conn; m; m &= m - 1ull) {
+            const int b = __ffsll((long long)m) - 1, q = env_local * B + b;
+            const double2 bp = bs_s[b];
+            bool ir;
+            float l;
+            big_pair(ox, oy, bp, p, ir, l);
+            const float out = big_share(mode_s[b], big_rate(l), agg_n[q], agg_s[q], inv_ewma_pre, mc_win[q] == (uint32_t)u);
+            curr_pre += out;
+            const double dx = bp.x - px, dy = bp.y - py;
+            const double dsq = __builtin_fma(dy, dy, dx * dx);
+            bool stays = dsq < p.dt2;
+            if ((float)dsq == p.dt2f || p.dsq_exact) stays = in_range_exact(px, py, bp.x, bp.y, p.dt2);
+            if (stays) stale += out;
+            else conn &= ~(1ull << b);
         }
         reward_before = clamp_med3(ue_utility(curr_pre, step_util, dr_req), MIN_UTIL, MAX_UTIL) * (1.0f / MAX_UTIL);
         ewma = __builtin_fmaf(0.9f, stale, 0.1f * ewma);           // one explicit contraction: every kernel variant rounds alike
@@ -592,15 +575,13 @@ __global__ __launch_bounds__(big_block(UPAD)) void big_kernel(const KParams p, c
         publish(ewma);
         __syncthreads();
         sharing_aggregates(px, py, ewma);
-        if (!(DCOMP_BIG_ABL & 64)) {
-            const float inv_ewma = fast_rcp(ewma + EPS);
-            for (unsigned long long m = conn; m; m &= m - 1ull) {
-                const int b = __ffsll((long long)m) - 1, q = env_local * B + b;
-                bool ir;
-                float l;
-                big_pair(px, py, bs_s[b], p, ir, l);
-                curr += big_share(mode_s[b], big_rate(l), agg_n[q], agg_s[q], inv_ewma, mc_win[q] == (uint32_t)u);
-            }
+        const float inv_ewma = fast_rcp(ewma + EPS);
+        for (unsigned long long m = conn; m; m &= m - 1ull) {
+            const int b = __ffsll((long long)m) - 1, q = env_local * B + b;
+            bool ir;
+            float l;
+            big_pair(px, py, bs_s[b], p, ir, l);
+            curr += big_share(mode_s[b], big_rate(l), agg_n[q], agg_s[q], inv_ewma, mc_win[q] == (uint32_t)u);
         }
         if (active) {                                              // state write-back: every slot (unlisted slots are cleared)
             p.pos[idx] = alive ? make_double2(px, py) : make_double2(0.0, 0.0);
@@ -621,7 +602,7 @@ __global__ __launch_bounds__(big_block(UPAD)) void big_kernel(const KParams p, c
     const int kind = p.kind, n_eff = cur;
     const bool want_min = p.reward_agg == DCOMP_REWARD_MIN;
     // 7. per-station utility aggregates (station.py:63-83) -- multi-agent envs only: central observations and rewards carry none
-    if (kind == DCOMP_MULTI && !(DCOMP_BIG_ABL & 2)) {
+    if (kind == DCOMP_MULTI) {
         float nn[EPW], su[EPW], mn[EPW];
 #pragma unroll
         for (int el = 0; el < EPW; el++) {
@@ -662,178 +643,174 @@ __global__ __launch_bounds__(big_block(UPAD)) void big_kernel(const KParams p, c
     constexpr bool compact = COMPACT;                              // (its own instantiation: the branch in the row loop cost the row format 3-8 %; multi-agent envs only: the host checks)
     const int CWC = B + 1 + (B > 32 ? 2 : 1), REC = U * CWC + 2 * B;     // words per UE / per env-step of the compact record (dcomp_frag::ue_words / env_words)
     const float inv_u = 1.0f / (float)n_eff;
-    if (!(DCOMP_BIG_ABL & 4)) {
 #pragma unroll
-        for (int el = 0; el < EPW; el++) {
-            int r0, envl, uu0;
-            const int nrows = piece_rows(el, r0, envl, uu0);
-            float n_col = 0.f, u_col = 0.f;
-            if (kind == DCOMP_MULTI && st_ok && nrows > 0) {
-                const float n = agg_n[envl * B + sb];
-                n_col = n * inv_u;
-                u_col = agg_u[envl * B + sb] * fast_rcp(fmaxf(n, 1.f)) * (1.0f / MAX_UTIL);
-            }
-            // where this env's rows go: the row format, or (multi-agent envs, dcomp_out.obs_compact) the compact record of dcomp_fragment.h --
-            // U x {dr[B], utility, connection word(s)} + ues_at_bs[B] | util_at_bs[B]: the station lanes store the dr blocks and, once per env,
-            // the two per-env columns; utility and the set words are the UE lanes' (below)
-            float *const dst_env = !o_obs ? nullptr : compact ? o_obs + (size_t)(env0 + envl) * REC : o_obs + (size_t)(env0 + envl) * U * (kind == DCOMP_MULTI ? ROW : 2 * B + 1);
-            if (compact && dst_env && st_writer && nrows > 0 && uu0 == 0) {
-                big_store(dst_env + U * CWC + sb, n_col);
-                big_store(dst_env + U * CWC + B + sb, u_col);
-            }
-            const unsigned long long ok_mask = __builtin_amdgcn_ballot_w64(st_ok);
-            const BigRsrc rs = big_rsrc(dst_env);
-            // Rows as 16-byte stores (BigParams::row_x4; multi-agent rows, more than 32 stations): the row's 4B words as they lie in memory, four per
-            // lane.  The lane-per-station values are transposed through ONE row of LDS per wavefront (two ds_write_b32 + one ds_read_b128 per lane and
-            // row; the two per-env blocks are written once per env; LDS operations of a wavefront complete in order: no barrier).  One store
-            // instruction then writes 1 KiB of consecutive bytes instead of four writing 256 B each at a stride of B floats: beyond the Infinity
-            // Cache the four-block form reached 3.1 TB/s of writes (65 536 x 32 x 64: rows alone 566 of 692 us).
-            const bool x4 = !COMPACT && LBP == 6 && x.row_x4 != 0 && kind == DCOMP_MULTI && dst_env != nullptr;
-            float *const stage = reinterpret_cast<float *>(big_smem + cv.stage) + wave * 4 * B;
-            if (x4 && st_ok) { stage[2 * B + lane] = n_col; stage[3 * B + lane] = u_col; }      // the two per-env blocks: once per env
-            if (LBP == 6) {
-                // more than 32 stations: ONE row per trip, everything about the row uniform (position / set: broadcast reads; destination: scalar).
-                // The loop exists once per output form (OUT: 0 nothing, 1 compact record, 2 rows as 16-byte stores, 3 rows in four blocks, 4 central):
-                // the form is picked per env piece, not per row (the chain of uniform branches in front of the central stores cost 65 536 x 10 x 40
-                // central 9 % when the 16-byte form was added to it).
-                auto rows6 = [&](auto out_tag) __attribute__((always_inline)) {
-                constexpr int OUT = decltype(out_tag)::value;
-                for (int uu = 0; uu < nrows; uu++) {
-                    const int r = r0 + uu, ue = uu0 + uu;
-                    const bool live = ue < cur;
-                    const double2 q = pos_s[r];
-                    const uint4 sl = slot_s[r];
-                    float l = -3.0e38f;
-                    unsigned long long bal = 0ull;
-                    if (!(DCOMP_BIG_ABL & 8)) {
-                        // the lane masks straight from the compares (a ballot of a derived bool costs a v_cndmask + v_cmp pair each)
-                        bool ir;
-                        float qf;
-                        pair_eval_q(q.x, q.y, mybs.x, mybs.y, p, ir, l, qf);
-                        const double dx = mybs.x - q.x, dy = mybs.y - q.y;
-                        const double dsq = __builtin_fma(dy, dy, dx * dx);             // (the same expression as inside pair_eval_q: one evaluation)
-                        bal = __builtin_amdgcn_ballot_w64(dsq < p.dt2) & ok_mask;
-                        const unsigned long long rare = (__builtin_amdgcn_ballot_w64(qf == p.dt2f) | __builtin_amdgcn_ballot_w64(qf < NEAR_D2)) & ok_mask;
-                        if (rare != 0ull || p.dsq_exact) {                               // wave-uniform: the fused d^2 cannot decide / a UE within 1.26 m of a station
-                            bool fix = st_ok && ((bal >> lane) & 1ull);
-                            if (st_ok && (qf == p.dt2f || p.dsq_exact)) fix = in_range_exact(q.x, q.y, mybs.x, mybs.y, p.dt2);
-                            if (st_ok && qf < NEAR_D2 && (float)dsq < 1e-20f) l = pair_eval_tiny(q.x, q.y, mybs.x, mybs.y, p);
-                            bal = __builtin_amdgcn_ballot_w64(fix);
-                        }
-                        l = st_ok ? l : -3.0e38f;
-                    }
-                    if (kind == DCOMP_MULTI) { if (lane == 0) inr_s[r] = bal; }      // (only the multi-agent rewards read the in-range sets)
-                    float lmax_p = 0.f;
-                    if (POL) {                                                       // dcomp_set_policy: the rules on the row's dr entries (the instantiation of its own)
-                        lmax_p = wave_max_f32(l);
-                        if (p.next_act) {
-                            const int a = big_policy_wave(p, (unsigned long long)sl.x | ((unsigned long long)sl.y << 32), live ? fast_exp2(l - lmax_p) : 0.f, st_ok, ok_mask, lane, B);
-                            if (lane == 0) p.next_act[(size_t)(env0 + envl) * U + ue] = (uint8_t)(live ? a : 0);
-                        }
-                    }
-                    if (OUT != 0) {
-                        // (buffer stores: the row's offset is a scalar, the lane's a loop-invariant register -- no address arithmetic per store;
-                        //  an unlisted slot -- `live` is uniform -- takes the zero-row branch instead of a select per value)
-                        const uint32_t lo = (uint32_t)lane * 4u, B4 = (uint32_t)B * 4u;
-                        if (OUT == 1) {
-                            const float lmax = POL ? lmax_p : wave_max_f32(l);
-                            if (st_ok) big_bstore(rs, lo, (uint32_t)(ue * CWC) * 4u, live ? fast_exp2(l - lmax) : 0.f);
-                        } else if (OUT == 2) {
-                            const uint32_t ro = (uint32_t)(ue * ROW) * 4u;
-                            float cf = 0.f, dr = 0.f, ut = 0.f;
-                            if (live) {
-                                const float lmax = POL ? lmax_p : wave_max_f32(l);
-                                dr = fast_exp2(l - lmax);                                    // variants.py:276-284
-                                cf = (float)__builtin_amdgcn_ubfe(hi_lane ? sl.y : sl.x, sh, 1u);
-                                ut = __uint_as_float(sl.z) * (1.0f / MAX_UTIL);
-                            }
-                            float v[4] = {0.f, 0.f, 0.f, 0.f};                                // (an unlisted slot: a zero row, the per-env blocks too)
-                            if (live) {
-                                if (st_ok) { stage[lane] = cf; stage[B + lane] = dr; }
-                                if (lane < B) {                                              // (4B words = B lanes of four; B <= 64)
-                                    const float4 q4 = *reinterpret_cast<const float4 *>(stage + 4 * lane);
-                                    v[0] = q4.x; v[1] = q4.y; v[2] = q4.z; v[3] = q4.w;
-                                }
-                            }
-                            if (lane < B) big_bstore4(rs, lo * 4u, ro, v);
-                            if (lane == 0) big_bstore(rs, 0u, ro + 4u * B4, ut);              // the row's own utility entry, right behind it
-                        } else if (OUT == 3) {
-                            const uint32_t ro = (uint32_t)(ue * ROW) * 4u;
-                            if (live) {
-                                const float lmax = POL ? lmax_p : wave_max_f32(l);
-                                const float dr = fast_exp2(l - lmax);                        // variants.py:276-284
-                                const float cf = (float)__builtin_amdgcn_ubfe(hi_lane ? sl.y : sl.x, sh, 1u);
-                                if (st_ok) {
-                                    big_bstore(rs, lo, ro, cf);
-                                    big_bstore(rs, lo, ro + B4, dr);
-                                    big_bstore(rs, lo, ro + 2u * B4, n_col);
-                                    big_bstore(rs, lo, ro + 3u * B4, u_col);
-                                }
-                            } else if (st_ok) {
-                                big_bstore(rs, lo, ro, 0.f); big_bstore(rs, lo, ro + B4, 0.f);
-                                big_bstore(rs, lo, ro + 2u * B4, 0.f); big_bstore(rs, lo, ro + 3u * B4, 0.f);
-                            }
-                        } else {
-                            const uint32_t ro = (uint32_t)(ue * B) * 4u, UB4 = (uint32_t)UB * 4u;
-                            if (live) {
-                                const float lmax = POL ? lmax_p : wave_max_f32(l);
-                                const float dr = fast_exp2(l - lmax);
-                                const float cf = (float)__builtin_amdgcn_ubfe(hi_lane ? sl.y : sl.x, sh, 1u);
-                                if (st_ok) { big_bstore(rs, lo, ro, cf); big_bstore(rs, lo, ro + UB4, dr); }
-                            } else if (st_ok) { big_bstore(rs, lo, ro, 0.f); big_bstore(rs, lo, ro + UB4, 0.f); }
-                        }
+    for (int el = 0; el < EPW; el++) {
+        int r0, envl, uu0;
+        const int nrows = piece_rows(el, r0, envl, uu0);
+        float n_col = 0.f, u_col = 0.f;
+        if (kind == DCOMP_MULTI && st_ok && nrows > 0) {
+            const float n = agg_n[envl * B + sb];
+            n_col = n * inv_u;
+            u_col = agg_u[envl * B + sb] * fast_rcp(fmaxf(n, 1.f)) * (1.0f / MAX_UTIL);
+        }
+        // where this env's rows go: the row format, or (multi-agent envs, dcomp_out.obs_compact) the compact record of dcomp_fragment.h --
+        // U x {dr[B], utility, connection word(s)} + ues_at_bs[B] | util_at_bs[B]: the station lanes store the dr blocks and, once per env,
+        // the two per-env columns; utility and the set words are the UE lanes' (below)
+        float *const dst_env = !o_obs ? nullptr : compact ? o_obs + (size_t)(env0 + envl) * REC : o_obs + (size_t)(env0 + envl) * U * (kind == DCOMP_MULTI ? ROW : 2 * B + 1);
+        if (compact && dst_env && st_writer && nrows > 0 && uu0 == 0) {
+            big_store(dst_env + U * CWC + sb, n_col);
+            big_store(dst_env + U * CWC + B + sb, u_col);
+        }
+        const unsigned long long ok_mask = __builtin_amdgcn_ballot_w64(st_ok);
+        const BigRsrc rs = big_rsrc(dst_env);
+        // Rows as 16-byte stores (BigParams::row_x4; multi-agent rows, more than 32 stations): the row's 4B words as they lie in memory, four per
+        // lane.  The lane-per-station values are transposed through ONE row of LDS per wavefront (two ds_write_b32 + one ds_read_b128 per lane and
+        // row; the two per-env blocks are written once per env; LDS operations of a wavefront complete in order: no barrier).  One store
+        // instruction then writes 1 KiB of consecutive bytes instead of four writing 256 B each at a stride of B floats: beyond the Infinity
+        // Cache the four-block form reached 3.1 TB/s of writes (65 536 x 32 x 64: rows alone 566 of 692 us).
+        const bool x4 = !COMPACT && LBP == 6 && x.row_x4 != 0 && kind == DCOMP_MULTI && dst_env != nullptr;
+        float *const stage = reinterpret_cast<float *>(big_smem + cv.stage) + wave * 4 * B;
+        if (x4 && st_ok) { stage[2 * B + lane] = n_col; stage[3 * B + lane] = u_col; }      // the two per-env blocks: once per env
+        if (LBP == 6) {
+            // more than 32 stations: ONE row per trip, everything about the row uniform (position / set: broadcast reads; destination: scalar).
+            // The loop exists once per output form (OUT: 0 nothing, 1 compact record, 2 rows as 16-byte stores, 3 rows in four blocks, 4 central):
+            // the form is picked per env piece, not per row (the chain of uniform branches in front of the central stores cost 65 536 x 10 x 40
+            // central 9 % when the 16-byte form was added to it).
+            auto rows6 = [&](auto out_tag) __attribute__((always_inline)) {
+            constexpr int OUT = decltype(out_tag)::value;
+            for (int uu = 0; uu < nrows; uu++) {
+                const int r = r0 + uu, ue = uu0 + uu;
+                const bool live = ue < cur;
+                const double2 q = pos_s[r];
+                const uint4 sl = slot_s[r];
+                float l = -3.0e38f;
+                unsigned long long bal = 0ull;
+                // the lane masks straight from the compares (a ballot of a derived bool costs a v_cndmask + v_cmp pair each)
+                bool ir;
+                float qf;
+                pair_eval_q(q.x, q.y, mybs.x, mybs.y, p, ir, l, qf);
+                const double dx = mybs.x - q.x, dy = mybs.y - q.y;
+                const double dsq = __builtin_fma(dy, dy, dx * dx);             // (the same expression as inside pair_eval_q: one evaluation)
+                bal = __builtin_amdgcn_ballot_w64(dsq < p.dt2) & ok_mask;
+                const unsigned long long rare = (__builtin_amdgcn_ballot_w64(qf == p.dt2f) | __builtin_amdgcn_ballot_w64(qf < NEAR_D2)) & ok_mask;
+                if (rare != 0ull || p.dsq_exact) {                               // wave-uniform: the fused d^2 cannot decide / a UE within 1.26 m of a station
+                    bool fix = st_ok && ((bal >> lane) & 1ull);
+                    if (st_ok && (qf == p.dt2f || p.dsq_exact)) fix = in_range_exact(q.x, q.y, mybs.x, mybs.y, p.dt2);
+                    if (st_ok && qf < NEAR_D2 && (float)dsq < 1e-20f) l = pair_eval_tiny(q.x, q.y, mybs.x, mybs.y, p);
+                    bal = __builtin_amdgcn_ballot_w64(fix);
+                }
+                l = st_ok ? l : -3.0e38f;
+                if (kind == DCOMP_MULTI) { if (lane == 0) inr_s[r] = bal; }      // (only the multi-agent rewards read the in-range sets)
+                float lmax_p = 0.f;
+                if (POL) {                                                       // dcomp_set_policy: the rules on the row's dr entries (the instantiation of its own)
+                    lmax_p = wave_max_f32(l);
+                    if (p.next_act) {
+                        const int a = big_policy_wave(p, (unsigned long long)sl.x | ((unsigned long long)sl.y << 32), live ? fast_exp2(l - lmax_p) : 0.f, st_ok, ok_mask, lane, B);
+                        if (lane == 0) p.next_act[(size_t)(env0 + envl) * U + ue] = (uint8_t)(live ? a : 0);
                     }
                 }
-                };
-                using std::integral_constant;
-                if (!dst_env) rows6(integral_constant<int, 0>{});
-                else if (compact) rows6(integral_constant<int, 1>{});
-                else if (x4) rows6(integral_constant<int, 2>{});
-                else if (kind == DCOMP_MULTI) rows6(integral_constant<int, 3>{});
-                else rows6(integral_constant<int, 4>{});
-            } else {
-                // up to 32 stations: SUB rows per trip, lane = (row sub, station sb)
-                const int trips = (nrows + SUB - 1) >> (6 - LBP);
-                for (int it = 0; it < trips; it++) {
-                    const int uu = it * SUB + sub;
-                    const bool rv = uu < nrows;
-                    const int r = r0 + (rv ? uu : 0), ue = uu0 + uu;
-                    const bool live = ue < cur;
-                    const double2 q = pos_s[r];
-                    const uint4 sl = slot_s[r];
-                    float l = -3.0e38f;
-                    bool ir = false;
-                    if (!(DCOMP_BIG_ABL & 8)) big_row_pair(q.x, q.y, mybs, p, st_ok && rv, ir, l);
-                    const unsigned long long bal = __builtin_amdgcn_ballot_w64(ir);
-                    if (sb == 0 && rv && kind == DCOMP_MULTI) inr_s[r] = (bal >> (sub * BP)) & ((1ull << BP) - 1ull);
-                    if (dst_env || (POL && p.next_act)) {
-                        const float lmax = BP == 32 ? group_reduce<32, OpMax>(l) : BP == 16 ? group_reduce<16, OpMax>(l) : group_reduce<8, OpMax>(l);
-                        const float dr = live ? fast_exp2(l - lmax) : 0.f;                // variants.py:276-284
-                        if (POL && p.next_act) {                                          // dcomp_set_policy: the rules on the rows of this trip
-                            const bool ok = st_ok && rv;
-                            const int a = BP == 32 ? big_policy_group<32>(p, sl.x, dr, ok, sub, sb, B) : BP == 16 ? big_policy_group<16>(p, sl.x, dr, ok, sub, sb, B)
-                                                                                                              : big_policy_group<8>(p, sl.x, dr, ok, sub, sb, B);
-                            if (sb == 0 && rv) p.next_act[(size_t)(env0 + envl) * U + ue] = (uint8_t)(live ? a : 0);
+                if (OUT != 0) {
+                    // (buffer stores: the row's offset is a scalar, the lane's a loop-invariant register -- no address arithmetic per store;
+                    //  an unlisted slot -- `live` is uniform -- takes the zero-row branch instead of a select per value)
+                    const uint32_t lo = (uint32_t)lane * 4u, B4 = (uint32_t)B * 4u;
+                    if (OUT == 1) {
+                        const float lmax = POL ? lmax_p : wave_max_f32(l);
+                        if (st_ok) big_bstore(rs, lo, (uint32_t)(ue * CWC) * 4u, live ? fast_exp2(l - lmax) : 0.f);
+                    } else if (OUT == 2) {
+                        const uint32_t ro = (uint32_t)(ue * ROW) * 4u;
+                        float cf = 0.f, dr = 0.f, ut = 0.f;
+                        if (live) {
+                            const float lmax = POL ? lmax_p : wave_max_f32(l);
+                            dr = fast_exp2(l - lmax);                                    // variants.py:276-284
+                            cf = (float)__builtin_amdgcn_ubfe(hi_lane ? sl.y : sl.x, sh, 1u);
+                            ut = __uint_as_float(sl.z) * (1.0f / MAX_UTIL);
                         }
-                        if (!dst_env) continue;
-                        const float cf = (float)__builtin_amdgcn_ubfe(sl.x, sh, 1u);
-                        const uint32_t B4 = (uint32_t)B * 4u;                              // (buffer stores: one 32-bit offset per lane, the blocks of the row as scalar offsets)
-                        if (compact) {
-                            if (st_ok && rv) big_bstore(rs, (uint32_t)(ue * CWC + sb) * 4u, 0u, dr);
-                        } else if (kind == DCOMP_MULTI) {
-                            const uint32_t off = (uint32_t)(ue * ROW + sb) * 4u;
-                            if (st_ok && rv) {
-                                big_bstore(rs, off, 0u, cf);
-                                big_bstore(rs, off, B4, dr);
-                                big_bstore(rs, off, 2u * B4, live ? n_col : 0.f);
-                                big_bstore(rs, off, 3u * B4, live ? u_col : 0.f);
+                        float v[4] = {0.f, 0.f, 0.f, 0.f};                                // (an unlisted slot: a zero row, the per-env blocks too)
+                        if (live) {
+                            if (st_ok) { stage[lane] = cf; stage[B + lane] = dr; }
+                            if (lane < B) {                                              // (4B words = B lanes of four; B <= 64)
+                                const float4 q4 = *reinterpret_cast<const float4 *>(stage + 4 * lane);
+                                v[0] = q4.x; v[1] = q4.y; v[2] = q4.z; v[3] = q4.w;
                             }
-                        } else {
-                            const uint32_t off = (uint32_t)(ue * B + sb) * 4u;
-                            if (st_ok && rv) {
-                                big_bstore(rs, off, 0u, cf);
-                                big_bstore(rs, off, (uint32_t)UB * 4u, dr);
+                        }
+                        if (lane < B) big_bstore4(rs, lo * 4u, ro, v);
+                        if (lane == 0) big_bstore(rs, 0u, ro + 4u * B4, ut);              // the row's own utility entry, right behind it
+                    } else if (OUT == 3) {
+                        const uint32_t ro = (uint32_t)(ue * ROW) * 4u;
+                        if (live) {
+                            const float lmax = POL ? lmax_p : wave_max_f32(l);
+                            const float dr = fast_exp2(l - lmax);                        // variants.py:276-284
+                            const float cf = (float)__builtin_amdgcn_ubfe(hi_lane ? sl.y : sl.x, sh, 1u);
+                            if (st_ok) {
+                                big_bstore(rs, lo, ro, cf);
+                                big_bstore(rs, lo, ro + B4, dr);
+                                big_bstore(rs, lo, ro + 2u * B4, n_col);
+                                big_bstore(rs, lo, ro + 3u * B4, u_col);
                             }
+                        } else if (st_ok) {
+                            big_bstore(rs, lo, ro, 0.f); big_bstore(rs, lo, ro + B4, 0.f);
+                            big_bstore(rs, lo, ro + 2u * B4, 0.f); big_bstore(rs, lo, ro + 3u * B4, 0.f);
+                        }
+                    } else {
+                        const uint32_t ro = (uint32_t)(ue * B) * 4u, UB4 = (uint32_t)UB * 4u;
+                        if (live) {
+                            const float lmax = POL ? lmax_p : wave_max_f32(l);
+                            const float dr = fast_exp2(l - lmax);
+                            const float cf = (float)__builtin_amdgcn_ubfe(hi_lane ? sl.y : sl.x, sh, 1u);
+                            if (st_ok) { big_bstore(rs, lo, ro, cf); big_bstore(rs, lo, ro + UB4, dr); }
+                        } else if (st_ok) { big_bstore(rs, lo, ro, 0.f); big_bstore(rs, lo, ro + UB4, 0.f); }
+                    }
+                }
+            }
+            };
+            using std::integral_constant;
+            if (!dst_env) rows6(integral_constant<int, 0>{});
+            else if (compact) rows6(integral_constant<int, 1>{});
+            else if (x4) rows6(integral_constant<int, 2>{});
+            else if (kind == DCOMP_MULTI) rows6(integral_constant<int, 3>{});
+            else rows6(integral_constant<int, 4>{});
+        } else {
+            // up to 32 stations: SUB rows per trip, lane = (row sub, station sb)
+            const int trips = (nrows + SUB - 1) >> (6 - LBP);
+            for (int it = 0; it < trips; it++) {
+                const int uu = it * SUB + sub;
+                const bool rv = uu < nrows;
+                const int r = r0 + (rv ? uu : 0), ue = uu0 + uu;
+                const bool live = ue < cur;
+                const double2 q = pos_s[r];
+                const uint4 sl = slot_s[r];
+                float l = -3.0e38f;
+                bool ir = false;
+                big_row_pair(q.x, q.y, mybs, p, st_ok && rv, ir, l);
+                const unsigned long long bal = __builtin_amdgcn_ballot_w64(ir);
+                if (sb == 0 && rv && kind == DCOMP_MULTI) inr_s[r] = (bal >> (sub * BP)) & ((1ull << BP) - 1ull);
+                if (dst_env || (POL && p.next_act)) {
+                    const float lmax = BP == 32 ? group_reduce<32, OpMax>(l) : BP == 16 ? group_reduce<16, OpMax>(l) : group_reduce<8, OpMax>(l);
+                    const float dr = live ? fast_exp2(l - lmax) : 0.f;                // variants.py:276-284
+                    if (POL && p.next_act) {                                          // dcomp_set_policy: the rules on the rows of this trip
+                        const bool ok = st_ok && rv;
+                        const int a = BP == 32 ? big_policy_group<32>(p, sl.x, dr, ok, sub, sb, B) : BP == 16 ? big_policy_group<16>(p, sl.x, dr, ok, sub, sb, B)
+                                                                                                          : big_policy_group<8>(p, sl.x, dr, ok, sub, sb, B);
+                        if (sb == 0 && rv) p.next_act[(size_t)(env0 + envl) * U + ue] = (uint8_t)(live ? a : 0);
+                    }
+                    if (!dst_env) continue;
+                    const float cf = (float)__builtin_amdgcn_ubfe(sl.x, sh, 1u);
+                    const uint32_t B4 = (uint32_t)B * 4u;                              // (buffer stores: one 32-bit offset per lane, the blocks of the row as scalar offsets)
+                    if (compact) {
+                        if (st_ok && rv) big_bstore(rs, (uint32_t)(ue * CWC + sb) * 4u, 0u, dr);
+                    } else if (kind == DCOMP_MULTI) {
+                        const uint32_t off = (uint32_t)(ue * ROW + sb) * 4u;
+                        if (st_ok && rv) {
+                            big_bstore(rs, off, 0u, cf);
+                            big_bstore(rs, off, B4, dr);
+                            big_bstore(rs, off, 2u * B4, live ? n_col : 0.f);
+                            big_bstore(rs, off, 3u * B4, live ? u_col : 0.f);
+                        }
+                    } else {
+                        const uint32_t off = (uint32_t)(ue * B + sb) * 4u;
+                        if (st_ok && rv) {
+                            big_bstore(rs, off, 0u, cf);
+                            big_bstore(rs, off, (uint32_t)UB * 4u, dr);
                         }
                     }
                 }
@@ -841,7 +818,7 @@ __global__ __launch_bounds__(big_block(UPAD)) void big_kernel(const KParams p, c
         }
     }
     // the rows' own utility entry: by the UE lanes (one store instruction per wavefront instead of a lane-0 store in every trip of the row loop)
-    if (active && o_obs && !(DCOMP_BIG_ABL & 4)) {
+    if (active && o_obs) {
         const float ut = alive ? util * (1.0f / MAX_UTIL) : 0.f;
         if (compact) {
             float *const rec = o_obs + (size_t)env * REC + (size_t)u * CWC;

@@ -18,72 +18,21 @@
 
 #include "../../include/dcomp_types.h"
 
-// Build switches.  The product build uses the defaults; tools/ablate.py builds timing-only variants.
-// DCOMP_ABLATE    bit mask of pipeline stages to leave out (results are wrong by construction; timing only)
-// DCOMP_NT_OBS    1: write-once output streams (observation rows, rewards, info) use non-temporal stores -- measured
-//                 0.1008 -> 0.0875 ms per step at config 3 (they stop competing with the state lines for L2)
-// DCOMP_BS_IN_LDS 1: read the BS table from an LDS copy instead of SGPRs (north_star wording) -- measured 10 % slower
-// DCOMP_BLOCK     workgroup size; 128 / 64 measured 3-6 % slower than 256
-#ifndef DCOMP_ABLATE
-#define DCOMP_ABLATE 0
-#endif
-#ifndef DCOMP_NT_OBS
-#define DCOMP_NT_OBS 1
-#endif
-#ifndef DCOMP_BS_IN_LDS
-#define DCOMP_BS_IN_LDS 0
-#endif
-#ifndef DCOMP_BLOCK
+// Shipped forms of the measured alternatives (DESIGN_LOG.md has the rejected ones); a variant is tried on a copy of the tree
+// (tools/ab/ab_lib.py build --src).
+// DCOMP_BLOCK        workgroup size; 128 / 64 measured 3-6 % slower than 256
+// DCOMP_WIDE_MIN_B   envs of >= 64 lanes use the wide kernel (dcomp_wide.h) above this many base stations
+//                    (4 096 x 128 UE: B = 16: narrow 0.046 / wide 0.055 ms; 20: 0.062 / 0.064; 24: 0.102 / 0.070)
+// DCOMP_SPARSE_MIN_B the sparse pre-move pass in step_kernel from this many stations up, where the LDS row fits (B <= 11;
+//                    B = 5: 0.5 % slower than the dense pass)
 #define DCOMP_BLOCK 256
-#endif
-#ifndef DCOMP_WIDE_MIN_B
-#define DCOMP_WIDE_MIN_B 20  // envs of >= 64 lanes use the wide kernel (dcomp_wide.h) above this many base stations
-                             // (4 096 x 128 UE: B = 16: narrow 0.046 / wide 0.055 ms; 20: 0.062 / 0.064; 24: 0.102 / 0.070)
-#endif
-#ifndef DCOMP_COMPILER_DIV
-#define DCOMP_COMPILER_DIV 0 // 1 = the compiler's generic FP64 sqrt / division in move_ue (A/B of norm_and_unit)
-#endif
-#ifndef DCOMP_LOG2_MODE
-#define DCOMP_LOG2_MODE 2    // log2(d^2): 0 = plain v_log_f32, 1 = frexp range reduction, 2 = 2^-12 prescale (default)
-#endif
-#ifndef DCOMP_SPARSE_PRE
-#define DCOMP_SPARSE_PRE 1      // 1: sparse pre-move pass in step_kernel where the LDS row fits (B <= 11); 0: dense (A/B)
-#endif
-#ifndef DCOMP_SPARSE_MIN_B
-#define DCOMP_SPARSE_MIN_B 7      // the sparse pre-move pass from this many stations up (B = 5: 0.5 % slower than the dense pass)
-#endif
-#ifndef DCOMP_CENTRAL_STAGED
-#define DCOMP_CENTRAL_STAGED 1  // 0: central observation rows are stored straight from registers (round 1; A/B only)
-#endif
-#ifndef DCOMP_BS_VOLATILE
-#define DCOMP_BS_VOLATILE 0    // experiment: re-read the BS table from the kernel-argument segment at every use (no hoisting out of the step loop)
-#endif
-#ifndef DCOMP_FORCE_KIND
-#define DCOMP_FORCE_KIND -1     // experiment: compile write_outputs for one env kind only (register-pressure bisection)
-#endif
-#ifndef DCOMP_SCALAR_DRAW
-#define DCOMP_SCALAR_DRAW 2    // Philox draws of the few redrawing lanes on the scalar unit (draw_triple_wave): 0 never, 1 every kernel, 2 fused rollout only
-#endif
-#ifndef DCOMP_MOVE_SELECTS
-#define DCOMP_MOVE_SELECTS 2   // move_ue as straight-line code with selects instead of branches: 0 never, 1 every kernel, 2 fused rollout only
-#endif
-#ifndef DCOMP_EXP_NO_RESET
-#define DCOMP_EXP_NO_RESET 0
-#endif
-#ifndef DCOMP_EXP_NO_TAPE
-#define DCOMP_EXP_NO_TAPE 0
-#endif
-#ifndef DCOMP_XCD_REMAP
-#define DCOMP_XCD_REMAP 1      // step kernels: every XCD owns a contiguous eighth of the env slots (xcd_contiguous_block)
-#endif
-#ifndef DCOMP_NT_STATE
-#define DCOMP_NT_STATE 0     // experiment: bit 0 non-temporal state loads, bit 1 non-temporal state stores
-#endif
+#define DCOMP_WIDE_MIN_B 20
+#define DCOMP_SPARSE_MIN_B 7
 
 // A rarely taken branch that LOADS from global memory (draw tape, velocity table, cluster table) consumes the value inside the
 // branch: the compiler then waits for it (s_waitcnt vmcnt) inside the branch too.  Left to itself it puts the wait at the join,
-// where every wave executes it -- and vmcnt counts loads AND stores in order, so a persistent kernel (step_kernel_wide) would wait
-// there for the previous slot's observation rows to drain, in the middle of its compute phase.
+// where every wave executes it -- and vmcnt counts loads AND stores in order, so the fused rollout would wait there for the
+// previous step's observation stores to drain, in the middle of its compute phase.
 #define VM_ARRIVED1(a) asm volatile("" : "+v"(a))
 #define VM_ARRIVED2(a, b) asm volatile("" : "+v"(a), "+v"(b))
 #define VM_ARRIVED3(a, b, c) asm volatile("" : "+v"(a), "+v"(b), "+v"(c))
@@ -203,17 +152,12 @@ struct OpMax { __device__ __forceinline__ static float f(float a, float b) { ret
 template <int W, class Op>
 __device__ __forceinline__ float group_reduce(float v)
 {
-#ifdef DCOMP_NO_DPP
-#pragma unroll
-    for (int m = 1; m < W; m <<= 1) v = Op::f(v, __shfl_xor(v, m, 64));
-#else
     if (W >= 2) v = Op::f(v, dpp_f32<DCOMP_DPP_QUAD_X1>(v));
     if (W >= 4) v = Op::f(v, dpp_f32<DCOMP_DPP_QUAD_X2>(v));
     if (W >= 8) v = Op::f(v, dpp_f32<DCOMP_DPP_HALF_MIRROR>(v));
     if (W >= 16) v = Op::f(v, dpp_f32<DCOMP_DPP_ROW_MIRROR>(v));
     if (W >= 32) v = Op::f(v, swz_xor16(v));
     if (W >= 64) v = Op::f(v, __shfl_xor(v, 32, 64));
-#endif
     return v;
 }
 // Set bits of a ballot mask inside my W-lane group.  All in 32-bit pieces: `(float)__popcll(m >> gbase & mask)` makes the
@@ -238,10 +182,6 @@ __device__ __forceinline__ int group_count(bool pred, int gbase)
 template <int W, class Op, int N>
 __device__ __forceinline__ void group_reduce_vec(float (&v)[N])
 {
-#ifdef DCOMP_NO_DPP
-#pragma unroll
-    for (int i = 0; i < N; i++) v[i] = group_reduce<W, Op>(v[i]);
-#else
     // The empty asm after every combine keeps the SLP vectoriser from pairing the N independent adds of a stage into v_pk_add_f32: a packed
     // add cannot take a DPP operand, so every pair then cost v_mov_b32_dpp x 2 + v_pk_add_f32 instead of v_add_f32_dpp x 2 (round 5: the
     // launch is VALU-issue-bound at the clock the part holds under it, profiles/r05_c3_clock_trace.txt)
@@ -254,7 +194,6 @@ __device__ __forceinline__ void group_reduce_vec(float (&v)[N])
     if (W >= 32) { DCOMP_STAGE(swz_xor16(v[i])) }
     if (W >= 64) { DCOMP_STAGE(__shfl_xor(v[i], 32, 64)) }
 #undef DCOMP_STAGE
-#endif
 }
 // ---- tight packing of UE lists whose length is not a power of two (step_kernel_tight only)
 // Padded groups waste lanes: U = 10 sits in groups of 16 (37.5 % idle), U = 5 in 8, U = 20 in 32.  In tight mode an env takes
@@ -303,14 +242,12 @@ __device__ __forceinline__ float seg_reduce(float x, const S &sg, int lane)
     return v[0];
 }
 
+// Write-once output streams (observation rows, rewards, info) are non-temporal: they stop competing with the state lines for
+// L2 (config 3: 0.1008 -> 0.0875 ms per step).
 template <class T>
 __device__ __forceinline__ void stream_store(T *ptr, T v)
 {
-#if DCOMP_NT_OBS
     __builtin_nontemporal_store(v, ptr);
-#else
-    *ptr = v;
-#endif
 }
 // N consecutive floats of one lane as 16-byte pieces + a remainder: global stores need dword alignment only, so a lane's run of
 // B or 4B+1 floats leaves as ceil(N / 4) store instructions instead of N -- what counts in the latency-bound fused rollout,
@@ -361,33 +298,17 @@ __device__ __forceinline__ float clamp_med3(float x, float lo, float hi) { retur
 // and redo the decision in the reference's literal form exactly where the two CAN differ: when (float)fused == (float)X.  The host checks
 // that every double within 4 ulp of X has that float image (dsq_exact = 1 otherwise: always the reference form).  Hit rate ~1e-7 per pair;
 // tests/test_threshold_gpu.py puts 1 000+ placements per kernel family there.
-#ifndef DCOMP_EDGE_MODE
-// How a lane notes "(float)fused d^2 == (float)X" over its stations: 0 = v_cmp_eq_f32 + s_or per pair (one vector + one scalar instruction, and a
-// VALU -> SALU hand-over), 1 = min |q - (float)X| (two vector instructions, nothing scalar), 2 = by kernel: form 0 where many waves per SIMD hide the
-// hand-over and the vector ALU is the co-limit (step_kernel: config 3 +0.1-0.3 % against +0.0-1.2 %), form 1 where one or two waves per SIMD run
-// (the fused rollout, the wide kernel beyond the Infinity Cache: config 2 +2.9 % against +4.2 %, config 5 whole +2.9 % against +4.8 %;
-// profiles/r06_ab_edge_mode*.txt, all against the round-5 predicate).
-#define DCOMP_EDGE_MODE 2
-#endif
-#ifndef DCOMP_DSQ_FUSED
-#define DCOMP_DSQ_FUSED 0          // 1: the round-5 predicate, fused value only (A/B; fails the threshold tests)
-#endif
+// How a lane notes "(float)fused d^2 == (float)X" over its stations (eval_pairs): v_cmp_eq_f32 + s_or per pair where many waves per SIMD
+// hide the VALU -> SALU hand-over and the vector ALU is the co-limit (step_kernel), min |q - (float)X| -- two vector instructions, nothing
+// scalar -- where one or two waves per SIMD run (the fused rollout, the wide kernel); profiles/r06_ab_edge_mode*.txt.
 __device__ __forceinline__ double dist_sq_ref(double dx, double dy)
 {
 #pragma clang fp contract(off)
     const double xx = dx * dx, yy = dy * dy;
     return xx + yy;
 }
-// the rare side of the decision, kept out of line: (float)fused d^2 == (float)X
-#ifndef DCOMP_EXACT_INLINE
-#define DCOMP_EXACT_INLINE 0         // 1: the rare reference-form re-check inlined at every site instead of one out-of-line function (A/B)
-#endif
-#if DCOMP_EXACT_INLINE
-__device__ __forceinline__
-#else
-__device__ __noinline__
-#endif
-bool in_range_exact(double px, double py, double bx, double by, double dt2)
+// the rare side of the decision, kept out of line (one function, not inlined at every site): (float)fused d^2 == (float)X
+__device__ __noinline__ bool in_range_exact(double px, double py, double bx, double by, double dt2)
 {
     return dist_sq_ref(bx - px, by - py) < dt2;
 }
@@ -398,9 +319,7 @@ __device__ __forceinline__ void pair_eval(double px, double py, double bx, doubl
     float q;
     pair_eval_q(px, py, bx, by, p, in_range, l2snr, q);
     tiny = q < NEAR_D2;                          // "near": superset of the d^2 < 1e-20 pairs the fix-up replaces
-#if !DCOMP_DSQ_FUSED
     if (q == p.dt2f || p.dsq_exact) in_range = in_range_exact(px, py, bx, by, p.dt2);       // rare, per lane: the reference's literal form
-#endif
 }
 __device__ __forceinline__ void pair_eval_q(double px, double py, double bx, double by, const KParams &p, bool &in_range, float &l2snr, float &q)
 {
@@ -412,16 +331,7 @@ __device__ __forceinline__ void pair_eval_q(double px, double py, double bx, dou
     // relative in snr = 2^l2snr).  Scaling d^2 by 2^-12 first puts every in-range pair at |log2| < 4 for the price
     // of one multiply (the exact alternative, frexp + two FMAs, costs 3 % of the step; tools/numerics_report.py has
     // the measured errors of all three).  Tiny pairs give -inf/NaN here and are replaced by eval_pairs' fix-up.
-#if DCOMP_LOG2_MODE == 0
-    l2snr = __builtin_fmaf(-p.half_gamma, fast_log2(fmaxf(q, 1e-20f)), p.log2k);
-#elif DCOMP_LOG2_MODE == 1
-    const float qc = fmaxf(q, 1e-20f);
-    const float lm = fast_log2(__builtin_amdgcn_frexp_mantf(qc));
-    const float ef = (float)__builtin_amdgcn_frexp_expf(qc);
-    l2snr = __builtin_fmaf(-p.half_gamma, ef, __builtin_fmaf(-p.half_gamma, lm, p.log2k));
-#else
     l2snr = __builtin_fmaf(-p.half_gamma, fast_log2(q * 0x1p-12f), p.log2k_s);
-#endif
 }
 __device__ __forceinline__ float pair_eval_tiny(double px, double py, double bx, double by, const KParams &p)
 {
@@ -431,53 +341,38 @@ __device__ __forceinline__ float pair_eval_tiny(double px, double py, double bx,
     return __builtin_fmaf(-2.0f * p.half_gamma, fast_log2(d), p.log2k);
 }
 // All B pairs of one UE; returns the in-range mask.
-#if DCOMP_BS_IN_LDS
-__shared__ double g_bs_lds[2 * DCOMP_MASK32_MAX_BS];
-#define DCOMP_BSX(b) (*(volatile double *)&g_bs_lds[b])
-#define DCOMP_BSY(b) (*(volatile double *)&g_bs_lds[DCOMP_MASK32_MAX_BS + (b)])
-#else
-#if DCOMP_BS_VOLATILE
-#define DCOMP_BSX(b) (*(const volatile double *)&p.bs_x[b])
-#define DCOMP_BSY(b) (*(const volatile double *)&p.bs_y[b])
-#else
-#define DCOMP_BSX(b) p.bs_x[b]
-#define DCOMP_BSY(b) p.bs_y[b]
-#endif
-#endif
 // `near_wave` (optional, wave-uniform): some lane of this wave is within NEAR_D2^(1/2) = 1.26 m of a BS.  That one test
 // triggers both rare fix-ups: the exact d + 1e-16 of a UE sitting ON a BS (here) and, in shared_rates, the rate of a pair
 // with snr > 1/64 (d < 1.24 m), which the short log1p series does not cover.
 // bsx / bsy (optional): the BS table in registers of the caller's choosing -- the fused rollout keeps it in VGPRs, see
-// step_kernel_body; nullptr: the kernel-argument segment (SGPRs).
+// step_kernel_body; nullptr: the kernel-argument segment (SGPRs; an LDS copy of the table measured 10 % slower, DESIGN_LOG.md).
 template <int B>
 __device__ __forceinline__ uint32_t eval_pairs(double px, double py, const KParams &p, float (&l2)[B], bool *near_wave = nullptr,
                                                const double *bsx = nullptr, const double *bsy = nullptr)
 {
     uint32_t in_range = 0;
     float qmin = 3.0e38f;
-    // some station of this lane sits where the fused d^2 cannot decide (pair_eval_q): noted by compares (form 0) or as min |q - (float)X| (form 1)
-    const bool vec_form = DCOMP_EDGE_MODE == 1 || (DCOMP_EDGE_MODE == 2 && bsx != nullptr);      // (bsx: the latency-bound fused rollout)
+    // some station of this lane sits where the fused d^2 cannot decide (pair_eval_q): noted by compares or as min |q - (float)X| (see dist_sq_ref)
+    const bool vec_form = bsx != nullptr;       // (bsx: the latency-bound fused rollout)
     bool edge = false;
     float emin = 3.0e38f;
 #pragma unroll
     for (int b = 0; b < B; b++) {
         bool ir;
         float q;
-        pair_eval_q(px, py, bsx ? bsx[b] : DCOMP_BSX(b), bsy ? bsy[b] : DCOMP_BSY(b), p, ir, l2[b], q);
+        pair_eval_q(px, py, bsx ? bsx[b] : p.bs_x[b], bsy ? bsy[b] : p.bs_y[b], p, ir, l2[b], q);
         in_range |= (uint32_t)ir << b;
         qmin = min_med3(qmin, q);
         if (vec_form) emin = min_med3(emin, __builtin_fabsf(q - p.dt2f));
         else edge |= q == p.dt2f;
     }
     if (vec_form) edge = emin == 0.f;
-#if !DCOMP_DSQ_FUSED
     if (__ballot(edge) != 0ull || p.dsq_exact) {  // rare (~1e-7 per pair), wave-uniform: every station of the wave again, in the reference's form
         in_range = 0;
 #pragma unroll
         for (int b = 0; b < B; b++)
             in_range |= (uint32_t)in_range_exact(px, py, bsx ? bsx[b] : p.bs_x[b], bsy ? bsy[b] : p.bs_y[b], p.dt2) << b;
     }
-#endif
     const bool nw = __ballot(qmin < NEAR_D2) != 0ull;
     if (near_wave) *near_wave = nw;
     if (nw) {                                    // rare (~3 % of the wavefronts): a lane within 1.26 m of a BS
@@ -569,7 +464,7 @@ __device__ __forceinline__ void draw_triple(const KParams &p, int env, uint32_t 
         VM_ARRIVED3(vel, wx, wy);
     } else {
         uint32_t r[4] = {0x12345678u + k * 977u, 0x9abcdef0u ^ uidw * 2654435761u, 0x0fedcba9u + (uint32_t)env * 40503u, 0u};
-        if (!(DCOMP_ABLATE & 128)) philox4x32_10(p.env_base + (uint32_t)env, id0 | (born ? UID_BORN : 0u), episode, k + 1, p.seed_lo, p.seed_hi, r);
+        philox4x32_10(p.env_base + (uint32_t)env, id0 | (born ? UID_BORN : 0u), episode, k + 1, p.seed_lo, p.seed_hi, r);
         const uint32_t vlo = (uint32_t)mcfg & 0xFFu, vhi = ((uint32_t)mcfg >> 8) & 0xFFu, bb = ((uint32_t)mcfg >> 23) & 0xFFu;
         vel = vlo + __umulhi(r[0], vhi - vlo + 1u);                                   // movement.py:112-117
         wx = bb + __umulhi(r[1], (uint32_t)(p.map_w - 2 * (int)bb + 1));              // movement.py:126-127
@@ -586,7 +481,7 @@ template <bool SCALAR>
 __device__ __forceinline__ void draw_triple_wave(const KParams &p, int env, uint32_t uidw, uint32_t k, uint32_t episode, bool redraw,
                                                  uint32_t &vel, uint32_t &wx, uint32_t &wy, int mcfg)
 {
-    if (!SCALAR || (!DCOMP_EXP_NO_TAPE && p.rng_mode == DCOMP_RNG_TAPE)) {           // host-drawn tape: a per-lane load
+    if (!SCALAR || p.rng_mode == DCOMP_RNG_TAPE) {           // host-drawn tape: a per-lane load
         if (redraw) draw_triple(p, env, uidw, k, episode, vel, wx, wy, mcfg);
         return;
     }
@@ -603,7 +498,7 @@ __device__ __forceinline__ void draw_triple_wave(const KParams &p, int env, uint
         const uint32_t e_s = (uint32_t)__builtin_amdgcn_readlane(env, l), u_s = (uint32_t)__builtin_amdgcn_readlane((int)uidw, l);
         const uint32_t k_s = (uint32_t)__builtin_amdgcn_readlane((int)k, l), m_s = (uint32_t)__builtin_amdgcn_readlane(mcfg, l);
         uint32_t r[4] = {0x12345678u + k_s * 977u, 0x9abcdef0u ^ u_s * 2654435761u, 0x0fedcba9u + e_s * 40503u, 0u};
-        if (!(DCOMP_ABLATE & 128)) philox4x32_10(eb + e_s, ((u_s & 0x7FFFu) - 1u) | (u_s & UID_BORN), episode, k_s + 1u, k0, k1, r);
+        philox4x32_10(eb + e_s, ((u_s & 0x7FFFu) - 1u) | (u_s & UID_BORN), episode, k_s + 1u, k0, k1, r);
         const uint32_t vlo = m_s & 0xFFu, vhi = (m_s >> 8) & 0xFFu, bb = (m_s >> 23) & 0xFFu;
         const uint32_t v_s = vlo + __umulhi(r[0], vhi - vlo + 1u);                              // movement.py:112-117
         const uint32_t x_s = bb + __umulhi(r[1], (uint32_t)(p.map_w - 2 * (int)bb + 1));        // movement.py:126-127
@@ -687,12 +582,7 @@ __device__ __forceinline__ void advance_ue(const KParams &p, uint32_t uidw, uint
         else {
             double vx = wx - px, vy = wy - py;
             double nrm, nx, ny;
-#if DCOMP_COMPILER_DIV
-            nrm = __builtin_sqrt(__builtin_fma(vy, vy, vx * vx));
-            nx = vx / nrm; ny = vy / nrm;
-#else
             norm_and_unit(vx, vy, nrm, nx, ny);                     // np.linalg.norm, then two divisions (movement.py:151)
-#endif
             px = px + velf * nx;
             py = py + velf * ny;
         }
@@ -712,8 +602,6 @@ __device__ __forceinline__ void move_ue(const KParams &p, int env, uint32_t uidw
                                         unsigned long long &mv, int mcfg)
 {
 #pragma clang fp contract(off)
-    constexpr bool SCALAR = DCOMP_SCALAR_DRAW == 1 || (DCOMP_SCALAR_DRAW == 2 && LAT);
-    constexpr bool SELECTS = DCOMP_MOVE_SELECTS == 1 || (DCOMP_MOVE_SELECTS == 2 && LAT);
     uint32_t wxi = (uint32_t)(mv & 0xFFFF), wyi = (uint32_t)((mv >> 16) & 0xFFFF), vel = (uint32_t)((mv >> 32) & 0xFF);
     uint32_t pz = (uint32_t)((mv >> 40) & 0xFF), cursor = (uint32_t)(mv >> 48);
     uint32_t pausing = (pz >> 7) & 1, cp = pz & 0x7Fu;
@@ -723,7 +611,7 @@ __device__ __forceinline__ void move_ue(const KParams &p, int env, uint32_t uidw
     const bool stay = pausing && cp < pause_dur;                    // movement.py:172-175
     const bool redraw = pausing && !stay;                           // movement.py:176 -> reset(): new velocity + waypoint, then move
     cp = stay ? cp + 1u : cp;
-    draw_triple_wave<SCALAR>(p, env, uidw, cursor, episode, redraw, vel, wxi, wyi, mcfg);
+    draw_triple_wave<LAT>(p, env, uidw, cursor, episode, redraw, vel, wxi, wyi, mcfg);
     cursor = redraw ? cursor + 1u : cursor;
     pausing = redraw ? 0u : pausing;
     cp = redraw ? 0u : cp;
@@ -735,8 +623,8 @@ __device__ __forceinline__ void move_ue(const KParams &p, int env, uint32_t uidw
     // Velocities that are not an integer in 0..255 (a caller's RandomWaypoint(map, velocity=2.5)): {velocity, qmax} from a per-UE
     // table the host built with the same definition -- a wave-uniform branch on a kernel argument, taken by no env of the
     // reference's own scenarios.
-    if (p.ue_velq != nullptr) advance_ue<SELECTS, true>(p, uidw, vel, stay, wx, wy, px, py);
-    else advance_ue<SELECTS, false>(p, uidw, vel, stay, wx, wy, px, py);
+    if (p.ue_velq != nullptr) advance_ue<LAT, true>(p, uidw, vel, stay, wx, wy, px, py);
+    else advance_ue<LAT, false>(p, uidw, vel, stay, wx, wy, px, py);
     mv = mv_pack(wxi, wyi, vel, pausing, cp, cursor);
 }
 
@@ -1054,12 +942,12 @@ __device__ __forceinline__ void write_outputs(const KParams &p, const Outs &o, B
     using G = Geo<B, UPAD>;
     using SG = StageGeo<B>;
     const int U = p.U;
-    const int kind = KIND >= 0 ? KIND : DCOMP_FORCE_KIND >= 0 ? DCOMP_FORCE_KIND : p.kind;
+    const int kind = KIND >= 0 ? KIND : p.kind;
     // per-BS utility aggregates over connected UEs (station.py:63-83)
     float tsum[B];
 #pragma unroll
     for (int b = 0; b < B; b++) tsum[b] = ((conn >> b) & 1u) ? util : 0.f;
-    if (!RESET && kind == DCOMP_MULTI && !(DCOMP_ABLATE & 16)) {     // central observations carry no per-station utilities
+    if (!RESET && kind == DCOMP_MULTI) {     // central observations carry no per-station utilities
         seg_reduce_vec<G::WG, OpSum, B>(tsum, sg, lane);
         if (G::NW > 1) xwave_reduce_<B, G::NW, OpSum>(tsum, sh, wave, lane);
     }
@@ -1157,11 +1045,7 @@ __device__ __forceinline__ void write_outputs(const KParams &p, const Outs &o, B
         if (active && o.next_act) o.next_act[idx] = (uint8_t)(live ? a : 0);
         if (pol_next) *pol_next = live ? (uint32_t)a : 0u;
     }
-    if ((DCOMP_ABLATE & 8) && kind == DCOMP_MULTI) {
-        float acc = util_n + reward;
-        for (int b = 0; b < B; b++) acc += l2[b] + cnt[b] + tsum[b];
-        if (active && acc == 123456.f) o.obs[idx] = acc;         // keeps the producers alive, writes nothing
-    } else if (kind == DCOMP_MULTI && !STAGED) {
+    if (kind == DCOMP_MULTI && !STAGED) {
         if (active && o.compact) {                              // (uniform) the compact record instead of the row, straight from registers
             if (o.reward) o.reward[idx] = alive ? reward : 0.f;
             float *rec = o.obs + (size_t)idx * (B + 2) + (size_t)env * (2 * B);     // word U (B + 2) env + (B + 2) u + 2B env
@@ -1233,11 +1117,7 @@ __device__ __forceinline__ void write_outputs(const KParams &p, const Outs &o, B
                 for (int j = lane * 4; j < n_end; j += 256) {
                     if (j >= ph && j + 4 <= n_end) {
                         typedef uint32_t u4v __attribute__((ext_vector_type(4)));
-#if DCOMP_NT_OBS
                         __builtin_nontemporal_store(*reinterpret_cast<const u4v *>(st + j), reinterpret_cast<u4v *>(gbase_ptr + j));
-#else
-                        *reinterpret_cast<u4v *>(gbase_ptr + j) = *reinterpret_cast<const u4v *>(st + j);
-#endif
                     } else {
                         for (int k = max(j, ph); k < min(j + 4, n_end); k++) gbase_ptr[k] = st[k];
                     }
@@ -1276,20 +1156,16 @@ __device__ __forceinline__ void write_outputs(const KParams &p, const Outs &o, B
             float *gbase_ptr = o.obs + g0 - ph;                            // 16-byte aligned
             for (int j = lane * 4; j < n_end; j += 256) {
                 if (j >= ph && j + 4 <= n_end) {
-#if DCOMP_NT_OBS
                     // observation rows are write-once streams nobody in this kernel re-reads: non-temporal stores
                     typedef float f4v __attribute__((ext_vector_type(4)));
                     __builtin_nontemporal_store(*reinterpret_cast<const f4v *>(st + j), reinterpret_cast<f4v *>(gbase_ptr + j));
-#else
-                    *reinterpret_cast<float4 *>(gbase_ptr + j) = *reinterpret_cast<const float4 *>(st + j);
-#endif
                 } else {
                     for (int k = max(j, ph); k < min(j + 4, n_end); k++) gbase_ptr[k] = st[k];
                 }
             }
             wave_lds_fence();
         }
-    } else if (G::NW == 1 && STAGED && DCOMP_CENTRAL_STAGED) {
+    } else if (G::NW == 1 && STAGED) {
         // Central layout: the records of the envs of one wave are contiguous in memory (REC floats each), so the wave stages
         // them in LDS exactly as they lie in memory and copies them out linearly -- every store instruction covers 1 KiB
         // instead of 64 scattered 4-byte pieces (round 1: 41 % of the HBM peak at 65 536 x 10 x 5).  Lane u owns B
@@ -1325,12 +1201,8 @@ __device__ __forceinline__ void write_outputs(const KParams &p, const Outs &o, B
                 float *gbase_ptr = o.obs + g0 + w0 - ph;                       // 16-byte aligned
                 for (int j = lane * 4; j < n_end; j += 256) {
                     if (j >= ph && j + 4 <= n_end) {
-#if DCOMP_NT_OBS
                         typedef float f4v __attribute__((ext_vector_type(4)));
                         __builtin_nontemporal_store(*reinterpret_cast<const f4v *>(st + j), reinterpret_cast<f4v *>(gbase_ptr + j));
-#else
-                        *reinterpret_cast<float4 *>(gbase_ptr + j) = *reinterpret_cast<const float4 *>(st + j);
-#endif
                     } else {
                         for (int k = max(j, ph); k < min(j + 4, n_end); k++) gbase_ptr[k] = st[k];
                     }
@@ -1373,19 +1245,10 @@ __device__ __forceinline__ void reset_ue(const KParams &p, int env, int u, uint3
 
 __device__ __forceinline__ void store_state(const KParams &p, int idx, double px, double py, unsigned long long mv, uint32_t conn, float ewma)
 {
-#if DCOMP_NT_STATE & 2
-    typedef double d2v __attribute__((ext_vector_type(2)));
-    d2v q; q.x = px; q.y = py;
-    __builtin_nontemporal_store(q, reinterpret_cast<d2v *>(p.pos) + idx);
-    __builtin_nontemporal_store(mv, p.mv + idx);
-    __builtin_nontemporal_store(conn, p.conn + idx);
-    __builtin_nontemporal_store(ewma, p.ewma + idx);
-#else
     p.pos[idx] = make_double2(px, py);
     p.mv[idx] = mv;
     p.conn[idx] = conn;
     p.ewma[idx] = ewma;
-#endif
 }
 
 // One MobileEnv.step (base.py:413-466) of the UE in this lane: toggle -> rates -> move -> drop -> EWMA -> rates -> outputs.
@@ -1421,7 +1284,7 @@ __device__ __forceinline__ void step_once(const KParams &p, BlockSharedT<B, UPAD
     // scratch: the dense form.
     // Only in the plain step (STORE): the fused rollout is latency-bound, one wave per SIMD, and the LDS look-ups of this pass
     // cost it 7 % (2.16 -> 2.32 us per step at 4 096 x 10 x 5); and only from 7 stations up (B = 5: 0.5 % slower).
-    constexpr bool SPARSE_OK = DCOMP_SPARSE_PRE && STORE && B >= DCOMP_SPARSE_MIN_B && !(DCOMP_ABLATE & 33) && 64 * (B + 1) <= StageGeo<B>::WORDS;
+    constexpr bool SPARSE_OK = STORE && B >= DCOMP_SPARSE_MIN_B && 64 * (B + 1) <= StageGeo<B>::WORDS;
     if (SPARSE_OK && !(MP == MP_GENERIC && p.any_maxcap)) {
         float *const prow = sh.stage[wave] + lane * (B + 1);
         const uint32_t act_bit = act ? 1u << (act - 1u) : 0u;
@@ -1453,8 +1316,7 @@ __device__ __forceinline__ void step_once(const KParams &p, BlockSharedT<B, UPAD
 #pragma unroll
             for (int b = 0; b < B; b++) l2[b] = carry->l2[b];
             in_range = carry->in_range; near_pre = carry->near;
-        } else if (!(DCOMP_ABLATE & 32)) in_range = eval_pairs<B>(px, py, p, l2, &near_pre, bsx, bsy);
-        else { for (int b = 0; b < B; b++) l2[b] = -20.f; }
+        } else in_range = eval_pairs<B>(px, py, p, l2, &near_pre, bsx, bsy);
         // 2. toggle (base.py:247-263 -> user.py:190-222)
         if (act > 0) {
             const uint32_t bit = 1u << (act - 1);
@@ -1466,8 +1328,7 @@ __device__ __forceinline__ void step_once(const KParams &p, BlockSharedT<B, UPAD
         }
         // 3. rates before the move (base.py:446) -> reward_before (base.py:158-167)
         if (CARRY) shared_rates<B, UPAD, MP, S, false, 2>(p, sh, conn, l2, ewma, px, py, u, idx, env_local, wave, lane, gbase, dr, cnt, (int)near_pre, sg, nullptr, carry->dru);
-        else if (!(DCOMP_ABLATE & 1)) shared_rates<B, UPAD, MP, S>(p, sh, conn, l2, ewma, px, py, u, idx, env_local, wave, lane, gbase, dr, cnt, (int)near_pre, sg);
-        else { for (int b = 0; b < B; b++) { dr[b] = 1.f; cnt[b] = 1.f; } }
+        else shared_rates<B, UPAD, MP, S>(p, sh, conn, l2, ewma, px, py, u, idx, env_local, wave, lane, gbase, dr, cnt, (int)near_pre, sg);
     }
     float curr = 0.f;
 #pragma unroll
@@ -1475,7 +1336,7 @@ __device__ __forceinline__ void step_once(const KParams &p, BlockSharedT<B, UPAD
     const float util_pre = ue_utility(curr, step_util, dr_req);
     const float reward_before = clamp_med3(util_pre, MIN_UTIL, MAX_UTIL) * (1.0f / MAX_UTIL);
     // 4. move (base.py:447 -> user.py:159-173)
-    if (active && !(DCOMP_ABLATE & 2)) {
+    if (active) {
         move_ue<!STORE>(p, env, (uint32_t)u + 1u, episode, px, py, mv, vrange);       // !STORE = the fused rollout
         // movement.py:165-166: inside [0, W] x [0, H].  Non-negative doubles order like their bit patterns, and a negative one (or a NaN) has
         // the top bit set: two unsigned 64-bit compares instead of four FP64 compares (px / py cannot be -0.0: a UE lands on integer waypoints
@@ -1484,7 +1345,7 @@ __device__ __forceinline__ void step_once(const KParams &p, BlockSharedT<B, UPAD
             (unsigned long long)__double_as_longlong(py) > (unsigned long long)__double_as_longlong((double)p.map_h)) atomicOr(p.flags, DCOMP_FLAG_OUTSIDE_MAP);
     }
     // 5. pairs at the new position; drop lost connections (user.py:175-188); EWMA from the stale rates (user.py:148-157)
-    if (!(DCOMP_ABLATE & 64)) in_range = eval_pairs<B>(px, py, p, l2, &near_post, bsx, bsy);
+    in_range = eval_pairs<B>(px, py, p, l2, &near_post, bsx, bsy);
     if (CARRY) {
 #pragma unroll
         for (int b = 0; b < B; b++) carry->l2[b] = l2[b];
@@ -1498,7 +1359,7 @@ __device__ __forceinline__ void step_once(const KParams &p, BlockSharedT<B, UPAD
     ewma = __builtin_fmaf(0.9f, stale, 0.1f * ewma);   // one explicit contraction: every kernel variant rounds alike
     // 6. rates after the move (base.py:451)
     if (CARRY) shared_rates<B, UPAD, MP, S, false, 1>(p, sh, conn, l2, ewma, px, py, u, idx, env_local, wave, lane, gbase, dr, cnt, (int)near_post, sg, nullptr, carry->dru);
-    else if (!(DCOMP_ABLATE & 4)) shared_rates<B, UPAD, MP, S>(p, sh, conn, l2, ewma, px, py, u, idx, env_local, wave, lane, gbase, dr, cnt, (int)near_post, sg);
+    else shared_rates<B, UPAD, MP, S>(p, sh, conn, l2, ewma, px, py, u, idx, env_local, wave, lane, gbase, dr, cnt, (int)near_post, sg);
     curr = 0.f;
 #pragma unroll
     for (int b = 0; b < B; b++) curr += dr[b];
@@ -1534,12 +1395,8 @@ __device__ __forceinline__ double in_vgpr(double v)
 // worth 15-19 % of the sustained write rate (tools/micro/store_patterns.hip, pattern 7 vs 5: 448.8 -> 377.5 us for 2.2 GB).
 __device__ __forceinline__ int xcd_contiguous_block()
 {
-#if DCOMP_XCD_REMAP
     const unsigned b = blockIdx.x, n = gridDim.x, q = n >> 3, r = n & 7u, x = b & 7u;
     return (int)(x * q + (x < r ? x : r) + (b >> 3));
-#else
-    return (int)blockIdx.x;
-#endif
 }
 
 template <int B, int UPAD, int MP, bool ROLLOUT, bool TIGHT = false, int POL = -1, int KIND = -1>
@@ -1565,16 +1422,10 @@ __device__ __forceinline__ void step_kernel_body(const KParams &p, BlockSharedT<
         sg = S{g, u, (gbase + g - 1) * 4, (uint32_t)m, (uint32_t)(m >> 32)};
     }
     const int idx = env * p.U + u;
-    if (DCOMP_SPARSE_PRE && !ROLLOUT && B >= DCOMP_SPARSE_MIN_B && 64 * (B + 1) <= StageGeo<B>::WORDS) {   // BS table for the sparse pre-move pass
+    if (!ROLLOUT && B >= DCOMP_SPARSE_MIN_B && 64 * (B + 1) <= StageGeo<B>::WORDS) {   // BS table for the sparse pre-move pass
         if (tid < B) sh.bs[tid] = make_double2(p.bs_x[tid], p.bs_y[tid]);
         __syncthreads();
     }
-
-#if DCOMP_BS_IN_LDS
-#pragma unroll
-    for (int b = 0; b < B; b++) if (tid == b) { g_bs_lds[b] = p.bs_x[b]; g_bs_lds[DCOMP_MASK32_MAX_BS + b] = p.bs_y[b]; }
-    __syncthreads();
-#endif
     double px = 0.0, py = 0.0;
     unsigned long long mv = 0;
     uint32_t conn = 0, act = 0;
@@ -1583,20 +1434,11 @@ __device__ __forceinline__ void step_kernel_body(const KParams &p, BlockSharedT<
     float dr_req = 1.f;
     int vrange = MV_CFG_ARRIVED;
     if (active) {
-#if DCOMP_NT_STATE & 1
-        typedef double d2v __attribute__((ext_vector_type(2)));
-        d2v q = __builtin_nontemporal_load(reinterpret_cast<const d2v *>(p.pos) + idx);
-        px = q.x; py = q.y;
-        mv = __builtin_nontemporal_load(p.mv + idx);
-        conn = __builtin_nontemporal_load(p.conn + idx);
-        ewma = __builtin_nontemporal_load(p.ewma + idx);
-#else
         double2 q = p.pos[idx];
         px = q.x; py = q.y;
         mv = p.mv[idx];
         conn = p.conn[idx];
         ewma = p.ewma[idx];
-#endif
         if (!ROLLOUT) act = p.action[idx];
         {
             const UeCfg c = p.ue_cfg[u];                                           // loaded here, next to the state
@@ -1643,7 +1485,7 @@ __device__ __forceinline__ void step_kernel_body(const KParams &p, BlockSharedT<
         int env_shift = 0, idx_shift = 0;                          // (dcomp_rollout_ex keeps T * E * U below 2^31)
 #pragma unroll 1
         for (int t = 0; t < T; t++) {
-            if (!DCOMP_EXP_NO_RESET && p.horizon > 0 && time == (uint32_t)p.horizon) {    // RLlib's horizon (env_setup.py:281): reset(), then step
+            if (p.horizon > 0 && time == (uint32_t)p.horizon) {    // RLlib's horizon (env_setup.py:281): reset(), then step
                 episode += p.episode_inc;
                 time = 0;
                 conn = 0u; ewma = 0.f;
@@ -1669,13 +1511,8 @@ __device__ __forceinline__ void step_kernel_body(const KParams &p, BlockSharedT<
     if (ROLLOUT && active) store_state(p, idx, px, py, mv, conn, ewma);
 }
 
-#ifdef DCOMP_MINW
-#define DCOMP_STEP_BOUNDS __launch_bounds__(DCOMP_BLOCK, DCOMP_MINW)
-#else
-#define DCOMP_STEP_BOUNDS __launch_bounds__(DCOMP_BLOCK)
-#endif
 template <int B, int UPAD, int MP>
-__global__ DCOMP_STEP_BOUNDS void step_kernel(const KParams p)
+__global__ __launch_bounds__(DCOMP_BLOCK) void step_kernel(const KParams p)
 {
     __shared__ BlockSharedT<B, UPAD> sh;
     step_kernel_body<B, UPAD, MP, false>(p, sh);

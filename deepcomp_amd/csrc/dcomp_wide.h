@@ -26,27 +26,8 @@
 
 namespace dcomp {
 
-#ifndef DCOMP_WIDE_PC
-#define DCOMP_WIDE_PC 8          // stations per trip of the dense post-move pair evaluation (BS positions: one s_load burst per trip)
-#endif
-#ifndef DCOMP_WIDE_QUAD_ROWS
-#define DCOMP_WIDE_QUAD_ROWS 1   // B % 4 == 0: observation rows leave as 16-byte pieces, a half-wave per row (0: round-3 form, 4-byte columns; A/B)
-#endif
-#ifndef DCOMP_WIDE_NT_ROWS
-#define DCOMP_WIDE_NT_ROWS 0     // non-temporal 16-byte row stores (A/B)
-#endif
-#ifndef DCOMP_WIDE_UTIL_EACH
-#define DCOMP_WIDE_UTIL_EACH 1   // the utility float of a row (its last) is stored in the trip that stores the row, not every other trip: the
-#endif                           // line it completes leaves L2 whole (32 768 envs: -3 %; tools/micro/store_patterns.hip pattern 5 vs 1)
-#ifndef DCOMP_WIDE_PERSIST
-#define DCOMP_WIDE_PERSIST 0     // experiment (round 4): persistent workgroups that request the next slot's state before they store this one's rows
-#endif
-#ifndef DCOMP_WIDE_STORE_PRIO
-#define DCOMP_WIDE_STORE_PRIO 0  // A/B: the row-store loop (1) / everything behind the step's last barrier (2) at raised issue priority: +-0.2 %
-#endif
-#ifndef DCOMP_WIDE_K
-#define DCOMP_WIDE_K 4           // connections per UE the register fast paths hold; a wave with a busier UE takes the LDS detours
-#endif
+#define DCOMP_WIDE_PC 8   // stations per trip of the dense post-move pair evaluation (BS positions: one s_load burst per trip)
+#define DCOMP_WIDE_K 4    // connections per UE the register fast paths hold; a wave with a busier UE takes the LDS detours
 
 template <int B, int UPAD>
 struct alignas(16) WideShared {
@@ -135,17 +116,13 @@ __device__ __forceinline__ WideIn wide_load(const KParams &p, int g)
     return in;
 }
 
-// One MobileEnv.step of the GPB envs of workgroup-slot g.  `in`: their state (already requested); on return it holds the state of
-// slot g_next when has_next -- requested before this slot's observation rows are stored, see step_kernel_wide.
+// One MobileEnv.step of the GPB envs of workgroup-slot g.  `in`: their state (already requested).
 template <int B, int UPAD, int MP>
 __device__ __forceinline__ void wide_step_one(const KParams &p, WideShared<B, UPAD> &sh, const int32_t *lds_modes, const WideCfg cfg,
-                                              const int g, WideIn &in, const bool has_next, const int g_next)
+                                              const int g, const WideIn &in)
 {
     constexpr int NW = UPAD / 64, GPB = 256 / UPAD, ROW = 4 * B + 1, K = DCOMP_WIDE_K, PC = DCOMP_WIDE_PC;
-    // (the thread index is hidden from the optimiser once per slot: everything derived from it -- lane constants, table addresses,
-    // output offsets -- would otherwise be hoisted out of step_kernel_wide's slot loop and live in ~100 extra VGPRs across it)
-    int tid = threadIdx.x;
-    if (DCOMP_WIDE_PERSIST) asm volatile("" : "+v"(tid));
+    const int tid = threadIdx.x;
     const int lane = tid & 63, wave = tid >> 6;
     const int env_local = wave / NW, u = (wave % NW) * 64 + lane;
     const int env = g * GPB + env_local;
@@ -279,11 +256,7 @@ __device__ __forceinline__ void wide_step_one(const KParams &p, WideShared<B, UP
         constexpr bool FULL = decltype(full_tag)::value;       // every slot of the chunk is a station: no bounds tests
         float l2n[PC];
         bool anytiny = false;
-#if DCOMP_EDGE_MODE == 0
-        bool edge = false;
-#else
-        float emin = 3.0e38f;                                    // (the wide kernel runs two to four waves per SIMD: the vector-only form, dcomp_device.h DCOMP_EDGE_MODE)
-#endif
+        float emin = 3.0e38f;                                    // (the wide kernel runs two to four waves per SIMD: the vector-only form, see dist_sq_ref)
 #pragma unroll
         for (int j = 0; j < PC; j++) {
             const int b = c0 + j;
@@ -293,18 +266,11 @@ __device__ __forceinline__ void wide_step_one(const KParams &p, WideShared<B, UP
                 float q;
                 pair_eval_q(px, py, p.bs_x[b], p.bs_y[b], p, inr_n, l2n[j], q);
                 anytiny |= q < NEAR_D2;
-#if DCOMP_EDGE_MODE == 0
-                edge |= q == p.dt2f;                             // the fused d^2 cannot decide this pair (dcomp_device.h, dist_sq_ref)
-#else
-                emin = min_med3(emin, __builtin_fabsf(q - p.dt2f));
-#endif
+                emin = min_med3(emin, __builtin_fabsf(q - p.dt2f));   // 0: the fused d^2 cannot decide this pair (dcomp_device.h, dist_sq_ref)
                 inr_new |= (uint32_t)inr_n << b;
             }
         }
-#if DCOMP_EDGE_MODE != 0
         const bool edge = emin == 0.f;
-#endif
-#if !DCOMP_DSQ_FUSED
         if (__ballot(edge) != 0ull || p.dsq_exact) {            // rare (~1e-7 per pair), wave-uniform: this chunk's decisions in the reference's form
 #pragma unroll
             for (int j = 0; j < PC; j++) {
@@ -312,7 +278,6 @@ __device__ __forceinline__ void wide_step_one(const KParams &p, WideShared<B, UP
                 if (FULL || b < B) inr_new = (inr_new & ~(1u << b)) | ((uint32_t)in_range_exact(px, py, p.bs_x[b], p.bs_y[b], p.dt2) << b);
             }
         }
-#endif
         if (__ballot(anytiny) != 0ull) {                       // a lane within 1.26 m of one of these stations (new position)
 #pragma unroll
             for (int j = 0; j < PC; j++) {
@@ -413,22 +378,6 @@ __device__ __forceinline__ void wide_step_one(const KParams &p, WideShared<B, UP
         p.conn[idx] = conn;
         p.ewma[idx] = ewma;
     }
-    // The next slot's state is requested HERE, before this slot's observation rows are stored, and its arrival is awaited right
-    // before the first row store (wide_arrived): vmcnt counts loads and stores in one in-order counter, so a load issued after
-    // the 40 row stores could only be waited for together with them -- the wave would sit out the drain of its own stores before
-    // it could compute again.  This way the rows of slot g drain while the wave computes slot g + grid (step_kernel_wide).
-    // (Unconditional on purpose -- the last slot of a workgroup requests its own state again and drops it: the compiler does not
-    // see that a conditional request and a conditional wait share their condition, and would guard every later write of these
-    // registers, and the top of the slot loop, with a wait for "the request that was never awaited".)
-    WideIn nx{0.0, 0.0, 0ull, 0u, 0.f, 0u};
-    if (DCOMP_WIDE_PERSIST) nx = wide_load<UPAD>(p, has_next ? g_next : g);
-    auto wide_arrived = [&]() {
-        if (DCOMP_WIDE_PERSIST) {
-            asm volatile("" : "+v"(nx.px), "+v"(nx.py), "+v"(nx.mv), "+v"(nx.conn), "+v"(nx.ewma), "+v"(nx.act));   // a use: the compiler's s_waitcnt goes here
-            in = nx;
-        }
-    };
-
     // ---- 7. per-BS utility aggregates (station.py:63-83), transposed like the rate sums: what a station needs -- |S_b|, sum and
     // min of the utilities of its UEs -- is a function of just TWO words per UE (connection mask, utility).
     const bool multi = p.kind == DCOMP_MULTI;
@@ -461,9 +410,6 @@ __device__ __forceinline__ void wide_step_one(const KParams &p, WideShared<B, UP
         if (lane < 32) sh.part_a[wave][sb] = make_float4(my_cnt, t, mn, ta);     // (the pre-move sums in part_a were consumed before the barrier of step 6)
     }
     __syncthreads();                                                              // per-wave tables (and nb_*) visible to the block
-#if DCOMP_WIDE_STORE_PRIO == 2
-    __builtin_amdgcn_s_setprio(3);                 // (A/B: everything behind the last barrier of the step at raised priority)
-#endif
     auto station = [&](int b) -> float4 {                                         // totals of station b over the env's waves
         float4 a = sh.part_a[w0][b];
 #pragma unroll
@@ -526,7 +472,6 @@ __device__ __forceinline__ void wide_step_one(const KParams &p, WideShared<B, UP
     const float util_n = util * (1.0f / MAX_UTIL);
 
     // ---- observation
-    wide_arrived();
     if (!multi) {                                                                 // central.py:31-57: connected | dr | utility blocks
         if (active) {
             float *base = p.obs + (size_t)env * p.U * (2 * B + 1);
@@ -586,7 +531,7 @@ __device__ __forceinline__ void wide_step_one(const KParams &p, WideShared<B, UP
         }
         return;
     }
-    if constexpr (B % 4 == 0 && DCOMP_WIDE_QUAD_ROWS) {
+    if constexpr (B % 4 == 0) {
         // ---- rows leave as 16-BYTE pieces, a half-wave per row (round 4).  With B a multiple of 4 the four blocks of a row start at
         // multiples of 4 floats, so piece j (floats 4j .. 4j+3, j < B) of a row lies inside ONE block: lanes 0 .. B-1 of a half-wave
         // take the B pieces of one row -- a lane's kind of column is a constant of the whole loop -- and one store instruction
@@ -636,7 +581,7 @@ __device__ __forceinline__ void wide_step_one(const KParams &p, WideShared<B, UP
         const int nrows = group_popcount<64>(am, 0);                              // active lanes are lanes [0, nrows)
         const size_t row0 = (size_t)env * p.U + (size_t)(wave % NW) * 64;
         float *const out0 = p.obs + (row0 + h) * ROW + 4 * j;                     // this lane's piece of row 2i + h, at i = 0
-        const int npairs = (DCOMP_ABLATE & 8) ? 0 : (nrows + 1) >> 1;
+        const int npairs = (nrows + 1) >> 1;
         typedef float f4u __attribute__((ext_vector_type(4), aligned(4)));
         // where this lane's piece of row 2i + h waits
         auto piece = [&](int i) -> const float4 * {
@@ -650,34 +595,19 @@ __device__ __forceinline__ void wide_step_one(const KParams &p, WideShared<B, UP
         auto put = [&](int i, const float4 v) {
             if (j < B && 2 * i + h < nrows) {
                 f4u w; w.x = v.x; w.y = v.y; w.z = v.z; w.w = v.w;
-                f4u *dst = reinterpret_cast<f4u *>(out0 + (size_t)i * (2 * ROW));
-#if DCOMP_WIDE_NT_ROWS
-                __builtin_nontemporal_store(w, dst);
-#else
-                *dst = w;
-#endif
+                *reinterpret_cast<f4u *>(out0 + (size_t)i * (2 * ROW)) = w;
             }
         };
-#if DCOMP_WIDE_STORE_PRIO == 1
-        __builtin_amdgcn_s_setprio(3);             // see step_kernel_wide: a wave that has rows to store goes first
-#endif
         for (int i = 0; i < npairs; i += 2) {                                     // two row pairs per trip: both LDS reads in flight
             const int i1 = min(i + 1, 31);
             const float4 *a0 = piece(i), *a1 = piece(i1);
             const float4 v0 = *a0, v1 = *a1;
             put(i, v0);
             if (i + 1 < npairs) put(i + 1, v1);
-            // the utility column (the row's last float) of the eight rows just completed: their own lanes store it, right behind
-#if DCOMP_WIDE_UTIL_EACH
-            if ((lane >> 2) == (i >> 1) && active) p.obs[(row0 + lane) * ROW + 4 * B] = util_n;      // the four rows of this trip, at once
-#else
-            if (((i & 2) || i + 2 >= npairs) && (lane >> 3) == (i >> 2) && active)
-                p.obs[(row0 + lane) * ROW + 4 * B] = util_n;
-#endif
+            // the utility column (the row's last float) of the four rows just completed: their own lanes store it in the trip that
+            // stores the rows, so the line it completes leaves L2 whole (32 768 envs: -3 % against every other trip; DESIGN_LOG.md)
+            if ((lane >> 2) == (i >> 1) && active) p.obs[(row0 + lane) * ROW + 4 * B] = util_n;
         }
-#if DCOMP_WIDE_STORE_PRIO
-        __builtin_amdgcn_s_setprio(0);
-#endif
         return;
     }
     // the per-UE dr columns: normalise in place, the row loop reads them column-wise (lane r's row -> output row r)
@@ -720,7 +650,7 @@ __device__ __forceinline__ void wide_step_one(const KParams &p, WideShared<B, UP
         is_dr[k] = c >= B && c < 2 * B;
         dcol[k] = is_dr[k] ? c - B : 0;
     }
-    for (int r0 = 0; r0 < ((DCOMP_ABLATE & 8) ? 0 : nrows); r0 += 4) {
+    for (int r0 = 0; r0 < nrows; r0 += 4) {
         float d[4][NSLOT];
 #pragma unroll
         for (int k4 = 0; k4 < 4; k4++) {
@@ -750,27 +680,19 @@ __device__ __forceinline__ void wide_step_one(const KParams &p, WideShared<B, UP
     }
 }
 
-// One workgroup per slot (GPB envs).  DCOMP_WIDE_PERSIST = 1 is the round-4 experiment that did NOT pay: persistent workgroups
-// (at most as many as the GPU holds at once, each walking the slots g, g + grid, ...) that request the next slot's state before
-// they store this slot's rows, so that a wave computes while its own rows drain -- vmcnt counts loads and stores in one in-order
-// counter, so every wait for a load inside the slot loop had to go (VM_ARRIVED in the rare branches, the unconditional request).
-// Same-box A/B: 4 096 x 128 x 32 54.5 -> 60.2 us, 32 768 envs 515 -> 541 us.  The slot loop costs 67 scalar spills and the
-// 128-VGPR cap, and the overlap it was built for does not come from a wave's own stores draining: a wave in its store loop is
-// held at ISSUE while the CU's memory pipe is backed up (tools/micro/store_patterns.hip: the rows alone take 39.5 us at 4 096
-// envs, 410-450 us at 32 768), and while it is held its SIMD can only run the OTHER waves.  What helps is that the storing wave
-// never waits for an issue slot behind computing waves: DCOMP_WIDE_STORE_PRIO.
+// One workgroup per slot (GPB envs).  (Persistent workgroups that request the next slot's state before they store this slot's rows
+// measured slower: DESIGN_LOG.md, round 4.)
 template <int B, int UPAD, int MP>
-__global__ __launch_bounds__(256, DCOMP_WIDE_PERSIST ? 4 : 1) void step_kernel_wide(const KParams p)
+__global__ __launch_bounds__(256, 1) void step_kernel_wide(const KParams p)
 {
     static_assert(UPAD >= 64, "wide kernel: one wavefront holds UEs of a single env");
-    constexpr int NW = UPAD / 64, GPB = 256 / UPAD;
+    constexpr int NW = UPAD / 64;
     using SH = WideShared<B, UPAD>;
     __shared__ SH sh;
     __shared__ int32_t lds_modes[32];
     const int tid = threadIdx.x;
-    const int total = (p.E + GPB - 1) / GPB;
-    const int slot0 = DCOMP_WIDE_PERSIST ? (int)blockIdx.x : xcd_contiguous_block();     // every XCD a contiguous eighth of the slots
-    WideIn in = wide_load<UPAD>(p, slot0);
+    const int slot = xcd_contiguous_block();                                      // every XCD a contiguous eighth of the slots
+    const WideIn in = wide_load<UPAD>(p, slot);
     WideCfg cfg{false, 1.f, MV_CFG_ARRIVED};
     {
         const int u = ((tid >> 6) % NW) * 64 + (tid & 63);
@@ -780,24 +702,10 @@ __global__ __launch_bounds__(256, DCOMP_WIDE_PERSIST ? 4 : 1) void step_kernel_w
             cfg.vrange = mv_cfg_pack(c.vel_lo, c.vel_hi, c.pause, c.border);
         }
     }
-    if (DCOMP_WIDE_PERSIST) {
-        // the first slot's state has ARRIVED before the slot loop: inside it no wait for a load may remain
-        asm volatile("" : "+v"(in.px), "+v"(in.py), "+v"(in.mv), "+v"(in.conn), "+v"(in.ewma), "+v"(in.act));
-        asm volatile("" : "+v"(cfg.dr_req), "+v"(cfg.vrange));
-    }
     if (tid < B) { sh.bs[tid] = make_double2(p.bs_x[tid], p.bs_y[tid]); lds_modes[tid] = p.bs_mode[tid]; }
     if (tid >= 64 && tid < 80) { const int n = tid - 64; sh.nib[n] = make_float4((float)(n & 1), (float)((n >> 1) & 1), (float)((n >> 2) & 1), (float)(n >> 3)); }
     __syncthreads();                                                              // BS table, nibble table
-    if (!DCOMP_WIDE_PERSIST) {
-        wide_step_one<B, UPAD, MP>(p, sh, lds_modes, cfg, slot0, in, false, 0);
-        return;
-    }
-#pragma unroll 1
-    for (int g = blockIdx.x; g < total; g += gridDim.x) {
-        const int gn = g + gridDim.x;
-        wide_step_one<B, UPAD, MP>(p, sh, lds_modes, cfg, g, in, gn < total, gn);
-        if (gn < total) __syncthreads();                  // this slot's per-station tables are read until its waves have built their pieces
-    }
+    wide_step_one<B, UPAD, MP>(p, sh, lds_modes, cfg, slot, in);
 }
 
 }  // namespace dcomp

@@ -1,9 +1,10 @@
 #!/usr/bin/env python3
 """A/B of library builds on ONE GPU box (boxes differ by +-3 %, so only same-box comparisons count).
 
-  python tools/ab/ab_lib.py build <tag> [--ref GITREF] [--b 5,10,32] [--flags "-DX=1 ..."]     (build container)
-        -> deepcomp_amd/csrc/variants/libdcomp_hip_<tag>.so from the working tree, or from the sources at GITREF
-           (csrc/ + include/ exported to a scratch directory); only the listed base-station counts (seconds, not minutes)
+  python tools/ab/ab_lib.py build <tag> [--ref GITREF | --src TREE] [--b 5,10,32] [--flags "-DX=1 ..."]     (build container)
+        -> deepcomp_amd/csrc/variants/libdcomp_hip_<tag>.so from the working tree, from the sources at GITREF
+           (csrc/ + include/ exported to a scratch directory) or from an edited copy of the tree (a variant: the product headers
+           carry no build switches); only the listed base-station counts (seconds, not minutes)
   python tools/ab/ab_lib.py run <tag> <tag> ... [--rounds 2] [--only c3,c2roll,...]              (GPU box, via gpurun)
         -> every workload timed with every library, interleaved `rounds` times, one child process per (library, round);
            prints kernel ms per step (HIP events, steady state) and the ratio to the first tag
