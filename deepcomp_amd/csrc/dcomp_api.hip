@@ -7,6 +7,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <memory>
 #include <mutex>
 #include <thread>
 #include <utility>
@@ -53,42 +54,74 @@ static int fail(int code, const char *fmt, ...)
         if (e_ != hipSuccess) return fail(DCOMP_EHIP, "%s failed: %s", #expr, hipGetErrorString(e_)); \
     } while (0)
 
+// Environment overrides (tests and A/B runs), read ONCE per handle by dcomp_create_v: INTEGRATION.md section 2 has the table of
+// names, values, effects and users.
+struct EnvInt { bool set; long v; };
+struct Overrides { EnvInt force_big, no_fused_big, dsq_exact, big_row_x4, wide_pad_lds, fuse_max_waves, tight, fused_row_limit_log2; };
+static Overrides read_overrides()
+{
+    auto get = [](const char *name) { const char *e = getenv(name); return EnvInt{e != nullptr, e ? atol(e) : 0}; };
+    return Overrides{get("DCOMP_FORCE_BIG"), get("DCOMP_NO_FUSED_BIG"), get("DCOMP_DSQ_EXACT"), get("DCOMP_BIG_ROW_X4"),
+                     get("DCOMP_WIDE_PAD_LDS"), get("DCOMP_FUSE_MAX_WAVES"), get("DCOMP_TIGHT"), get("DCOMP_FUSED_ROW_LIMIT_LOG2")};
+}
+
+// The launch plan of a handle: which kernels it launches and how, decided once by make_plan (dcomp_create_v) and only read afterwards.
+// StepPath, the step kernel: Special = step_kernel (padded power-of-two lane groups), Wide = step_kernel_wide (one workgroup per env slot),
+// Dyn = step_kernel_dyn (the UE list changes: cfg.max_ues > 0), Tight = step_kernel_tight (U lanes per env), Generic = big_kernel
+// (dcomp_big.h: 33 ... 64 stations, more than DCOMP_SPECIAL_MAX_UE slots, or DCOMP_FORCE_BIG=1).
+// Fuse, what dcomp_rollout does with T steps: None = the step kernel once per step, Always = one launch of the fused rollout kernel,
+// Long = that for rollouts of >= 4 steps and for the closed loop only, Stretch = the generic kernel's: one launch per stretch of an episode.
+enum class StepPath { Special, Wide, Dyn, Tight, Generic };
+enum class Fuse { None, Always, Long, Stretch };
+enum class Launch { Reset, Step, Rollout };
+struct LaunchPlan {
+    StepPath path = StepPath::Special;
+    Fuse fuse = Fuse::None;
+    // the specialised kernels (path != Generic); rollout / rollout_pol: the fused rollout without / with the in-step policy
+    dcomp::KernelFn reset = nullptr, step = nullptr, rollout = nullptr, rollout_pol = nullptr;
+    bool tight_central = false;        // Tight: `step` is the central-only instantiation (dcomp_step_kernel_name)
+    bool rollout_tight = false;        // `rollout` is the tightly packed instantiation: launched with the tight grid and packing
+    dcomp::BigKernels big{};           // the generic kernel (path == Generic)
+    int big_step = 0;                  // BigKernels::fn's `which` of a step: 0, or 2 with UE arrival / departure
+    int grid = 0, block = DCOMP_BLOCK;
+    size_t lds = 0;                    // dynamic LDS per workgroup: Generic every launch (big_carve); Wide the steps that write rows (occupancy cap)
+    int lanes = 0;                     // lanes per env: the padded width, or U when the step is tightly packed
+    int tight_grid = 0, tight_g = 0, tight_gpw = 0, tight_magic = 0;   // the tight packing (KParams::tight_*), 0 = off
+    uint64_t row_limit = 0;            // rows (num_steps * num_envs * num_ue) from which an every-step fragment no longer fits the fused rollout kernel
+};
 struct dcomp_env {
     dcomp_cfg cfg;
     KParams kp;                 // constant part pre-filled
-    dcomp::KernelPair kern;
-    UeCfg *d_ue_cfg;
+    Overrides ovr;
+    LaunchPlan plan;            // decided by dcomp_create_v, read-only afterwards
+    UeCfg *d_ue_cfg = nullptr;
     double2 *d_ue_velq = nullptr;   // {velocity, qmax} of UEs whose fixed velocity is no integer in 0..255 (cfg.ue_velocity)
     bool dyn;                  // UE list changes during an episode (cfg.max_ues > 0)
     int mp_pattern;            // sharing-pattern specialisation the kernels were looked up with (dcomp::MP_*)
-    bool fused;                // kern.step is step_kernel: T steps in one launch (the wide / dynamic kernels step once per launch)
-    bool fused_big = false;    // the generic kernel's fused rollout (fixed UE list): T steps = one launch per stretch of an episode
-    bool fused_long;           // ... for rollouts of >= 4 steps at ANY batch size (small central rows: see dcomp_create)
-    int upad, grid;
-    int wide_pad_lds = 0;      // step_kernel_wide: extra dynamic LDS per workgroup = fewer resident workgroups per CU (see dcomp_create)
-    int tight_g, tight_gpw, tight_magic, tight_grid;   // step_kernel's tight packing of non-power-of-two UE lists (0 = off)
+    int upad;                  // padded lanes per env
     int cap, cur_ue;            // slots per env; UEs currently listed
-    uint32_t n_removed, n_arrived;   // this episode (Philox draw words)
-    int time;
-    int64_t episode;            // index of the current episode (-1 before the first reset)
-    // 33 ... 64 stations (or DCOMP_FORCE_BIG=1): the generic kernel of dcomp_big.h instead of `kern`
-    bool big = false;
-    dcomp::BigKernels bigk{};
-    int big_step = 0;                                      // BigKernels::fn's `which` of a step: 0, or 2 with UE arrival / departure
-    dcomp::BigParams bigp{};
+    uint32_t n_removed = 0, n_arrived = 0;   // this episode (Philox draw words)
+    int time = 0;
+    int64_t episode = -1;       // index of the current episode (-1 before the first reset)
+    dcomp::BigParams bigp{};   // the generic kernel's second argument
     double2 *d_bs = nullptr;
     int32_t *d_mode = nullptr;
-    size_t big_lds = 0;
 };
+struct EnvDeleter { void operator()(dcomp_env *env) const { dcomp_destroy(env); } };
 
 // ---- channel constants from the reference's own formula (station.py:26-30,110-127), FP64 on the host ----
+struct PathLoss { double c1, c2; };     // pl(d) = c1 + c2 * log10(d)
+static PathLoss path_loss()
+{
+    const double f = 2500.0, hb = 50.0, hu = 1.5;
+    const double ch = 0.8 + (1.1 * std::log10(f) - 0.7) * hu - 1.56 * std::log10(f);
+    return PathLoss{69.55 + 26.16 * std::log10(f) - 13.82 * std::log10(hb) - ch, 44.9 - 6.55 * std::log10(hb)};
+}
 static double ref_snr(double d)
 {
-    const double f = 2500.0, hb = 50.0, hu = 1.5, tx = 30.0, noise = 1e-9;
-    double ch = 0.8 + (1.1 * std::log10(f) - 0.7) * hu - 1.56 * std::log10(f);
-    double c1 = 69.55 + 26.16 * std::log10(f) - 13.82 * std::log10(hb) - ch;
-    double c2 = 44.9 - 6.55 * std::log10(hb);
-    double pl = c1 + c2 * std::log10(d + 1e-16);
+    const double tx = 30.0, noise = 1e-9;
+    const PathLoss c = path_loss();
+    double pl = c.c1 + c.c2 * std::log10(d + 1e-16);
     return std::pow(10.0, (tx - pl) / 10.0) / noise;
 }
 // d_T = the smallest double d whose snr, computed the reference's way, is NOT above the threshold; -1 when that computed snr is not
@@ -154,14 +187,8 @@ static hipError_t raise_lds_limit(const void *fn, int bytes)
 
 static int next_pow2(int v) { int p = 1; while (p < v) p <<= 1; return p; }
 
-// Rows (num_steps * num_envs * num_ue) from which an every-step fragment no longer fits the fused rollout kernel's 32-bit row indices.
-// DCOMP_FUSED_ROW_LIMIT_LOG2 lowers it (tests: the one-launch-per-step fallback of dcomp_rollout_ex without a 2^31-row fragment).
-static uint64_t fused_row_limit()
-{
-    const char *e = getenv("DCOMP_FUSED_ROW_LIMIT_LOG2");
-    const int l2 = e ? atoi(e) : 31;
-    return (uint64_t)1 << (l2 >= 1 && l2 <= 31 ? l2 : 31);
-}
+// Floats per observation row of one UE (variants.py: multi-agent connected | dr | ues_at_bs | util_at_bs | utility, central connected | dr | utility).
+static int row_floats(int env_kind, int B) { return env_kind == DCOMP_MULTI ? 4 * B + 1 : 2 * B + 1; }
 
 extern "C" const char *dcomp_last_error(void) { return g_err; }
 #define DCOMP_STR2(x) #x
@@ -178,23 +205,15 @@ extern "C" int dcomp_create(const dcomp_cfg *, dcomp_env **out)
                             "(its dcomp_create macro calls dcomp_create_v) or call dcomp_create_v with the caller's struct sizes", DCOMP_ABI_VERSION);
 }
 
-extern "C" int dcomp_create_v(int32_t abi_version, size_t cfg_size, size_t state_size, size_t out_size, size_t rollout_opts_size,
-                              const dcomp_cfg *cfg, dcomp_env **out)
+// ---- dcomp_create_v in steps: validate, per-UE tables, channel constants, launch plan, device uploads ----
+// What can be wrong with a configuration -- the velocities and utilities: ue_tables -- before anything is allocated.
+static int validate_cfg(const dcomp_cfg *cfg)
 {
-    if (out) *out = nullptr;
-    if (abi_version != DCOMP_ABI_VERSION || cfg_size != sizeof(dcomp_cfg) || state_size != sizeof(dcomp_state) || out_size != sizeof(dcomp_out) ||
-        rollout_opts_size != sizeof(dcomp_rollout_opts))
-        return fail(DCOMP_EABI, "ABI mismatch: caller has version %d, sizeof dcomp_cfg / dcomp_state / dcomp_out / dcomp_rollout_opts = %zu / %zu / %zu / %zu; "
-                                "this library has version %d and %zu / %zu / %zu / %zu", (int)abi_version, cfg_size, state_size, out_size, rollout_opts_size,
-                    DCOMP_ABI_VERSION, sizeof(dcomp_cfg), sizeof(dcomp_state), sizeof(dcomp_out), sizeof(dcomp_rollout_opts));
-    if (!cfg || !out) return fail(DCOMP_EINVAL, "null argument");
-    *out = nullptr;
     const int E = cfg->num_envs, U = cfg->num_ue, B = cfg->num_bs;
     if (E < 1 || U < 1 || U > DCOMP_MAX_UE || B < 1 || B > DCOMP_MAX_BS)
         return fail(DCOMP_EINVAL, "need num_envs>=1, 1<=num_ue<=%d, 1<=num_bs<=%d (got %d, %d, %d)", DCOMP_MAX_UE, DCOMP_MAX_BS, E, U, B);
     const int CAP = cfg->max_ues > 0 ? cfg->max_ues : U;           // slots per env (base.py:79-84)
     if (CAP < U) return fail(DCOMP_EINVAL, "max_ues (%d) < num_ue (%d)", CAP, U);                 // base.py:84
-    const bool DYN = cfg->max_ues > 0;                             // departures alone need no extra slots: max_ues == num_ue
     if ((int64_t)E * CAP > (int64_t)1 << 30) return fail(DCOMP_EINVAL, "num_envs*max_ues too large");
     if (cfg->map_w < 3 || cfg->map_h < 3 || cfg->map_w > 65535 || cfg->map_h > 65535)
         return fail(DCOMP_EINVAL, "map must be 3..65535 in both dimensions");
@@ -213,75 +232,39 @@ extern "C" int dcomp_create_v(int32_t abi_version, size_t cfg_size, size_t state
     if (cfg->rng_mode == DCOMP_RNG_TAPE && cfg->tape_depth < 1) return fail(DCOMP_EINVAL, "tape mode needs tape_depth >= 1");
     if (!cfg->bs_x || !cfg->bs_y || !cfg->bs_sharing || !cfg->ue_vel_lo || !cfg->ue_vel_hi)
         return fail(DCOMP_EINVAL, "bs_x, bs_y, bs_sharing, ue_vel_lo, ue_vel_hi are required");
+    for (int b = 0; b < B; b++)
+        if (cfg->bs_sharing[b] < 0 || cfg->bs_sharing[b] > 3) return fail(DCOMP_EINVAL, "bs_sharing[%d]=%d not supported", b, cfg->bs_sharing[b]);   // station.py:22
+    return DCOMP_OK;
+}
 
-    dcomp_env *env = new dcomp_env();
-    env->cfg = *cfg;
-    env->cfg.bs_x = env->cfg.bs_y = nullptr;   // host arrays are not retained
-    env->cfg.ue_pause_duration = env->cfg.ue_border_buffer = nullptr;
-    env->cfg.ue_velocity = nullptr;
-    env->cap = CAP; env->dyn = DYN; env->cur_ue = U; env->n_removed = env->n_arrived = 0;
-    env->upad = next_pow2(CAP) < 4 ? 4 : next_pow2(CAP);
-    int mp = dcomp::MP_RES_FAIR;            // sharing pattern -> specialised kernel (dcomp_device.h bs_mode_of)
-    for (int b = 0; b < B; b++) if (cfg->bs_sharing[b] != DCOMP_RES_FAIR) mp = dcomp::MP_MIXED;
-    if (mp == dcomp::MP_MIXED) {
-        static const int cyc[3] = {DCOMP_RES_FAIR, DCOMP_RATE_FAIR, DCOMP_PROP_FAIR};   // env_setup.py:40-49
-        for (int b = 0; b < B; b++) if (cfg->bs_sharing[b] != cyc[b % 3]) mp = dcomp::MP_GENERIC;
-    }
-    // More than 32 stations: the generic kernel (dcomp_big.h; one instantiation per lane width, B a run-time value, connection set in two
-    // state words).  DCOMP_FORCE_BIG=1 sends smaller station counts there too (tests: generic against specialised kernels).
-    env->big = B > DCOMP_MASK32_MAX_BS || CAP > DCOMP_SPECIAL_MAX_UE || (getenv("DCOMP_FORCE_BIG") && atoi(getenv("DCOMP_FORCE_BIG")) != 0);
-    env->mp_pattern = mp;
-    if (env->big) {
-        env->bigk = dcomp::big_kernels_for_upad(env->upad);
-        if (!env->bigk.fn[0][0][0]) { delete env; return fail(DCOMP_EUNSUPPORTED, "no generic kernel for %d lanes per env", env->upad); }
-        env->big_step = DYN ? 2 : 0;
-        env->fused_big = !DYN && !getenv("DCOMP_NO_FUSED_BIG");                               // UE arrival / departure (round 6: the generic kernel has the event phase too)
-        if ((size_t)dcomp::big_carve(B, env->bigk.gpb, env->bigk.block).total > 160 * 1024) {
-            delete env;
-            return fail(DCOMP_EINVAL, "%d UE slots x %d stations do not fit one workgroup's LDS (generic kernel)", CAP, B);
-        }
-        env->kern = dcomp::KernelPair{nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-        env->grid = (E + env->bigk.gpb - 1) / env->bigk.gpb;
-    } else {
-        env->kern = dcomp::lookup_kernels(B, env->upad, mp);
-        if (!env->kern.step) { delete env; return fail(DCOMP_EUNSUPPORTED, "no kernel built for num_bs=%d (built: " DCOMP_B_LIST_STR ")", B); }
-        // the wide kernel (UPAD >= 64) always uses 256-thread workgroups; the others DCOMP_BLOCK
-        const int gpb = DCOMP_BLOCK >= env->upad ? DCOMP_BLOCK / env->upad : 1;
-        env->grid = (E + gpb - 1) / gpb;
-    }
-    env->time = 0;
-    env->episode = -1;
-
+// KParams' constant part: shape, seeds, the channel constants, the station table.  Refuses a host whose libm / sqrt would not
+// reproduce the reference's range decision or the kernels' closed form of qmax.
+static int fill_constants(dcomp_env *env, const dcomp_cfg *cfg, const std::vector<UeCfg> &uc)
+{
+    const int U = cfg->num_ue, B = cfg->num_bs;
     KParams &kp = env->kp;
     std::memset(&kp, 0, sizeof(kp));
-    kp.E = E; kp.U = CAP; kp.U0 = U; kp.cur_ue = U; kp.tape_ids = U;
+    kp.E = cfg->num_envs; kp.U = env->cap; kp.U0 = U; kp.cur_ue = U; kp.tape_ids = U;
     kp.map_w = cfg->map_w; kp.map_h = cfg->map_h;
     kp.kind = cfg->env_kind; kp.reward_agg = cfg->reward_agg; kp.rng_mode = cfg->rng_mode;
     kp.tape_depth = cfg->tape_depth;
     kp.seed_lo = (uint32_t)cfg->seed; kp.seed_hi = (uint32_t)(cfg->seed >> 32);
     kp.env_base = (uint32_t)cfg->env_id_base;
-    {   // snr = K * (d + eps)^(-gamma): gamma = c2/10, K = snr(1 m)   (station.py:110-127)
-        double c2 = 44.9 - 6.55 * std::log10(50.0);
-        {   // the same two constants as ref_snr, for the kernel's FP64 max-cap rate key
-            const double f = 2500.0, hb = 50.0, hu = 1.5;
-            const double ch = 0.8 + (1.1 * std::log10(f) - 0.7) * hu - 1.56 * std::log10(f);
-            kp.pl_c1 = 69.55 + 26.16 * std::log10(f) - 13.82 * std::log10(hb) - ch;
-            kp.pl_c2 = c2;
-        }
-        kp.half_gamma = (float)(c2 / 20.0);
-        kp.log2k = (float)(std::log2(ref_snr(1.0)) + (double)dcomp::L2_OFF);
-        kp.log2k_s = (float)(std::log2(ref_snr(1.0)) + (double)dcomp::L2_OFF - 12.0 * (c2 / 20.0));
-        kp.dt2 = dcomp_connect_boundary_sq();       // X: q < X  <=>  snr(sqrt(q)) > 2e-8 in the reference's own arithmetic
-        {   // the kernels decide on a FUSED d^2 and redo a pair in the reference's form when (float)fused == (float)X (dcomp_device.h, dist_sq_ref):
-            // sound iff every double within 4 ulp of X has the float image of X -- else every pair takes the reference form
-            kp.dt2f = (float)kp.dt2;
-            double lo = kp.dt2, hi = kp.dt2;
-            for (int k = 0; k < 4; k++) { lo = std::nextafter(lo, 0.0); hi = std::nextafter(hi, INFINITY); }
-            kp.dsq_exact = ((float)lo == kp.dt2f && (float)hi == kp.dt2f) ? 0u : 1u;
-            if (getenv("DCOMP_DSQ_EXACT") && atoi(getenv("DCOMP_DSQ_EXACT")) != 0) kp.dsq_exact = 1u;      // tests: the always-exact path
-        }
-        if (!(kp.dt2 > 0.0)) { delete env; return fail(DCOMP_EUNSUPPORTED, "the host's log10 / pow make snr(d) non-monotone around the connect threshold: d < d_T would not be the reference's decision"); }
-    }
+    // snr = K * (d + eps)^(-gamma): gamma = c2/10, K = snr(1 m)   (station.py:110-127); c1 / c2 also feed the kernel's FP64 max-cap rate key
+    const PathLoss pl = path_loss();
+    kp.pl_c1 = pl.c1; kp.pl_c2 = pl.c2;
+    kp.half_gamma = (float)(pl.c2 / 20.0);
+    kp.log2k = (float)(std::log2(ref_snr(1.0)) + (double)dcomp::L2_OFF);
+    kp.log2k_s = (float)(std::log2(ref_snr(1.0)) + (double)dcomp::L2_OFF - 12.0 * (pl.c2 / 20.0));
+    kp.dt2 = dcomp_connect_boundary_sq();       // X: q < X  <=>  snr(sqrt(q)) > 2e-8 in the reference's own arithmetic
+    if (!(kp.dt2 > 0.0)) return fail(DCOMP_EUNSUPPORTED, "the host's log10 / pow make snr(d) non-monotone around the connect threshold: d < d_T would not be the reference's decision");
+    // the kernels decide on a FUSED d^2 and redo a pair in the reference's form when (float)fused == (float)X (dcomp_device.h, dist_sq_ref):
+    // sound iff every double within 4 ulp of X has the float image of X -- else every pair takes the reference form
+    kp.dt2f = (float)kp.dt2;
+    double lo = kp.dt2, hi = kp.dt2;
+    for (int k = 0; k < 4; k++) { lo = std::nextafter(lo, 0.0); hi = std::nextafter(hi, INFINITY); }
+    kp.dsq_exact = ((float)lo == kp.dt2f && (float)hi == kp.dt2f) ? 0u : 1u;
+    if (env->ovr.dsq_exact.set && env->ovr.dsq_exact.v != 0) kp.dsq_exact = 1u;      // tests: the always-exact path
     for (unsigned v = 0; v < 256; v++) {
         // the kernel's closed form of qmax(v) = max{q : sqrt_rn(q) <= v} (move_ue) against brute force
         double q = (double)(v * v);
@@ -291,141 +274,211 @@ extern "C" int dcomp_create_v(int32_t abi_version, size_t cfg_size, size_t state
             int e2 = 2 * (31 - __builtin_clz(v));
             if (v * v < (2u << e2)) cf += std::ldexp(1.0, e2 - 52);
         }
-        if (cf != q) { delete env; return fail(DCOMP_EUNSUPPORTED, "host sqrt is not IEEE-correct: qmax(%u) mismatch", v); }
+        if (cf != q) return fail(DCOMP_EUNSUPPORTED, "host sqrt is not IEEE-correct: qmax(%u) mismatch", v);
     }
-    kp.any_maxcap = 0;
     for (int b = 0; b < B; b++) {
-        int m = cfg->bs_sharing[b];
-        if (m < 0 || m > 3) { delete env; return fail(DCOMP_EINVAL, "bs_sharing[%d]=%d not supported", b, m); }   // station.py:22
+        const int m = cfg->bs_sharing[b];
         if (b < DCOMP_MASK32_MAX_BS) { kp.bs_x[b] = cfg->bs_x[b]; kp.bs_y[b] = cfg->bs_y[b]; kp.bs_mode[b] = m; }
         if (m == DCOMP_MAX_CAP) { kp.any_maxcap = 1; if (b < 32) kp.maxcap_mask |= 1u << b; env->bigp.maxcap_mask |= 1ull << b; }
         if (m == DCOMP_RATE_FAIR || m == DCOMP_PROP_FAIR) { kp.any_sum_mode = 1; env->bigp.summode_mask |= 1ull << b; }
     }
-    std::vector<UeCfg> uc(U);
+    env->bigp.B = B;
     kp.all_log_util = 1;
-    for (int u = 0; u < U; u++) {
+    for (const UeCfg &c : uc) if (c.util != DCOMP_UTIL_LOG) kp.all_log_util = 0;
+    return DCOMP_OK;
+}
+
+// The per-UE tables the kernels read from device memory, checked entry by entry while they are built (on the host).  uc: the UE's
+// configuration.  vq: {v, qmax(v)} of UEs whose fixed velocity is no integer in 0..255 (movement.py:116-117 / 142-156), qmax(v) = largest
+// double q with sqrt_rn(q) <= v -- `distance <= velocity` without a square root, as for the integers; empty when there is no such UE.
+static int ue_tables(const dcomp_cfg *cfg, std::vector<UeCfg> &uc, std::vector<double> &vq)
+{
+    for (int u = 0; u < cfg->num_ue; u++) {
+        const int lo = cfg->ue_vel_lo[u], hi = cfg->ue_vel_hi[u];
+        if (lo < 0 || hi < lo || hi > 255) return fail(DCOMP_EINVAL, "ue %d: velocity range [%d,%d] invalid", u, lo, hi);
         UeCfg c;
         std::memset(&c, 0, sizeof(c));
-        int lo = cfg->ue_vel_lo[u], hi = cfg->ue_vel_hi[u];
-        if (lo < 0 || hi < lo || hi > 255) { delete env; return fail(DCOMP_EINVAL, "ue %d: velocity range [%d,%d] invalid", u, lo, hi); }
         c.vel_lo = (uint8_t)lo; c.vel_hi = (uint8_t)hi;
         c.init_x = cfg->ue_init_x ? (int16_t)cfg->ue_init_x[u] : (int16_t)-1;
         c.init_y = cfg->ue_init_y ? (int16_t)cfg->ue_init_y[u] : (int16_t)-1;
         c.util = cfg->ue_util ? (uint8_t)cfg->ue_util[u] : (uint8_t)DCOMP_UTIL_LOG;
-        if (c.util > DCOMP_UTIL_STEP) { delete env; return fail(DCOMP_EUNSUPPORTED, "ue %d: utility %d not implemented", u, (int)c.util); }   // user.py:92
-        if (c.util != DCOMP_UTIL_LOG) kp.all_log_util = 0;
+        if (c.util > DCOMP_UTIL_STEP) return fail(DCOMP_EUNSUPPORTED, "ue %d: utility %d not implemented", u, (int)c.util);   // user.py:92
         c.dr_req = cfg->ue_dr_req ? cfg->ue_dr_req[u] : 1.0f;
         c.pause = (uint8_t)(cfg->ue_pause_duration ? cfg->ue_pause_duration[u] : 2);
         c.border = (uint8_t)(cfg->ue_border_buffer ? cfg->ue_border_buffer[u] : 10);
-        uc[u] = c;
+        uc.push_back(c);
+        const double v = cfg->ue_velocity ? cfg->ue_velocity[u] : -1.0;
+        if (!(v >= 0.0)) continue;
+        if (!std::isfinite(v) || v > 1e6) return fail(DCOMP_EINVAL, "ue %d: velocity %g out of range", u, v);
+        if (lo != hi) return fail(DCOMP_EINVAL, "ue %d: ue_velocity needs a fixed range (lo == hi)", u);
+        double q = v * v;
+        while (q > 0.0 && std::sqrt(q) > v) q = std::nextafter(q, 0.0);
+        while (std::sqrt(std::nextafter(q, INFINITY)) <= v) q = std::nextafter(q, INFINITY);
+        if (vq.empty()) vq.assign(2 * (size_t)cfg->num_ue, -1.0);
+        vq[2 * u] = v; vq[2 * u + 1] = q;
     }
-    hipError_t e = hipSetDevice(cfg->device);
-    if (e == hipSuccess) e = hipMalloc((void **)&env->d_ue_cfg, sizeof(UeCfg) * U);
-    if (e == hipSuccess) e = hipMemcpy(env->d_ue_cfg, uc.data(), sizeof(UeCfg) * U, hipMemcpyHostToDevice);
-    if (e != hipSuccess) { delete env; return fail(DCOMP_EHIP, "device setup failed: %s", hipGetErrorString(e)); }
-    kp.ue_cfg = env->d_ue_cfg;
-    if (env->big) {
-        std::vector<double> xy(2 * (size_t)B);
-        std::vector<int32_t> md(B);
-        for (int b = 0; b < B; b++) { xy[2 * b] = cfg->bs_x[b]; xy[2 * b + 1] = cfg->bs_y[b]; md[b] = cfg->bs_sharing[b]; }
-        e = hipMalloc((void **)&env->d_bs, sizeof(double) * 2 * B);
-        if (e == hipSuccess) e = hipMalloc((void **)&env->d_mode, sizeof(int32_t) * B);
-        if (e == hipSuccess) e = hipMemcpy(env->d_bs, xy.data(), sizeof(double) * 2 * B, hipMemcpyHostToDevice);
-        if (e == hipSuccess) e = hipMemcpy(env->d_mode, md.data(), sizeof(int32_t) * B, hipMemcpyHostToDevice);
-        env->big_lds = (size_t)dcomp::big_carve(B, env->bigk.gpb, env->bigk.block).total;
-        for (int pol = 0; pol < 2; pol++)
-            for (int c = 0; c < 2; c++)
-                for (int w = 0; w < 3; w++)                        // the step this env launches (plain or with events), the reset, the fused rollout
-                    if (e == hipSuccess) e = raise_lds_limit(reinterpret_cast<const void *>(env->bigk.fn[pol][c][w == 0 ? env->big_step : w == 1 ? 1 : 3]), (int)env->big_lds);
-        if (e != hipSuccess) { dcomp_destroy(env); return fail(DCOMP_EHIP, "device setup failed (generic kernel, %zu bytes of LDS per workgroup): %s", env->big_lds, hipGetErrorString(e)); }
-        env->bigp.bs = env->d_bs; env->bigp.mode = env->d_mode; env->bigp.B = B;
+    return DCOMP_OK;
+}
+
+// Which kernels this handle launches, with which grid, block and LDS -- the only place that decides it (needs kp.any_maxcap).
+static int make_plan(dcomp_env *env)
+{
+    const dcomp_cfg &cfg = env->cfg;
+    const Overrides &ovr = env->ovr;
+    LaunchPlan &pl = env->plan;
+    const int E = cfg.num_envs, B = cfg.num_bs, CAP = env->cap;
+    const bool DYN = env->dyn, central = cfg.env_kind == DCOMP_CENTRAL;
+    const double row_bytes = (double)E * CAP * row_floats(cfg.env_kind, B) * 4.0;     // one step's observation rows
+    pl.lanes = env->upad;
+    const long l2 = ovr.fused_row_limit_log2.v;                    // (tests: the one-launch-per-step fallback without a 2^31-row fragment)
+    pl.row_limit = (uint64_t)1 << (ovr.fused_row_limit_log2.set && l2 >= 1 && l2 <= 31 ? l2 : 31);
+    // More than 32 stations: the generic kernel (dcomp_big.h; one instantiation per lane width, B a run-time value, connection set in two
+    // state words).  DCOMP_FORCE_BIG=1 sends smaller station counts there too (tests: generic against specialised kernels).
+    if (B > DCOMP_MASK32_MAX_BS || CAP > DCOMP_SPECIAL_MAX_UE || (ovr.force_big.set && ovr.force_big.v != 0)) {
+        pl.path = StepPath::Generic;
+        pl.big = dcomp::big_kernels_for_upad(env->upad);
+        if (!pl.big.fn[0][0][0]) return fail(DCOMP_EUNSUPPORTED, "no generic kernel for %d lanes per env", env->upad);
+        pl.big_step = DYN ? 2 : 0;
+        if (!DYN && !ovr.no_fused_big.set) pl.fuse = Fuse::Stretch;   // (the fused rollout steps a fixed UE list)
+        pl.block = pl.big.block;
+        pl.grid = (E + pl.big.gpb - 1) / pl.big.gpb;
+        pl.lds = (size_t)dcomp::big_carve(B, pl.big.gpb, pl.big.block).total;
+        if (pl.lds > 160 * 1024) return fail(DCOMP_EINVAL, "%d UE slots x %d stations do not fit one workgroup's LDS (generic kernel)", CAP, B);
         // multi-agent rows of more than 32 stations: one 16-byte store per lane and row (dcomp_big.h, row loop) once a step's rows no longer sit in
         // the Infinity Cache (measured at 32 x 64: 2 048 envs = 67 MB 41.4 -> 43.1 us, 8 192 = 270 MB 63.9 -> 62.5, 16 384 = 539 MB 196 -> 145,
         // 65 536 = 2.2 GB 693 -> 495); DCOMP_BIG_ROW_X4=0 / 1 forces the four-block form / the 16-byte form
-        env->bigp.row_x4 = getenv("DCOMP_BIG_ROW_X4") ? atoi(getenv("DCOMP_BIG_ROW_X4")) : ((size_t)E * CAP * (4 * B + 1) * 4 >= ((size_t)128 << 20) ? 1 : 0);
+        env->bigp.row_x4 = ovr.big_row_x4.set ? (int32_t)ovr.big_row_x4.v
+                                              : ((size_t)E * CAP * row_floats(DCOMP_MULTI, B) * 4 >= ((size_t)128 << 20) ? 1 : 0);
+        return DCOMP_OK;
     }
-    if (cfg->ue_velocity) {
-        // movement.py:116-117 / 142-156 with a velocity that is no integer in 0..255: the device takes {v, qmax(v)} from a table,
-        // qmax(v) = largest double q with sqrt_rn(q) <= v -- `distance <= velocity` without a square root, as for the integers
-        std::vector<double> vq(2 * (size_t)U, -1.0);
-        bool any = false;
-        for (int u = 0; u < U; u++) {
-            const double v = cfg->ue_velocity[u];
-            if (!(v >= 0.0)) continue;
-            if (!std::isfinite(v) || v > 1e6) { dcomp_destroy(env); return fail(DCOMP_EINVAL, "ue %d: velocity %g out of range", u, v); }
-            if (cfg->ue_vel_lo[u] != cfg->ue_vel_hi[u]) { dcomp_destroy(env); return fail(DCOMP_EINVAL, "ue %d: ue_velocity needs a fixed range (lo == hi)", u); }
-            double q = v * v;
-            while (q > 0.0 && std::sqrt(q) > v) q = std::nextafter(q, 0.0);
-            while (std::sqrt(std::nextafter(q, INFINITY)) <= v) q = std::nextafter(q, INFINITY);
-            vq[2 * u] = v; vq[2 * u + 1] = q;
-            any = true;
-        }
-        if (any) {
-            e = hipMalloc((void **)&env->d_ue_velq, sizeof(double) * 2 * U);
-            if (e == hipSuccess) e = hipMemcpy(env->d_ue_velq, vq.data(), sizeof(double) * 2 * U, hipMemcpyHostToDevice);
-            if (e != hipSuccess) { dcomp_destroy(env); return fail(DCOMP_EHIP, "device setup failed: %s", hipGetErrorString(e)); }
-            kp.ue_velq = env->d_ue_velq;
-        }
+    env->mp_pattern = dcomp::MP_RES_FAIR;      // sharing pattern -> specialised kernel (dcomp_device.h bs_mode_of)
+    for (int b = 0; b < B; b++) if (env->kp.bs_mode[b] != DCOMP_RES_FAIR) env->mp_pattern = dcomp::MP_MIXED;
+    static const int cyc[3] = {DCOMP_RES_FAIR, DCOMP_RATE_FAIR, DCOMP_PROP_FAIR};   // env_setup.py:40-49
+    for (int b = 0; b < B && env->mp_pattern != dcomp::MP_RES_FAIR; b++) if (env->kp.bs_mode[b] != cyc[b % 3]) env->mp_pattern = dcomp::MP_GENERIC;
+    const dcomp::KernelPair k = dcomp::lookup_kernels(B, env->upad, env->mp_pattern);
+    if (!k.step) return fail(DCOMP_EUNSUPPORTED, "no kernel built for num_bs=%d (built: " DCOMP_B_LIST_STR ")", B);
+    // the wide kernel (UPAD >= 64) always uses 256-thread workgroups; the others DCOMP_BLOCK
+    const int gpb = DCOMP_BLOCK >= env->upad ? DCOMP_BLOCK / env->upad : 1;
+    pl.grid = (E + gpb - 1) / gpb;
+    pl.reset = k.reset; pl.step = k.step;
+    if (DYN) {                                                    // one launch per step, padded lane groups
+        if (!k.step_dyn) return fail(DCOMP_EUNSUPPORTED, "no dynamic-UE kernel for this shape");
+        pl.path = StepPath::Dyn; pl.step = k.step_dyn;
+        return DCOMP_OK;
     }
-    if (!env->big && env->kern.step_wide && !kp.any_maxcap && !getenv("DCOMP_NO_WIDE")) {
-        env->kern.step = env->kern.step_wide;                                                       // one workgroup per slot
+    if (k.step_wide && !env->kp.any_maxcap) {
+        pl.path = StepPath::Wide; pl.step = k.step_wide;         // one workgroup per slot
         // Batches whose observation rows are >= 1 GB per step -- four times the Infinity Cache: every byte goes out at the sustained HBM
         // write rate -- run with TWO workgroups per CU instead of the four the kernel's 39.8 KB of LDS allow (24 000 B of unused dynamic
         // LDS per workgroup): 16 384 x 128 x 32 252-272 -> 251 us, 32 768 envs 517 -> 477 us (0.60 -> 0.65 of the HBM peak), repeatably;
         // at 8 192 envs (0.54 GB) the same cap costs 6 %, at 4 096 envs (inside the cache) 25 %.  Fewer waves writing at once stream better.
-        const double row_bytes = (double)E * CAP * (cfg->env_kind == DCOMP_MULTI ? 4 * B + 1 : 2 * B + 1) * 4.0;
         // Between 0.4 and 1 GB three per CU (13 000 B) are the best of the three: 8 192 envs 141 -> 134 us, 6 144 envs 101.5 -> 98.5 us.
-        env->wide_pad_lds = row_bytes >= 1.0e9 ? 24000 : row_bytes >= 4.0e8 ? 13000 : 0;
-        if (const char *e = getenv("DCOMP_WIDE_PAD_LDS")) env->wide_pad_lds = atoi(e);                 // A/B
+        pl.lds = row_bytes >= 1.0e9 ? 24000 : row_bytes >= 4.0e8 ? 13000 : 0;
+        if (ovr.wide_pad_lds.set) pl.lds = (size_t)(int)ovr.wide_pad_lds.v;                         // A/B
+        return DCOMP_OK;                                          // never fused, never tight
     }
-    if (DYN && !env->big) {
-        if (!env->kern.step_dyn) { dcomp_destroy(env); return fail(DCOMP_EUNSUPPORTED, "no dynamic-UE kernel for this shape"); }
-        env->kern.step = env->kern.step_dyn;
-    }
-    {
-        // The fused rollout kernel is the LATENCY-optimised variant (state in registers, no LDS staging, no kernel boundaries):
-        // it wins while the grid leaves the SIMDs under-occupied (4 096 x 10 x 5: one wave per SIMD, 2.2 vs 5.3 us per step).  A
-        // grid of many waves per SIMD is throughput-bound: there the plain step kernel (fewer registers, coalesced staged
-        // stores) launched once per step is faster and launch latency hides behind the running kernel.
-        long max_waves = 3 * 1024;                                   // 3 waves per SIMD of the 256 CUs: what the rollout kernel's ~136 VGPRs leave room for
-                                                                     // (a fourth wave per SIMD would wait for a second round)
-        if (const char *e = getenv("DCOMP_FUSE_MAX_WAVES")) max_waves = atol(e);
-        const long waves = (long)env->grid * (DCOMP_BLOCK / 64);
-        env->fused = !DYN && !env->big && env->kern.step != env->kern.step_wide && env->kern.rollout != nullptr && waves <= max_waves;
-        // Central envs with short rows (2B + 1 <= 17 floats per UE) are faster through the fused kernel at EVERY batch size once a
-        // rollout is a few steps long: no kernel boundary (5.4 us per launch, a quarter of a 65 536 x 10 x 5 step), no state round
-        // trip, pairs carried from step to step -- 65 536 x 10 x 5: 16.3 vs 19-20 us per step, 16 384: 4.2 vs 11.2, 262 144: 58 vs
-        // 63 (T = 50).  Rows of the multi-agent layout (4B + 1 floats per lane, stored straight from registers) stream too
-        // badly for that: 65 536 x 32 x 10: 129 vs 77 us.
-        // Multi-agent rows (4B + 1 floats per lane) are short enough up to three stations -- the reference's stock small and medium
-        // maps: 65 536 x 5 x 3 multi 8.1 vs 12.1 us per step (T = 50); at 10 x 5 it is a draw (23.4 vs 23.3), at 16 x 8 a loss (51.8 vs 38.2).
-        env->fused_long = !DYN && !env->big && env->kern.step != env->kern.step_wide && env->kern.rollout != nullptr &&
-                          ((cfg->env_kind == DCOMP_CENTRAL && B <= 8) || (cfg->env_kind == DCOMP_MULTI && B <= 3)) && !getenv("DCOMP_NO_FUSED_LONG");
-        // Tight packing of UE lists whose length is not a power of two (dcomp_device.h, struct Seg): G = U lanes per env,
-        // 64 / G envs per wavefront, segmented ds_bpermute reductions (~13 instead of 4 instructions each).  It pays where the
-        // launch is throughput-bound and the padding wastes many lanes: >= 4 padded waves per SIMD and >= 1.4x the lanes in use
-        // (U = 5, 9, 10, 17-21; measured: 10 x 5 central +10 %, 20 x 10 multi +8 %, 5 x 3 central +14 %, but 12 x 7 multi -2 % at 1.25x).
-        // Not with max-cap BSs (their LDS scratch is indexed by padded env slots), not for UE lists that change.
-        env->tight_g = 0;
-        const int U1 = CAP;
-        if (!DYN && env->kern.step_tight && U1 >= 3 && (U1 & (U1 - 1)) != 0 && !kp.any_maxcap && env->kern.step != env->kern.step_wide) {
-            const int gpw = 64 / U1;
-            const double padded_use = (double)U1 / env->upad, tight_use = (double)(gpw * U1) / 64.0;
-            int want = waves >= 4 * 1024 && tight_use >= 1.4 * padded_use;     // (never together with the fused rollout: <= 3 * 1024 waves)
-            if (const char *e = getenv("DCOMP_TIGHT")) want = atoi(e) != 0;       // tests / A-B: force on or off
-            if (want) {
-                const int magic = 65536 / U1 + 1;
-                bool ok = true;
-                for (int l = 0; l < 64; l++) if (((l * magic) >> 16) != l / U1) ok = false;
-                if (ok) {
-                    env->tight_g = U1; env->tight_gpw = gpw; env->tight_magic = magic;
-                    const int epb = gpw * (DCOMP_BLOCK / 64);
-                    env->tight_grid = (E + epb - 1) / epb;
-                }
-            }
-        }
-    }
-    *out = env;
+    // The fused rollout kernel is the LATENCY-optimised variant (state in registers, no LDS staging, no kernel boundaries):
+    // it wins while the grid leaves the SIMDs under-occupied (4 096 x 10 x 5: one wave per SIMD, 2.2 vs 5.3 us per step).  A
+    // grid of many waves per SIMD is throughput-bound: there the plain step kernel (fewer registers, coalesced staged
+    // stores) launched once per step is faster and launch latency hides behind the running kernel.
+    // 3 waves per SIMD of the 256 CUs: what the rollout kernel's ~136 VGPRs leave room for (a fourth would wait for a second round)
+    const long max_waves = ovr.fuse_max_waves.set ? ovr.fuse_max_waves.v : 3 * 1024;
+    const long waves = (long)pl.grid * (DCOMP_BLOCK / 64);
+    // Central envs with short rows (2B + 1 <= 17 floats per UE) are faster through the fused kernel at EVERY batch size once a
+    // rollout is a few steps long: no kernel boundary (5.4 us per launch, a quarter of a 65 536 x 10 x 5 step), no state round
+    // trip, pairs carried from step to step -- 65 536 x 10 x 5: 16.3 vs 19-20 us per step, 16 384: 4.2 vs 11.2, 262 144: 58 vs
+    // 63 (T = 50).  Rows of the multi-agent layout (4B + 1 floats per lane, stored straight from registers) stream too
+    // badly for that: 65 536 x 32 x 10: 129 vs 77 us.
+    // Multi-agent rows (4B + 1 floats per lane) are short enough up to three stations -- the reference's stock small and medium
+    // maps: 65 536 x 5 x 3 multi 8.1 vs 12.1 us per step (T = 50); at 10 x 5 it is a draw (23.4 vs 23.3), at 16 x 8 a loss (51.8 vs 38.2).
+    if (k.rollout && waves <= max_waves) pl.fuse = Fuse::Always;
+    else if (k.rollout && (central ? B <= 8 : B <= 3)) pl.fuse = Fuse::Long;
+    // with a registered policy: the variant that carries the rules; tape-driven central envs: the central-only instantiation
+    pl.rollout = (central && k.rollout_central) ? k.rollout_central : k.rollout;
+    pl.rollout_pol = k.rollout_pol;
+    // Tight packing of UE lists whose length is not a power of two (dcomp_device.h, struct Seg): G = U lanes per env,
+    // 64 / G envs per wavefront, segmented ds_bpermute reductions (~13 instead of 4 instructions each).  It pays where the
+    // launch is throughput-bound and the padding wastes many lanes: >= 4 padded waves per SIMD and >= 1.4x the lanes in use
+    // (U = 5, 9, 10, 17-21; measured: 10 x 5 central +10 %, 20 x 10 multi +8 %, 5 x 3 central +14 %, but 12 x 7 multi -2 % at 1.25x).
+    // Not with max-cap BSs (their LDS scratch is indexed by padded env slots), not for UE lists that change.
+    const int G = CAP, gpw = 64 / G, magic = 65536 / G + 1;
+    if (!k.step_tight || G < 3 || (G & (G - 1)) == 0 || env->kp.any_maxcap) return DCOMP_OK;
+    const double padded_use = (double)G / env->upad, tight_use = (double)(gpw * G) / 64.0;
+    bool want = waves >= 4 * 1024 && tight_use >= 1.4 * padded_use;   // (by itself never together with Fuse::Always: <= 3 * 1024 waves)
+    if (ovr.tight.set) want = ovr.tight.v != 0;                       // tests / A-B: force on or off
+    for (int l = 0; l < 64; l++) if (((l * magic) >> 16) != l / G) want = false;   // (the kernels divide lane indices by G with this multiplier)
+    if (!want) return DCOMP_OK;
+    pl.path = StepPath::Tight;
+    pl.tight_central = central && k.tight_central;
+    pl.step = pl.tight_central ? k.tight_central : k.step_tight;
+    pl.lanes = pl.tight_g = G; pl.tight_gpw = gpw; pl.tight_magic = magic;
+    pl.tight_grid = (E + gpw * (DCOMP_BLOCK / 64) - 1) / (gpw * (DCOMP_BLOCK / 64));   // gpw envs per wavefront
+    // A batch packed tightly for dcomp_step (throughput-bound: >= 4 padded waves per SIMD, >= 1.4x the lanes in use) runs
+    // its tape-driven central rollouts tightly packed too: the fused kernel is bound by its VALU work there, and a third fewer
+    // waves do the same steps (65 536 x 10 x 5: six envs per wavefront instead of four).  Same packing, same summation order as
+    // dcomp_step uses for this env.
+    if (central && k.rollout_tight_central) { pl.rollout = k.rollout_tight_central; pl.rollout_tight = true; }
+    return DCOMP_OK;
+}
+
+static hipError_t upload(void **dst, const void *src, size_t bytes)
+{
+    hipError_t e = hipMalloc(dst, bytes);
+    return e == hipSuccess ? hipMemcpy(*dst, src, bytes, hipMemcpyHostToDevice) : e;
+}
+// The handle's device tables; with the generic kernel also its station table and the LDS limit of the kernels the plan launches.
+static int upload_tables(dcomp_env *env, const dcomp_cfg *cfg, const std::vector<UeCfg> &uc, const std::vector<double> &vq)
+{
+    const int U = cfg->num_ue, B = cfg->num_bs;
+    hipError_t e = hipSetDevice(cfg->device);
+    if (e == hipSuccess) e = upload((void **)&env->d_ue_cfg, uc.data(), sizeof(UeCfg) * U);
+    if (e == hipSuccess && !vq.empty()) e = upload((void **)&env->d_ue_velq, vq.data(), sizeof(double) * 2 * U);
+    if (e != hipSuccess) return fail(DCOMP_EHIP, "device setup failed: %s", hipGetErrorString(e));
+    env->kp.ue_cfg = env->d_ue_cfg; env->kp.ue_velq = env->d_ue_velq;
+    if (env->plan.path != StepPath::Generic) return DCOMP_OK;
+    const LaunchPlan &pl = env->plan;
+    std::vector<double> xy(2 * (size_t)B);
+    std::vector<int32_t> md(B);
+    for (int b = 0; b < B; b++) { xy[2 * b] = cfg->bs_x[b]; xy[2 * b + 1] = cfg->bs_y[b]; md[b] = cfg->bs_sharing[b]; }
+    e = upload((void **)&env->d_bs, xy.data(), sizeof(double) * 2 * B);
+    if (e == hipSuccess) e = upload((void **)&env->d_mode, md.data(), sizeof(int32_t) * B);
+    for (int pol = 0; pol < 2; pol++)
+        for (int c = 0; c < 2; c++)
+            for (int w : {pl.big_step, 1, 3})                      // the step this env launches (plain or with events), the reset, the fused rollout
+                if (e == hipSuccess) e = raise_lds_limit(reinterpret_cast<const void *>(pl.big.fn[pol][c][w]), (int)pl.lds);
+    if (e != hipSuccess) return fail(DCOMP_EHIP, "device setup failed (generic kernel, %zu bytes of LDS per workgroup): %s", pl.lds, hipGetErrorString(e));
+    env->bigp.bs = env->d_bs; env->bigp.mode = env->d_mode;
+    return DCOMP_OK;
+}
+
+extern "C" int dcomp_create_v(int32_t abi_version, size_t cfg_size, size_t state_size, size_t out_size, size_t rollout_opts_size,
+                              const dcomp_cfg *cfg, dcomp_env **out)
+{
+    if (out) *out = nullptr;
+    if (abi_version != DCOMP_ABI_VERSION || cfg_size != sizeof(dcomp_cfg) || state_size != sizeof(dcomp_state) || out_size != sizeof(dcomp_out) ||
+        rollout_opts_size != sizeof(dcomp_rollout_opts))
+        return fail(DCOMP_EABI, "ABI mismatch: caller has version %d, sizeof dcomp_cfg / dcomp_state / dcomp_out / dcomp_rollout_opts = %zu / %zu / %zu / %zu; "
+                                "this library has version %d and %zu / %zu / %zu / %zu", (int)abi_version, cfg_size, state_size, out_size, rollout_opts_size,
+                    DCOMP_ABI_VERSION, sizeof(dcomp_cfg), sizeof(dcomp_state), sizeof(dcomp_out), sizeof(dcomp_rollout_opts));
+    if (!cfg || !out) return fail(DCOMP_EINVAL, "null argument");
+    std::vector<UeCfg> uc;
+    std::vector<double> vq;
+    int rc = validate_cfg(cfg);
+    if (!rc) rc = ue_tables(cfg, uc, vq);
+    if (rc) return rc;
+    std::unique_ptr<dcomp_env, EnvDeleter> env(new dcomp_env());     // every exit below frees it, device tables included
+    env->cfg = *cfg;
+    env->cfg.bs_x = env->cfg.bs_y = nullptr;   // host arrays are not retained
+    env->cfg.ue_pause_duration = env->cfg.ue_border_buffer = nullptr; env->cfg.ue_velocity = nullptr;
+    env->ovr = read_overrides();
+    env->dyn = cfg->max_ues > 0;               // departures alone need no extra slots: max_ues == num_ue
+    env->cap = env->dyn ? cfg->max_ues : cfg->num_ue;
+    env->cur_ue = cfg->num_ue;
+    env->upad = next_pow2(env->cap) < 4 ? 4 : next_pow2(env->cap);
+    if ((rc = fill_constants(env.get(), cfg, uc))) return rc;
+    if ((rc = make_plan(env.get()))) return rc;
+    if ((rc = upload_tables(env.get(), cfg, uc, vq))) return rc;
+    *out = env.release();
     return DCOMP_OK;
 }
 
@@ -457,41 +510,56 @@ extern "C" int dcomp_state_sizes(const dcomp_env *env, size_t *pos_bytes, size_t
 extern "C" int dcomp_obs_dim(const dcomp_env *env, int32_t *floats_per_env, int32_t *reward_per_env)
 {
     if (!env) return fail(DCOMP_EINVAL, "null env");
-    const int U = env->cap, B = env->cfg.num_bs;
-    if (floats_per_env) *floats_per_env = env->cfg.env_kind == DCOMP_MULTI ? U * (4 * B + 1) : U * (2 * B + 1);
-    if (reward_per_env) *reward_per_env = env->cfg.env_kind == DCOMP_MULTI ? U : 1;
+    if (floats_per_env) *floats_per_env = env->cap * row_floats(env->cfg.env_kind, env->cfg.num_bs);
+    if (reward_per_env) *reward_per_env = env->cfg.env_kind == DCOMP_MULTI ? env->cap : 1;
     return DCOMP_OK;
 }
 
-// The generic kernel's instantiation for this launch: with / without the in-step policy, row format / compact record.
-static dcomp::BigKernelFn big_fn(const dcomp_env *env, const KParams &kp, int which)
+// Every kernel launch of a handle: `which` kernel of its plan, for either kernel family; the instantiation with / without the in-step
+// policy (kp.next_act) and the compact record (kp.obs_compact).  A tightly packed launch gets its packing written into kp.
+static void launch(const dcomp_env *env, Launch which, KParams &kp, void *stream)
 {
-    return env->bigk.fn[kp.next_act ? 1 : 0][kp.obs_compact ? 1 : 0][which];
-}
-
-// One launch of the step kernel (plain step; also the per-step launches of a rollout that is not fused).
-static void launch_step(dcomp_env *env, KParams &kp, void *stream)
-{
-    if (env->big) {
-        hipLaunchKernelGGL(big_fn(env, kp, env->big_step), dim3(env->grid), dim3(env->bigk.block), env->big_lds, (hipStream_t)stream, kp, env->bigp);
+    const LaunchPlan &pl = env->plan;
+    if (pl.path == StepPath::Generic) {
+        const int w = which == Launch::Reset ? 1 : which == Launch::Rollout ? 3 : pl.big_step;
+        hipLaunchKernelGGL(pl.big.fn[kp.next_act ? 1 : 0][kp.obs_compact ? 1 : 0][w], dim3(pl.grid), dim3(pl.block), pl.lds, (hipStream_t)stream, kp, env->bigp);
         return;
     }
-    if (env->tight_g) {
-        kp.tight_g = env->tight_g; kp.tight_gpw = env->tight_gpw; kp.tight_magic = env->tight_magic;
-        const dcomp::KernelFn k = (env->cfg.env_kind == DCOMP_CENTRAL && env->kern.tight_central) ? env->kern.tight_central : env->kern.step_tight;
-        hipLaunchKernelGGL(k, dim3(env->tight_grid), dim3(DCOMP_BLOCK), 0, (hipStream_t)stream, kp);
-        return;
+    dcomp::KernelFn fn = pl.reset;
+    bool tight = false;
+    size_t lds = 0;
+    if (which == Launch::Step) {
+        fn = pl.step;
+        tight = pl.path == StepPath::Tight;
+        // (the wide kernel's occupancy cap is for launches that stream GBs of ROWS; with the compact record a launch is bound by its arithmetic
+        // and wants every wave it can get: 32 768 x 128 x 32 236 us with four workgroups per CU, 369 us with two)
+        if (!kp.obs_compact) lds = pl.lds;
+    } else if (which == Launch::Rollout) {
+        fn = kp.next_act ? pl.rollout_pol : pl.rollout;
+        tight = pl.rollout_tight && !kp.next_act;
     }
-    const bool wide = env->kern.step == env->kern.step_wide;
-    // (the occupancy cap is for launches that stream GBs of ROWS; with the compact record a launch is bound by its arithmetic and wants
-    // every wave it can get: 32 768 x 128 x 32 236 us with four workgroups per CU, 369 us with two)
-    hipLaunchKernelGGL(env->kern.step, dim3(env->grid), dim3(DCOMP_BLOCK), wide && !kp.obs_compact ? env->wide_pad_lds : 0, (hipStream_t)stream, kp);
+    if (tight) { kp.tight_g = pl.tight_g; kp.tight_gpw = pl.tight_gpw; kp.tight_magic = pl.tight_magic; }
+    hipLaunchKernelGGL(fn, dim3(tight ? pl.tight_grid : pl.grid), dim3(pl.block), lds, (hipStream_t)stream, kp);
 }
 
 static int check_horizon(const dcomp_env *env, int steps)
 {
     if (env && (int64_t)env->time + steps > 65536)
         return fail(DCOMP_EUNSUPPORTED, "episodes longer than 65536 steps: conn_since and the draw cursor are 16-bit (reset() first)");
+    return DCOMP_OK;
+}
+
+// One step's departures / arrivals against the `cur` UEs listed before it (base.py:433-443); idx / xy: tape mode's host-drawn list
+// positions / border points.  step >= 0: the step of a rollout, named in the message.
+static int check_events(const dcomp_env *env, int cur, int nrem, int nadd, const void *idx, const void *xy, int step)
+{
+    char at[24] = "";
+    if (step >= 0) std::snprintf(at, sizeof(at), "step %d: ", step);
+    if (nrem < 0 || nadd < 0 || (nrem > 0 && nadd > 0)) return fail(DCOMP_EINVAL, "%sone step either adds or removes UEs (base.py:436-443)", at);
+    if (cur - nrem < 1) return fail(DCOMP_EINVAL, "%scannot remove %d of %d UEs", at, nrem, cur);
+    if (cur + nadd > env->cap) return fail(DCOMP_EINVAL, "%s%d + %d UEs exceed max_ues = %d", at, cur, nadd, env->cap);
+    if (env->cfg.rng_mode == DCOMP_RNG_TAPE && ((nrem && !idx) || (nadd && !xy)))
+        return fail(DCOMP_EINVAL, "tape mode: events need the host-drawn indices / border points");
     return DCOMP_OK;
 }
 
@@ -505,7 +573,7 @@ static int fill_params(dcomp_env *env, const dcomp_state *st, const dcomp_out *o
         if (env->cfg.env_kind != DCOMP_MULTI) return fail(DCOMP_EINVAL, "out->obs_compact: the compact record is defined for multi-agent observations (central observations carry no per-env columns)");
     }
     if (env->kp.any_maxcap && !st->conn_since) return fail(DCOMP_EINVAL, "a max-cap BS needs state.conn_since (see dcomp_state_sizes)");
-    if (env->big) {
+    if (env->plan.path == StepPath::Generic) {
         if (!st->conn_hi) return fail(DCOMP_EINVAL, "more than %d stations: state.conn_hi (stations 32-63 of the connection set, sized like conn) is required", DCOMP_MASK32_MAX_BS);
         env->bigp.conn_hi = st->conn_hi;
     }
@@ -542,67 +610,60 @@ extern "C" int dcomp_reset(dcomp_env *env, const dcomp_state *st, const dcomp_ta
     env->cur_ue = env->cfg.num_ue; env->n_removed = env->n_arrived = 0;      // base.py:177-182
     kp.cur_ue = env->cur_ue;
     kp.episode = (uint32_t)env->episode;
-    if (env->big) hipLaunchKernelGGL(big_fn(env, kp, 1), dim3(env->grid), dim3(env->bigk.block), env->big_lds, (hipStream_t)stream, kp, env->bigp);
-    else hipLaunchKernelGGL(env->kern.reset, dim3(env->grid), dim3(DCOMP_BLOCK), 0, (hipStream_t)stream, kp);
+    launch(env, Launch::Reset, kp, stream);
     HIP_TRY(hipGetLastError());
     return DCOMP_OK;
 }
 
-extern "C" int dcomp_step(dcomp_env *env, const dcomp_state *st, const uint8_t *action, const dcomp_out *out, void *stream)
-{
-    KParams kp;
-    int rc = fill_params(env, st, out, kp);
-    if (rc) return rc;
-    if (!action) return fail(DCOMP_EINVAL, "null action");
-    if (env->episode < 0) return fail(DCOMP_EINVAL, "step() before reset()");
-    if ((rc = check_horizon(env, 1))) return rc;
-    kp.action = action;
-    kp.n_remove = kp.n_add = 0;
-    launch_step(env, kp, stream);
-    HIP_TRY(hipGetLastError());
-    env->time += 1;
-    return DCOMP_OK;
-}
-
+// One step; ev == NULL (dcomp_step): no UE arrives or leaves.
 extern "C" int dcomp_step_dyn(dcomp_env *env, const dcomp_state *st, const uint8_t *action, const dcomp_out *out,
                               const dcomp_events *ev, void *stream)
 {
-    if (!env) return fail(DCOMP_EINVAL, "null env");
-    if (!env->dyn) {
-        if (ev && (ev->n_remove || ev->n_add)) return fail(DCOMP_EINVAL, "handle was created without max_ues (fixed UE list)");
-        return dcomp_step(env, st, action, out, stream);
-    }
     KParams kp;
     int rc = fill_params(env, st, out, kp);
     if (rc) return rc;
+    if (!env->dyn) {
+        if (ev && (ev->n_remove || ev->n_add)) return fail(DCOMP_EINVAL, "handle was created without max_ues (fixed UE list)");
+        ev = nullptr;
+    }
     if (!action) return fail(DCOMP_EINVAL, "null action");
     if (env->episode < 0) return fail(DCOMP_EINVAL, "step() before reset()");
     if ((rc = check_horizon(env, 1))) return rc;
     const int nrem = ev ? ev->n_remove : 0, nadd = ev ? ev->n_add : 0;
-    if (nrem < 0 || nadd < 0 || (nrem > 0 && nadd > 0)) return fail(DCOMP_EINVAL, "one step either adds or removes UEs (base.py:436-443)");
-    if (env->cur_ue - nrem < 1) return fail(DCOMP_EINVAL, "cannot remove %d of %d UEs", nrem, env->cur_ue);
-    if (env->cur_ue + nadd > env->cap) return fail(DCOMP_EINVAL, "%d + %d UEs exceed max_ues = %d", env->cur_ue, nadd, env->cap);
-    if (env->cfg.rng_mode == DCOMP_RNG_TAPE && ((nrem && !ev->remove_idx) || (nadd && !ev->add_xy)))
-        return fail(DCOMP_EINVAL, "tape mode: events need the host-drawn indices / border points");
+    if (ev && (rc = check_events(env, env->cur_ue, nrem, nadd, ev->remove_idx, ev->add_xy, -1))) return rc;
     kp.action = action;
     kp.n_remove = nrem; kp.n_add = nadd;
     kp.ev_remove = ev ? ev->remove_idx : nullptr; kp.ev_add_xy = ev ? ev->add_xy : nullptr;
     kp.ev_rem_base = env->n_removed; kp.ev_add_base = env->n_arrived;
-    if (env->big) hipLaunchKernelGGL(big_fn(env, kp, env->big_step), dim3(env->grid), dim3(env->bigk.block), env->big_lds, (hipStream_t)stream, kp, env->bigp);
-    else hipLaunchKernelGGL(env->kern.step, dim3(env->grid), dim3(DCOMP_BLOCK), 0, (hipStream_t)stream, kp);
+    launch(env, Launch::Step, kp, stream);
     HIP_TRY(hipGetLastError());
     env->time += 1;
     env->cur_ue += nadd - nrem;
     env->n_removed += (uint32_t)nrem; env->n_arrived += (uint32_t)nadd;
     return DCOMP_OK;
 }
+extern "C" int dcomp_step(dcomp_env *env, const dcomp_state *st, const uint8_t *action, const dcomp_out *out, void *stream)
+{
+    return dcomp_step_dyn(env, st, action, out, nullptr, stream);
+}
 extern "C" int dcomp_num_ue(const dcomp_env *env) { return env ? env->cur_ue : -1; }
 
-// T consecutive steps.  step_kernel runs them in ONE launch (state in registers in between); the wide and the dynamic-UE
-// kernels are launched once per step.  Same results either way, and the same as T dcomp_step / dcomp_step_dyn calls (+
-// dcomp_reset calls at the horizon).
-static int rollout_impl(dcomp_env *env, const dcomp_state *st, const uint8_t *actions, int32_t T, const dcomp_out *out,
-                        const dcomp_rollout_opts *opts, void *stream)
+// Whether a rollout of T steps goes through the plan's fused kernel: fusion of the short-row shapes (Fuse::Long) depends on the number
+// of steps, and an every-step fragment of >= 2^31 rows does not fit the specialised fused kernel, which addresses step t's outputs as
+// (idx + t * E * U) on the caller's base pointers with 32-bit row indices.  Otherwise: one launch per step, same results.
+static bool rollout_fused(const dcomp_env *env, int T, bool every, bool loop)
+{
+    const LaunchPlan &pl = env->plan;
+    if (pl.fuse == Fuse::Stretch) return true;                     // (64-bit offsets: no row limit)
+    if (every && (uint64_t)T * ((uint64_t)env->cfg.num_envs * env->cap) >= pl.row_limit) return false;
+    return pl.fuse == Fuse::Always || (pl.fuse == Fuse::Long && (T >= 4 || loop));
+}
+
+// T consecutive steps, in one of three ways: ONE launch of the fused rollout kernel with the horizon inside it (state in registers in
+// between); one launch of it per stretch of an episode, the reset kernel in between; one launch of the step kernel per step.  Same
+// results either way, and the same as T dcomp_step / dcomp_step_dyn calls (+ dcomp_reset calls at the horizon).
+extern "C" int dcomp_rollout_ex(dcomp_env *env, const dcomp_state *st, const uint8_t *actions, int32_t T, const dcomp_out *out,
+                                const dcomp_rollout_opts *opts, void *stream)
 {
     KParams kp;
     int rc = fill_params(env, st, out, kp);
@@ -612,6 +673,7 @@ static int rollout_impl(dcomp_env *env, const dcomp_state *st, const uint8_t *ac
     const int L = opts ? opts->horizon : 0, every = opts ? (opts->every_step != 0) : 0;
     const uint32_t inc = (opts && opts->new_episode_draws) ? 1u : 0u;
     const int32_t *ev_rem = opts ? opts->ev_n_remove : nullptr, *ev_add = opts ? opts->ev_n_add : nullptr;
+    const int32_t *ev_idx = opts ? opts->ev_remove_idx : nullptr, *ev_xy = opts ? opts->ev_add_xy : nullptr;
     const bool tape = env->cfg.rng_mode == DCOMP_RNG_TAPE;
     if (L < 0 || L > 65536) return fail(DCOMP_EINVAL, "horizon must be 0 (none) .. 65536");
     if (L > 0) {
@@ -622,12 +684,10 @@ static int rollout_impl(dcomp_env *env, const dcomp_state *st, const uint8_t *ac
     } else if ((rc = check_horizon(env, T))) return rc;
     if (!env->dyn && (ev_rem || ev_add)) return fail(DCOMP_EINVAL, "handle was created without max_ues (fixed UE list): no arrival / departure events");
     const bool loop = opts && opts->policy_loop != 0;
-    // (round 6: the closed loop runs on every kernel -- where rollouts are not fused, one launch per step, each reading the actions the
-    //  previous one wrote)
     if (loop && !env->kp.next_act) return fail(DCOMP_EINVAL, "policy_loop needs a policy (dcomp_set_policy)");
     const size_t EU = (size_t)env->cfg.num_envs * env->cap, E = (size_t)env->cfg.num_envs;
     const bool multi = env->cfg.env_kind == DCOMP_MULTI;
-    const size_t obs_step = EU * (size_t)(multi ? 4 * env->cfg.num_bs + 1 : 2 * env->cfg.num_bs + 1);
+    const size_t obs_step = EU * (size_t)row_floats(env->cfg.env_kind, env->cfg.num_bs);
     auto out_slice = [&](KParams &k, int t) {                  // where step t's outputs go
         if (!every) return;
         k.obs = out->obs_compact ? reinterpret_cast<float *>(out->obs_compact) + E * (size_t)dcomp_frag::env_words(env->cap, env->cfg.num_bs) * t
@@ -645,104 +705,54 @@ static int rollout_impl(dcomp_env *env, const dcomp_state *st, const uint8_t *ac
         k.cur_ue = env->cur_ue;
         k.episode = (uint32_t)env->episode;
         k.time = 0u;
-        if (env->big) hipLaunchKernelGGL(big_fn(env, k, 1), dim3(env->grid), dim3(env->bigk.block), env->big_lds, (hipStream_t)stream, k, env->bigp);
-        else hipLaunchKernelGGL(env->kern.reset, dim3(env->grid), dim3(DCOMP_BLOCK), 0, (hipStream_t)stream, k);
+        launch(env, Launch::Reset, k, stream);
     };
     if (env->dyn) {
-        // The whole arrival / departure schedule of the T steps is validated BEFORE the first launch (it used to be checked step by
-        // step inside the loop below: an invalid entry at step t then left the env t steps advanced and the caller's host-side
-        // event streams consumed).  The call either enqueues all T steps or nothing.
+        // The whole schedule is validated BEFORE the first launch: the call enqueues all T steps or nothing (an invalid entry at step t
+        // must not leave the env t steps advanced and the caller's event streams consumed).
         int cur = env->cur_ue, time = env->time;
         for (int t = 0; t < T; t++) {
             if (L > 0 && time == L) { time = 0; cur = env->cfg.num_ue; }
             const int nrem = ev_rem ? ev_rem[t] : 0, nadd = ev_add ? ev_add[t] : 0;
-            if (nrem < 0 || nadd < 0 || (nrem > 0 && nadd > 0)) return fail(DCOMP_EINVAL, "step %d: one step either adds or removes UEs (base.py:436-443)", t);
-            if (cur - nrem < 1) return fail(DCOMP_EINVAL, "step %d: cannot remove %d of %d UEs", t, nrem, cur);
-            if (cur + nadd > env->cap) return fail(DCOMP_EINVAL, "step %d: %d + %d UEs exceed max_ues = %d", t, cur, nadd, env->cap);
-            if (tape && ((nrem && !opts->ev_remove_idx) || (nadd && !opts->ev_add_xy)))
-                return fail(DCOMP_EINVAL, "tape mode: events need the host-drawn indices / border points");
+            if ((rc = check_events(env, cur, nrem, nadd, ev_idx, ev_xy, t))) return rc;
             cur += nadd - nrem;
             time += 1;
         }
     }
-    // the fused kernel addresses step t's outputs as (idx + t * E * U) on the caller's base pointers with 32-bit row indices: a
-    // fragment beyond that takes the one-launch-per-step path below (same results)
-    const bool fits32 = !(every && (uint64_t)T * EU >= fused_row_limit());
-    if (fits32 && (env->fused || (env->fused_long && (T >= 4 || loop)))) {
-        // with a registered policy: the variant that carries the rules; tape-driven central envs: the central-only instantiation
-        dcomp::KernelFn kern = kp.next_act ? env->kern.rollout_pol : (!multi && env->kern.rollout_central) ? env->kern.rollout_central : env->kern.rollout;
-        int grid = env->grid;
-        // A batch dcomp_create packs tightly for dcomp_step (throughput-bound: >= 4 padded waves per SIMD, >= 1.4x the lanes in use) runs
-        // its tape-driven central rollouts tightly packed too: the fused kernel is bound by its VALU work there, and a third fewer
-        // waves do the same steps (65 536 x 10 x 5: six envs per wavefront instead of four).  Same packing, same summation order as
-        // dcomp_step uses for this env.
-        if (env->tight_g && !multi && !kp.next_act && env->kern.rollout_tight_central && !getenv("DCOMP_NO_TIGHT_ROLLOUT")) {
-            kern = env->kern.rollout_tight_central;
-            grid = env->tight_grid;
-            kp.tight_g = env->tight_g; kp.tight_gpw = env->tight_gpw; kp.tight_magic = env->tight_magic;
-        }
-        if (!loop || L == 0 || env->time + T <= L) {
+    // The closed loop: step 0 acts on actions[0] (the next_action the previous launch wrote), every later step -- and the first step of a
+    // new episode, on the reset kernel's observation -- on what the launch before it decided.  next_action is ONE buffer read and written
+    // in place: a lane reads the action of its own slot when the kernel starts and writes the decision for that same slot at its end (with
+    // UE arrival / departure the UEs move between slots through LDS, not through this buffer).
+    const uint8_t *act_src = actions;
+    if (rollout_fused(env, T, every, loop)) {
+        if (env->plan.fuse != Fuse::Stretch && (!loop || L == 0 || env->time + T <= L)) {
             // ONE launch; resets at the horizon of a tape-driven rollout happen inside the kernel
             kp.action = actions; kp.num_steps = T; kp.out_every_step = every; kp.horizon = L; kp.episode_inc = inc; kp.policy_loop = loop;
-            hipLaunchKernelGGL(kern, dim3(grid), dim3(DCOMP_BLOCK), 0, (hipStream_t)stream, kp);
-            int time = env->time;
-            int64_t episode = env->episode;
+            launch(env, Launch::Rollout, kp, stream);
             for (int t = 0; t < T; t++) {
-                if (L > 0 && time == L) { time = 0; episode += tape ? 1 : inc; }
-                time += 1;
+                if (L > 0 && env->time == L) { env->time = 0; env->episode += tape ? 1 : inc; }
+                env->time += 1;
             }
-            env->time = time;
-            env->episode = episode;
         } else {
-            // Closed loop across episode boundaries: one launch per stretch of an episode; at the horizon the reset kernel computes
-            // the first observation of the new episode and the policy's action on it (next_action), which the next stretch starts from.
-            const uint8_t *act_src = actions;
+            // One launch per stretch of an episode (the generic kernel; the specialised one in a closed loop that crosses episode
+            // boundaries); at the horizon the reset kernel, which with a policy also decides the first action of the new episode.
             for (int t = 0; t < T;) {
-                if (env->time == L) {
-                    out_slice(kp, t);
-                    launch_reset(kp);
-                    act_src = kp.next_act;
-                }
-                const int n = T - t < L - env->time ? T - t : L - env->time;
                 out_slice(kp, t);
-                kp.action = act_src; kp.num_steps = n; kp.out_every_step = every; kp.horizon = 0; kp.episode_inc = 0; kp.policy_loop = 1;
+                if (L > 0 && env->time == L) { launch_reset(kp); if (loop) act_src = kp.next_act; }
+                const int n = (L > 0 && L - env->time < T - t) ? L - env->time : T - t;
+                kp.action = loop ? act_src : actions + EU * t;
+                kp.num_steps = n; kp.out_every_step = every; kp.policy_loop = loop; kp.horizon = 0; kp.episode_inc = 0;
                 kp.time = (uint32_t)env->time; kp.episode = (uint32_t)env->episode;
-                hipLaunchKernelGGL(kern, dim3(grid), dim3(DCOMP_BLOCK), 0, (hipStream_t)stream, kp);
+                launch(env, Launch::Rollout, kp, stream);
                 env->time += n;
                 t += n;
-                act_src = kp.next_act;                             // (a lane reads its slot before it writes it)
+                if (loop) act_src = kp.next_act;                   // (a lane reads its slot before it writes it)
             }
         }
         HIP_TRY(hipGetLastError());
         return DCOMP_OK;
     }
-    // one launch per step: wide envs, envs whose UE list changes (event feed), batches too large for the latency-optimised kernel
-    if (env->fused_big) {
-        // The generic kernel's fused rollout (big_kernel<..., ROLL>): one launch per stretch of an episode, the UE state in registers from step to
-        // step, step t's outputs in slice t of the caller's buffers; at the horizon the reset kernel (which, with a policy, also decides the first
-        // action of the new episode).  64-bit offsets throughout: no row limit.
-        const uint8_t *act_src = actions;
-        for (int t = 0; t < T;) {
-            out_slice(kp, t);
-            if (L > 0 && env->time == L) { launch_reset(kp); if (loop) act_src = kp.next_act; }
-            const int n = (L > 0 && L - env->time < T - t) ? L - env->time : T - t;
-            kp.action = loop ? act_src : actions + EU * t;
-            kp.num_steps = n; kp.out_every_step = every; kp.policy_loop = loop; kp.horizon = 0; kp.episode_inc = 0;
-            kp.time = (uint32_t)env->time; kp.episode = (uint32_t)env->episode;
-            hipLaunchKernelGGL(big_fn(env, kp, 3), dim3(env->grid), dim3(env->bigk.block), env->big_lds, (hipStream_t)stream, kp, env->bigp);
-            env->time += n;
-            t += n;
-            if (loop) act_src = kp.next_act;
-        }
-        HIP_TRY(hipGetLastError());
-        return DCOMP_OK;
-    }
-    // The closed loop here: step 0 acts on actions[0] (the next_action the previous launch wrote), every later step -- and the first step of a
-    // new episode -- on what the launch before it decided.  next_action is ONE buffer read and written in place: a lane reads the action of
-    // its own slot when the kernel starts and writes the decision for that same slot at its end (with UE arrival / departure the UEs move
-    // between slots through LDS, not through this buffer).
     size_t rem_off = 0, add_off = 0;
-    const uint8_t *act_src = actions;
     for (int t = 0; t < T; t++) {
         out_slice(kp, t);
         if (L > 0 && env->time == L) { launch_reset(kp); if (loop) act_src = kp.next_act; }
@@ -754,14 +764,14 @@ static int rollout_impl(dcomp_env *env, const dcomp_state *st, const uint8_t *ac
             const int nrem = ev_rem ? ev_rem[t] : 0, nadd = ev_add ? ev_add[t] : 0;       // (validated above, all T steps)
             kp.cur_ue = env->cur_ue;
             kp.n_remove = nrem; kp.n_add = nadd;
-            kp.ev_remove = (tape && nrem) ? opts->ev_remove_idx + rem_off : nullptr;
-            kp.ev_add_xy = (tape && nadd) ? opts->ev_add_xy + add_off : nullptr;
+            kp.ev_remove = (tape && nrem) ? ev_idx + rem_off : nullptr;
+            kp.ev_add_xy = (tape && nadd) ? ev_xy + add_off : nullptr;
             kp.ev_rem_base = env->n_removed; kp.ev_add_base = env->n_arrived;
             rem_off += E * (size_t)nrem; add_off += E * (size_t)nadd * 2;
             env->cur_ue += nadd - nrem;
             env->n_removed += (uint32_t)nrem; env->n_arrived += (uint32_t)nadd;
         }
-        launch_step(env, kp, stream);
+        launch(env, Launch::Step, kp, stream);
         env->time += 1;
         if (loop) act_src = kp.next_act;
     }
@@ -772,30 +782,19 @@ static int rollout_impl(dcomp_env *env, const dcomp_state *st, const uint8_t *ac
 extern "C" int dcomp_rollout(dcomp_env *env, const dcomp_state *st, const uint8_t *actions, int32_t num_steps, const dcomp_out *out,
                              void *stream)
 {
-    return rollout_impl(env, st, actions, num_steps, out, nullptr, stream);
+    return dcomp_rollout_ex(env, st, actions, num_steps, out, nullptr, stream);
 }
 
-extern "C" int dcomp_rollout_ex(dcomp_env *env, const dcomp_state *st, const uint8_t *actions, int32_t num_steps, const dcomp_out *out,
-                                const dcomp_rollout_opts *opts, void *stream)
-{
-    return rollout_impl(env, st, actions, num_steps, out, opts, stream);
-}
-
-extern "C" int dcomp_rollout_is_fused(const dcomp_env *env) { return env ? ((env->fused || env->fused_long || env->fused_big) ? 1 : 0) : -1; }
-// Whether THIS rollout is one launch: fusion of the short-row shapes (fused_long) depends on the number of steps -- a rollout of
-// fewer than 4 tape-driven steps goes out as one launch per step, as does an every-step fragment of >= 2^31 rows.
+extern "C" int dcomp_rollout_is_fused(const dcomp_env *env) { return env ? (env->plan.fuse != Fuse::None ? 1 : 0) : -1; }
 extern "C" int dcomp_rollout_fused_for(const dcomp_env *env, int32_t num_steps, int32_t every_step, int32_t policy_loop)
 {
     if (!env || num_steps < 1) return -1;
-    const uint64_t EU = (uint64_t)env->cfg.num_envs * env->cap;
-    if (env->fused_big) return 1;                                  // (one launch per stretch of an episode; 64-bit offsets: no row limit)
-    if (every_step && (uint64_t)num_steps * EU >= fused_row_limit()) return 0;
-    return (env->fused || (env->fused_long && (num_steps >= 4 || policy_loop))) ? 1 : 0;
+    return rollout_fused(env, num_steps, every_step != 0, policy_loop != 0) ? 1 : 0;
 }
 // 1: this env runs on the generic kernel, whose connection sets take two words per UE -- dcomp_state.conn_hi is REQUIRED (dcomp_reset / dcomp_step
 // fail with DCOMP_EINVAL without it); 0: the specialised kernels, conn_hi is ignored.  The caller asks instead of re-deriving the rule.
-extern "C" int dcomp_needs_conn_hi(const dcomp_env *env) { return env ? (env->big ? 1 : 0) : -1; }
-extern "C" int dcomp_lanes_per_env(const dcomp_env *env) { return env ? (env->tight_g ? env->tight_g : env->upad) : -1; }
+extern "C" int dcomp_needs_conn_hi(const dcomp_env *env) { return env ? (env->plan.path == StepPath::Generic ? 1 : 0) : -1; }
+extern "C" int dcomp_lanes_per_env(const dcomp_env *env) { return env ? env->plan.lanes : -1; }
 
 // The instantiation dcomp_step launches for this env, spelled as rocprofv3 prints it ("step_kernel<10, 32, 2>"): bench.py ties a
 // tracked --pmc profile to the kernel the library really dispatches to.
@@ -803,13 +802,13 @@ extern "C" int dcomp_step_kernel_name(const dcomp_env *env, char *buf, int32_t l
 {
     if (!env || !buf || len < 1) return fail(DCOMP_EINVAL, "null argument");
     const int B = env->cfg.num_bs, W = env->upad, MP = env->mp_pattern;
-    if (env->big) std::snprintf(buf, (size_t)len, "big_kernel<%d, false, %s, false, %s, false>", W < 4 ? 4 : W, env->dyn ? "true" : "false", env->kp.next_act ? "true" : "false");
-    else if (env->tight_g) {
-        const bool cen = env->cfg.env_kind == DCOMP_CENTRAL && env->kern.tight_central;
-        std::snprintf(buf, (size_t)len, "step_kernel_tight<%d, %d, %d, %d>", B, W, MP, cen ? 0 : -1);
-    } else if (env->dyn) std::snprintf(buf, (size_t)len, "step_kernel_dyn<%d, %d, %d>", B, W, MP);
-    else if (env->kern.step == env->kern.step_wide && env->kern.step_wide) std::snprintf(buf, (size_t)len, "step_kernel_wide<%d, %d, %d>", B, W, MP);
-    else std::snprintf(buf, (size_t)len, "step_kernel<%d, %d, %d>", B, W, MP);
+    switch (env->plan.path) {
+    case StepPath::Generic: std::snprintf(buf, (size_t)len, "big_kernel<%d, false, %s, false, %s, false>", W, env->dyn ? "true" : "false", env->kp.next_act ? "true" : "false"); break;
+    case StepPath::Tight: std::snprintf(buf, (size_t)len, "step_kernel_tight<%d, %d, %d, %d>", B, W, MP, env->plan.tight_central ? 0 : -1); break;
+    case StepPath::Dyn: std::snprintf(buf, (size_t)len, "step_kernel_dyn<%d, %d, %d>", B, W, MP); break;
+    case StepPath::Wide: std::snprintf(buf, (size_t)len, "step_kernel_wide<%d, %d, %d>", B, W, MP); break;
+    case StepPath::Special: std::snprintf(buf, (size_t)len, "step_kernel<%d, %d, %d>", B, W, MP); break;
+    }
     return DCOMP_OK;
 }
 

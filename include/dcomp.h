@@ -107,9 +107,10 @@ int dcomp_rollout(dcomp_env *env, const dcomp_state *st, const uint8_t *actions,
  *                       (simulation.py:512-541) in one call; `actions` holds ONE step.  With a horizon the run may cross episode
  *                       boundaries: at each one the library launches the reset kernel -- which writes the first observation of
  *                       the new episode AND the policy's action on it -- and continues the loop from that action: one launch
- *                       per stretch of an episode plus one reset launch per episode, no host work in between.  Where rollouts
- *                       are not fused (dcomp_rollout_fused_for: wide and generic kernels, UE arrival / departure) the same loop is
- *                       one launch per step, each step reading the next_action buffer the launch before it wrote (round 6).
+ *                       per stretch of an episode plus one reset launch per episode, no host work in between (the generic
+ *                       kernel of more than 32 stations runs every fused rollout that way).  Where rollouts are not fused
+ *                       (dcomp_rollout_fused_for: the wide kernel, UE arrival / departure, throughput-bound batches of long rows)
+ *                       the same loop is one launch per step, each step reading the next_action buffer the launch before it wrote.
  *   ev_n_remove/ev_n_add  UE departures / arrivals of an env with a changing UE list (cfg.max_ues > 0), per step of THIS
  *                       rollout: host arrays [num_steps]; entry t = the UEs that leave / arrive in step t (base.py:433-443; the
  *                       schedule is configuration, identical in every env).  NULL: no events.  Such envs are launched once
