@@ -333,12 +333,15 @@ __global__ __launch_bounds__(big_block(UPAD)) void big_kernel(const KParams p, c
                     p.orig_consumed[(size_t)env * p.U0 + ((uidw & 0x7FFFu) - 1u)] = (uint16_t)(mv >> 48);
                 const bool take = active && u >= r && u + 1 < cur;                        // slots behind the leaver move up
                 if (any_maxcap) {                                  // the step-of-connection rows travel with their UEs (rare: an event step with max-cap stations)
+                    // barrier -> read the neighbour's entry -> barrier -> write one's own: the first barrier orders the neighbour's stores before the
+                    // read -- the toggle's stamp above (the neighbour may be lane 0 of the NEXT wavefront) and the previous departure's row move and
+                    // row clear; the second orders every read of an entry before that entry is overwritten
                     for (int b = 0; b < B; b++) {
                         uint16_t t = 0;
+                        __syncthreads();
                         if (take) t = p.conn_since[(size_t)(idx + 1) * B + b];
                         __syncthreads();
                         if (take) p.conn_since[(size_t)idx * B + b] = t;
-                        __syncthreads();
                     }
                 }
                 if constexpr (UPAD <= 64) {

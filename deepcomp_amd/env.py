@@ -790,6 +790,8 @@ class BatchedMobileEnv:
         for k in ('pos', 'mv', 'conn', 'conn_hi', 'ewma', 'conn_since', 'uid', 'orig_consumed'):
             if sd.get(k) is not None and getattr(self, k) is not None:      # (e.g. conn_hi of a checkpoint written under DCOMP_FORCE_BIG, read without it: stations 32-63 do not exist)
                 getattr(self, k).copy_(sd[k])
+            elif k in ('conn_since', 'conn_hi', 'uid') and getattr(self, k) is not None:
+                getattr(self, k).zero_()                                     # the checkpoint has no such buffer: not the contents of whatever this env ran before
         self._outbuf.copy_(sd['outbuf'])
         self.flags.zero_()
         c = (ctypes.c_int64 * 5)(*sd['counters'])

@@ -237,6 +237,10 @@ class OracleEnv:
             self._border = np.asarray([10] * self.U0 if border is None else border, dtype=np.int32)
             L.orc_set_movement(self.h, self.U0, _p(self._pause, _c_ip), _p(self._border, _c_ip))
 
+    def max_cap_stations(self):
+        """Indices of the stations whose sharing model is max-cap (station.py:183-187)."""
+        return [b for b in range(self.B) if int(self._sh[b]) == SHARING_CODE['max-cap']]
+
     def probe_data_rate(self, b, u, ewma=None):
         """Basestation.data_rate(ue) (station.py:204-220) in the current state; ewma: replace the UEs' EWMA rates first."""
         e = None if ewma is None else np.ascontiguousarray(ewma, dtype=np.float64)

@@ -21,6 +21,7 @@ Round 2 compared the packed observation tensor with ``rtol=1e-5, atol=1e-5``: fo
 import numpy as np
 
 RTOL_RATE = 1e-5
+MAX_CAP = 2                                                # sharing code of a max-cap station (deepcomp_amd._lib.SHARING, oracle.SHARING_CODE)
 F32_MIN_NORMAL = float(np.finfo(np.float32).tiny)          # 2^-126
 ATOL_OBS = 5e-6
 ATOL_UTIL = 5e-5
@@ -95,3 +96,99 @@ def assert_step(core, ob, o_obs, o_rew, o_conn, o_pos, kind, reward='avg', msg='
     if o_rew is not None:
         tol = (ATOL_UTIL if kind == 'multi' else ATOL_OBS) * (U if reward == 'sum' else 1)
         np.testing.assert_allclose(core.reward.cpu().numpy(), o_rew, rtol=0, atol=tol, err_msg=f'{msg}: reward')
+
+
+def near_actions(rng, pos, bs, frac=0.6):
+    """Actions biased towards stations that are in range, so that UEs hold several connections and stations several UEs.
+    pos: host positions [E, U, 2]; bs: station positions [B, 2].  The one copy of the rule the Philox-batch tests draw their actions with."""
+    E, U, B = pos.shape[0], pos.shape[1], len(bs)
+    d = np.linalg.norm(pos[:, :, None, :] - np.asarray(bs, float)[None, None, :, :], axis=-1)     # [E, U, B]
+    near = d < 68.0
+    a = rng.integers(0, B + 1, size=(E, U))
+    pick = np.where(near.any(-1), (near * rng.random((E, U, B))).argmax(-1) + 1, a)
+    a = np.where(rng.random((E, U)) < frac, pick, a)
+    a[rng.random((E, U)) < 0.15] = 0
+    return a.astype(np.uint8)
+
+
+def conn_order_lists(conn, conn_since, num_ue, b):
+    """One env's device state -> the connection list of station b that it encodes: the slots u < num_ue whose bit b is set in conn[u],
+    sorted by (conn_since[u, b] as uint16, u) -- the step of the connection, then the slot (dcomp_state.conn_since)."""
+    slots = [u for u in range(num_ue) if (int(conn[u]) >> b) & 1]
+    return sorted(slots, key=lambda u: (int(conn_since[u, b]), u))
+
+
+def assert_conn_order(core, oracle_envs, msg=''):
+    """The connection ORDER of every max-cap station (station.py:183-187: among equal FP64 rates the first UE of the station's list is served)
+    against the oracle's list, exactly.  The device keeps the list implicitly: dcomp_state.conn_since, uint16 [E*U][B], the step at which
+    each connection was made; the list is the connected slots by (step, slot).  The oracle exports the list itself
+    (OracleEnv.state()['conn_order'], int32 [B, U], -1 padded).  Which stations are max-cap is taken from the oracle.
+    Returns the number of lists compared.  Host copies only."""
+    E, U, B = core.E, core.U, core.B
+    assert len(oracle_envs) == E, f'{msg}: {len(oracle_envs)} oracle envs for {E} device envs'
+    mc = oracle_envs[0].max_cap_stations()
+    if not mc:
+        return 0
+    assert core.conn_since is not None, f'{msg}: the env has max-cap stations {mc} and no conn_since table'
+    cs = core.conn_since
+    cs = np.asarray(cs.cpu().numpy() if hasattr(cs, 'cpu') else cs)
+    assert cs.size == E * U * B, f'{msg}: conn_since has {cs.size} entries, E*U*B = {E * U * B}'
+    since = cs.astype(np.int16).view(np.uint16).reshape(E, U, B)
+    conn = core.state_host()['conn']
+    n = int(core.num_ue)
+    checked = 0
+    for e, o in enumerate(oracle_envs):
+        assert o.num_ue() == n, f'{msg}: env {e}: {n} UEs on the device, {o.num_ue()} in the oracle'
+        order = o.state()['conn_order']
+        for b in mc:
+            got = conn_order_lists(conn[e], since[e], n, b)
+            w = order[b]
+            stop = np.nonzero(w < 0)[0]
+            want = [int(v) for v in (w[:stop[0]] if len(stop) else w)]
+            if got != want:
+                involved = sorted(set(got) | set(want))
+                raise AssertionError(f'{msg}: env {e} max-cap station {b}: connection order {got} on the device, {want} in the oracle; '
+                                     f'conn_since[slot] = {{{", ".join(f"{u}: {int(since[e, u, b])}" for u in involved)}}}')
+            checked += 1
+    return checked
+
+
+class ConnOrderStats:
+    """What keeps a connection-order test from being vacuous, counted on the ORACLE's side (so it does not depend on the code under test):
+    max-cap lists with >= 2 UEs, those of them that are not in ascending slot order (the step decides, not the slot), UEs that changed
+    slot while holding a max-cap connection, and those of them that crossed a 64-slot (wavefront) boundary.  update() after every step."""
+
+    def __init__(self, oracle_envs):
+        self.envs = list(oracle_envs)
+        self.mc = self.envs[0].max_cap_stations()
+        self.multi = self.nonasc = self.moved = self.cross64 = 0
+        self._prev = None
+
+    def update(self):
+        cur = []
+        for e, o in enumerate(self.envs):
+            s, uid, n = o.state(), o.uids(), o.num_ue()
+            for b in self.mc:
+                w = [int(v) for v in s['conn_order'][b] if v >= 0]
+                if len(w) >= 2:
+                    self.multi += 1
+                    self.nonasc += w != sorted(w)
+            if self._prev is not None:
+                p_uid, p_held = self._prev[e]
+                old = {int(x): i for i, x in enumerate(p_uid) if x}
+                for sl in range(n):
+                    i = old.get(int(uid[sl]))
+                    if i is not None and i != sl and p_held[i]:
+                        self.moved += 1
+                        self.cross64 += i // 64 != sl // 64
+            cur.append((uid, s['conn'][:, self.mc].any(-1)))
+        self._prev = cur
+
+    def new_episode(self):
+        self._prev = None
+
+    def require(self, dynamic=False, wide=False):
+        got = f'lists with >= 2 UEs {self.multi}, not in slot order {self.nonasc}, UEs moved with a max-cap connection {self.moved}, across a 64-slot boundary {self.cross64}'
+        assert self.multi >= 100 and self.nonasc >= 20, f'the scenario does not exercise the connection order: {got}'
+        assert not dynamic or self.moved >= 20, f'too few slot shifts of connected UEs: {got}'
+        assert not wide or self.cross64 >= 5, f'too few slot shifts across a wavefront boundary: {got}'

@@ -47,16 +47,7 @@ def _oracle_batch(scn, kind, reward, E, seed):
 
 def _near_actions(rng, core, B, frac=0.6):
     """Actions biased towards stations that are in range (so that UEs hold several connections, high stations included)."""
-    E, U = core.E, core.U
-    pos = core.state_host()['pos']                                             # [E, U, 2]
-    bs = np.stack([core._bs_x, core._bs_y], axis=1)                            # [B, 2]
-    d = np.linalg.norm(pos[:, :, None, :] - bs[None, None, :, :], axis=-1)     # [E, U, B]
-    near = d < 68.0
-    a = rng.integers(0, B + 1, size=(E, U))
-    pick = np.where(near.any(-1), (near * rng.random((E, U, B))).argmax(-1) + 1, a)
-    a = np.where(rng.random((E, U)) < frac, pick, a)
-    a[rng.random((E, U)) < 0.15] = 0
-    return a.astype(np.uint8)
+    return parity.near_actions(rng, core.state_host()['pos'], np.stack([core._bs_x, core._bs_y], axis=1), frac)
 
 
 SHAPES = [('multi', 32, 64, 96, 'avg', 'mixed'), ('central', 10, 40, 128, 'avg', 'mixed'), ('multi', 3, 33, 200, 'min', 'mixed'),
@@ -448,6 +439,7 @@ def test_generic_kernel_with_ue_arrival_and_departure(torch_cuda, shape):
             assert np.array_equal(st['uid'], np.stack([o.uids() for o in oenvs])), f'step {t}: UE ids differ'
             assert np.array_equal(st['conn'], o_conn), f'episode {ep} step {t}: connection sets'
             assert np.array_equal(st['pos'], o_pos), f'episode {ep} step {t}: positions'
+            parity.assert_conn_order(core, oenvs, f'episode {ep} step {t}')         # (max-cap shapes: the step-of-connection rows really travel with their UEs)
             parity.assert_obs(core.obs.cpu().numpy(), o_obs, kind, M, B, msg=f'episode {ep} step {t}')
             tol = (ATOL_UTIL if kind == 'multi' else ATOL_OBS) * (M if reward == 'sum' else 1)
             np.testing.assert_allclose(core.reward.cpu().numpy(), o_rew, atol=tol, rtol=0)

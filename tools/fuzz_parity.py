@@ -19,6 +19,9 @@ RTOL_RATE, ATOL_UTIL, ATOL_OBS = parity.RTOL_RATE, parity.ATOL_UTIL, parity.ATOL
 SHARING = ['resource-fair', 'rate-fair', 'max-cap', 'proportional-fair']
 
 
+_warned = []
+
+
 class AmbiguousTie(Exception):
     """A max-cap station served a different UE than the oracle's, and the two UEs' FP64 rates are within an ulp of log10 of each other: the
     reference itself decides that case in the last bit of the host's np.log10 (AVX-512 SVML or libm) -- DESIGN.md section 6."""
@@ -26,12 +29,15 @@ class AmbiguousTie(Exception):
 
 def maxcap_libm_tie(core, ob, c, st):
     """The per-UE rates differ from the oracle's: is every difference a swapped max-cap winner between two UEs whose squared distances to the
-    station agree to 1e-11 relative?  Returns a description, or None (a real mismatch)."""
+    station agree to 1e-11 relative WITHOUT being equal (equal distances give bit-equal rate keys on every libm: the connection order
+    decides, and that is checked, not excused), and are the two wrong rates the oracle's two rates swapped?  Returns a description, or
+    None (a real mismatch)."""
     r = ob.rates(want_dr_rel=False)
     want = r['curr_dr']
     E, U = want.shape
     got = core.ue_dr.cpu().numpy().reshape(E, U).astype(np.float64)
-    bad = np.argwhere(np.abs(got - want) > parity.RTOL_RATE * np.abs(want) + 1e-30)
+    tol = lambda w: parity.RTOL_RATE * np.abs(w) + 1e-30       # noqa: E731
+    bad = np.argwhere(np.abs(got - want) > tol(want))
     if len(bad) == 0 or len(bad) % 2:
         return None
     mc = [b for b, m in enumerate(c['sh']) if m == 'max-cap']
@@ -41,14 +47,16 @@ def maxcap_libm_tie(core, ob, c, st):
         if len(us) != 2:
             return None
         u1, u2 = us
-        pos, conn = st['pos'][e], st['conn'][e]
+        if abs(got[e, u1] - want[e, u2]) > tol(want[e, u2]) or abs(got[e, u2] - want[e, u1]) > tol(want[e, u1]):
+            return None                                        # not the oracle's two rates swapped
+        pos, conn = st['pos'][e], st['conn'][e]                # (conn: one mask per UE, 64-bit above 32 stations)
         hit = None
         for b in mc:
             if (int(conn[u1]) >> b) & 1 and (int(conn[u2]) >> b) & 1:
                 bx, by = c['bs_xy'][b]
                 d1 = (pos[u1][0] - bx) ** 2 + (pos[u1][1] - by) ** 2
                 d2 = (pos[u2][0] - bx) ** 2 + (pos[u2][1] - by) ** 2
-                if abs(d1 - d2) <= 1e-11 * max(d1, d2):
+                if d1 != d2 and abs(d1 - d2) <= 1e-11 * max(d1, d2):
                     hit = (b, d1, d2)
         if hit is None:
             return None
@@ -271,6 +279,11 @@ def run_case(c, torch):
             if arrival:
                 assert core.num_ue == envs[0].num_ue(), f'{tag}: number of UEs'
                 assert np.array_equal(st['uid'], np.stack([o.uids() for o in envs])), f'{tag}: UE ids differ'
+            if 'max-cap' in c['sh']:                     # the connection order of every max-cap station (dcomp_state.conn_since) against the oracle's list
+                if hasattr(parity, 'assert_conn_order'):
+                    parity.assert_conn_order(core, envs, tag)
+                elif not _warned:                        # this tool driven with a tests/parity.py older than the checker: say so, once
+                    _warned.append(sys.stderr.write('fuzz_parity: tests/parity.py has no assert_conn_order -- the connection order is NOT checked\n'))
         # per-UE data rate, EWMA and the relative-SNR block 1e-5 RELATIVE against the oracle's FP64 values (tests/parity.py)
         try:
             r = parity.assert_rates(core, ob, tag)
