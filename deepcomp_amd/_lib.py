@@ -68,11 +68,28 @@ class DcompPolicy(ctypes.Structure):
 
 POLICY = {'3gpp': 0, 'fullcomp': 1, 'dynamic': 2, 'cluster': 3}
 
+ACTIVATION = {'tanh': 0, 'relu': 1}
+ACTOR_ROWS, ACTOR_COMPACT = 0, 1
+ACTOR_MAX_HIDDEN, ACTOR_MAX_IN, ACTOR_MAX_LOGITS = 256, 1024, 512
+
+
+class DcompActorCfg(ctypes.Structure):
+    _fields_ = [('struct_size', ctypes.c_int32), ('obs_kind', ctypes.c_int32), ('num_ue', ctypes.c_int32), ('num_bs', ctypes.c_int32),
+                ('hidden', ctypes.c_int32), ('activation', ctypes.c_int32), ('w1', _fp), ('b1', _fp), ('w2', _fp), ('b2', _fp),
+                ('w3', _fp), ('b3', _fp)]
+
+
+class DcompActorRun(ctypes.Structure):
+    _fields_ = [('struct_size', ctypes.c_int32), ('obs_format', ctypes.c_int32), ('num_envs', ctypes.c_int32),
+                ('num_active', ctypes.c_int32), ('sample', ctypes.c_int32), ('step', ctypes.c_uint32), ('seed', ctypes.c_uint64),
+                ('row_base', ctypes.c_int64), ('logits', ctypes.c_void_p), ('logp', ctypes.c_void_p)]
+
 EXPORTS = ['dcomp_abi_version', 'dcomp_create_v', 'dcomp_create', 'dcomp_destroy', 'dcomp_state_sizes', 'dcomp_obs_dim', 'dcomp_reset', 'dcomp_step',
            'dcomp_step_dyn', 'dcomp_num_ue',
            'dcomp_rollout', 'dcomp_rollout_ex', 'dcomp_rollout_is_fused', 'dcomp_rollout_fused_for', 'dcomp_lanes_per_env', 'dcomp_needs_conn_hi', 'dcomp_step_kernel_name', 'dcomp_check', 'dcomp_time', 'dcomp_episode', 'dcomp_set_episode', 'dcomp_set_seed', 'dcomp_set_tape', 'dcomp_get_counters', 'dcomp_set_counters', 'dcomp_mt_draw_tape',
            'dcomp_connect_threshold', 'dcomp_connect_boundary_sq', 'dcomp_last_error', 'dcomp_version', 'dcomp_selftest', 'dcomp_heuristic_actions', 'dcomp_set_policy',
-           'dcomp_fragment_words', 'dcomp_pack_fragment', 'dcomp_unpack_fragment']
+           'dcomp_fragment_words', 'dcomp_pack_fragment', 'dcomp_unpack_fragment',
+           'dcomp_actor_create', 'dcomp_actor_destroy', 'dcomp_actor_actions']
 
 _lib = None
 
@@ -144,6 +161,10 @@ def load():
         L.dcomp_fragment_words.argtypes = [i32, i32]
         L.dcomp_pack_fragment.argtypes = [vp, i64, i32, i32, vp, vp, vp]
         L.dcomp_unpack_fragment.argtypes = [vp, i64, i32, i32, vp, vp]
+    if hasattr(L, 'dcomp_actor_create'):
+        L.dcomp_actor_create.argtypes = [ctypes.POINTER(DcompActorCfg), ctypes.POINTER(vp)]
+        L.dcomp_actor_destroy.argtypes = [vp]
+        L.dcomp_actor_actions.argtypes = [vp, ctypes.POINTER(DcompActorRun), vp, vp, vp]
     if os.environ.get('DCOMP_LIB'):              # timing variants built from older sources lack the newest entry points
         EXPORTS[:] = [n for n in EXPORTS if hasattr(L, n)]
     for name in EXPORTS:

@@ -3,7 +3,7 @@
     python -m deepcomp_amd.build [--force] [--jobs N]
 
 One object per base-station count listed in csrc/dcomp_blist.h (all UE-group widths inside), compiled
-in parallel, plus the API object; linked into deepcomp_amd/csrc/libdcomp_hip.so.  hipcc cross-compiles
+in parallel, plus the API object, the generic kernel's and the actor's (csrc/dcomp_actor.hip); linked into deepcomp_amd/csrc/libdcomp_hip.so.  hipcc cross-compiles
 for gfx950 without a GPU present.
 """
 import argparse
@@ -35,7 +35,7 @@ def b_list():
 
 def _sources():
     return [os.path.join(CSRC, f) for f in ('dcomp_device.h', 'dcomp_wide.h', 'dcomp_dyn.h', 'dcomp_blist.h', 'dcomp_inst.hip', 'dcomp_api.hip', 'dcomp_fragment.h',
-                                            'dcomp_big.h', 'dcomp_big.hip')] + \
+                                            'dcomp_big.h', 'dcomp_big.hip', 'dcomp_actor.hip')] + \
         [os.path.join(os.path.dirname(HERE), 'include', f) for f in ('dcomp.h', 'dcomp_types.h')]
 
 
@@ -123,6 +123,8 @@ def build(force=False, jobs=None, extra_flags=()):
     tasks.append((o_api, [hipcc] + CXXFLAGS + list(extra_flags) + ['-c', os.path.join(CSRC, 'dcomp_api.hip'), '-o', o_api]))
     o_big = os.path.join(OBJ, 'dcomp_big.o')        # the generic kernel for 33 ... 64 stations: one object for every station count
     tasks.append((o_big, [hipcc] + CXXFLAGS + list(extra_flags) + ['-c', os.path.join(CSRC, 'dcomp_big.hip'), '-o', o_big]))
+    o_actor = os.path.join(OBJ, 'dcomp_actor.o')    # the fcnet actor (MFMA forward + action sampling): its own object, it shares no kernel code
+    tasks.append((o_actor, [hipcc] + CXXFLAGS + list(extra_flags) + ['-c', os.path.join(CSRC, 'dcomp_actor.hip'), '-o', o_actor]))
 
     def obj_stamp(t):
         """An object is rebuilt when its command line or one of ITS inputs changed: the per-station-count objects do not
@@ -130,7 +132,11 @@ def build(force=False, jobs=None, extra_flags=()):
         only -- so an ABI-side edit recompiles one file and relinks, seconds instead of ten minutes."""
         h = hashlib.sha256(' '.join(t[1]).encode())
         for f in _sources():
-            if f.endswith(('dcomp_api.hip', 'dcomp_fragment.h', os.sep + 'dcomp.h')) and not t[0].endswith('dcomp_api.o'):
+            if f.endswith(('dcomp_api.hip', 'dcomp_fragment.h')) and not t[0].endswith('dcomp_api.o'):
+                continue
+            if f.endswith(os.sep + 'dcomp.h') and not t[0].endswith(('dcomp_api.o', 'dcomp_actor.o')):
+                continue
+            if f.endswith('dcomp_actor.hip') and not t[0].endswith('dcomp_actor.o'):
                 continue
             if f.endswith(('dcomp_big.h', 'dcomp_big.hip')) and not t[0].endswith(('dcomp_api.o', 'dcomp_big.o')):
                 continue

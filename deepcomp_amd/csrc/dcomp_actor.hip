@@ -1,0 +1,480 @@
+// dcomp_actor.hip -- a trained fcnet actor on the device (include/dcomp.h: dcomp_actor_create / dcomp_actor_actions).
+//
+// What the reference does with a trained policy (simulation.py:347,375,512-541: trainer.compute_action per env and step) for a
+// whole batch in one launch: observation tensor -> two hidden layers -> logits -> categorical draw -> the uint8 action tensor
+// dcomp_step takes.  The arithmetic is the specification:
+//     x = bf16(obs row);  h1 = bf16(act(x W1 + b1));  h2 = bf16(act(h1 W2 + b2));  logits = h2 W3 + b3
+// with bf16 products, f32 accumulation (v_mfma_f32_32x32x16_bf16), bias and activation in f32.
+//
+// Shape of the kernel.  One WAVEFRONT owns a tile of 32 decision rows and shares nothing with the other waves of its workgroup
+// (no workgroup barrier).  Everything is computed transposed, H^T = W^T X^T: the weights are the A operand, the 32 decision rows
+// sit on the lanes as the B operand.  The 32 x 32 f32 accumulator of a tile of 32 hidden units then has the hidden unit in its
+// 16 registers and the decision row on its lane -- and the next layer sums over exactly that register index, so after bias,
+// activation and the bf16 conversion registers 8s ... 8s+7 ARE the B fragment of the next layer's k-step s: the activations never
+// leave the registers.  Inside such a step the k order is permuted (element j of lane half h is hidden unit 16s + 8(j>>2) + 4h +
+// (j&3)); dcomp_actor_create lays W2 and W3 out in that order, and W1 in the natural order of a fragment read from LDS.
+//   - observation rows: read once, coalesced, converted to bf16 into the wave's LDS slice [32][chunk + 8] (chunks of <= 144
+//     inputs: a central row of 1 024 inputs needs no more LDS than a multi-agent row, four waves stay under 64 KB); the compact record
+//     (dcomp_fragment.h) is expanded on the way in, to the values dcomp_unpack_fragment would have written
+//   - weights: packed fragments, 1 KiB per wave-instruction, from L2 (<= 170 KB in all); K and N are padded with zeros in the
+//     packed weights, the hidden width to 32 / 64 / 128 / 256 (act(0 + 0) = 0 contributes nothing)
+//   - logits: 32 at a time through a [32][33] LDS tile; lane r < 32 walks row r's columns in order -- Gumbel noise, first
+//     maximum, online log-sum-exp -- carrying (head, action) across tiles, so heads need not align with anything
+//   - rows beyond the batch in the last tile are computed on zeros and never stored
+#include <hip/hip_runtime.h>
+
+#include <cmath>
+#include <cstdarg>
+#include <cstdint>
+#include <cstdio>
+#include <cstring>
+#include <vector>
+
+#define DCOMP_BUILDING_LIBRARY 1
+#include "../../include/dcomp.h"
+
+namespace dcomp { int report(int code, const char *msg); }       // dcomp_api.hip: the thread's dcomp_last_error() text
+
+namespace dactor {
+
+typedef float f32x16 __attribute__((ext_vector_type(16)));
+typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
+
+constexpr int WAVES = 4, BLOCK = WAVES * 64, TILE = 32;
+constexpr int KC = 144;               // inputs staged at a time (a multiple of 16; KC + 8 elements = an odd number of 16-byte slots per row)
+constexpr int LT = 33;                // row stride of the logit tile (floats): lanes walk their rows conflict-free
+constexpr uint32_t DRAW_TAG = 0x00AC7012u;
+
+// the compact record of one env-step (dcomp_fragment.h, whose kernels live in the API object): U x { dr[B] | utility | connection
+// mask word(s) } then ues_at_bs[B] | util_at_bs[B]
+__host__ __device__ inline int ue_words(int B) { return B + 1 + (B > 32 ? 2 : 1); }
+__host__ __device__ inline int env_words(int U, int B) { return U * ue_words(B) + 2 * B; }
+
+struct Params {
+    const void *obs;
+    uint8_t *action;
+    float *logits, *logp;
+    const uint4 *w1, *w2, *w3;        // packed bf16 fragments [m tile][k step][lane] x 8 elements
+    const float *b1, *b2, *b3;        // padded with zeros to the padded widths
+    int64_t rows, tiles, row_base;
+    int32_t K1, K1p, XS, N3, NT3, heads, B, U, num_active, multi, compact, sample;
+    uint32_t step, seed_lo, seed_hi;
+    int32_t lds_per_wave;
+};
+
+__device__ __forceinline__ void philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0, uint32_t k1, uint32_t (&out)[4])
+{
+#pragma unroll
+    for (int r = 0; r < 10; r++) {
+        const unsigned long long p0 = (unsigned long long)0xD2511F53u * c0, p1 = (unsigned long long)0xCD9E8D57u * c2;
+        const uint32_t hi0 = (uint32_t)(p0 >> 32), lo0 = (uint32_t)p0, hi1 = (uint32_t)(p1 >> 32), lo1 = (uint32_t)p1;
+        c0 = hi1 ^ c1 ^ k0; c1 = lo1; c2 = hi0 ^ c3 ^ k1; c3 = lo0;
+        k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
+    }
+    out[0] = c0; out[1] = c1; out[2] = c2; out[3] = c3;
+}
+
+// LDS ops of one wave execute in order; this only stops the compiler from moving LDS accesses across it.
+__device__ __forceinline__ void wave_fence()
+{
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    __builtin_amdgcn_wave_barrier();
+}
+
+template <bool RELU> __device__ __forceinline__ float activate(float x)
+{
+    if (RELU) return fmaxf(x, 0.f);
+    // tanh(x) = 1 - 2 / (exp(2x) + 1): exp -> inf gives 1, exp -> 0 gives -1; absolute error ~1e-7, far inside the bf16 rounding of the result
+    const float e = __builtin_amdgcn_exp2f(x * 2.885390081777927f);
+    return 1.f - 2.f * __builtin_amdgcn_rcpf(e + 1.f);
+}
+
+// registers 8s ... 8s+7 of an accumulator tile (+ bias, activation) -> the B fragment of the next layer's k-step s.
+// bias points at the tile's first unit + 4 * (lane half): register i holds unit (i & 3) + 8 (i >> 2) + 4h of the tile.
+template <bool RELU> __device__ __forceinline__ bf16x8 next_fragment(const f32x16 &acc, int s, const float *bias)
+{
+    const float4 ba = *reinterpret_cast<const float4 *>(bias + 16 * s), bb = *reinterpret_cast<const float4 *>(bias + 16 * s + 8);
+    bf16x8 f;
+    f[0] = (__bf16)activate<RELU>(acc[8 * s + 0] + ba.x);
+    f[1] = (__bf16)activate<RELU>(acc[8 * s + 1] + ba.y);
+    f[2] = (__bf16)activate<RELU>(acc[8 * s + 2] + ba.z);
+    f[3] = (__bf16)activate<RELU>(acc[8 * s + 3] + ba.w);
+    f[4] = (__bf16)activate<RELU>(acc[8 * s + 4] + bb.x);
+    f[5] = (__bf16)activate<RELU>(acc[8 * s + 5] + bb.y);
+    f[6] = (__bf16)activate<RELU>(acc[8 * s + 6] + bb.z);
+    f[7] = (__bf16)activate<RELU>(acc[8 * s + 7] + bb.w);
+    return f;
+}
+
+// fragment `idx` (uniform) of a packed weight array for this lane: a uniform base + the lane's 32-bit byte offset.  The offset is
+// made opaque at every call: the tile loop's ~150 load addresses are loop-invariant, and hoisted out of it as 64-bit lane
+// addresses they were 290 spilled registers.
+__device__ __forceinline__ uint4 load_frag(const uint4 *w, size_t idx, uint32_t lane16)
+{
+    asm volatile("" : "+v"(lane16));
+    return *reinterpret_cast<const uint4 *>(reinterpret_cast<const char *>(w + idx * 64) + lane16);
+}
+
+__device__ __forceinline__ bf16x8 as_frag(uint4 v)
+{
+    union { uint4 u; bf16x8 f; } c;
+    c.u = v;
+    return c.f;
+}
+
+// MT = hidden width / 32 (padded: 1, 2, 4 or 8)
+template <int MT, bool RELU>
+__global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(2, 2))) void actor_kernel(const Params p)
+{
+    extern __shared__ uint4 lds4[];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, r = lane & 31, h = lane >> 5;
+    const uint32_t lane16 = (uint32_t)lane * 16u;
+    unsigned char *base = reinterpret_cast<unsigned char *>(lds4) + (size_t)wave * p.lds_per_wave;
+    __bf16 *xs = reinterpret_cast<__bf16 *>(base);                                   // [32][XS] bf16: the chunk of the tile's rows
+    float *lt = reinterpret_cast<float *>(base + (size_t)TILE * p.XS * 2);           // [32][LT] f32: 32 logits of every row
+    uint32_t *ri = reinterpret_cast<uint32_t *>(lt + TILE * LT);                     // [32][4]: compact record of row r: word offset lo, hi | listed | UE slot
+    const int XS = p.XS, K1 = p.K1, B = p.B, U = p.U, NA = B + 1;
+    const int KS1 = p.K1p >> 4;
+    constexpr int KS2 = 2 * MT;                                  // k steps of layers 2 and 3
+    constexpr int D = KS2 < 8 ? KS2 : 8;                         // weight fragments in flight (32 registers at most)
+    constexpr int Q2 = MT * KS2;                                 // MFMAs of layer 2
+    const int CW = ue_words(B);
+    const uint32_t *cwords = reinterpret_cast<const uint32_t *>(p.obs);
+    const float *rowsf = reinterpret_cast<const float *>(p.obs);
+
+    for (int64_t tile = (int64_t)blockIdx.x * WAVES + wave; tile < p.tiles; tile += (int64_t)gridDim.x * WAVES) {
+        const int64_t row0 = tile * TILE;
+        const int nrow = (int)(p.rows - row0 < TILE ? p.rows - row0 : TILE);
+        const int64_t myrow = row0 + r;                                              // the decision row on this lane
+        const bool have = r < nrow;
+        int slot = 0;                                                                // multi-agent: the row's UE slot
+        if (p.multi && have) slot = (int)(myrow % U);
+        if (p.compact) {
+            if (lane < TILE) {
+                uint32_t lo = 0, hi = 0, listed = 0;
+                if (have) {
+                    const int64_t env = myrow / U;
+                    const uint64_t off = (uint64_t)env * (uint64_t)env_words(U, B) + (uint64_t)slot * CW;
+                    uint32_t any = 0;
+                    for (int b = 0; b < B; b++) any |= cwords[off + b] & 0x7FFFFFFFu;          // listed <=> some dr entry is non-zero
+                    lo = (uint32_t)off; hi = (uint32_t)(off >> 32); listed = any != 0u;
+                }
+                ri[lane * 4 + 0] = lo; ri[lane * 4 + 1] = hi; ri[lane * 4 + 2] = listed; ri[lane * 4 + 3] = (uint32_t)slot;
+            }
+            wave_fence();
+        }
+
+        // ---- layer 1: acc[m] = W1^T (units 32m ...) x X^T, the inputs in chunks through LDS
+        f32x16 acc[MT];
+#pragma unroll
+        for (int m = 0; m < MT; m++)
+#pragma unroll
+            for (int i = 0; i < 16; i++) acc[m][i] = 0.f;
+        uint4 wq1[MT];                                                               // layer 1's weights, one k step ahead
+#pragma unroll
+        for (int m = 0; m < MT; m++) wq1[m] = load_frag(p.w1, (size_t)m * KS1, lane16);
+        for (int k0 = 0; k0 < p.K1p; k0 += KC) {
+            const int kc = p.K1p - k0 < KC ? p.K1p - k0 : KC;                        // a multiple of 16
+            const uint32_t magic = (uint32_t)(0x100000000ull / (uint32_t)kc) + 1u;   // f / kc = umulhi(f, magic): f < 2^14, f kc < 2^32
+            const int nf = TILE * kc;
+#pragma unroll 4
+            for (int f = lane; f < nf; f += 64) {
+                const int rr = (int)__umulhi((uint32_t)f, magic), c = f - rr * kc, k = k0 + c;
+                float v = 0.f;
+                if (rr < nrow && k < K1) {
+                    if (!p.compact) {
+                        v = rowsf[(size_t)(row0 + rr) * K1 + k];
+                    } else {
+                        const uint64_t off = (uint64_t)ri[rr * 4] | ((uint64_t)ri[rr * 4 + 1] << 32);
+                        if (k < B) v = (float)((cwords[off + B + 1 + (k >> 5)] >> (k & 31)) & 1u);      // connected
+                        else if (k < 2 * B) v = __uint_as_float(cwords[off + (k - B)]);                // dr
+                        else if (k < 4 * B) v = ri[rr * 4 + 2] ? __uint_as_float(cwords[off + (uint64_t)(U - (int)ri[rr * 4 + 3]) * CW + (k - 2 * B)]) : 0.f;
+                        else v = __uint_as_float(cwords[off + B]);                                    // utility
+                    }
+                }
+                xs[rr * XS + c] = (__bf16)v;
+            }
+            wave_fence();
+            for (int s = 0; s < (kc >> 4); s++) {
+                const bf16x8 b = as_frag(*reinterpret_cast<const uint4 *>(xs + r * XS + 16 * s + 8 * h));
+                const int ksn = (k0 >> 4) + s + 1 < KS1 ? (k0 >> 4) + s + 1 : KS1 - 1;          // (the last step re-reads itself)
+                uint4 nx[MT];
+#pragma unroll
+                for (int m = 0; m < MT; m++) nx[m] = load_frag(p.w1, (size_t)m * KS1 + ksn, lane16);
+#pragma unroll
+                for (int m = 0; m < MT; m++) acc[m] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(as_frag(wq1[m]), b, acc[m], 0, 0, 0);
+#pragma unroll
+                for (int m = 0; m < MT; m++) wq1[m] = nx[m];
+            }
+            wave_fence();
+        }
+
+        // ---- h1 = bf16(act(. + b1)) as the B fragments of layer 2 (whose first weights are on their way meanwhile)
+        // The weights of layers 2 and 3 come through a ring of D fragments, D MFMAs ahead of their use: fragment q is loaded into
+        // slot q % D right after the MFMA that read the slot.  (The scheduling barriers pin that order: left alone the compiler
+        // hoists every load of a layer to its top -- 512 registers and spills.)
+        uint4 ring[D];
+#pragma unroll
+        for (int i = 0; i < D; i++) ring[i] = load_frag(p.w2, i, lane16);
+        bf16x8 h1[MT][2];
+#pragma unroll
+        for (int t = 0; t < MT; t++) {
+            h1[t][0] = next_fragment<RELU>(acc[t], 0, p.b1 + 32 * t + 4 * h);
+            h1[t][1] = next_fragment<RELU>(acc[t], 1, p.b1 + 32 * t + 4 * h);
+            asm volatile("" : "+v"(h1[t][0]), "+v"(h1[t][1]));
+            __builtin_amdgcn_sched_barrier(0);                   // (tile by tile: 16 registers become 8, not every bias load first)
+        }
+
+        // ---- layer 2, one tile of 32 units at a time
+        bf16x8 h2[MT][2];
+        {
+#pragma unroll
+            for (int m = 0; m < MT; m++) {
+                f32x16 a2;
+#pragma unroll
+                for (int e = 0; e < 16; e++) a2[e] = 0.f;
+#pragma unroll
+                for (int ks = 0; ks < KS2; ks++) {
+                    const int q = m * KS2 + ks;
+                    a2 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(as_frag(ring[q % D]), h1[ks >> 1][ks & 1], a2, 0, 0, 0);
+                    ring[q % D] = q + D < Q2 ? load_frag(p.w2, q + D, lane16) : load_frag(p.w3, q + D - Q2, lane16);   // behind layer 2: layer 3's first
+                    __builtin_amdgcn_sched_barrier(0);
+                }
+                h2[m][0] = next_fragment<RELU>(a2, 0, p.b2 + 32 * m + 4 * h);
+                h2[m][1] = next_fragment<RELU>(a2, 1, p.b2 + 32 * m + 4 * h);
+                asm volatile("" : "+v"(h2[m][0]), "+v"(h2[m][1]));       // converted HERE: sunk towards layer 3, the 16 raw floats stay live instead of 8 registers
+                __builtin_amdgcn_sched_barrier(0);
+            }
+        }
+
+        // ---- layer 3 and the choice, 32 logits of every row at a time
+        int hd = 0, a = 0, best_a = 0;                           // the walk's state: head, action within it
+        float best_y = -INFINITY, best_l = 0.f, first_l = 0.f, mx = -INFINITY, sm = 0.f;
+        uint32_t rnd[4] = {0u, 0u, 0u, 0u};
+        const uint32_t grow = (uint32_t)(p.row_base + myrow);
+        for (int nt = 0; nt < p.NT3; nt++) {
+            f32x16 a3;
+#pragma unroll
+            for (int i = 0; i < 16; i++) a3[i] = 0.f;
+#pragma unroll
+            for (int ks = 0; ks < KS2; ks++) {
+                a3 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(as_frag(ring[ks % D]), h2[ks >> 1][ks & 1], a3, 0, 0, 0);      // (Q2 and KS2 are multiples of D)
+                const int f = nt * KS2 + ks + D;
+                ring[ks % D] = load_frag(p.w3, f < p.NT3 * KS2 ? f : 0, lane16);                // (behind the last: any valid one)
+                __builtin_amdgcn_sched_barrier(0);
+            }
+            const float *bias = p.b3 + 32 * nt + 4 * h;
+#pragma unroll
+            for (int g = 0; g < 4; g++) {
+                const float4 bv = *reinterpret_cast<const float4 *>(bias + 8 * g);
+                float *d = lt + r * LT + 8 * g + 4 * h;
+                d[0] = a3[4 * g + 0] + bv.x; d[1] = a3[4 * g + 1] + bv.y; d[2] = a3[4 * g + 2] + bv.z; d[3] = a3[4 * g + 3] + bv.w;
+            }
+            wave_fence();
+            const int ncol = p.N3 - 32 * nt < 32 ? p.N3 - 32 * nt : 32;
+            if (lane < TILE && have) {
+                for (int c = 0; c < ncol; c++) {
+                    const float x = lt[r * LT + c];
+                    float y = x;
+                    if (p.sample) {
+                        if ((a & 3) == 0) philox4x32_10(grow, ((uint32_t)hd << 16) | (uint32_t)(a >> 2), p.step, DRAW_TAG, p.seed_lo, p.seed_hi, rnd);
+                        const uint32_t w = (a & 3) == 0 ? rnd[0] : (a & 3) == 1 ? rnd[1] : (a & 3) == 2 ? rnd[2] : rnd[3];
+                        // u in (0, 1): the f32 sum rounds the top values to 1.0, where the Gumbel draw would be infinite
+                        const float u = fminf(((float)(w >> 8) + 0.5f) * 5.9604644775390625e-8f, 0.99999994f);
+                        y = x - logf(-logf(u));
+                    }
+                    if (a == 0) first_l = x;
+                    if (y > best_y) { best_y = y; best_a = a; best_l = x; }       // strict: the FIRST maximum
+                    if (p.logp) {
+                        const float m2 = fmaxf(mx, x);
+                        sm = sm * expf(mx - m2) + expf(x - m2);
+                        mx = m2;
+                    }
+                    if (++a == NA) {
+                        const bool off = (p.multi ? slot : hd) >= p.num_active;    // unlisted slot / head: action 0
+                        const size_t at = (size_t)myrow * p.heads + hd;
+                        p.action[at] = (uint8_t)(off ? 0 : best_a);
+                        if (p.logp) p.logp[at] = (off ? first_l : best_l) - (mx + logf(sm));
+                        a = 0; hd++;
+                        best_y = -INFINITY; best_a = 0; mx = -INFINITY; sm = 0.f;
+                    }
+                }
+            }
+            if (p.logits) {
+                for (int i = lane; i < TILE * 32; i += 64) {
+                    const int rr = i >> 5, c = i & 31;
+                    if (rr < nrow && c < ncol) p.logits[(size_t)(row0 + rr) * p.N3 + 32 * nt + c] = lt[rr * LT + c];
+                }
+            }
+            wave_fence();
+        }
+    }
+}
+
+typedef void (*kernel_fn)(const Params);
+static kernel_fn pick(int mt, bool relu)
+{
+    switch (mt) {
+    case 1: return relu ? actor_kernel<1, true> : actor_kernel<1, false>;
+    case 2: return relu ? actor_kernel<2, true> : actor_kernel<2, false>;
+    case 4: return relu ? actor_kernel<4, true> : actor_kernel<4, false>;
+    default: return relu ? actor_kernel<8, true> : actor_kernel<8, false>;
+    }
+}
+
+static uint16_t bf16_rne(float f)
+{
+    uint32_t u;
+    memcpy(&u, &f, 4);
+    if ((u & 0x7FFFFFFFu) > 0x7F800000u) return (uint16_t)((u >> 16) | 0x40u);      // NaN stays a NaN
+    return (uint16_t)((u + 0x7FFFu + ((u >> 16) & 1u)) >> 16);
+}
+
+// A fragments of W^T for [tiles of 32 outputs][k steps of 16][lane][8]: lane (r, h) holds output 32 m + r and the inputs
+// 16 ks + 8h + j (natural: the B operand is read from LDS) or 16 ks + 8 (j >> 2) + 4h + (j & 3) (permuted: the B operand is the
+// previous layer's accumulator).  w is [in][out] row-major; everything outside [nin][nout] is zero.
+static void pack(std::vector<uint16_t> &dst, const float *w, int nin, int nout, int ksteps, int mtiles, bool permuted)
+{
+    dst.assign((size_t)mtiles * ksteps * 64 * 8, 0);
+    for (int m = 0; m < mtiles; m++)
+        for (int ks = 0; ks < ksteps; ks++)
+            for (int lane = 0; lane < 64; lane++)
+                for (int j = 0; j < 8; j++) {
+                    const int r = lane & 31, h = lane >> 5, o = 32 * m + r;
+                    const int k = 16 * ks + (permuted ? 8 * (j >> 2) + 4 * h + (j & 3) : 8 * h + j);
+                    if (k < nin && o < nout) dst[(((size_t)m * ksteps + ks) * 64 + lane) * 8 + j] = bf16_rne(w[(size_t)k * nout + o]);
+                }
+}
+
+}  // namespace dactor
+
+struct dcomp_actor {
+    int32_t kind, U, B, hidden, mt, relu, device;
+    int32_t K1, K1p, N3, NT3, heads, XS, lds_per_wave, max_blocks;
+    void *dev_mem;
+    const uint4 *w1, *w2, *w3;
+    const float *b1, *b2, *b3;
+};
+
+static int afail(int code, const char *fmt, ...) __attribute__((format(printf, 2, 3)));
+static int afail(int code, const char *fmt, ...)
+{
+    char buf[512];
+    va_list ap;
+    va_start(ap, fmt);
+    vsnprintf(buf, sizeof(buf), fmt, ap);
+    va_end(ap);
+    return dcomp::report(code, buf);
+}
+#define ACTOR_HIP_TRY(expr)                                                                          \
+    do {                                                                                             \
+        hipError_t e_ = (expr);                                                                      \
+        if (e_ != hipSuccess) return afail(DCOMP_EHIP, "%s failed: %s", #expr, hipGetErrorString(e_)); \
+    } while (0)
+
+extern "C" int dcomp_actor_create(const dcomp_actor_cfg *cfg, dcomp_actor **out)
+{
+    using namespace dactor;
+    if (out) *out = nullptr;
+    if (!cfg || !out) return afail(DCOMP_EINVAL, "dcomp_actor_create: cfg and out must not be NULL");
+    if (cfg->struct_size != (int32_t)sizeof(dcomp_actor_cfg))
+        return afail(DCOMP_EABI, "dcomp_actor_create: caller's dcomp_actor_cfg has %d bytes, the library's %d", cfg->struct_size, (int)sizeof(dcomp_actor_cfg));
+    // host-only validation first: nothing below touches HIP before the arguments are known to be good
+    if (cfg->obs_kind != DCOMP_MULTI && cfg->obs_kind != DCOMP_CENTRAL) return afail(DCOMP_EINVAL, "dcomp_actor_create: obs_kind %d is neither DCOMP_CENTRAL nor DCOMP_MULTI", cfg->obs_kind);
+    if (cfg->num_ue < 1 || cfg->num_bs < 1) return afail(DCOMP_EINVAL, "dcomp_actor_create: num_ue %d / num_bs %d must be >= 1", cfg->num_ue, cfg->num_bs);
+    if (cfg->hidden < 32 || cfg->hidden % 32) return afail(DCOMP_EINVAL, "dcomp_actor_create: hidden %d is not a multiple of 32 >= 32", cfg->hidden);
+    if (cfg->activation != DCOMP_ACT_TANH && cfg->activation != DCOMP_ACT_RELU) return afail(DCOMP_EINVAL, "dcomp_actor_create: unknown activation %d", cfg->activation);
+    if (!cfg->w1 || !cfg->b1 || !cfg->w2 || !cfg->b2 || !cfg->w3 || !cfg->b3) return afail(DCOMP_EINVAL, "dcomp_actor_create: a weight or bias pointer is NULL");
+    if (cfg->num_bs > DCOMP_MAX_BS) return afail(DCOMP_EUNSUPPORTED, "dcomp_actor_create: num_bs %d > %d", cfg->num_bs, DCOMP_MAX_BS);
+    if (cfg->num_ue > DCOMP_MAX_UE) return afail(DCOMP_EUNSUPPORTED, "dcomp_actor_create: num_ue %d > %d", cfg->num_ue, DCOMP_MAX_UE);
+    if (cfg->hidden > DCOMP_ACTOR_MAX_HIDDEN) return afail(DCOMP_EUNSUPPORTED, "dcomp_actor_create: hidden %d > %d", cfg->hidden, DCOMP_ACTOR_MAX_HIDDEN);
+    const bool multi = cfg->obs_kind == DCOMP_MULTI;
+    const int U = cfg->num_ue, B = cfg->num_bs, H = cfg->hidden;
+    const int K1 = multi ? 4 * B + 1 : U * (2 * B + 1), heads = multi ? 1 : U, N3 = heads * (B + 1);
+    if (K1 > DCOMP_ACTOR_MAX_IN) return afail(DCOMP_EUNSUPPORTED, "dcomp_actor_create: a central row of %d x %d has %d inputs > %d", U, B, K1, DCOMP_ACTOR_MAX_IN);
+    if (N3 > DCOMP_ACTOR_MAX_LOGITS) return afail(DCOMP_EUNSUPPORTED, "dcomp_actor_create: a central row of %d x %d has %d logits > %d", U, B, N3, DCOMP_ACTOR_MAX_LOGITS);
+
+    dcomp_actor *a = new dcomp_actor();
+    a->kind = cfg->obs_kind; a->U = U; a->B = B; a->hidden = H;
+    a->mt = H <= 32 ? 1 : H <= 64 ? 2 : H <= 128 ? 4 : 8;
+    a->relu = cfg->activation == DCOMP_ACT_RELU;
+    a->K1 = K1; a->K1p = (K1 + 15) & ~15; a->N3 = N3; a->NT3 = (N3 + 31) / 32; a->heads = heads;
+    const int kcp = a->K1p < KC ? a->K1p : KC;
+    a->XS = kcp + 8;                                         // row stride = an odd number of 16-byte slots: 16 rows, 16 slots
+    a->lds_per_wave = TILE * a->XS * 2 + TILE * LT * 4 + TILE * 16;
+    const int Hp = 32 * a->mt, KS2 = 2 * a->mt;
+    std::vector<uint16_t> p1, p2, p3;
+    pack(p1, cfg->w1, K1, H, a->K1p / 16, a->mt, false);
+    pack(p2, cfg->w2, H, H, KS2, a->mt, true);
+    pack(p3, cfg->w3, H, N3, KS2, a->NT3, true);
+    std::vector<float> bias((size_t)2 * Hp + 32 * a->NT3, 0.f);
+    memcpy(bias.data(), cfg->b1, sizeof(float) * H);
+    memcpy(bias.data() + Hp, cfg->b2, sizeof(float) * H);
+    memcpy(bias.data() + 2 * Hp, cfg->b3, sizeof(float) * N3);
+    auto up = [](size_t v) { return (v + 255) & ~(size_t)255; };
+    const size_t o1 = 0, o2 = up(o1 + p1.size() * 2), o3 = up(o2 + p2.size() * 2), ob = up(o3 + p3.size() * 2), total = ob + bias.size() * 4;
+    std::vector<unsigned char> img(total, 0);
+    memcpy(img.data() + o1, p1.data(), p1.size() * 2);
+    memcpy(img.data() + o2, p2.data(), p2.size() * 2);
+    memcpy(img.data() + o3, p3.data(), p3.size() * 2);
+    memcpy(img.data() + ob, bias.data(), bias.size() * 4);
+
+    hipError_t e = hipGetDevice(&a->device);
+    int cus = 0;
+    if (e == hipSuccess) e = hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, a->device);
+    if (e == hipSuccess) e = hipMalloc(&a->dev_mem, total);
+    if (e == hipSuccess) {
+        e = hipMemcpy(a->dev_mem, img.data(), total, hipMemcpyHostToDevice);
+        if (e != hipSuccess) (void)hipFree(a->dev_mem);
+    }
+    if (e != hipSuccess) {
+        delete a;
+        return afail(DCOMP_EHIP, "dcomp_actor_create: %s", hipGetErrorString(e));
+    }
+    a->max_blocks = (cus > 0 ? cus : 256) * 2;               // two workgroups of four waves per CU: two waves per SIMD
+    unsigned char *d = static_cast<unsigned char *>(a->dev_mem);
+    a->w1 = reinterpret_cast<const uint4 *>(d + o1); a->w2 = reinterpret_cast<const uint4 *>(d + o2); a->w3 = reinterpret_cast<const uint4 *>(d + o3);
+    a->b1 = reinterpret_cast<const float *>(d + ob); a->b2 = a->b1 + Hp; a->b3 = a->b2 + Hp;
+    *out = a;
+    return DCOMP_OK;
+}
+
+extern "C" int dcomp_actor_destroy(dcomp_actor *a)
+{
+    if (!a) return DCOMP_OK;
+    hipError_t e = hipFree(a->dev_mem);
+    delete a;
+    return e == hipSuccess ? DCOMP_OK : afail(DCOMP_EHIP, "dcomp_actor_destroy: hipFree failed: %s", hipGetErrorString(e));
+}
+
+extern "C" int dcomp_actor_actions(dcomp_actor *a, const dcomp_actor_run *r, const void *obs, uint8_t *action, void *stream)
+{
+    using namespace dactor;
+    if (!a || !r) return afail(DCOMP_EINVAL, "dcomp_actor_actions: handle and run must not be NULL");
+    if (r->struct_size != (int32_t)sizeof(dcomp_actor_run))
+        return afail(DCOMP_EABI, "dcomp_actor_actions: caller's dcomp_actor_run has %d bytes, the library's %d", r->struct_size, (int)sizeof(dcomp_actor_run));
+    if (r->obs_format != DCOMP_ACTOR_ROWS && r->obs_format != DCOMP_ACTOR_COMPACT) return afail(DCOMP_EINVAL, "dcomp_actor_actions: unknown obs_format %d", r->obs_format);
+    if (r->obs_format == DCOMP_ACTOR_COMPACT && a->kind != DCOMP_MULTI)
+        return afail(DCOMP_EUNSUPPORTED, "dcomp_actor_actions: the compact record exists for multi-agent observations only");
+    if (!obs || !action) return afail(DCOMP_EINVAL, "dcomp_actor_actions: obs and action must not be NULL");
+    if (r->num_envs < 1) return afail(DCOMP_EINVAL, "dcomp_actor_actions: num_envs %d < 1", r->num_envs);
+    if (r->num_active < 0 || r->num_active > a->U) return afail(DCOMP_EINVAL, "dcomp_actor_actions: num_active %d outside [0, %d]", r->num_active, a->U);
+    const int64_t rows = a->kind == DCOMP_MULTI ? (int64_t)r->num_envs * a->U : (int64_t)r->num_envs;
+    if (r->row_base < 0 || r->row_base + rows > 0x100000000ll)
+        return afail(DCOMP_EINVAL, "dcomp_actor_actions: decision rows %lld ... %lld do not fit the 32-bit draw counter word", (long long)r->row_base,
+                     (long long)(r->row_base + rows - 1));
+    Params p;
+    memset(&p, 0, sizeof(p));
+    p.obs = obs; p.action = action; p.logits = r->logits; p.logp = r->logp;
+    p.w1 = a->w1; p.w2 = a->w2; p.w3 = a->w3; p.b1 = a->b1; p.b2 = a->b2; p.b3 = a->b3;
+    p.rows = rows; p.tiles = (rows + TILE - 1) / TILE; p.row_base = r->row_base;
+    p.K1 = a->K1; p.K1p = a->K1p; p.XS = a->XS; p.N3 = a->N3; p.NT3 = a->NT3; p.heads = a->heads; p.B = a->B; p.U = a->U;
+    p.num_active = r->num_active; p.multi = a->kind == DCOMP_MULTI; p.compact = r->obs_format == DCOMP_ACTOR_COMPACT; p.sample = r->sample != 0;
+    p.step = r->step; p.seed_lo = (uint32_t)r->seed; p.seed_hi = (uint32_t)(r->seed >> 32);
+    p.lds_per_wave = a->lds_per_wave;
+    const int64_t want = (p.tiles + WAVES - 1) / WAVES;
+    const int grid = (int)(want < a->max_blocks ? want : a->max_blocks);
+    hipLaunchKernelGGL(pick(a->mt, a->relu != 0), dim3(grid), dim3(BLOCK), (size_t)a->lds_per_wave * WAVES, static_cast<hipStream_t>(stream), p);
+    ACTOR_HIP_TRY(hipGetLastError());
+    return DCOMP_OK;
+}

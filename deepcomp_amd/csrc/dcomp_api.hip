@@ -48,6 +48,8 @@ static int fail(int code, const char *fmt, ...)
     va_end(ap);
     return code;
 }
+// the other objects of the library (dcomp_actor.hip) report through the same thread-local text
+namespace dcomp { int report(int code, const char *msg) { return fail(code, "%s", msg); } }
 #define HIP_TRY(expr)                                                                              \
     do {                                                                                           \
         hipError_t e_ = (expr);                                                                    \

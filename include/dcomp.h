@@ -38,7 +38,7 @@
 #include <stddef.h>
 #include <stdint.h>
 
-#include "dcomp_types.h"      /* limits, enums, dcomp_cfg / dcomp_state / dcomp_out / dcomp_tape / dcomp_events */
+#include "dcomp_types.h"      /* limits, enums, dcomp_cfg / dcomp_state / dcomp_out / dcomp_tape / dcomp_events / dcomp_actor_cfg / dcomp_actor_run */
 
 #ifdef __cplusplus
 extern "C" {
@@ -250,6 +250,26 @@ int dcomp_pack_fragment(const float *obs, int64_t num_env_steps, int32_t num_ue,
 int dcomp_unpack_fragment(const uint32_t *packed, int64_t num_env_steps, int32_t num_ue, int32_t num_bs, float *obs, void *stream);
 
 int dcomp_selftest(int op, int width, const double *x, const double *y, double *out, int64_t n, void *stream);
+
+/* A trained fcnet actor on the device: what trainer.compute_action (simulation.py:347,375) does per env and step, for a whole batch in
+ * ONE launch -- observation tensor (rows, or the compact record) -> two hidden layers on the matrix cores, activations kept on
+ * chip -> logits -> greedy or sampled choice -> the uint8 action tensor [E][U] that dcomp_step takes.  The arithmetic is the
+ * specification:
+ *     x = bf16(observation row);  h1 = bf16(act(x W1 + b1));  h2 = bf16(act(h1 W2 + b2));  logits = h2 W3 + b3
+ * bf16 products, f32 accumulation, bias and activation in f32.  DCOMP_MULTI: one decision row per (env, UE slot), shared weights
+ * (DD-CoMP), one head; DCOMP_CENTRAL: one row per env, one head per UE.  Sampling (run.sample = 1) is Gumbel-max with counter-based
+ * draws: for (row, head, action a) word a & 3 of philox4x32_10(ctr = {(uint32) (row_base + row), head << 16 | a >> 2, step, 0x00AC7012},
+ * key = {seed lo, seed hi}) gives u = min(((w >> 8) + 0.5f) 2^-24, 1 - 2^-24) and g = -logf(-logf(u)); the action is the FIRST maximum of
+ * logits + g.  row_base + rows must not exceed 2^32 (DCOMP_EINVAL).
+ * dcomp_actor_create rounds the HOST weights to bf16 (nearest even; biases stay f32), lays them out for the kernel's MFMA fragments
+ * in device memory that the handle owns (allocated once, on the device current in the calling thread); it validates on the host
+ * before the first HIP call.  Limits: num_bs <= DCOMP_MAX_BS, num_ue <= DCOMP_MAX_UE, hidden <= 256, a central row of at most 1 024
+ * inputs and 512 logits (beyond: DCOMP_EUNSUPPORTED).  dcomp_actor_actions only enqueues on `stream` and allocates nothing;
+ * obs, action, run.logits and run.logp are device pointers; DCOMP_ACTOR_COMPACT gives bit-identical results to DCOMP_ACTOR_ROWS
+ * of the rows the record stands for. */
+int dcomp_actor_create(const dcomp_actor_cfg *cfg, dcomp_actor **out);
+int dcomp_actor_destroy(dcomp_actor *a);
+int dcomp_actor_actions(dcomp_actor *a, const dcomp_actor_run *r, const void *obs, uint8_t *action, void *stream);
 
 #ifndef DCOMP_BUILDING_LIBRARY
 /* callers compiled against this header create their handles through the guarded entry point (see "ABI guard" above) */

@@ -125,6 +125,43 @@ typedef struct dcomp_events {
 /* heuristic policies (deepcomp/agent/heuristics.py; see dcomp_heuristic_actions in dcomp.h) */
 enum { DCOMP_POLICY_3GPP = 0, DCOMP_POLICY_FULLCOMP = 1, DCOMP_POLICY_DYNAMIC = 2, DCOMP_POLICY_CLUSTER = 3 };
 
+/* A trained fcnet actor on the device (dcomp_actor_create / dcomp_actor_actions in dcomp.h): two hidden layers of one width and a
+ * categorical head per decision, bf16 products with f32 accumulation on the matrix cores.  Both structs carry their own size as
+ * their first field (anything else -> DCOMP_EABI); they are not part of the dcomp_create_v guard. */
+enum { DCOMP_ACT_TANH = 0, DCOMP_ACT_RELU = 1 };
+enum { DCOMP_ACTOR_ROWS = 0, DCOMP_ACTOR_COMPACT = 1 };
+#define DCOMP_ACTOR_MAX_HIDDEN 256
+#define DCOMP_ACTOR_MAX_IN     1024  /* inputs of a central row, U(2B+1) */
+#define DCOMP_ACTOR_MAX_LOGITS 512   /* logits of a central row, U(B+1) */
+
+typedef struct dcomp_actor dcomp_actor;
+
+typedef struct dcomp_actor_cfg {
+    int32_t struct_size;          /* sizeof(dcomp_actor_cfg) of the caller */
+    int32_t obs_kind;             /* DCOMP_MULTI: one decision row per (env, UE), 4B+1 inputs, ONE head of B+1 logits
+                                   * DCOMP_CENTRAL: one row per env, U(2B+1) inputs, U heads of B+1 logits (MultiDiscrete, central.py:28) */
+    int32_t num_ue, num_bs;       /* UE slots per env (max_ues of a dynamic env), stations */
+    int32_t hidden;               /* width of both hidden layers: a multiple of 32, 32 ... 256 */
+    int32_t activation;           /* DCOMP_ACT_TANH (RLlib's default) | DCOMP_ACT_RELU */
+    const float *w1, *b1;         /* HOST float32, [in][hidden] row-major (the layout of a TF / RLlib kernel: y = x W + b), [hidden] */
+    const float *w2, *b2;         /* [hidden][hidden], [hidden] */
+    const float *w3, *b3;         /* [hidden][heads*(B+1)], [heads*(B+1)] */
+} dcomp_actor_cfg;                /* the weights go to the HIP device that is current in the calling thread */
+
+typedef struct dcomp_actor_run {
+    int32_t struct_size;          /* sizeof(dcomp_actor_run) of the caller */
+    int32_t obs_format;           /* DCOMP_ACTOR_ROWS: the float tensor dcomp_reset / dcomp_step write;
+                                   * DCOMP_ACTOR_COMPACT (DCOMP_MULTI only): the record of dcomp_out.obs_compact / dcomp_pack_fragment */
+    int32_t num_envs, num_active; /* envs in this call; UEs listed (<= num_ue): slots / heads >= num_active get action 0 */
+    int32_t sample;               /* 0: greedy, the FIRST maximum logit (explore=False); 1: Gumbel-max draw from softmax(logits) */
+    uint32_t step;                /* draw counter word: a value the caller never reuses with the same seed (env.time + episode * horizon, say) */
+    uint64_t seed;
+    int64_t row_base;             /* global index of this call's first decision row: draws are keyed by row_base + local row, so a batch split
+                                   * over calls or GPUs (env_base * U) draws what the whole batch would */
+    float *logits;                /* optional device [rows][heads*(B+1)] f32: what the action was chosen from */
+    float *logp;                  /* optional device [rows][heads] f32: log-softmax of the chosen action (PPO's action_logp) */
+} dcomp_actor_run;
+
 #ifdef __cplusplus
 }
 #endif

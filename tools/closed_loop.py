@@ -4,7 +4,12 @@
 next action tensor -- everything stays in HBM, no per-env Python.  The policy is random-init and NOT part of the product;
 this only shows where the time goes once the env runs at ~10^8-10^9 env-steps/s.
 
-    python tools/closed_loop.py [--envs 65536] [--steps 200] [--dtype bf16]
+    python tools/closed_loop.py [--envs 65536] [--steps 200] [--dtype bf16] [--kind multi] [--actor hip [--compact]]
+
+--actor torch (default): the actor as torch ops (bf16 matmuls, Gumbel-max through torch.rand).  --actor hip: the same weights in
+deepcomp_amd.actor.FcnetActor -- one HIP kernel from observation tensor to action tensor -- and BOTH loops are timed in this
+process, one after the other on the same env.  --compact (multi-agent, hip): the env writes only the compact record
+(env.step_compact) and the actor reads it.
 """
 import argparse
 import sys
@@ -15,6 +20,7 @@ import torch
 
 from deepcomp_amd import scenarios
 from deepcomp_amd.entities import build_from_scenario
+from deepcomp_amd.actor import FcnetActor
 from deepcomp_amd.env import BatchedMobileEnv
 
 ap = argparse.ArgumentParser()
@@ -23,49 +29,77 @@ ap.add_argument('--ues', type=int, default=32)
 ap.add_argument('--bs', type=int, default=10)
 ap.add_argument('--steps', type=int, default=200)
 ap.add_argument('--dtype', default='bf16', choices=['bf16', 'fp32'])
+ap.add_argument('--kind', default='multi', choices=['multi', 'central'])
+ap.add_argument('--actor', default='torch', choices=['torch', 'hip'])
+ap.add_argument('--compact', action='store_true', help='hip actor, multi-agent: the env writes only the compact record and the actor reads it')
 a = ap.parse_args()
+if a.compact and (a.actor != 'hip' or a.kind != 'multi'):
+    ap.error('--compact needs --actor hip and --kind multi')
 
 dev = torch.device('cuda', 0)
 E, U, B = a.envs, a.ues, a.bs
 scn = scenarios.grid_map(B, 'mixed').with_ues(num_slow=U)
 m, bs, ues = build_from_scenario(scn)
-env = BatchedMobileEnv(m, bs, ues, 'multi', num_envs=E, seed=42, episode_length=100, rng='philox', rand_episodes=True, device=dev)
+multi = a.kind == 'multi'
+env = BatchedMobileEnv(m, bs, ues, a.kind, num_envs=E, seed=42, episode_length=100, rng='philox', rand_episodes=True, device=dev)
 dt = torch.bfloat16 if a.dtype == 'bf16' else torch.float32
-D = 4 * B + 1
-g = torch.Generator(device=dev).manual_seed(0)
-W1 = (torch.randn(D, 256, generator=g, device=dev) / D ** 0.5).to(dt)
-W2 = (torch.randn(256, 256, generator=g, device=dev) / 16).to(dt)
-W3 = (torch.randn(256, B + 1, generator=g, device=dev) / 16).to(dt)
+D = 4 * B + 1 if multi else U * (2 * B + 1)
+heads = 1 if multi else U
+host_w = FcnetActor.random_weights(a.kind, U, B, 256, seed=0)           # N(0, 1 / fan_in) kernels, zero biases
+W1, W2, W3 = (torch.from_numpy(host_w[n]).to(dev).to(dt) for n in ('w1', 'w2', 'w3'))
 
 
-def policy(obs):                                   # obs [E, U, 4B+1] f32 in HBM -> uint8 actions [E, U]
-    x = obs.view(E * U, D).to(dt)
+def policy(obs):                                   # obs [E, U, 4B+1] / [E, U(2B+1)] f32 in HBM -> uint8 actions [E, U]
+    x = obs.view(-1, D).to(dt)
     h = torch.tanh(torch.tanh(x @ W1) @ W2)
-    logits = (h @ W3).float()
+    logits = (h @ W3).float().view(-1, heads, B + 1)
     gumbel = -torch.log(-torch.log(torch.rand_like(logits).clamp_(1e-20, 1.0)))
-    return (logits + gumbel).argmax(dim=1).to(torch.uint8).view(E, U)
+    return (logits + gumbel).argmax(dim=-1).to(torch.uint8).view(E, U)
 
 
-def run(n, with_policy):
-    obs = env.reset()
+hip = FcnetActor(a.kind, U, B, host_w, device=dev) if a.actor == 'hip' else None
+packed = torch.zeros((E, env.compact_words), dtype=torch.int32, device=dev) if a.compact else None
+act_buf = torch.zeros((E, U), dtype=torch.uint8, device=dev)
+
+
+def run(n, actor):
+    """n steps of the loop; actor: None (a fixed action tensor), 'torch' or 'hip'."""
+    compact = actor == 'hip' and a.compact
+    obs = env.reset_compact(packed) if compact else env.reset()
     act = torch.zeros((E, U), dtype=torch.uint8, device=dev)
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     for t in range(n):
         if t and t % 100 == 0:
-            obs = env.reset()
-        if with_policy:
+            obs = env.reset_compact(packed) if compact else env.reset()
+        if actor == 'torch':
             act = policy(obs)
-        obs = env.step(act)[0]
+        elif actor == 'hip':
+            act = hip.act(env, obs=packed if compact else None, compact=compact, out=act_buf)
+        if compact:
+            env.step_compact(act, packed, env.reward)
+        else:
+            obs = env.step(act)[0]
     torch.cuda.synchronize()
     return (time.perf_counter() - t0) / n
 
 
-run(20, True)
-t_env = run(a.steps, False)
-t_all = run(a.steps, True)
+def report(name, t):
+    print(f'{name:<34}: {t * 1e3:8.3f} ms/step  {E / t:.3e} env-steps/s  ({E * U / t:.3e} agent-steps/s)  env share {100 * t_env / t:.1f} %')
+
+
+run(20, 'torch')
+if hip is not None:
+    run(20, 'hip')
+t_env = run(a.steps, None)
+print(f'{E} envs x {U} UE x {B} BS ({a.kind}), actor 2x256 tanh, sampled actions')
+print(f'{"env only":<34}: {t_env * 1e3:8.3f} ms/step  {E / t_env:.3e} env-steps/s')
+t_torch = run(a.steps, 'torch')
+report(f'env + torch actor ({a.dtype})', t_torch)
+if hip is not None:
+    t_hip = run(a.steps, 'hip')
+    report('env + hip actor' + (' (compact record)' if a.compact else ''), t_hip)
+    t_torch2 = run(a.steps, 'torch')               # the torch loop again: drift of the clocks between the two measurements
+    report(f'env + torch actor ({a.dtype}), again', t_torch2)
+    print(f'hip actor loop vs torch actor loop: {min(t_torch, t_torch2) / t_hip:.2f} x')
 env.check()
-print(f'{E} envs x {U} UE x {B} BS, actor 2x256 tanh ({a.dtype}), sampled actions')
-print(f'env only          : {t_env * 1e3:8.3f} ms/step  {E / t_env:.3e} env-steps/s')
-print(f'env + policy loop : {t_all * 1e3:8.3f} ms/step  {E / t_all:.3e} env-steps/s  ({E * U / t_all:.3e} agent-steps/s)')
-print(f'share of the env in the loop: {100 * t_env / t_all:.1f} %')
