@@ -84,12 +84,26 @@ class DcompActorRun(ctypes.Structure):
                 ('num_active', ctypes.c_int32), ('sample', ctypes.c_int32), ('step', ctypes.c_uint32), ('seed', ctypes.c_uint64),
                 ('row_base', ctypes.c_int64), ('logits', ctypes.c_void_p), ('logp', ctypes.c_void_p)]
 
+
+class DcompActorValueCfg(ctypes.Structure):
+    _fields_ = [('struct_size', ctypes.c_int32), ('shared', ctypes.c_int32), ('w1', _fp), ('b1', _fp), ('w2', _fp), ('b2', _fp),
+                ('wv', _fp), ('bv', _fp)]
+
+
+class DcompGaeArgs(ctypes.Structure):
+    _fields_ = [('struct_size', ctypes.c_int32), ('num_steps', ctypes.c_int32), ('num_rows', ctypes.c_int64),
+                ('gamma', ctypes.c_float), ('lambda', ctypes.c_float), ('reward', ctypes.c_void_p), ('vf', ctypes.c_void_p),
+                ('last_vf', ctypes.c_void_p), ('end', ctypes.c_void_p), ('advantages', ctypes.c_void_p),
+                ('value_targets', ctypes.c_void_p)]
+
+
 EXPORTS = ['dcomp_abi_version', 'dcomp_create_v', 'dcomp_create', 'dcomp_destroy', 'dcomp_state_sizes', 'dcomp_obs_dim', 'dcomp_reset', 'dcomp_step',
            'dcomp_step_dyn', 'dcomp_num_ue',
            'dcomp_rollout', 'dcomp_rollout_ex', 'dcomp_rollout_is_fused', 'dcomp_rollout_fused_for', 'dcomp_lanes_per_env', 'dcomp_needs_conn_hi', 'dcomp_step_kernel_name', 'dcomp_check', 'dcomp_time', 'dcomp_episode', 'dcomp_set_episode', 'dcomp_set_seed', 'dcomp_set_tape', 'dcomp_get_counters', 'dcomp_set_counters', 'dcomp_mt_draw_tape',
            'dcomp_connect_threshold', 'dcomp_connect_boundary_sq', 'dcomp_last_error', 'dcomp_version', 'dcomp_selftest', 'dcomp_heuristic_actions', 'dcomp_set_policy',
            'dcomp_fragment_words', 'dcomp_pack_fragment', 'dcomp_unpack_fragment',
-           'dcomp_actor_create', 'dcomp_actor_destroy', 'dcomp_actor_actions']
+           'dcomp_actor_create', 'dcomp_actor_destroy', 'dcomp_actor_actions',
+           'dcomp_actor_set_value', 'dcomp_actor_actions_v', 'dcomp_gae']
 
 _lib = None
 
@@ -165,6 +179,10 @@ def load():
         L.dcomp_actor_create.argtypes = [ctypes.POINTER(DcompActorCfg), ctypes.POINTER(vp)]
         L.dcomp_actor_destroy.argtypes = [vp]
         L.dcomp_actor_actions.argtypes = [vp, ctypes.POINTER(DcompActorRun), vp, vp, vp]
+    if hasattr(L, 'dcomp_actor_set_value'):
+        L.dcomp_actor_set_value.argtypes = [vp, ctypes.POINTER(DcompActorValueCfg)]
+        L.dcomp_actor_actions_v.argtypes = [vp, ctypes.POINTER(DcompActorRun), vp, vp, vp, vp]
+        L.dcomp_gae.argtypes = [ctypes.POINTER(DcompGaeArgs), vp]
     if os.environ.get('DCOMP_LIB'):              # timing variants built from older sources lack the newest entry points
         EXPORTS[:] = [n for n in EXPORTS if hasattr(L, n)]
     for name in EXPORTS:

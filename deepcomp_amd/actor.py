@@ -1,4 +1,4 @@
-"""A trained fcnet actor on the device (include/dcomp.h: dcomp_actor_create / dcomp_actor_actions).
+"""A trained fcnet actor on the device (include/dcomp.h: dcomp_actor_create / dcomp_actor_actions / dcomp_actor_actions_v).
 
 What the reference does with a trained policy -- ``trainer.compute_action(obs, policy_id=...)`` per env and step
 (util/simulation.py:347,375,512-541) -- for the whole batch in one HIP launch: the observation tensor the env kernel wrote (rows,
@@ -9,8 +9,12 @@ the activations kept on chip, and out comes the uint8 action tensor ``env.step``
     act = actor.act(env)                               # uint8 [E, U], feed straight into env.step(act)
 
 ``multi``: one decision row per (env, UE slot), the weights shared across UEs (DD-CoMP), one categorical head of B + 1 actions.
-``central``: one row per env, U heads (MultiDiscrete, central.py:28).  D3-CoMP's per-UE networks, the value head and training are
-not covered.
+``central``: one row per env, U heads (MultiDiscrete, central.py:28).  D3-CoMP's per-UE networks and training are not covered.
+
+The value function of a PPO policy rides in the same launch once attached (``value_weights=`` / ``set_value``): RLlib's fcnet has it
+as a trunk of its own (``fc_value_1``, ``fc_value_2``, ``value_out``: PPO's default, vf_share_layers=False) or as ``value_out`` on
+the actor's second hidden layer (shared).  ``actions(..., vf=buf)`` then also writes the value predictions, ``value(obs)`` is the
+value-only call (the bootstrap of a sample batch); deepcomp_amd.sampler collects whole PPO sample batches with them.
 
 The arithmetic is the specification, and ``reference_logits`` spells it out in torch on the CPU (as agents.py does for the
 heuristics): x = bf16(obs row); h1 = bf16(act(x W1 + b1)); h2 = bf16(act(h1 W2 + b2)); logits = h2 W3 + b3 -- bf16 products, f32
@@ -25,6 +29,7 @@ import torch
 from . import _lib
 
 _NAMES = ('w1', 'b1', 'w2', 'b2', 'w3', 'b3')
+_VALUE_TRUNK, _VALUE_OUT = ('w1', 'b1', 'w2', 'b2'), ('wv', 'bv')
 DRAW_TAG = 0x00AC7012
 
 
@@ -59,7 +64,7 @@ def gumbel_noise(philox, seed, step, rows, heads, num_actions):
 class FcnetActor:
     """RLlib's default fcnet actor (two hidden layers, categorical heads) running as one HIP kernel."""
 
-    def __init__(self, kind, num_ue, num_bs, weights, activation='tanh', device='cuda'):
+    def __init__(self, kind, num_ue, num_bs, weights, activation='tanh', device='cuda', value_weights=None):
         self.kind = _lib.MULTI if kind in ('multi', _lib.MULTI) else _lib.CENTRAL
         self.U, self.B = int(num_ue), int(num_bs)
         self.activation = activation
@@ -92,6 +97,33 @@ class FcnetActor:
         with torch.cuda.device(self.device):
             _lib.check(L.dcomp_actor_create(ctypes.byref(cfg), ctypes.byref(h)))
         self._h = h
+        self.value_weights, self.value_shared = None, None
+        if value_weights is not None:
+            self.set_value(value_weights, shared='w1' not in value_weights)
+
+    def set_value(self, weights, shared=False):
+        """Attach the value function, once per actor.  shared=False: a trunk of its own, weights 'w1' [in][hidden], 'b1', 'w2', 'b2'
+        (fc_value_1 / fc_value_2) and 'wv' [hidden], 'bv' [1] (value_out); shared=True (vf_share_layers): 'wv' and 'bv' only, on
+        the actor's own second hidden layer."""
+        names = _VALUE_OUT if shared else _VALUE_TRUNK + _VALUE_OUT
+        missing = [n for n in names if n not in weights]
+        if missing:
+            raise ValueError(f"value weights lack {missing}")
+        if shared and any(n in weights for n in _VALUE_TRUNK):
+            raise ValueError("shared=True takes 'wv' and 'bv' only")
+        w = {n: np.ascontiguousarray(np.asarray(weights[n], dtype=np.float32)) for n in names}
+        w['wv'], w['bv'] = np.ascontiguousarray(w['wv'].reshape(-1)), np.ascontiguousarray(w['bv'].reshape(-1))
+        H = self.hidden
+        shapes = {'w1': (self.num_in, H), 'b1': (H,), 'w2': (H, H), 'b2': (H,), 'wv': (H,), 'bv': (1,)}
+        for n in names:
+            if w[n].shape != shapes[n]:
+                raise ValueError(f"value {n} has shape {w[n].shape}, expected {shapes[n]}")
+        fp = ctypes.POINTER(ctypes.c_float)
+        ptr = lambda n: w[n].ctypes.data_as(fp) if n in w else None      # noqa: E731
+        cfg = _lib.DcompActorValueCfg(ctypes.sizeof(_lib.DcompActorValueCfg), 1 if shared else 0, *[ptr(n) for n in _VALUE_TRUNK + _VALUE_OUT])
+        with torch.cuda.device(self.device):
+            _lib.check(self._L.dcomp_actor_set_value(self._h, ctypes.byref(cfg)))
+        self.value_weights, self.value_shared = w, bool(shared)
 
     def __del__(self):
         h = getattr(self, '_h', None)
@@ -108,6 +140,18 @@ class FcnetActor:
         out = {}
         for n in _NAMES:
             std = bias_std if n[0] == 'b' else shapes[n][0] ** -0.5
+            out[n] = (torch.randn(shapes[n], generator=g) * std).numpy()
+        return out
+
+    @staticmethod
+    def random_value_weights(kind, num_ue, num_bs, hidden=256, seed=0, bias_std=0.0, shared=False):
+        """Random-init value weights (as random_weights; value_out N(0, 1 / hidden)) for tools and tests."""
+        g = torch.Generator().manual_seed(int(seed) + 0x5EED)
+        nin = layer_shapes(kind, num_ue, num_bs, hidden)[0]
+        shapes = {'w1': (nin, hidden), 'b1': (hidden,), 'w2': (hidden, hidden), 'b2': (hidden,), 'wv': (hidden,), 'bv': (1,)}
+        out = {}
+        for n in (_VALUE_OUT if shared else _VALUE_TRUNK + _VALUE_OUT):
+            std = bias_std if n[0] == 'b' else (hidden if n == 'wv' else shapes[n][0]) ** -0.5
             out[n] = (torch.randn(shapes[n], generator=g) * std).numpy()
         return out
 
@@ -135,9 +179,35 @@ class FcnetActor:
             raise ValueError("more than two hidden layers")
         return out
 
+    @staticmethod
+    def map_rllib_value_weights(weights):
+        """The value branch of RLlib's fcnet weight dict -> the value arrays of set_value: 'fc_value_1', 'fc_value_2' -> w1, b1, w2,
+        b2 and 'value_out' (kernel [hidden][1]) -> wv [hidden], bv [1].  With vf_share_layers the dict has value_out only, and so
+        has the result (set_value(..., shared=True))."""
+        want = {'fc_value_1/kernel': 'w1', 'fc_value_1/bias': 'b1', 'fc_value_2/kernel': 'w2', 'fc_value_2/bias': 'b2',
+                'value_out/kernel': 'wv', 'value_out/bias': 'bv'}
+        out = {}
+        for key, val in weights.items():
+            k = key[:-2] if key.endswith(':0') else key
+            for suffix, name in want.items():
+                if k == suffix or k.endswith('/' + suffix):
+                    if name in out:
+                        raise ValueError(f"two entries for {suffix}")
+                    out[name] = np.asarray(val, dtype=np.float32)
+        if 'wv' not in out or 'bv' not in out:
+            raise ValueError("no entry for value_out: the weights have no value branch")
+        trunk = [n for n in _VALUE_TRUNK if n in out]
+        if trunk and len(trunk) != len(_VALUE_TRUNK):
+            raise ValueError(f"the value trunk is incomplete: only {trunk} of fc_value_1 / fc_value_2")
+        if any(k.endswith('fc_value_3/kernel') or k.endswith('fc_value_3/kernel:0') for k in weights):
+            raise ValueError("more than two hidden layers")
+        out['wv'], out['bv'] = out['wv'].reshape(-1), out['bv'].reshape(-1)
+        return out
+
     @classmethod
-    def from_rllib_weights(cls, kind, num_ue, num_bs, weights, activation='tanh', device='cuda'):
-        return cls(kind, num_ue, num_bs, cls.map_rllib_weights(weights), activation, device)
+    def from_rllib_weights(cls, kind, num_ue, num_bs, weights, activation='tanh', device='cuda', with_value=False):
+        return cls(kind, num_ue, num_bs, cls.map_rllib_weights(weights), activation, device,
+                   value_weights=cls.map_rllib_value_weights(weights) if with_value else None)
 
     # ------------------------------------------------------------------ the specification
     @staticmethod
@@ -159,6 +229,34 @@ class FcnetActor:
         h = _bf16(act(h @ _bf16(w['w2']) + w['b2']))
         return h @ _bf16(w['w3']) + w['b3']
 
+    @staticmethod
+    def reference_value_of(weights, value_weights, obs_rows, activation='tanh', form='bf16'):
+        """The value's arithmetic in torch on the CPU, the twin of reference_logits_of: [rows].  value_weights with 'w1' ... 'b2': a
+        trunk of its own; without: value_out on the actor's second hidden layer (weights' w1 ... b2)."""
+        act = torch.tanh if activation == 'tanh' else torch.relu
+        trunk = value_weights if 'w1' in value_weights else weights
+        w = {n: torch.as_tensor(np.asarray(trunk[n], dtype=np.float32)) for n in _VALUE_TRUNK}
+        wv = torch.as_tensor(np.asarray(value_weights['wv'], dtype=np.float32)).reshape(-1)
+        bv = torch.as_tensor(np.asarray(value_weights['bv'], dtype=np.float32)).reshape(-1)[0]
+        x = _bf16(torch.as_tensor(np.asarray(obs_rows, dtype=np.float32)).reshape(-1, w['w1'].shape[0]))
+        if form == 'float64':
+            d = torch.float64
+            h = act(x.to(d) @ _bf16(w['w1']).to(d) + w['b1'].to(d))
+            h = act(h @ _bf16(w['w2']).to(d) + w['b2'].to(d))
+            return h @ _bf16(wv).to(d) + bv.to(d)
+        if form != 'bf16':
+            raise ValueError("form is 'bf16' or 'float64'")
+        h = _bf16(act(x @ _bf16(w['w1']) + w['b1']))
+        h = _bf16(act(h @ _bf16(w['w2']) + w['b2']))
+        return h @ _bf16(wv) + bv
+
+    def reference_value(self, obs_rows, form='bf16'):
+        if self.value_weights is None:
+            raise ValueError("the actor has no value function (set_value)")
+        if torch.is_tensor(obs_rows):
+            obs_rows = obs_rows.detach().cpu().numpy()
+        return self.reference_value_of(self.weights, self.value_weights, obs_rows, self.activation, form)
+
     def reference_logits(self, obs_rows, form='bf16'):
         if torch.is_tensor(obs_rows):
             obs_rows = obs_rows.detach().cpu().numpy()
@@ -173,10 +271,25 @@ class FcnetActor:
         if not isinstance(t, torch.Tensor) or t.dtype != dtype or t.device != self.device or not t.is_contiguous() or t.numel() != numel:
             raise ValueError(f"{what} must be a contiguous {dtype} tensor with {numel} elements on {self.device}")
 
-    def actions(self, obs, *, compact=False, sample=True, seed=0, step=0, row_base=0, num_active=None, out=None, logits=None, logp=None):
+    def actions(self, obs, *, compact=False, sample=True, seed=0, step=0, row_base=0, num_active=None, out=None, logits=None, logp=None,
+                vf=None):
         """Actions for a batch of observations.  obs: float32 [E, U, 4B+1] (multi) / [E, U(2B+1)] (central), or with compact=True
         the int32 record [E, U(B+2)+2B] of env.step_compact.  Returns uint8 [E, U].  logits [rows, heads*(B+1)] / logp [rows, heads]
-        (float32, optional) receive what the action was chosen from / the log-probability of the chosen action."""
+        (float32, optional) receive what the action was chosen from / the log-probability of the chosen action; vf [rows] (float32,
+        optional, needs a value function) the value predictions, from the same launch."""
+        return self._launch(obs, compact, sample, seed, step, row_base, num_active, out, logits, logp, vf, True)
+
+    def value(self, obs, *, compact=False, out=None):
+        """The value predictions alone (float32 [rows]): the bootstrap value of a sample batch's last observation.  The policy's
+        head and the draws are skipped."""
+        E, rows = self._batch(obs, compact)
+        if out is None:
+            out = torch.empty(rows, dtype=torch.float32, device=self.device)
+        self._launch(obs, compact, False, 0, 0, 0, None, None, None, None, out, False)
+        return out
+
+    def _batch(self, obs, compact):
+        """(envs, decision rows) of an observation tensor, after its pointer, dtype and size checks."""
         if compact:
             if self.kind != _lib.MULTI:
                 raise NotImplementedError("compact observation records exist for multi-agent observations only")
@@ -188,10 +301,18 @@ class FcnetActor:
             raise ValueError(f"obs must hold a whole number of envs of {per_env} elements")
         E = obs.numel() // per_env
         self._check(obs, dtype, E * per_env, 'obs')
-        rows = E * self.U if self.kind == _lib.MULTI else E
-        if out is None:
-            out = torch.empty((E, self.U), dtype=torch.uint8, device=self.device)
-        self._check(out, torch.uint8, E * self.U, 'out')
+        return E, (E * self.U if self.kind == _lib.MULTI else E)
+
+    def _launch(self, obs, compact, sample, seed, step, row_base, num_active, out, logits, logp, vf, policy):
+        E, rows = self._batch(obs, compact)
+        if policy:
+            if out is None:
+                out = torch.empty((E, self.U), dtype=torch.uint8, device=self.device)
+            self._check(out, torch.uint8, E * self.U, 'out')
+        if vf is not None:
+            if self.value_weights is None:
+                raise ValueError("the actor has no value function (set_value)")
+            self._check(vf, torch.float32, rows, 'vf')
         if logits is not None:
             self._check(logits, torch.float32, rows * self.num_logits, 'logits')
         if logp is not None:
@@ -201,11 +322,16 @@ class FcnetActor:
                                  int(seed) & 0xFFFFFFFFFFFFFFFF, int(row_base),
                                  logits.data_ptr() if logits is not None else None, logp.data_ptr() if logp is not None else None)
         with torch.cuda.device(self.device):
-            _lib.check(self._L.dcomp_actor_actions(self._h, ctypes.byref(run), ctypes.c_void_p(obs.data_ptr()),
-                                                   ctypes.c_void_p(out.data_ptr()), self._stream()))
+            if vf is None:
+                _lib.check(self._L.dcomp_actor_actions(self._h, ctypes.byref(run), ctypes.c_void_p(obs.data_ptr()),
+                                                       ctypes.c_void_p(out.data_ptr()), self._stream()))
+            else:
+                _lib.check(self._L.dcomp_actor_actions_v(self._h, ctypes.byref(run), ctypes.c_void_p(obs.data_ptr()),
+                                                         ctypes.c_void_p(out.data_ptr()) if policy else None,
+                                                         ctypes.c_void_p(vf.data_ptr()), self._stream()))
         return out
 
-    def act(self, env, sample=True, obs=None, compact=False, out=None):
+    def act(self, env, sample=True, obs=None, compact=False, out=None, logp=None, vf=None):
         """The actor's actions on env.obs (or on `obs`, e.g. the record env.step_compact wrote: compact=True) as the tensor
         env.step takes.  Draws are keyed by the env's seed, step = env.time + episode * episode_length and the GLOBAL decision row
         (env_id_base * U on a sharded env): reproducible, and independent of how the env axis is split over GPUs."""
@@ -214,4 +340,4 @@ class FcnetActor:
         rows_per_env = self.U if self.kind == _lib.MULTI else 1
         return self.actions(env.obs if obs is None else obs, compact=compact, sample=sample, seed=env.seed_value,
                             step=env.time + max(env.episode, 0) * env.episode_length, row_base=env.env_id_base * rows_per_env,
-                            num_active=env.num_ue, out=out)
+                            num_active=env.num_ue, out=out, logp=logp, vf=vf)

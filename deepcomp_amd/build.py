@@ -3,7 +3,7 @@
     python -m deepcomp_amd.build [--force] [--jobs N]
 
 One object per base-station count listed in csrc/dcomp_blist.h (all UE-group widths inside), compiled
-in parallel, plus the API object, the generic kernel's and the actor's (csrc/dcomp_actor.hip); linked into deepcomp_amd/csrc/libdcomp_hip.so.  hipcc cross-compiles
+in parallel, plus the API object, the generic kernel's and the actor's (csrc/dcomp_actor.hip: actor, value function, GAE); linked into deepcomp_amd/csrc/libdcomp_hip.so.  hipcc cross-compiles
 for gfx950 without a GPU present.
 """
 import argparse

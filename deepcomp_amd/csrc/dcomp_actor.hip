@@ -1,4 +1,5 @@
-// dcomp_actor.hip -- a trained fcnet actor on the device (include/dcomp.h: dcomp_actor_create / dcomp_actor_actions).
+// dcomp_actor.hip -- a trained fcnet actor on the device (include/dcomp.h: dcomp_actor_create / dcomp_actor_actions), its value
+// function (dcomp_actor_set_value / dcomp_actor_actions_v) and the advantages of a sample batch (dcomp_gae).
 //
 // What the reference does with a trained policy (simulation.py:347,375,512-541: trainer.compute_action per env and step) for a
 // whole batch in one launch: observation tensor -> two hidden layers -> logits -> categorical draw -> the uint8 action tensor
@@ -21,6 +22,15 @@
 //   - logits: 32 at a time through a [32][33] LDS tile; lane r < 32 walks row r's columns in order -- Gumbel noise, first
 //     maximum, online log-sum-exp -- carrying (head, action) across tiles, so heads need not align with anything
 //   - rows beyond the batch in the last tile are computed on zeros and never stored
+//
+// The value function (dcomp_actor_set_value / dcomp_actor_actions_v) rides in the same launch, in instantiations of their own (VF):
+//   - VF = 1, a trunk of its own (vf_share_layers=False): a SECOND SWEEP over the wave's tile with the value weights -- layer 1's
+//     accumulators of both trunks do not fit the register file side by side.  A row that fits one input chunk is still in the
+//     wave's LDS slice as bf16 and is not staged again; multi-chunk rows are re-staged (L2-hot).  value_out is one more 32-wide
+//     output tile with a single live column
+//   - VF = 2, value_out on the actor's h2: one more column behind the last head in the packed W3; the row walk never sees it
+//   - the value-only call (action == NULL) runs the value sweep alone (VF = 1) / the one output tile that holds the column (VF = 2)
+// VF = 0 is what dcomp_actor_actions launches, with or without a value function attached.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -53,13 +63,16 @@ __host__ __device__ inline int env_words(int U, int B) { return U * ue_words(B) 
 struct Params {
     const void *obs;
     uint8_t *action;
-    float *logits, *logp;
+    float *logits, *logp, *vf;
     const uint4 *w1, *w2, *w3;        // packed bf16 fragments [m tile][k step][lane] x 8 elements
     const float *b1, *b2, *b3;        // padded with zeros to the padded widths
+    const uint4 *vw1, *vw2, *vw3;     // VF = 1: the value trunk, packed like the actor's; vw3 = value_out as ONE output tile, column 0
+    const float *vb1, *vb2, *vb3;
     int64_t rows, tiles, row_base;
     int32_t K1, K1p, XS, N3, NT3, heads, B, U, num_active, multi, compact, sample;
     uint32_t step, seed_lo, seed_hi;
     int32_t lds_per_wave;
+    int32_t vcol, policy;             // VF = 2: the value's column of the packed W3; policy = 0: the value-only call
 };
 
 __device__ __forceinline__ void philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0, uint32_t k1, uint32_t (&out)[4])
@@ -122,8 +135,8 @@ __device__ __forceinline__ bf16x8 as_frag(uint4 v)
     return c.f;
 }
 
-// MT = hidden width / 32 (padded: 1, 2, 4 or 8)
-template <int MT, bool RELU>
+// MT = hidden width / 32 (padded: 1, 2, 4 or 8); VF: 0 = no value, 1 = a value trunk of its own, 2 = value_out on the actor's h2
+template <int MT, bool RELU, int VF>
 __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(2, 2))) void actor_kernel(const Params p)
 {
     extern __shared__ uint4 lds4[];
@@ -164,6 +177,16 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(2, 2))) v
             wave_fence();
         }
 
+        // VF = 1: sweep 0 is the policy, sweep 1 the value trunk (alone in the value-only call); otherwise one sweep
+#pragma nounroll
+        for (int sweep = (VF == 1 && !p.policy) ? 1 : 0; sweep < (VF == 1 ? 2 : 1); sweep++) {
+        const bool val = VF == 1 && sweep != 0;
+        const uint4 *w1 = val ? p.vw1 : p.w1, *w2 = val ? p.vw2 : p.w2, *w3 = val ? p.vw3 : p.w3;
+        const float *b1 = val ? p.vb1 : p.b1, *b2 = val ? p.vb2 : p.b2, *b3 = val ? p.vb3 : p.b3;
+        const int NT3 = val ? 1 : p.NT3, N3 = val ? 0 : p.N3;                        // (the value trunk has no logits to walk or store)
+        const int vcol = VF == 0 ? -1 : VF == 1 ? (val ? 0 : -1) : p.vcol;
+        const bool staged = val && p.policy && p.K1p <= KC;                          // the policy sweep left the bf16 rows in LDS
+
         // ---- layer 1: acc[m] = W1^T (units 32m ...) x X^T, the inputs in chunks through LDS
         f32x16 acc[MT];
 #pragma unroll
@@ -172,11 +195,11 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(2, 2))) v
             for (int i = 0; i < 16; i++) acc[m][i] = 0.f;
         uint4 wq1[MT];                                                               // layer 1's weights, one k step ahead
 #pragma unroll
-        for (int m = 0; m < MT; m++) wq1[m] = load_frag(p.w1, (size_t)m * KS1, lane16);
+        for (int m = 0; m < MT; m++) wq1[m] = load_frag(w1, (size_t)m * KS1, lane16);
         for (int k0 = 0; k0 < p.K1p; k0 += KC) {
             const int kc = p.K1p - k0 < KC ? p.K1p - k0 : KC;                        // a multiple of 16
             const uint32_t magic = (uint32_t)(0x100000000ull / (uint32_t)kc) + 1u;   // f / kc = umulhi(f, magic): f < 2^14, f kc < 2^32
-            const int nf = TILE * kc;
+            const int nf = staged ? 0 : TILE * kc;
 #pragma unroll 4
             for (int f = lane; f < nf; f += 64) {
                 const int rr = (int)__umulhi((uint32_t)f, magic), c = f - rr * kc, k = k0 + c;
@@ -200,7 +223,7 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(2, 2))) v
                 const int ksn = (k0 >> 4) + s + 1 < KS1 ? (k0 >> 4) + s + 1 : KS1 - 1;          // (the last step re-reads itself)
                 uint4 nx[MT];
 #pragma unroll
-                for (int m = 0; m < MT; m++) nx[m] = load_frag(p.w1, (size_t)m * KS1 + ksn, lane16);
+                for (int m = 0; m < MT; m++) nx[m] = load_frag(w1, (size_t)m * KS1 + ksn, lane16);
 #pragma unroll
                 for (int m = 0; m < MT; m++) acc[m] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(as_frag(wq1[m]), b, acc[m], 0, 0, 0);
 #pragma unroll
@@ -215,12 +238,12 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(2, 2))) v
         // hoists every load of a layer to its top -- 512 registers and spills.)
         uint4 ring[D];
 #pragma unroll
-        for (int i = 0; i < D; i++) ring[i] = load_frag(p.w2, i, lane16);
+        for (int i = 0; i < D; i++) ring[i] = load_frag(w2, i, lane16);
         bf16x8 h1[MT][2];
 #pragma unroll
         for (int t = 0; t < MT; t++) {
-            h1[t][0] = next_fragment<RELU>(acc[t], 0, p.b1 + 32 * t + 4 * h);
-            h1[t][1] = next_fragment<RELU>(acc[t], 1, p.b1 + 32 * t + 4 * h);
+            h1[t][0] = next_fragment<RELU>(acc[t], 0, b1 + 32 * t + 4 * h);
+            h1[t][1] = next_fragment<RELU>(acc[t], 1, b1 + 32 * t + 4 * h);
             asm volatile("" : "+v"(h1[t][0]), "+v"(h1[t][1]));
             __builtin_amdgcn_sched_barrier(0);                   // (tile by tile: 16 registers become 8, not every bias load first)
         }
@@ -237,11 +260,11 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(2, 2))) v
                 for (int ks = 0; ks < KS2; ks++) {
                     const int q = m * KS2 + ks;
                     a2 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(as_frag(ring[q % D]), h1[ks >> 1][ks & 1], a2, 0, 0, 0);
-                    ring[q % D] = q + D < Q2 ? load_frag(p.w2, q + D, lane16) : load_frag(p.w3, q + D - Q2, lane16);   // behind layer 2: layer 3's first
+                    ring[q % D] = q + D < Q2 ? load_frag(w2, q + D, lane16) : load_frag(w3, q + D - Q2, lane16);   // behind layer 2: layer 3's first
                     __builtin_amdgcn_sched_barrier(0);
                 }
-                h2[m][0] = next_fragment<RELU>(a2, 0, p.b2 + 32 * m + 4 * h);
-                h2[m][1] = next_fragment<RELU>(a2, 1, p.b2 + 32 * m + 4 * h);
+                h2[m][0] = next_fragment<RELU>(a2, 0, b2 + 32 * m + 4 * h);
+                h2[m][1] = next_fragment<RELU>(a2, 1, b2 + 32 * m + 4 * h);
                 asm volatile("" : "+v"(h2[m][0]), "+v"(h2[m][1]));       // converted HERE: sunk towards layer 3, the 16 raw floats stay live instead of 8 registers
                 __builtin_amdgcn_sched_barrier(0);
             }
@@ -252,7 +275,7 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(2, 2))) v
         float best_y = -INFINITY, best_l = 0.f, first_l = 0.f, mx = -INFINITY, sm = 0.f;
         uint32_t rnd[4] = {0u, 0u, 0u, 0u};
         const uint32_t grow = (uint32_t)(p.row_base + myrow);
-        for (int nt = 0; nt < p.NT3; nt++) {
+        for (int nt = 0; nt < NT3; nt++) {
             f32x16 a3;
 #pragma unroll
             for (int i = 0; i < 16; i++) a3[i] = 0.f;
@@ -260,10 +283,10 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(2, 2))) v
             for (int ks = 0; ks < KS2; ks++) {
                 a3 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(as_frag(ring[ks % D]), h2[ks >> 1][ks & 1], a3, 0, 0, 0);      // (Q2 and KS2 are multiples of D)
                 const int f = nt * KS2 + ks + D;
-                ring[ks % D] = load_frag(p.w3, f < p.NT3 * KS2 ? f : 0, lane16);                // (behind the last: any valid one)
+                ring[ks % D] = load_frag(w3, f < NT3 * KS2 ? f : 0, lane16);                // (behind the last: any valid one)
                 __builtin_amdgcn_sched_barrier(0);
             }
-            const float *bias = p.b3 + 32 * nt + 4 * h;
+            const float *bias = b3 + 32 * nt + 4 * h;
 #pragma unroll
             for (int g = 0; g < 4; g++) {
                 const float4 bv = *reinterpret_cast<const float4 *>(bias + 8 * g);
@@ -271,7 +294,7 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(2, 2))) v
                 d[0] = a3[4 * g + 0] + bv.x; d[1] = a3[4 * g + 1] + bv.y; d[2] = a3[4 * g + 2] + bv.z; d[3] = a3[4 * g + 3] + bv.w;
             }
             wave_fence();
-            const int ncol = p.N3 - 32 * nt < 32 ? p.N3 - 32 * nt : 32;
+            const int ncol = N3 - 32 * nt < 32 ? N3 - 32 * nt : 32;                          // (<= 0: a tile that holds the value's column only)
             if (lane < TILE && have) {
                 for (int c = 0; c < ncol; c++) {
                     const float x = lt[r * LT + c];
@@ -303,22 +326,66 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(2, 2))) v
             if (p.logits) {
                 for (int i = lane; i < TILE * 32; i += 64) {
                     const int rr = i >> 5, c = i & 31;
-                    if (rr < nrow && c < ncol) p.logits[(size_t)(row0 + rr) * p.N3 + 32 * nt + c] = lt[rr * LT + c];
+                    if (rr < nrow && c < ncol) p.logits[(size_t)(row0 + rr) * N3 + 32 * nt + c] = lt[rr * LT + c];
                 }
             }
+            if (VF != 0) {
+                const int vc = vcol - 32 * nt;                                       // the value's column, if this tile holds it
+                if (vc >= 0 && vc < 32 && lane < TILE && have) p.vf[myrow] = lt[r * LT + vc];
+            }
             wave_fence();
+        }
         }
     }
 }
 
 typedef void (*kernel_fn)(const Params);
-static kernel_fn pick(int mt, bool relu)
+template <int VF> static kernel_fn pick_width(int mt, bool relu)
 {
     switch (mt) {
-    case 1: return relu ? actor_kernel<1, true> : actor_kernel<1, false>;
-    case 2: return relu ? actor_kernel<2, true> : actor_kernel<2, false>;
-    case 4: return relu ? actor_kernel<4, true> : actor_kernel<4, false>;
-    default: return relu ? actor_kernel<8, true> : actor_kernel<8, false>;
+    case 1: return relu ? actor_kernel<1, true, VF> : actor_kernel<1, false, VF>;
+    case 2: return relu ? actor_kernel<2, true, VF> : actor_kernel<2, false, VF>;
+    case 4: return relu ? actor_kernel<4, true, VF> : actor_kernel<4, false, VF>;
+    default: return relu ? actor_kernel<8, true, VF> : actor_kernel<8, false, VF>;
+    }
+}
+static kernel_fn pick(int mt, bool relu, int vf)
+{
+    return vf == 0 ? pick_width<0>(mt, relu) : vf == 1 ? pick_width<1>(mt, relu) : pick_width<2>(mt, relu);
+}
+
+// RLlib's compute_advantages(use_gae=True) as pinned f32 operations (include/dcomp.h: dcomp_gae): one lane per column walks t
+// backwards, every access coalesced across the columns; 16 bytes per (t, r) and nothing to reuse.
+struct GaeParams {
+    const float *reward, *vf, *last_vf;
+    const uint8_t *end;
+    float *adv, *target;
+    int64_t R;
+    int32_t T;
+    float gamma, lambda;
+};
+
+__global__ __launch_bounds__(256) void gae_kernel(const GaeParams g)
+{
+    // every operation rounded on its own (what __fmul_rn / __fadd_rn / __fsub_rn promise): written as plain operators under this
+    // pragma, because the HIP headers spell those intrinsics as * and + in THEIR contraction mode and -ffp-contract=fast fuses them
+#pragma clang fp contract(off)
+    const float *__restrict__ reward = g.reward, *__restrict__ vf = g.vf;
+    float *__restrict__ adv = g.adv, *__restrict__ target = g.target;
+    const float gl = g.gamma * g.lambda;
+    for (int64_t r = (int64_t)blockIdx.x * 256 + threadIdx.x; r < g.R; r += (int64_t)gridDim.x * 256) {
+        float nv = g.last_vf ? g.last_vf[r] : 0.f, A = 0.f;
+#pragma unroll 4
+        for (int t = g.T - 1; t >= 0; t--) {
+            const size_t i = (size_t)t * (size_t)g.R + (size_t)r;
+            const float rw = reward[i], v = vf[i];
+            if (g.end && g.end[t]) { nv = 0.f; A = 0.f; }
+            const float d = (rw + g.gamma * nv) - v;
+            A = d + gl * A;
+            adv[i] = A;
+            target[i] = A + v;
+            nv = v;
+        }
     }
 }
 
@@ -354,6 +421,11 @@ struct dcomp_actor {
     void *dev_mem;
     const uint4 *w1, *w2, *w3;
     const float *b1, *b2, *b3;
+    // the value function (dcomp_actor_set_value): value = 0 none, 1 a trunk of its own, 2 value_out on the actor's h2
+    int32_t value, NT3v;
+    void *value_mem;
+    const uint4 *vw1, *vw2, *vw3;                            // value = 2: vw3 / vb3 = the actor's W3 / b3 with the value's column N3 behind the last head
+    const float *vb1, *vb2, *vb3;
 };
 
 static int afail(int code, const char *fmt, ...) __attribute__((format(printf, 2, 3)));
@@ -443,38 +515,166 @@ extern "C" int dcomp_actor_destroy(dcomp_actor *a)
 {
     if (!a) return DCOMP_OK;
     hipError_t e = hipFree(a->dev_mem);
+    if (a->value_mem) {
+        const hipError_t e2 = hipFree(a->value_mem);
+        if (e == hipSuccess) e = e2;
+    }
     delete a;
     return e == hipSuccess ? DCOMP_OK : afail(DCOMP_EHIP, "dcomp_actor_destroy: hipFree failed: %s", hipGetErrorString(e));
 }
 
-extern "C" int dcomp_actor_actions(dcomp_actor *a, const dcomp_actor_run *r, const void *obs, uint8_t *action, void *stream)
+// dcomp_actor_actions (vf_call = false) and dcomp_actor_actions_v: every check on the host first, then ONE launch
+static int actor_launch(const char *fn, bool vf_call, dcomp_actor *a, const dcomp_actor_run *r, const void *obs, uint8_t *action, float *vf, void *stream)
 {
     using namespace dactor;
-    if (!a || !r) return afail(DCOMP_EINVAL, "dcomp_actor_actions: handle and run must not be NULL");
+    if (!a || !r) return afail(DCOMP_EINVAL, "%s: handle and run must not be NULL", fn);
     if (r->struct_size != (int32_t)sizeof(dcomp_actor_run))
-        return afail(DCOMP_EABI, "dcomp_actor_actions: caller's dcomp_actor_run has %d bytes, the library's %d", r->struct_size, (int)sizeof(dcomp_actor_run));
-    if (r->obs_format != DCOMP_ACTOR_ROWS && r->obs_format != DCOMP_ACTOR_COMPACT) return afail(DCOMP_EINVAL, "dcomp_actor_actions: unknown obs_format %d", r->obs_format);
+        return afail(DCOMP_EABI, "%s: caller's dcomp_actor_run has %d bytes, the library's %d", fn, r->struct_size, (int)sizeof(dcomp_actor_run));
+    if (r->obs_format != DCOMP_ACTOR_ROWS && r->obs_format != DCOMP_ACTOR_COMPACT) return afail(DCOMP_EINVAL, "%s: unknown obs_format %d", fn, r->obs_format);
     if (r->obs_format == DCOMP_ACTOR_COMPACT && a->kind != DCOMP_MULTI)
-        return afail(DCOMP_EUNSUPPORTED, "dcomp_actor_actions: the compact record exists for multi-agent observations only");
-    if (!obs || !action) return afail(DCOMP_EINVAL, "dcomp_actor_actions: obs and action must not be NULL");
-    if (r->num_envs < 1) return afail(DCOMP_EINVAL, "dcomp_actor_actions: num_envs %d < 1", r->num_envs);
-    if (r->num_active < 0 || r->num_active > a->U) return afail(DCOMP_EINVAL, "dcomp_actor_actions: num_active %d outside [0, %d]", r->num_active, a->U);
+        return afail(DCOMP_EUNSUPPORTED, "%s: the compact record exists for multi-agent observations only", fn);
+    if (!vf_call) {
+        if (!obs || !action) return afail(DCOMP_EINVAL, "%s: obs and action must not be NULL", fn);
+    } else {
+        if (!obs) return afail(DCOMP_EINVAL, "%s: obs must not be NULL", fn);
+        if (!vf) return afail(DCOMP_EINVAL, "%s: vf must not be NULL (dcomp_actor_actions is the call without a value)", fn);
+        if (!action && (r->logits || r->logp)) return afail(DCOMP_EINVAL, "%s: action == NULL is the value-only call: run.logits and run.logp must be NULL", fn);
+        if (!a->value) return afail(DCOMP_EINVAL, "%s: the handle has no value function (dcomp_actor_set_value)", fn);
+    }
+    if (r->num_envs < 1) return afail(DCOMP_EINVAL, "%s: num_envs %d < 1", fn, r->num_envs);
+    if (r->num_active < 0 || r->num_active > a->U) return afail(DCOMP_EINVAL, "%s: num_active %d outside [0, %d]", fn, r->num_active, a->U);
     const int64_t rows = a->kind == DCOMP_MULTI ? (int64_t)r->num_envs * a->U : (int64_t)r->num_envs;
     if (r->row_base < 0 || r->row_base + rows > 0x100000000ll)
-        return afail(DCOMP_EINVAL, "dcomp_actor_actions: decision rows %lld ... %lld do not fit the 32-bit draw counter word", (long long)r->row_base,
+        return afail(DCOMP_EINVAL, "%s: decision rows %lld ... %lld do not fit the 32-bit draw counter word", fn, (long long)r->row_base,
                      (long long)(r->row_base + rows - 1));
+    const int mode = vf_call ? a->value : 0;
     Params p;
     memset(&p, 0, sizeof(p));
-    p.obs = obs; p.action = action; p.logits = r->logits; p.logp = r->logp;
+    p.obs = obs; p.action = action; p.logits = r->logits; p.logp = r->logp; p.vf = vf;
     p.w1 = a->w1; p.w2 = a->w2; p.w3 = a->w3; p.b1 = a->b1; p.b2 = a->b2; p.b3 = a->b3;
     p.rows = rows; p.tiles = (rows + TILE - 1) / TILE; p.row_base = r->row_base;
     p.K1 = a->K1; p.K1p = a->K1p; p.XS = a->XS; p.N3 = a->N3; p.NT3 = a->NT3; p.heads = a->heads; p.B = a->B; p.U = a->U;
     p.num_active = r->num_active; p.multi = a->kind == DCOMP_MULTI; p.compact = r->obs_format == DCOMP_ACTOR_COMPACT; p.sample = r->sample != 0;
     p.step = r->step; p.seed_lo = (uint32_t)r->seed; p.seed_hi = (uint32_t)(r->seed >> 32);
     p.lds_per_wave = a->lds_per_wave;
+    p.policy = action != nullptr; p.vcol = -1;
+    if (mode == 1) {
+        p.vw1 = a->vw1; p.vw2 = a->vw2; p.vw3 = a->vw3; p.vb1 = a->vb1; p.vb2 = a->vb2; p.vb3 = a->vb3;
+    } else if (mode == 2) {
+        const int first = p.policy ? 0 : a->NT3v - 1;        // value only: the one output tile that holds the value's column, no logits
+        p.w3 = a->vw3 + (size_t)first * 2 * a->mt * 64; p.b3 = a->vb3 + 32 * first;
+        p.NT3 = a->NT3v - first; p.vcol = a->N3 - 32 * first;
+        if (!p.policy) p.N3 = 0;
+    }
     const int64_t want = (p.tiles + WAVES - 1) / WAVES;
     const int grid = (int)(want < a->max_blocks ? want : a->max_blocks);
-    hipLaunchKernelGGL(pick(a->mt, a->relu != 0), dim3(grid), dim3(BLOCK), (size_t)a->lds_per_wave * WAVES, static_cast<hipStream_t>(stream), p);
+    hipLaunchKernelGGL(pick(a->mt, a->relu != 0, mode), dim3(grid), dim3(BLOCK), (size_t)a->lds_per_wave * WAVES, static_cast<hipStream_t>(stream), p);
+    ACTOR_HIP_TRY(hipGetLastError());
+    return DCOMP_OK;
+}
+
+extern "C" int dcomp_actor_actions(dcomp_actor *a, const dcomp_actor_run *r, const void *obs, uint8_t *action, void *stream)
+{
+    return actor_launch("dcomp_actor_actions", false, a, r, obs, action, nullptr, stream);
+}
+
+extern "C" int dcomp_actor_actions_v(dcomp_actor *a, const dcomp_actor_run *r, const void *obs, uint8_t *action, float *vf, void *stream)
+{
+    return actor_launch("dcomp_actor_actions_v", true, a, r, obs, action, vf, stream);
+}
+
+extern "C" int dcomp_actor_set_value(dcomp_actor *a, const dcomp_actor_value_cfg *cfg)
+{
+    using namespace dactor;
+    if (!a || !cfg) return afail(DCOMP_EINVAL, "dcomp_actor_set_value: handle and cfg must not be NULL");
+    if (cfg->struct_size != (int32_t)sizeof(dcomp_actor_value_cfg))
+        return afail(DCOMP_EABI, "dcomp_actor_set_value: caller's dcomp_actor_value_cfg has %d bytes, the library's %d", cfg->struct_size, (int)sizeof(dcomp_actor_value_cfg));
+    if (cfg->shared != 0 && cfg->shared != 1) return afail(DCOMP_EINVAL, "dcomp_actor_set_value: shared %d is neither 0 nor 1", cfg->shared);
+    if (!cfg->wv || !cfg->bv) return afail(DCOMP_EINVAL, "dcomp_actor_set_value: wv or bv is NULL");
+    const bool any = cfg->w1 || cfg->b1 || cfg->w2 || cfg->b2, all = cfg->w1 && cfg->b1 && cfg->w2 && cfg->b2;
+    if (cfg->shared && any) return afail(DCOMP_EINVAL, "dcomp_actor_set_value: shared = 1 takes value_out only: the trunk pointers w1 ... b2 must be NULL");
+    if (!cfg->shared && !all) return afail(DCOMP_EINVAL, "dcomp_actor_set_value: shared = 0 needs the value trunk: a pointer of w1 ... b2 is NULL");
+    if (a->value) return afail(DCOMP_EINVAL, "dcomp_actor_set_value: the handle has a value function already (once per handle)");
+
+    int dev = -1;
+    hipError_t e = hipGetDevice(&dev);
+    if (e == hipSuccess && dev != a->device) return afail(DCOMP_EINVAL, "dcomp_actor_set_value: the handle lives on device %d, the calling thread's current device is %d", a->device, dev);
+    if (e != hipSuccess) return afail(DCOMP_EHIP, "dcomp_actor_set_value: %s", hipGetErrorString(e));
+
+    const int H = a->hidden, Hp = 32 * a->mt, KS2 = 2 * a->mt;
+    const size_t frag = (size_t)KS2 * 64 * 8;                // bf16 elements of one output tile of a hidden -> out layer
+    std::vector<uint16_t> p1, p2, p3;
+    std::vector<float> bias;
+    int nt3v;
+    if (cfg->shared) {
+        // the actor's packed W3 (read back from the handle's device memory) with one more column: output N3 = lane r = N3 % 32 of
+        // tile N3 / 32 (a new tile when N3 % 32 == 0)
+        nt3v = a->N3 / 32 + 1;
+        p3.assign((size_t)nt3v * frag, 0);
+        bias.assign((size_t)32 * nt3v, 0.f);
+        ACTOR_HIP_TRY(hipMemcpy(p3.data(), a->w3, (size_t)a->NT3 * frag * 2, hipMemcpyDeviceToHost));
+        ACTOR_HIP_TRY(hipMemcpy(bias.data(), a->b3, sizeof(float) * 32 * a->NT3, hipMemcpyDeviceToHost));
+        const int m = a->N3 / 32, rr = a->N3 % 32;
+        for (int ks = 0; ks < KS2; ks++)
+            for (int hh = 0; hh < 2; hh++)
+                for (int j = 0; j < 8; j++) {
+                    const int k = 16 * ks + 8 * (j >> 2) + 4 * hh + (j & 3);
+                    if (k < H) p3[(((size_t)m * KS2 + ks) * 64 + 32 * hh + rr) * 8 + j] = bf16_rne(cfg->wv[k]);
+                }
+        bias[a->N3] = cfg->bv[0];
+    } else {
+        nt3v = 1;
+        pack(p1, cfg->w1, a->K1, H, a->K1p / 16, a->mt, false);
+        pack(p2, cfg->w2, H, H, KS2, a->mt, true);
+        pack(p3, cfg->wv, H, 1, KS2, 1, true);
+        bias.assign((size_t)2 * Hp + 32, 0.f);
+        memcpy(bias.data(), cfg->b1, sizeof(float) * H);
+        memcpy(bias.data() + Hp, cfg->b2, sizeof(float) * H);
+        bias[2 * Hp] = cfg->bv[0];
+    }
+    auto up = [](size_t v) { return (v + 255) & ~(size_t)255; };
+    const size_t o1 = 0, o2 = up(o1 + p1.size() * 2), o3 = up(o2 + p2.size() * 2), ob = up(o3 + p3.size() * 2), total = ob + bias.size() * 4;
+    std::vector<unsigned char> img(total, 0);
+    if (!p1.empty()) memcpy(img.data() + o1, p1.data(), p1.size() * 2);
+    if (!p2.empty()) memcpy(img.data() + o2, p2.data(), p2.size() * 2);
+    memcpy(img.data() + o3, p3.data(), p3.size() * 2);
+    memcpy(img.data() + ob, bias.data(), bias.size() * 4);
+
+    void *mem = nullptr;
+    e = hipMalloc(&mem, total);
+    if (e == hipSuccess) {
+        e = hipMemcpy(mem, img.data(), total, hipMemcpyHostToDevice);
+        if (e != hipSuccess) (void)hipFree(mem);
+    }
+    if (e != hipSuccess) return afail(DCOMP_EHIP, "dcomp_actor_set_value: %s", hipGetErrorString(e));
+    unsigned char *d = static_cast<unsigned char *>(mem);
+    a->value_mem = mem;
+    a->vw1 = reinterpret_cast<const uint4 *>(d + o1); a->vw2 = reinterpret_cast<const uint4 *>(d + o2); a->vw3 = reinterpret_cast<const uint4 *>(d + o3);
+    const float *b = reinterpret_cast<const float *>(d + ob);
+    if (cfg->shared) { a->vb1 = a->vb2 = nullptr; a->vb3 = b; }
+    else { a->vb1 = b; a->vb2 = b + Hp; a->vb3 = b + 2 * Hp; }
+    a->NT3v = nt3v;
+    a->value = cfg->shared ? 2 : 1;
+    return DCOMP_OK;
+}
+
+extern "C" int dcomp_gae(const dcomp_gae_args *g, void *stream)
+{
+    using namespace dactor;
+    if (!g) return afail(DCOMP_EINVAL, "dcomp_gae: args must not be NULL");
+    if (g->struct_size != (int32_t)sizeof(dcomp_gae_args))
+        return afail(DCOMP_EABI, "dcomp_gae: caller's dcomp_gae_args has %d bytes, the library's %d", g->struct_size, (int)sizeof(dcomp_gae_args));
+    if (!g->reward || !g->vf || !g->advantages || !g->value_targets) return afail(DCOMP_EINVAL, "dcomp_gae: reward, vf, advantages and value_targets must not be NULL");
+    if (g->num_steps < 1) return afail(DCOMP_EINVAL, "dcomp_gae: num_steps %d < 1", g->num_steps);
+    if (g->num_rows < 1) return afail(DCOMP_EINVAL, "dcomp_gae: num_rows %lld < 1", (long long)g->num_rows);
+    if (g->num_rows >= (1ll << 40) || (int64_t)g->num_steps * g->num_rows >= (1ll << 40))
+        return afail(DCOMP_EINVAL, "dcomp_gae: num_steps x num_rows = %d x %lld is 2^40 elements or more", g->num_steps, (long long)g->num_rows);
+    GaeParams k;
+    k.reward = g->reward; k.vf = g->vf; k.last_vf = g->last_vf; k.end = g->end; k.adv = g->advantages; k.target = g->value_targets;
+    k.R = g->num_rows; k.T = g->num_steps; k.gamma = g->gamma; k.lambda = g->lambda;
+    const int64_t want = (g->num_rows + 255) / 256;
+    const int grid = (int)(want < (1 << 20) ? want : (1 << 20));          // (beyond: the kernel strides over the columns)
+    hipLaunchKernelGGL(gae_kernel, dim3(grid), dim3(256), 0, static_cast<hipStream_t>(stream), k);
     ACTOR_HIP_TRY(hipGetLastError());
     return DCOMP_OK;
 }

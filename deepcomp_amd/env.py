@@ -499,6 +499,12 @@ class BatchedMobileEnv:
         with torch.cuda.device(self.device):
             self._launch_step(action, out)
 
+    def reset_into(self, obs):
+        """Like reset() but writes the first observation into a caller-provided tensor (a slot of a rollout buffer).  self.obs is
+        NOT updated by this call."""
+        self._require(obs, torch.float32, self.obs.numel(), 'obs')
+        self.reset(_out=self._make_out(obs, self.reward))
+
     @property
     def compact_words(self):
         """int32 words of one env-step in the compact record (deepcomp_amd.fragment: U (B + 2) + 2B); multi-agent envs only."""

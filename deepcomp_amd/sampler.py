@@ -1,0 +1,167 @@
+"""PPO sample batches collected on the device (include/dcomp.h: dcomp_actor_actions_v, dcomp_gae).
+
+What an RLlib rollout worker does per env and step -- compute_action, env.step, append to a SampleBatch, then
+``compute_advantages(use_gae=True)`` over the finished fragment -- for a whole env batch with everything in HBM:
+
+    actor = FcnetActor.from_rllib_weights('multi', U, B, policy.get_weights(), with_value=True)
+    batch = collect(env, actor, num_steps=50, gamma=0.99, lam=0.95)
+    # batch['obs'] [T, E, U, 4B+1], 'actions' [T, E, U], 'action_logp', 'vf_preds', 'rewards', 'advantages', 'value_targets' [T, rows]
+
+Per step two launches (the actor with its value function, the env step writing straight into the next slot of the buffers), after
+the loop one value-only launch for the bootstrap and one for the advantages.  With Philox draws nothing synchronises and nothing is
+allocated per step.  The PPO loss and the optimiser are not part of this package.
+"""
+import ctypes
+
+import numpy as np
+import torch
+
+from . import _lib
+
+
+def gae_reference(reward, vf, last_vf=None, end=None, gamma=0.99, lam=1.0):
+    """The specification of dcomp_gae: RLlib's compute_advantages(use_gae=True) as float32 operations, each rounded on its own,
+    in this order.  reward, vf: [T, R]; last_vf: [R] or None (= 0); end: [T] (1 = step t was the last of its episode) or None.
+    Returns (advantages, value_targets), float32 [T, R]."""
+    reward, vf = np.asarray(reward, dtype=np.float32), np.asarray(vf, dtype=np.float32)
+    T = reward.shape[0]
+    reward, vf = reward.reshape(T, -1), vf.reshape(T, -1)
+    g = np.float32(gamma)
+    gl = np.float32(g * np.float32(lam))
+    nv = np.zeros(reward.shape[1], dtype=np.float32) if last_vf is None else np.asarray(last_vf, dtype=np.float32).reshape(-1).copy()
+    A = np.zeros_like(nv)
+    adv, target = np.empty_like(reward), np.empty_like(reward)
+    with np.errstate(invalid='ignore'):
+        for t in range(T - 1, -1, -1):
+            if end is not None and end[t]:
+                nv, A = np.zeros_like(nv), np.zeros_like(A)
+            d = (reward[t] + g * nv) - vf[t]               # float32 arrays: every operation rounds to float32
+            A = d + gl * A
+            adv[t], target[t] = A, A + vf[t]
+            nv = vf[t]
+    return adv, target
+
+
+def _require(t, dtype, numel, what, device):
+    if not isinstance(t, torch.Tensor) or t.dtype != dtype or t.device != device or not t.is_contiguous() or t.numel() != numel:
+        raise ValueError(f"{what} must be a contiguous {dtype} tensor with {numel} elements on {device}")
+
+
+def gae(reward, vf, last_vf=None, end=None, gamma=0.99, lam=1.0, out=None):
+    """dcomp_gae on torch tensors: reward, vf float32 [T, ...] on one GPU, last_vf [...] or None, end uint8 [T] or None.
+    Returns (advantages, value_targets) of reward's shape; out: a pair of such tensors to write into.  The outputs must not
+    overlap the inputs."""
+    if not isinstance(reward, torch.Tensor) or reward.dim() < 1 or reward.numel() == 0 or reward.device.type != 'cuda':
+        raise ValueError("reward must be a non-empty float32 tensor [T, ...] on the GPU")
+    dev, T = reward.device, reward.shape[0]
+    R = reward.numel() // T
+    _require(reward, torch.float32, T * R, 'reward', dev)
+    _require(vf, torch.float32, T * R, 'vf', dev)
+    if last_vf is not None:
+        _require(last_vf, torch.float32, R, 'last_vf', dev)
+    if end is not None:
+        _require(end, torch.uint8, T, 'end', dev)
+    adv, target = out if out is not None else (torch.empty_like(reward), torch.empty_like(reward))
+    _require(adv, torch.float32, T * R, 'advantages', dev)
+    _require(target, torch.float32, T * R, 'value_targets', dev)
+    L = _lib.load()
+    args = _lib.DcompGaeArgs(ctypes.sizeof(_lib.DcompGaeArgs), T, R, float(gamma), float(lam), reward.data_ptr(), vf.data_ptr(),
+                             last_vf.data_ptr() if last_vf is not None else None, end.data_ptr() if end is not None else None,
+                             adv.data_ptr(), target.data_ptr())
+    with torch.cuda.device(dev):
+        _lib.check(L.dcomp_gae(ctypes.byref(args), ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)))
+    return adv, target
+
+
+_CODECS = {}
+
+
+def _codec(env):
+    """The compact record's codec for this env's shape and device (its flag word is allocated once)."""
+    from .fragment import FragmentCodec
+    key = (env.U, env.B, env.device)
+    if key not in _CODECS:
+        _CODECS[key] = FragmentCodec(env.U, env.B, env.device)
+    return _CODECS[key]
+
+
+def buffers(env, actor, num_steps, compact=False):
+    """The device buffers of a num_steps batch, allocated once."""
+    T, E, U, dev = int(num_steps), env.E, env.U, env.device
+    rows = E * U if env.kind == _lib.MULTI else E
+    b = {}
+    if compact:
+        b['obs_compact'] = torch.zeros((T, E, env.compact_words), dtype=torch.int32, device=dev)
+        b['new_obs_last'] = torch.zeros((E, env.compact_words), dtype=torch.int32, device=dev)
+    else:
+        b['obs'] = torch.zeros((T,) + tuple(env.obs.shape), dtype=torch.float32, device=dev)
+        b['new_obs_last'] = torch.zeros_like(env.obs)
+    b['actions'] = torch.zeros((T, E, U), dtype=torch.uint8, device=dev)
+    b['action_logp'] = torch.zeros((T, rows, actor.heads), dtype=torch.float32, device=dev)
+    for name in ('vf_preds', 'rewards', 'advantages', 'value_targets'):
+        b[name] = torch.zeros((T, rows), dtype=torch.float32, device=dev)
+    b['dones'] = torch.zeros(T, dtype=torch.uint8, device=dev)
+    b['last_vf'] = torch.zeros(rows, dtype=torch.float32, device=dev)
+    return b
+
+
+def collect(env, actor, num_steps, gamma=0.99, lam=1.0, sample=True, compact=False, out=None):
+    """num_steps steps of `env` driven by `actor` (which needs a value function) as one PPO train batch: a dict of device tensors
+    under RLlib's SampleBatch names -- obs [T, ...] (compact=True: obs_compact [T, E, words], the record of env.step_compact),
+    actions [T, E, U] uint8, action_logp [T, rows, heads], vf_preds / rewards / advantages / value_targets [T, rows], dones [T]
+    uint8 (the env batch runs in lock-step) and new_obs_last, the observation after step T-1 (last_vf [rows] holds its value, the
+    bootstrap, where the batch ended inside an episode).
+
+    The batch starts from env.obs -- the observation of the caller's reset() / step(), or of the previous collect() -- and from a
+    reset of its own where the env has never been reset; it leaves new_obs_last in env.obs, so batches follow each other (and the
+    caller's own steps) without a gap, with or without `out`.  When env.time reaches env.episode_length, dones[t] = 1 and the env
+    is reset into the next slot, as RLlib does at its horizon (env_setup.py:281).  A batch that ends inside an episode bootstraps
+    from the value of new_obs_last.  Draws are keyed as in FcnetActor.act.  out: the dict of an earlier call with the same
+    num_steps and format, to reuse its buffers.  compact=True packs env.obs into the first slot and unpacks new_obs_last into
+    env.obs (one launch each per batch; pack(rows) is the record the step writes, word for word)."""
+    T = int(num_steps)
+    if T < 1:
+        raise ValueError("num_steps must be >= 1")
+    if env.dynamic:
+        raise NotImplementedError("envs with UE arrival / departure: slots shift on departure, a column is not one UE's trajectory")
+    if env.kind != actor.kind or env.U != actor.U or env.B != actor.B:
+        raise ValueError("the env's kind / UE slots / stations differ from the actor's")
+    if actor.value_weights is None:
+        raise ValueError("the actor has no value function (set_value)")
+    if compact and env.kind != _lib.MULTI:
+        raise NotImplementedError("compact observation records exist for multi-agent observations only")
+    key = 'obs_compact' if compact else 'obs'
+    b = out if out is not None else buffers(env, actor, T, compact)
+    if not isinstance(b, dict) or key not in b or b[key].shape[0] != T or b['actions'].shape != (T, env.E, env.U):
+        raise ValueError(f"out must be the dict of a collect() call with the same env shape, num_steps and compact={compact}")
+    obs, last = b[key], b['new_obs_last']
+    reset_into = env.reset_compact if compact else env.reset_into
+
+    if env.episode < 0:
+        env.reset()
+    if compact:
+        _codec(env).pack(env.obs, out=obs[0])
+    else:
+        obs[0].copy_(env.obs)
+
+    b['dones'].zero_()
+    done = False
+    for t in range(T):
+        actor.act(env, sample=sample, obs=obs[t], compact=compact, out=b['actions'][t], logp=b['action_logp'][t], vf=b['vf_preds'][t])
+        nxt = obs[t + 1] if t + 1 < T else last
+        if compact:
+            env.step_compact(b['actions'][t], nxt, b['rewards'][t])
+        else:
+            env.step_into(b['actions'][t], nxt, b['rewards'][t])
+        done = env.time >= env.episode_length
+        if done:                                       # the horizon: what the step wrote is discarded, the new episode's first observation takes its place
+            b['dones'][t].fill_(1)
+            reset_into(nxt)
+    if not done:
+        actor.value(last, compact=compact, out=b['last_vf'])
+    gae(b['rewards'], b['vf_preds'], None if done else b['last_vf'], b['dones'], gamma, lam, out=(b['advantages'], b['value_targets']))
+    if compact:                                        # env.obs is the current observation again: the next batch, or the caller, goes on from it
+        _codec(env).unpack(last, out=env.obs)
+    else:
+        env.obs.copy_(last)
+    return b

@@ -271,6 +271,29 @@ int dcomp_actor_create(const dcomp_actor_cfg *cfg, dcomp_actor **out);
 int dcomp_actor_destroy(dcomp_actor *a);
 int dcomp_actor_actions(dcomp_actor *a, const dcomp_actor_run *r, const void *obs, uint8_t *action, void *stream);
 
+/* The value function of the policy, for PPO sample batches (vf_preds, the bootstrap value).  dcomp_actor_set_value attaches it to a
+ * handle ONCE (a second call: DCOMP_EINVAL); it validates on the host before the first HIP call, rounds the HOST weights to bf16 and
+ * packs them like the actor's into device memory that the handle owns (dcomp_actor_destroy frees it).  The arithmetic:
+ *     shared = 0:  h1v = bf16(act(x Wv1 + bv1));  h2v = bf16(act(h1v Wv2 + bv2));  v = h2v . bf16(wv) + bv
+ *     shared = 1:  v = h2 . bf16(wv) + bv          (h2: the actor's own)
+ * bf16 products, f32 accumulation on the matrix cores, bias and activation in f32.
+ * dcomp_actor_actions_v does what dcomp_actor_actions does -- action, run.logits and run.logp are bit-identical -- in the same
+ * single launch and also writes vf[rows] (f32, device; unlisted slots get the value of their zero row).  action == NULL: the value
+ * only (the bootstrap call; run.logits and run.logp must be NULL, the policy's head and the draws are skipped).  vf == NULL or a
+ * handle without a value function: DCOMP_EINVAL. */
+int dcomp_actor_set_value(dcomp_actor *a, const dcomp_actor_value_cfg *cfg);
+int dcomp_actor_actions_v(dcomp_actor *a, const dcomp_actor_run *r, const void *obs, uint8_t *action, float *vf, void *stream);
+
+/* RLlib's compute_advantages(use_gae=True) over a [T][R] batch in one launch, pinned as f32 operations each rounded on its own (no
+ * contraction), per column r:
+ *     gl = gamma * lambda;  nv = last_vf ? last_vf[r] : 0;  A = 0
+ *     for t = T-1 ... 0:  if (end && end[t]) { nv = 0; A = 0; }
+ *                         d = (reward[t][r] + gamma * nv) - vf[t][r];  A = d + gl * A
+ *                         advantages[t][r] = A;  value_targets[t][r] = A + vf[t][r];  nv = vf[t][r]
+ * Only enqueues on `stream`, allocates nothing.  advantages and value_targets must not overlap reward, vf, last_vf or each other (the
+ * kernel reads ahead of its stores; not checked).  NULL pointers, T < 1, R < 1, T R >= 2^40: DCOMP_EINVAL. */
+int dcomp_gae(const dcomp_gae_args *args, void *stream);
+
 #ifndef DCOMP_BUILDING_LIBRARY
 /* callers compiled against this header create their handles through the guarded entry point (see "ABI guard" above) */
 #define dcomp_create(cfg, out) \

@@ -126,8 +126,9 @@ typedef struct dcomp_events {
 enum { DCOMP_POLICY_3GPP = 0, DCOMP_POLICY_FULLCOMP = 1, DCOMP_POLICY_DYNAMIC = 2, DCOMP_POLICY_CLUSTER = 3 };
 
 /* A trained fcnet actor on the device (dcomp_actor_create / dcomp_actor_actions in dcomp.h): two hidden layers of one width and a
- * categorical head per decision, bf16 products with f32 accumulation on the matrix cores.  Both structs carry their own size as
- * their first field (anything else -> DCOMP_EABI); they are not part of the dcomp_create_v guard. */
+ * categorical head per decision, bf16 products with f32 accumulation on the matrix cores.  These structs (and dcomp_actor_value_cfg,
+ * dcomp_gae_args below) carry their own size as their first field (anything else -> DCOMP_EABI); they are not part of the
+ * dcomp_create_v guard. */
 enum { DCOMP_ACT_TANH = 0, DCOMP_ACT_RELU = 1 };
 enum { DCOMP_ACTOR_ROWS = 0, DCOMP_ACTOR_COMPACT = 1 };
 #define DCOMP_ACTOR_MAX_HIDDEN 256
@@ -161,6 +162,31 @@ typedef struct dcomp_actor_run {
     float *logits;                /* optional device [rows][heads*(B+1)] f32: what the action was chosen from */
     float *logp;                  /* optional device [rows][heads] f32: log-softmax of the chosen action (PPO's action_logp) */
 } dcomp_actor_run;
+
+/* The value function of a PPO policy (dcomp_actor_set_value / dcomp_actor_actions_v in dcomp.h), RLlib's fcnet in both its forms:
+ * shared = 0 (vf_share_layers=False, PPO's default): a trunk of its own (fc_value_1, fc_value_2, value_out) of the actor's width
+ * and activation; shared = 1: value_out on the actor's own second hidden layer, w1 ... b2 must be NULL. */
+typedef struct dcomp_actor_value_cfg {
+    int32_t struct_size;          /* sizeof(dcomp_actor_value_cfg) of the caller */
+    int32_t shared;               /* 0 | 1 */
+    const float *w1, *b1;         /* HOST float32 [in][hidden], [hidden] (shared = 0 only) */
+    const float *w2, *b2;         /* [hidden][hidden], [hidden] (shared = 0 only) */
+    const float *wv, *bv;         /* [hidden], [1] */
+} dcomp_actor_value_cfg;
+
+/* Generalised advantage estimation over a [T][R] batch (dcomp_gae in dcomp.h): every pointer is a DEVICE pointer. */
+typedef struct dcomp_gae_args {
+    int32_t struct_size;          /* sizeof(dcomp_gae_args) of the caller */
+    int32_t num_steps;            /* T >= 1 */
+    int64_t num_rows;             /* R >= 1 columns (decision rows: E U multi-agent, E central); T R < 2^40 */
+    float gamma, lambda;
+    const float *reward;          /* [T][R] */
+    const float *vf;              /* [T][R] value predictions */
+    const float *last_vf;         /* optional [R]: value of the observation after step T-1 (NULL = 0) */
+    const uint8_t *end;           /* optional [T]: 1 = step t was the last of its episode (the env batch runs in lock-step); NULL = none */
+    float *advantages;            /* [T][R] */
+    float *value_targets;         /* [T][R] */
+} dcomp_gae_args;
 
 #ifdef __cplusplus
 }

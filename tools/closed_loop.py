@@ -5,11 +5,17 @@ next action tensor -- everything stays in HBM, no per-env Python.  The policy is
 this only shows where the time goes once the env runs at ~10^8-10^9 env-steps/s.
 
     python tools/closed_loop.py [--envs 65536] [--steps 200] [--dtype bf16] [--kind multi] [--actor hip [--compact]]
+    python tools/closed_loop.py --collect 50 [--envs 65536] [--kind multi] [--compact] [--shared-value]
 
 --actor torch (default): the actor as torch ops (bf16 matmuls, Gumbel-max through torch.rand).  --actor hip: the same weights in
 deepcomp_amd.actor.FcnetActor -- one HIP kernel from observation tensor to action tensor -- and BOTH loops are timed in this
 process, one after the other on the same env.  --compact (multi-agent, hip): the env writes only the compact record
 (env.step_compact) and the actor reads it.
+
+--collect T: PPO sample batches of T steps instead -- deepcomp_amd.sampler.collect (actor + value function in one launch per step,
+the bootstrap value, dcomp_gae) against the same loop with the HIP actor but the value network as torch ops (bf16 matmuls) and GAE
+as a torch loop over t: what a user had before the value function moved into the kernel.  Both are timed in this process,
+interleaved, --steps / T batches each.
 """
 import argparse
 import sys
@@ -32,7 +38,11 @@ ap.add_argument('--dtype', default='bf16', choices=['bf16', 'fp32'])
 ap.add_argument('--kind', default='multi', choices=['multi', 'central'])
 ap.add_argument('--actor', default='torch', choices=['torch', 'hip'])
 ap.add_argument('--compact', action='store_true', help='hip actor, multi-agent: the env writes only the compact record and the actor reads it')
+ap.add_argument('--collect', type=int, default=0, metavar='T', help='time sampler.collect of T-step batches against the torch-value + torch-GAE loop')
+ap.add_argument('--shared-value', action='store_true', help='--collect: value_out on the actor\'s second hidden layer (vf_share_layers)')
 a = ap.parse_args()
+if a.collect:
+    a.actor = 'hip'
 if a.compact and (a.actor != 'hip' or a.kind != 'multi'):
     ap.error('--compact needs --actor hip and --kind multi')
 
@@ -58,6 +68,82 @@ def policy(obs):                                   # obs [E, U, 4B+1] / [E, U(2B
 
 
 hip = FcnetActor(a.kind, U, B, host_w, device=dev) if a.actor == 'hip' else None
+
+
+def collect_mode(T):
+    from deepcomp_amd.sampler import collect
+    gamma, lam = 0.99, 0.95
+    host_v = FcnetActor.random_value_weights(a.kind, U, B, 256, seed=0, shared=a.shared_value)
+    hip.set_value(host_v, shared=a.shared_value)
+    trunk = host_v if not a.shared_value else host_w
+    V1, V2 = (torch.from_numpy(trunk[n]).to(dev).to(dt) for n in ('w1', 'w2'))
+    Vo = torch.from_numpy(host_v['wv']).to(dev).to(dt).view(-1, 1)
+    rows = E * U if multi else E
+    obs_t = torch.zeros((T + 1,) + tuple(env.obs.shape), device=dev)
+    act_t = torch.zeros((T, E, U), dtype=torch.uint8, device=dev)
+    logp_t = torch.zeros((T, rows, heads), device=dev)
+    vf_t, rew_t = torch.zeros((T + 1, rows), device=dev), torch.zeros((T, rows), device=dev)
+    adv_t, tgt_t = torch.zeros((T, rows), device=dev), torch.zeros((T, rows), device=dev)
+
+    def value(o):
+        return (torch.tanh(torch.tanh(o.view(-1, D).to(dt) @ V1) @ V2) @ Vo).float().view(-1)
+
+    def torch_batch():
+        """The same batch with the HIP actor (actions + logp), the value network and GAE as torch ops; rows only."""
+        obs_t[0].copy_(env.obs)
+        ends = []
+        for t in range(T):
+            hip.act(env, obs=obs_t[t], out=act_t[t], logp=logp_t[t])
+            vf_t[t] = value(obs_t[t])
+            env.step_into(act_t[t], obs_t[t + 1], rew_t[t])
+            ends.append(env.time >= env.episode_length)
+            if ends[-1]:
+                env.reset_into(obs_t[t + 1])
+        vf_t[T] = value(obs_t[T])
+        nv, A = (torch.zeros_like(vf_t[T]) if ends[-1] else vf_t[T]), torch.zeros_like(vf_t[T])
+        for t in range(T - 1, -1, -1):
+            if ends[t]:
+                nv, A = torch.zeros_like(nv), torch.zeros_like(A)
+            A = rew_t[t] + gamma * nv - vf_t[t] + gamma * lam * A
+            adv_t[t], tgt_t[t] = A, A + vf_t[t]
+            nv = vf_t[t]
+        env.obs.copy_(obs_t[T])
+
+    state = {'buf': None}
+
+    def hip_batch():
+        state['buf'] = collect(env, hip, T, gamma, lam, compact=a.compact, out=state['buf'])
+
+    def timed(fn, n):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        for _ in range(n):
+            fn()
+        torch.cuda.synchronize()
+        return (time.perf_counter() - t0) / (n * T)
+
+    n = max(1, a.steps // T)
+    env.reset()
+    torch_batch()
+    hip_batch()
+    res = {'torch': [], 'hip': []}
+    for _ in range(3):                                  # interleaved: drift of the clocks shows as spread, not as a difference
+        env.reset()
+        res['torch'].append(timed(torch_batch, n))
+        env.reset()
+        res['hip'].append(timed(hip_batch, n))
+    form = 'shared value_out' if a.shared_value else 'value trunk of its own'
+    print(f'{E} envs x {U} UE x {B} BS ({a.kind}), actor 2x256 tanh + {form}, batches of T = {T}, {n} batches per timing')
+    for k, name in (('torch', f'hip actor + torch value ({a.dtype}) + torch GAE'), ('hip', 'sampler.collect' + (' (compact record)' if a.compact else ''))):
+        ts = res[k]
+        print(f'{name:<46}: ' + ' / '.join(f'{t * 1e3:.3f}' for t in ts) + f' ms/step  (best {E / min(ts):.3e} env-steps/s)')
+    print(f'collect vs torch value + torch GAE: {min(res["torch"]) / min(res["hip"]):.2f} x')
+    env.check()
+
+
+if a.collect:
+    collect_mode(a.collect)
+    sys.exit(0)
 packed = torch.zeros((E, env.compact_words), dtype=torch.int32, device=dev) if a.compact else None
 act_buf = torch.zeros((E, U), dtype=torch.uint8, device=dev)
 

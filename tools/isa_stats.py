@@ -3,6 +3,7 @@
 instruction counts by class, for the whole kernel and for its outermost loop (the step loop of the fused rollout).
 
     python tools/isa_stats.py --b 5 --upad 16 [--filter rollout] [--flags=-DDCOMP_X=1] [--keep /tmp/isa]
+    python tools/isa_stats.py --src dcomp_actor.hip [--filter actor_kernel]      # another translation unit (--b / --upad do not apply)
 
 Compiles deepcomp_amd/csrc/dcomp_inst.hip to assembly (hipcc -S --cuda-device-only, a few seconds with --upad).  Static counts are
 not dynamic counts (rare branches are in there), but a change that removes spills or a block of VALU work shows up here
@@ -50,12 +51,14 @@ def main():
     ap.add_argument('--filter', default='')
     ap.add_argument('--flags', default='')
     ap.add_argument('--keep', default='/tmp/isa')
+    ap.add_argument('--src', default='dcomp_inst.hip', help='translation unit under deepcomp_amd/csrc')
     a = ap.parse_args()
     os.makedirs(a.keep, exist_ok=True)
-    out = os.path.join(a.keep, f'b{a.b}_u{a.upad}.s')
+    inst = a.src == 'dcomp_inst.hip'
+    out = os.path.join(a.keep, f'b{a.b}_u{a.upad}.s' if inst else os.path.splitext(a.src)[0] + '.s')
     cmd = ['hipcc', '--offload-arch=gfx950', '-O3', '-std=c++17', '-fPIC', '-ffp-contract=fast-honor-pragmas', f'-DDCOMP_B={a.b}',
-           '-S', '--cuda-device-only', '-o', out, os.path.join(REPO, 'deepcomp_amd', 'csrc', 'dcomp_inst.hip')]
-    if a.upad:
+           '-S', '--cuda-device-only', '-o', out, os.path.join(REPO, 'deepcomp_amd', 'csrc', a.src)]
+    if a.upad and inst:
         cmd.insert(-4, f'-DDCOMP_ONLY_UPAD={a.upad}')
     cmd[1:1] = [f for f in a.flags.split() if f]
     r = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
@@ -65,7 +68,7 @@ def main():
     meta = {}
     for m in re.finditer(r'\.name:\s+(\S+)\n(?:.*\n)*?\s+\.sgpr_count:\s+(\d+)\n\s+\.sgpr_spill_count:\s+(\d+)\n(?:.*\n)*?\s+\.vgpr_count:\s+(\d+)\n\s+\.vgpr_spill_count:\s+(\d+)', txt):
         meta[m.group(1)] = tuple(int(x) for x in m.groups()[1:])
-    lds = {m.group(1): int(m.group(2)) for m in re.finditer(r'\.group_segment_fixed_size:\s+(\d+)', '')}
+    scratch = {m.group(1): int(m.group(2)) for m in re.finditer(r'\.name:\s+(\S+)\n(?:.*\n)*?\s+\.private_segment_fixed_size:\s+(\d+)', txt)}
     for name in sorted(meta):
         dem = subprocess.run(['c++filt', name], stdout=subprocess.PIPE, text=True).stdout.strip()
         if a.filter and a.filter not in dem:
@@ -83,7 +86,7 @@ def main():
             return c
         whole = count(body)
         s, sp, v, vsp = meta[name]
-        print(f'{dem}\n   sgpr {s} (spilled {sp})  vgpr {v} (spilled {vsp})')
+        print(f'{dem}\n   sgpr {s} (spilled {sp})  vgpr {v} (spilled {vsp})  scratch {scratch.get(name, "?")} B')
         print('   whole kernel:', dict(sorted(whole.items())), 'total', sum(whole.values()))
         if loop_at is not None:
             lp = count(body[loop_at:])
