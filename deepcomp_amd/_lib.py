@@ -105,6 +105,37 @@ EXPORTS = ['dcomp_abi_version', 'dcomp_create_v', 'dcomp_create', 'dcomp_destroy
            'dcomp_actor_create', 'dcomp_actor_destroy', 'dcomp_actor_actions',
            'dcomp_actor_set_value', 'dcomp_actor_actions_v', 'dcomp_gae']
 
+# include/dcomp_learner.h: the PPO learner.  A list of its own: EXPORTS is what include/dcomp.h declares.
+LEARNER_EXPORTS = ['dcomp_learner_create', 'dcomp_learner_destroy', 'dcomp_learner_grads', 'dcomp_learner_evaluate', 'dcomp_learner_apply',
+                   'dcomp_learner_read', 'dcomp_learner_load_state']
+LEARNER_ARRAYS = ('w1', 'b1', 'w2', 'b2', 'w3', 'b3', 'vw1', 'vb1', 'vw2', 'vb2', 'wv', 'bv')
+LEARNER_WEIGHTS, LEARNER_GRADS, LEARNER_ADAM_M, LEARNER_ADAM_V = 0, 1, 2, 3
+PPO_NUM_STATS = 5
+PPO_STATS = ('total_loss', 'policy_loss', 'vf_loss', 'kl', 'entropy')
+
+
+class DcompLearnerArrays(ctypes.Structure):
+    _fields_ = [('struct_size', ctypes.c_int32), ('reserved', ctypes.c_int32)] + [(n, _fp) for n in LEARNER_ARRAYS]
+
+
+class DcompLearnerCfg(ctypes.Structure):
+    _fields_ = [('struct_size', ctypes.c_int32), ('value_shared', ctypes.c_int32), ('max_rows', ctypes.c_int64),
+                ('beta1', ctypes.c_float), ('beta2', ctypes.c_float), ('eps', ctypes.c_float), ('reserved', ctypes.c_int32),
+                ('weights', ctypes.POINTER(DcompLearnerArrays))]
+
+
+class DcompPpoBatch(ctypes.Structure):
+    _fields_ = [('struct_size', ctypes.c_int32), ('obs_format', ctypes.c_int32), ('rows', ctypes.c_int64),
+                ('num_active', ctypes.c_int32), ('reserved', ctypes.c_int32)] + \
+               [(n, ctypes.c_void_p) for n in ('obs', 'actions', 'old_logp', 'old_logits', 'advantages', 'value_targets', 'old_vf',
+                                               'logp', 'entropy', 'kl', 'vf', 'ratio', 'dlogits', 'dvalue')]
+
+
+class DcompPpoHyper(ctypes.Structure):
+    _fields_ = [('struct_size', ctypes.c_int32), ('clip_param', ctypes.c_float), ('vf_clip_param', ctypes.c_float),
+                ('vf_loss_coeff', ctypes.c_float), ('entropy_coeff', ctypes.c_float), ('kl_coeff', ctypes.c_float)]
+
+
 _lib = None
 
 
@@ -185,6 +216,17 @@ def load():
         L.dcomp_gae.argtypes = [ctypes.POINTER(DcompGaeArgs), vp]
     if os.environ.get('DCOMP_LIB'):              # timing variants built from older sources lack the newest entry points
         EXPORTS[:] = [n for n in EXPORTS if hasattr(L, n)]
+    if hasattr(L, 'dcomp_learner_create') or not os.environ.get('DCOMP_LIB'):
+        ap = ctypes.POINTER(DcompLearnerArrays)
+        L.dcomp_learner_create.argtypes = [vp, ctypes.POINTER(DcompLearnerCfg), ctypes.POINTER(vp)]
+        L.dcomp_learner_destroy.argtypes = [vp]
+        L.dcomp_learner_grads.argtypes = [vp, ctypes.POINTER(DcompPpoBatch), ctypes.POINTER(DcompPpoHyper), vp, vp]
+        L.dcomp_learner_evaluate.argtypes = [vp, ctypes.POINTER(DcompPpoBatch), vp]
+        L.dcomp_learner_apply.argtypes = [vp, ctypes.c_float, vp]
+        L.dcomp_learner_read.argtypes = [vp, i32, ap, ctypes.POINTER(i64), vp]
+        L.dcomp_learner_load_state.argtypes = [vp, ap, ap, ap, i64, vp]
+        for name in LEARNER_EXPORTS:
+            getattr(L, name)
     for name in EXPORTS:
         getattr(L, name)
     _lib = L

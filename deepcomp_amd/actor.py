@@ -9,7 +9,8 @@ the activations kept on chip, and out comes the uint8 action tensor ``env.step``
     act = actor.act(env)                               # uint8 [E, U], feed straight into env.step(act)
 
 ``multi``: one decision row per (env, UE slot), the weights shared across UEs (DD-CoMP), one categorical head of B + 1 actions.
-``central``: one row per env, U heads (MultiDiscrete, central.py:28).  D3-CoMP's per-UE networks and training are not covered.
+``central``: one row per env, U heads (MultiDiscrete, central.py:28).  D3-CoMP's per-UE networks are not covered; training is
+deepcomp_amd.learner.PPOLearner, on this actor's handle.
 
 The value function of a PPO policy rides in the same launch once attached (``value_weights=`` / ``set_value``): RLlib's fcnet has it
 as a trunk of its own (``fc_value_1``, ``fc_value_2``, ``value_out``: PPO's default, vf_share_layers=False) or as ``value_out`` on
@@ -331,7 +332,7 @@ class FcnetActor:
                                                          ctypes.c_void_p(vf.data_ptr()), self._stream()))
         return out
 
-    def act(self, env, sample=True, obs=None, compact=False, out=None, logp=None, vf=None):
+    def act(self, env, sample=True, obs=None, compact=False, out=None, logp=None, vf=None, logits=None):
         """The actor's actions on env.obs (or on `obs`, e.g. the record env.step_compact wrote: compact=True) as the tensor
         env.step takes.  Draws are keyed by the env's seed, step = env.time + episode * episode_length and the GLOBAL decision row
         (env_id_base * U on a sharded env): reproducible, and independent of how the env axis is split over GPUs."""
@@ -340,4 +341,4 @@ class FcnetActor:
         rows_per_env = self.U if self.kind == _lib.MULTI else 1
         return self.actions(env.obs if obs is None else obs, compact=compact, sample=sample, seed=env.seed_value,
                             step=env.time + max(env.episode, 0) * env.episode_length, row_base=env.env_id_base * rows_per_env,
-                            num_active=env.num_ue, out=out, logp=logp, vf=vf)
+                            num_active=env.num_ue, out=out, logp=logp, vf=vf, logits=logits)

@@ -3,7 +3,8 @@
     python -m deepcomp_amd.build [--force] [--jobs N]
 
 One object per base-station count listed in csrc/dcomp_blist.h (all UE-group widths inside), compiled
-in parallel, plus the API object, the generic kernel's and the actor's (csrc/dcomp_actor.hip: actor, value function, GAE); linked into deepcomp_amd/csrc/libdcomp_hip.so.  hipcc cross-compiles
+in parallel, plus the API object, the generic kernel's, the actor's (csrc/dcomp_actor.hip: actor, value function, GAE) and the learner's
+(csrc/dcomp_learner.hip: PPO loss, backward pass, Adam); linked into deepcomp_amd/csrc/libdcomp_hip.so.  hipcc cross-compiles
 for gfx950 without a GPU present.
 """
 import argparse
@@ -35,8 +36,8 @@ def b_list():
 
 def _sources():
     return [os.path.join(CSRC, f) for f in ('dcomp_device.h', 'dcomp_wide.h', 'dcomp_dyn.h', 'dcomp_blist.h', 'dcomp_inst.hip', 'dcomp_api.hip', 'dcomp_fragment.h',
-                                            'dcomp_big.h', 'dcomp_big.hip', 'dcomp_actor.hip')] + \
-        [os.path.join(os.path.dirname(HERE), 'include', f) for f in ('dcomp.h', 'dcomp_types.h')]
+                                            'dcomp_big.h', 'dcomp_big.hip', 'dcomp_actor.hip', 'dcomp_actor_impl.h', 'dcomp_learner.hip')] + \
+        [os.path.join(os.path.dirname(HERE), 'include', f) for f in ('dcomp.h', 'dcomp_types.h', 'dcomp_learner.h')]
 
 
 def _dev_flags():
@@ -125,6 +126,8 @@ def build(force=False, jobs=None, extra_flags=()):
     tasks.append((o_big, [hipcc] + CXXFLAGS + list(extra_flags) + ['-c', os.path.join(CSRC, 'dcomp_big.hip'), '-o', o_big]))
     o_actor = os.path.join(OBJ, 'dcomp_actor.o')    # the fcnet actor (MFMA forward + action sampling): its own object, it shares no kernel code
     tasks.append((o_actor, [hipcc] + CXXFLAGS + list(extra_flags) + ['-c', os.path.join(CSRC, 'dcomp_actor.hip'), '-o', o_actor]))
+    o_learner = os.path.join(OBJ, 'dcomp_learner.o')    # the PPO learner on the actor's handle (shares csrc/dcomp_actor_impl.h with it)
+    tasks.append((o_learner, [hipcc] + CXXFLAGS + list(extra_flags) + ['-c', os.path.join(CSRC, 'dcomp_learner.hip'), '-o', o_learner]))
 
     def obj_stamp(t):
         """An object is rebuilt when its command line or one of ITS inputs changed: the per-station-count objects do not
@@ -134,9 +137,13 @@ def build(force=False, jobs=None, extra_flags=()):
         for f in _sources():
             if f.endswith(('dcomp_api.hip', 'dcomp_fragment.h')) and not t[0].endswith('dcomp_api.o'):
                 continue
-            if f.endswith(os.sep + 'dcomp.h') and not t[0].endswith(('dcomp_api.o', 'dcomp_actor.o')):
+            if f.endswith(os.sep + 'dcomp.h') and not t[0].endswith(('dcomp_api.o', 'dcomp_actor.o', 'dcomp_learner.o')):
                 continue
             if f.endswith('dcomp_actor.hip') and not t[0].endswith('dcomp_actor.o'):
+                continue
+            if f.endswith('dcomp_actor_impl.h') and not t[0].endswith(('dcomp_actor.o', 'dcomp_learner.o')):
+                continue
+            if f.endswith(('dcomp_learner.hip', 'dcomp_learner.h')) and not t[0].endswith('dcomp_learner.o'):
                 continue
             if f.endswith(('dcomp_big.h', 'dcomp_big.hip')) and not t[0].endswith(('dcomp_api.o', 'dcomp_big.o')):
                 continue

@@ -1,0 +1,965 @@
+// dcomp_learner.hip -- the PPO learner of the fcnet a dcomp_actor runs (include/dcomp_learner.h): loss, backward pass and Adam.
+//
+// Four kernels per minibatch, all deterministic (no floating-point atomics; every sum has an order fixed by the row count):
+//   learner_kernel   forward + loss + backward-data.  The shape of actor_kernel: a wavefront owns 32 decision rows on its lanes and
+//                    runs layers 1-3 transposed on v_mfma_f32_32x32x16_bf16, the logits pass through the [32][33] LDS tile and lane r
+//                    walks row r's columns -- with the GIVEN action, and the same online log-sum-exp in the same order, so at unchanged
+//                    weights logp is what the actor wrote, bit for bit.  A second walk over the recomputed logits writes dlogits back
+//                    into the tile.  Backward stays transposed: dH2^T = W3 dlogits^T, dH1^T = W2 dA2^T with the weights as the A
+//                    operand in the OTHER orientation (a second packed copy, w2b / w3b); the accumulator has the hidden unit in its
+//                    register and the row on its lane exactly like the h fragments, so (.) act'(h) and the bf16 conversion stay in
+//                    registers.  The value trunk is a second sweep.  x, h1, h2, dA1, dA2, dlogits go to HBM as bf16 [width][rows]
+//                    (64-byte runs per store instruction) for the weight gradients; per-tile sums of the statistics to a workspace.
+//   wgrad_kernel     dW[in][out] = sum over rows a (x) d: rows are the K axis here, and in [width][rows] order both MFMA operands are
+//                    one 16-byte load per lane.  One wave per (block of up to 2 x 4 tiles of 32 x 32, row chunk): six operand loads
+//                    feed eight MFMAs; f32 partials per chunk; the bias gradient is one more MFMA against a fragment of ones.
+//   reduce_kernel    sums the chunk partials in chunk order, applies 1 / N once, writes the natural [in][out] gradients; and the
+//                    five statistics from the per-tile sums.
+//   adam_kernel      adam_reference (deepcomp_amd/learner.py) under `#pragma clang fp contract(off)`, then each thread scatters
+//                    its weight as bf16 into the actor handle's packed fragments, in both orientations: the device form of pack().
+// Padded hidden units: the packed copies hold zeros there, forward (h = act(0) = 0) and backward (a zero row of w3b / w2b gives
+// dH = 0), no kernel ever writes a padded entry, and reduce / adam only visit real entries.
+#include <hip/hip_runtime.h>
+
+#include <cmath>
+#include <cstdarg>
+#include <cstdint>
+#include <cstdio>
+#include <cstring>
+#include <vector>
+
+#define DCOMP_BUILDING_LIBRARY 1
+#include "../../include/dcomp.h"
+#include "../../include/dcomp_learner.h"
+#include "dcomp_actor_impl.h"
+
+namespace dcomp { int report(int code, const char *msg); }       // dcomp_api.hip: the thread's dcomp_last_error() text
+
+namespace dlearn {
+
+using namespace dactor;
+
+constexpr int NARR = 12;                  // w1 b1 w2 b2 w3 b3 | vw1 vb1 vw2 vb2 wv bv
+constexpr int CHUNK_UNIT = 2048;          // rows of a weight-gradient chunk: CHUNK_UNIT x the smallest factor that keeps ...
+constexpr int MAX_CHUNKS = 128;           // ... the chunk count at or below this
+
+struct LParams {
+    const float *obs;
+    const uint8_t *actions;
+    const float *old_logp, *old_logits, *adv, *vtarg, *old_vf;
+    float *o_logp, *o_ent, *o_kl, *o_vf, *o_ratio;
+    const float *up_dlogits, *up_dvalue;
+    const uint4 *w1, *w2, *w3, *vw1, *vw2, *vw3;      // the actor handle's forward fragments
+    const float *b1, *b2, *b3, *vb1, *vb2, *vb3;
+    const uint4 *w2b, *w3b, *vw2b, *vw3b;             // the backward orientation
+    __bf16 *X, *H1, *H2, *D1, *D2, *D3, *VH1, *VH2, *VD1, *VD2, *VD3;    // [width][ld]
+    float4 *headws;                                   // [rows][heads]: lse, old lse, entropy of the head
+    float4 *part;                                     // [tiles]: sums of surrogate, kl, entropy, vf loss over the tile's counted rows
+    int64_t rows, tiles, ld;
+    int32_t K1, K1p, XS, N3, NT3, heads, B, U, num_active, multi, lds_per_wave, fwd_only, upstream;
+    float clip, vf_clip, vf_coeff, ent_coeff, kl_coeff;
+};
+
+// one output tile of a hidden -> out layer: sum over the 2 MT k steps of fragments first ... of w with the B fragments b
+template <int MT> __device__ __forceinline__ f32x16 tile_dot(const uint4 *w, size_t first, const bf16x8 (&b)[MT][2], uint32_t lane16)
+{
+    constexpr int KS2 = 2 * MT, D = KS2 < 8 ? KS2 : 8;
+    f32x16 acc;
+#pragma unroll
+    for (int i = 0; i < 16; i++) acc[i] = 0.f;
+#pragma unroll
+    for (int g = 0; g < KS2; g += D) {
+        uint4 q[D];
+#pragma unroll
+        for (int i = 0; i < D; i++) q[i] = load_frag(w, first + g + i, lane16);
+#pragma unroll
+        for (int i = 0; i < D; i++) acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(as_frag(q[i]), b[(g + i) >> 1][(g + i) & 1], acc, 0, 0, 0);
+        __builtin_amdgcn_sched_barrier(0);               // (group by group: left alone every load of the layer is hoisted to its top)
+    }
+    return acc;
+}
+
+// the fragments of a layer's activations or deltas -> ws[unit][ld] at column col: element j of f[t][s] on lane half h is unit
+// 32 t + 16 s + 8 (j >> 2) + 4 h + (j & 3); the 32 lanes of a half write one 64-byte run per element
+template <int MT> __device__ __forceinline__ void store_frags(__bf16 *ws, int64_t ld, uint32_t voff, const bf16x8 (&f)[MT][2])
+{
+    // voff = the lane's byte offset 2 (column + 4 h ld) (< 2^32: dcomp_learner_create bounds max_rows); the unit's part of the address is
+    // uniform.  Opaque at every store, as in load_frag: hoisted out of the tile loop the ~600 lane addresses would be spilled registers.
+#pragma unroll
+    for (int t = 0; t < MT; t++)
+#pragma unroll
+        for (int s = 0; s < 2; s++)
+#pragma unroll
+            for (int j = 0; j < 8; j++) {
+                asm volatile("" : "+v"(voff));
+                char *row = reinterpret_cast<char *>(ws) + (size_t)(32 * t + 16 * s + 8 * (j >> 2) + (j & 3)) * (size_t)ld * 2;
+                *reinterpret_cast<__bf16 *>(row + voff) = f[t][s][j];
+            }
+}
+
+// d = bf16(dH (.) act'(h)), h the stored bf16 activation
+template <int MT, bool RELU> __device__ __forceinline__ void delta_frags(const f32x16 (&dh)[MT], const bf16x8 (&hf)[MT][2], bf16x8 (&d)[MT][2])
+{
+#pragma unroll
+    for (int t = 0; t < MT; t++)
+#pragma unroll
+        for (int s = 0; s < 2; s++)
+#pragma unroll
+            for (int j = 0; j < 8; j++) {
+                const float hv = (float)hf[t][s][j], g = dh[t][8 * s + j];
+                d[t][s][j] = (__bf16)(RELU ? (hv > 0.f ? g : 0.f) : g * (1.f - hv * hv));
+            }
+}
+
+// one step of actor_kernel's online log-sum-exp (its expression, term for term): the sum rescaled to the new maximum; e1, e2 are
+// the two exponentials, for the sums that ride along
+__device__ __forceinline__ void lse_push(float x, float &mx, float &sm, float &e1, float &e2)
+{
+    const float m2 = fmaxf(mx, x);
+    e1 = expf(mx - m2); e2 = expf(x - m2);
+    sm = sm * e1 + e2;
+    mx = m2;
+}
+
+__device__ __forceinline__ float wave_sum(float v)       // a fixed tree over the 64 lanes
+{
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+    return v;
+}
+
+template <int MT, bool RELU>
+__global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(1, 1))) void learner_kernel(const LParams p)
+{
+    extern __shared__ uint4 lds4[];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, r = lane & 31, h = lane >> 5;
+    const uint32_t lane16 = (uint32_t)lane * 16u;
+    unsigned char *base = reinterpret_cast<unsigned char *>(lds4) + (size_t)wave * p.lds_per_wave;
+    __bf16 *xs = reinterpret_cast<__bf16 *>(base);                                   // [32][XS] bf16: the chunk of the tile's rows
+    float *lt = reinterpret_cast<float *>(base + (size_t)TILE * p.XS * 2);           // [32][LT] f32: 32 logits / dlogits of every row
+    uint32_t *ri = reinterpret_cast<uint32_t *>(lt + TILE * LT);                     // [32]: the row is read and counted
+    const int XS = p.XS, K1 = p.K1, U = p.U, NA = p.B + 1;
+    const int KS1 = p.K1p >> 4;
+    constexpr int KS2 = 2 * MT;
+    const int64_t ld = p.ld;
+
+    for (int64_t tile = (int64_t)blockIdx.x * WAVES + wave; tile < p.tiles; tile += (int64_t)gridDim.x * WAVES) {
+        const int64_t row0 = tile * TILE;
+        const int nrow = (int)(p.rows - row0 < TILE ? p.rows - row0 : TILE);
+        const int64_t myrow = row0 + r;                                              // the decision row on this lane
+        const bool have = r < nrow;
+        // a row beyond the batch, or a multi-agent row of an unlisted slot: computed on zeros, every delta zero, nothing of it read
+        const bool live = have && !(p.multi && (int)(myrow % U) >= p.num_active);
+        const bool walker = lane < TILE && live;
+        const uint32_t voff = (uint32_t)(2 * ((uint64_t)myrow + (uint64_t)(4 * h) * (uint64_t)ld));      // store_frags: this lane's column
+        if (lane < TILE) ri[lane] = live ? 1u : 0u;
+        wave_fence();
+        float s_surr = 0.f, s_kl = 0.f, s_ent = 0.f, s_vfl = 0.f;                     // this row's terms (lanes < 32)
+        float c_lp = 0.f;                                                            // d(-surrogate) / d(logp)
+
+#pragma nounroll
+        for (int sweep = 0; sweep < 2; sweep++) {
+        const bool val = sweep != 0;
+        const uint4 *w1 = val ? p.vw1 : p.w1, *w2 = val ? p.vw2 : p.w2, *w3 = val ? p.vw3 : p.w3;
+        const uint4 *w2b = val ? p.vw2b : p.w2b, *w3b = val ? p.vw3b : p.w3b;
+        const float *b1 = val ? p.vb1 : p.b1, *b2 = val ? p.vb2 : p.b2, *b3 = val ? p.vb3 : p.b3;
+        __bf16 *H1 = val ? p.VH1 : p.H1, *H2 = val ? p.VH2 : p.H2, *D1 = val ? p.VD1 : p.D1, *D2 = val ? p.VD2 : p.D2, *D3 = val ? p.VD3 : p.D3;
+        const int NT3 = val ? 1 : p.NT3, N3 = val ? 1 : p.N3;
+        const bool staged = val && p.K1p <= KC;                                      // the policy sweep left the bf16 rows in LDS
+
+        // ---- layer 1: acc[m] = W1^T (units 32m ...) x X^T, the inputs in chunks through LDS (as actor_kernel)
+        f32x16 acc[MT];
+#pragma unroll
+        for (int m = 0; m < MT; m++)
+#pragma unroll
+            for (int i = 0; i < 16; i++) acc[m][i] = 0.f;
+        uint4 wq1[MT];
+#pragma unroll
+        for (int m = 0; m < MT; m++) wq1[m] = load_frag(w1, (size_t)m * KS1, lane16);
+        for (int k0 = 0; k0 < p.K1p; k0 += KC) {
+            const int kc = p.K1p - k0 < KC ? p.K1p - k0 : KC;                        // a multiple of 16
+            const uint32_t magic = (uint32_t)(0x100000000ull / (uint32_t)kc) + 1u;   // f / kc = umulhi(f, magic): f < 2^14, f kc < 2^32
+            const int nf = staged ? 0 : TILE * kc;
+#pragma unroll 4
+            for (int f = lane; f < nf; f += 64) {
+                const int rr = (int)__umulhi((uint32_t)f, magic), c = f - rr * kc, k = k0 + c;
+                float v = 0.f;
+                if (ri[rr] && k < K1) v = p.obs[(size_t)(row0 + rr) * K1 + k];
+                xs[rr * XS + c] = (__bf16)v;
+            }
+            wave_fence();
+            if (!val && !p.fwd_only) {                                               // x as bf16 [input][rows] for dW1 of both trunks
+                for (int i = lane; i < kc * TILE; i += 64) {
+                    const int c = i >> 5, rr = i & 31;
+                    p.X[(size_t)(k0 + c) * (size_t)ld + (size_t)(row0 + rr)] = xs[rr * XS + c];
+                }
+            }
+            for (int s = 0; s < (kc >> 4); s++) {
+                const bf16x8 b = as_frag(*reinterpret_cast<const uint4 *>(xs + r * XS + 16 * s + 8 * h));
+                const int ksn = (k0 >> 4) + s + 1 < KS1 ? (k0 >> 4) + s + 1 : KS1 - 1;          // (the last step re-reads itself)
+                uint4 nx[MT];
+#pragma unroll
+                for (int m = 0; m < MT; m++) nx[m] = load_frag(w1, (size_t)m * KS1 + ksn, lane16);
+#pragma unroll
+                for (int m = 0; m < MT; m++) acc[m] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(as_frag(wq1[m]), b, acc[m], 0, 0, 0);
+#pragma unroll
+                for (int m = 0; m < MT; m++) wq1[m] = nx[m];
+            }
+            wave_fence();
+        }
+
+        bf16x8 h1[MT][2];
+#pragma unroll
+        for (int t = 0; t < MT; t++) {
+            h1[t][0] = next_fragment<RELU>(acc[t], 0, b1 + 32 * t + 4 * h);
+            h1[t][1] = next_fragment<RELU>(acc[t], 1, b1 + 32 * t + 4 * h);
+            asm volatile("" : "+v"(h1[t][0]), "+v"(h1[t][1]));
+            __builtin_amdgcn_sched_barrier(0);
+        }
+        if (!p.fwd_only) store_frags<MT>(H1, ld, voff, h1);
+
+        // ---- layer 2
+        bf16x8 h2[MT][2];
+#pragma unroll
+        for (int m = 0; m < MT; m++) {
+            const f32x16 a2 = tile_dot<MT>(w2, (size_t)m * KS2, h1, lane16);
+            h2[m][0] = next_fragment<RELU>(a2, 0, b2 + 32 * m + 4 * h);
+            h2[m][1] = next_fragment<RELU>(a2, 1, b2 + 32 * m + 4 * h);
+            asm volatile("" : "+v"(h2[m][0]), "+v"(h2[m][1]));
+            __builtin_amdgcn_sched_barrier(0);
+        }
+        if (!p.fwd_only) store_frags<MT>(H2, ld, voff, h2);
+
+        // ---- layer 3, first walk: the log-sum-exp of every head (new and old logits), logp of the given action, the entropy
+        float logp_sum = 0.f, oldlp_sum = 0.f, ent_sum = 0.f;
+        {
+            int hd = 0, a = 0, act = 0;
+            float xa = 0.f, mx = -INFINITY, sm = 0.f, tn = 0.f, mo = -INFINITY, so = 0.f;
+            for (int nt = 0; nt < NT3; nt++) {
+                const f32x16 a3 = tile_dot<MT>(w3, (size_t)nt * KS2, h2, lane16);
+                const float *bias = b3 + 32 * nt + 4 * h;
+#pragma unroll
+                for (int g = 0; g < 4; g++) {
+                    const float4 bv = *reinterpret_cast<const float4 *>(bias + 8 * g);
+                    float *d = lt + r * LT + 8 * g + 4 * h;
+                    d[0] = a3[4 * g + 0] + bv.x; d[1] = a3[4 * g + 1] + bv.y; d[2] = a3[4 * g + 2] + bv.z; d[3] = a3[4 * g + 3] + bv.w;
+                }
+                wave_fence();
+                if (!val && walker && p.actions) {
+                    const int ncol = N3 - 32 * nt < 32 ? N3 - 32 * nt : 32;
+                    for (int c = 0; c < ncol; c++) {
+                        const float x = lt[r * LT + c];
+                        if (a == 0) act = p.actions[(size_t)myrow * p.heads + hd];
+                        if (a == act) xa = x;
+                        float e1, e2;
+                        lse_push(x, mx, sm, e1, e2);
+                        tn = tn * e1 + x * e2;
+                        if (p.old_logits) lse_push(p.old_logits[(size_t)myrow * p.N3 + 32 * nt + c], mo, so, e1, e2);
+                        if (++a == NA) {
+                            const size_t at = (size_t)myrow * p.heads + hd;
+                            const float lse = mx + logf(sm), lp = xa - lse, eh = lse - tn / sm;
+                            if (p.o_logp) p.o_logp[at] = lp;
+                            if (p.multi || hd < p.num_active) {
+                                logp_sum += lp; ent_sum += eh;
+                                if (p.old_logp) oldlp_sum += p.old_logp[at];
+                            }
+                            if (!p.fwd_only) p.headws[at] = make_float4(lse, mo + logf(so), eh, 0.f);
+                            a = 0; hd++; xa = 0.f;
+                            mx = -INFINITY; sm = 0.f; tn = 0.f; mo = -INFINITY; so = 0.f;
+                        }
+                    }
+                }
+                wave_fence();
+            }
+        }
+        if (!val) {
+            if (walker && p.o_ent) p.o_ent[myrow] = ent_sum;
+            s_ent = walker ? ent_sum : 0.f;
+            if (!p.fwd_only && !p.upstream && walker) {
+                const float adv = p.adv[myrow], ratio = expf(logp_sum - oldlp_sum);
+                const float s1 = adv * ratio, s2 = adv * fminf(fmaxf(ratio, 1.f - p.clip), 1.f + p.clip);
+                s_surr = fminf(s1, s2);
+                c_lp = s1 <= s2 ? -s1 : 0.f;                                          // d(-min) / d(logp): d(adv ratio) / d(logp) = adv ratio
+                if (p.o_ratio) p.o_ratio[myrow] = ratio;
+            }
+        } else if (lane < TILE && have && p.o_vf) {
+            p.o_vf[myrow] = lt[r * LT];                                              // (the tile of the value sweep is still in LDS)
+        }
+        if (p.fwd_only) continue;
+
+        // ---- dlogits tile by tile into the LDS tile, and dH2^T = W3 dlogits^T
+        f32x16 dh[MT];
+#pragma unroll
+        for (int m = 0; m < MT; m++)
+#pragma unroll
+            for (int i = 0; i < 16; i++) dh[m][i] = 0.f;
+        {
+            int hd = 0, a = 0, act = 0;
+            float4 hw = make_float4(0.f, 0.f, 0.f, 0.f);
+            float kl_sum = 0.f;
+            for (int nt = 0; nt < NT3; nt++) {
+                const int ncol = N3 - 32 * nt < 32 ? N3 - 32 * nt : 32;
+                if (val) {
+                    // the value's one column: d(vf_loss_coeff max((v - vt)^2, (old_v + clip(v - old_v) - vt)^2)) / dv
+                    if (lane < TILE) {
+                        float dv = 0.f;
+                        if (walker) {
+                            if (p.upstream) dv = p.up_dvalue[myrow];
+                            else {
+                                const float v = lt[r * LT], vt = p.vtarg[myrow], ov = p.old_vf[myrow];
+                                const float d1 = v - vt, dc = fminf(fmaxf(v - ov, -p.vf_clip), p.vf_clip), d2 = (ov + dc) - vt;
+                                const float l1 = d1 * d1, l2 = d2 * d2;
+                                s_vfl = fmaxf(l1, l2);
+                                dv = p.vf_coeff * (l1 >= l2 ? 2.f * d1 : (fabsf(v - ov) < p.vf_clip ? 2.f * d2 : 0.f));
+                            }
+                        }
+                        for (int c = 1; c < 32; c++) lt[r * LT + c] = 0.f;
+                        lt[r * LT] = dv;
+                    }
+                } else if (p.upstream) {
+                    for (int i = lane; i < TILE * 32; i += 64) {
+                        const int rr = i >> 5, c = i & 31;
+                        lt[rr * LT + c] = ri[rr] && c < ncol ? p.up_dlogits[(size_t)(row0 + rr) * p.N3 + 32 * nt + c] : 0.f;
+                    }
+                } else {
+                    const f32x16 a3 = tile_dot<MT>(w3, (size_t)nt * KS2, h2, lane16);
+                    const float *bias = b3 + 32 * nt + 4 * h;
+#pragma unroll
+                    for (int g = 0; g < 4; g++) {
+                        const float4 bv = *reinterpret_cast<const float4 *>(bias + 8 * g);
+                        float *d = lt + r * LT + 8 * g + 4 * h;
+                        d[0] = a3[4 * g + 0] + bv.x; d[1] = a3[4 * g + 1] + bv.y; d[2] = a3[4 * g + 2] + bv.z; d[3] = a3[4 * g + 3] + bv.w;
+                    }
+                    wave_fence();
+                    if (lane < TILE) {
+                        if (!walker) {
+                            for (int c = 0; c < 32; c++) lt[r * LT + c] = 0.f;
+                        } else {
+                            for (int c = 0; c < ncol; c++) {
+                                const float x = lt[r * LT + c];
+                                if (a == 0) {
+                                    hw = p.headws[(size_t)myrow * p.heads + hd];
+                                    act = p.actions[(size_t)myrow * p.heads + hd];
+                                }
+                                float dl = 0.f;
+                                if (p.multi || hd < p.num_active) {
+                                    const float lpn = x - hw.x, pn = expf(lpn);
+                                    const float lpo = p.old_logits[(size_t)myrow * p.N3 + 32 * nt + c] - hw.y, po = expf(lpo);
+                                    kl_sum += po * (lpo - lpn);
+                                    dl = c_lp * ((a == act ? 1.f : 0.f) - pn) + p.kl_coeff * (pn - po) + p.ent_coeff * (pn * (lpn + hw.z));
+                                }
+                                lt[r * LT + c] = dl;
+                                if (++a == NA) { a = 0; hd++; }
+                            }
+                            for (int c = ncol; c < 32; c++) lt[r * LT + c] = 0.f;
+                        }
+                    }
+                }
+                wave_fence();
+                // dlogits as bf16 [logit][rows] for dW3 (columns beyond N3 are zeros)
+                for (int i = lane; i < TILE * 32; i += 64) {
+                    const int c = i >> 5, rr = i & 31;
+                    D3[(size_t)(32 * nt + c) * (size_t)ld + (size_t)(row0 + rr)] = (__bf16)lt[rr * LT + c];
+                }
+#pragma unroll
+                for (int s = 0; s < 2; s++) {
+                    bf16x8 b;
+#pragma unroll
+                    for (int j = 0; j < 8; j++) b[j] = (__bf16)lt[r * LT + 16 * s + 8 * h + j];
+                    uint4 q[MT];
+#pragma unroll
+                    for (int m = 0; m < MT; m++) q[m] = load_frag(w3b, ((size_t)m * NT3 + nt) * 2 + s, lane16);
+#pragma unroll
+                    for (int m = 0; m < MT; m++) dh[m] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(as_frag(q[m]), b, dh[m], 0, 0, 0);
+                    __builtin_amdgcn_sched_barrier(0);
+                }
+                wave_fence();
+            }
+            if (!val) {
+                s_kl = walker && !p.upstream ? kl_sum : 0.f;
+                if (walker && p.o_kl && !p.upstream) p.o_kl[myrow] = kl_sum;
+            }
+        }
+
+        // ---- dA2 = bf16(dH2 (.) act'(h2)), dH1^T = W2 dA2^T, dA1
+        bf16x8 d2[MT][2];
+        delta_frags<MT, RELU>(dh, h2, d2);
+        store_frags<MT>(D2, ld, voff, d2);
+        bf16x8 d1[MT][2];
+#pragma unroll
+        for (int m = 0; m < MT; m++) {
+            const f32x16 g = tile_dot<MT>(w2b, (size_t)m * KS2, d2, lane16);
+#pragma unroll
+            for (int s = 0; s < 2; s++)
+#pragma unroll
+                for (int j = 0; j < 8; j++) {
+                    const float hv = (float)h1[m][s][j], gv = g[8 * s + j];
+                    d1[m][s][j] = (__bf16)(RELU ? (hv > 0.f ? gv : 0.f) : gv * (1.f - hv * hv));
+                }
+            asm volatile("" : "+v"(d1[m][0]), "+v"(d1[m][1]));
+            __builtin_amdgcn_sched_barrier(0);
+        }
+        store_frags<MT>(D1, ld, voff, d1);
+        }
+
+        if (!p.fwd_only) {
+            const float a0 = wave_sum(lane < TILE ? s_surr : 0.f), a1 = wave_sum(lane < TILE ? s_kl : 0.f);
+            const float a2 = wave_sum(lane < TILE ? s_ent : 0.f), a3 = wave_sum(lane < TILE ? s_vfl : 0.f);
+            if (lane == 0) p.part[tile] = make_float4(a0, a1, a2, a3);
+        }
+        wave_fence();
+    }
+}
+
+typedef void (*learner_fn)(const LParams);
+static learner_fn pick(int mt, bool relu)
+{
+    switch (mt) {
+    case 1: return relu ? learner_kernel<1, true> : learner_kernel<1, false>;
+    case 2: return relu ? learner_kernel<2, true> : learner_kernel<2, false>;
+    case 4: return relu ? learner_kernel<4, true> : learner_kernel<4, false>;
+    default: return relu ? learner_kernel<8, true> : learner_kernel<8, false>;
+    }
+}
+
+// ---------------------------------------------------------------- weight gradients
+struct WDesc {
+    const __bf16 *a, *d;                  // [in_p][ld], [out_p][ld]
+    float *part, *bpart;                  // [chunk][in_p][out_p], [chunk][out_p]
+    int32_t mi_tiles, ni_tiles, first_task, nmain;     // nmain block tasks, then ni_tiles / NB bias tasks
+};
+struct WParams {
+    WDesc g[6];
+    int64_t ld, rows_pad, chunk_rows;
+    int32_t ntask;
+};
+
+// a wave's block of dW: MB x NB tiles of 32 x 32 -- 2 x 4 (six operand loads feed eight MFMAs per 16 rows) where the tile counts
+// divide, 1 where they do not (the out = 1 tile of a small head, an odd number of input tiles)
+__host__ __device__ inline int wgrad_mb(int mi_tiles) { return mi_tiles % 2 == 0 ? 2 : 1; }
+__host__ __device__ inline int wgrad_nb(int ni_tiles) { return ni_tiles % 4 == 0 ? 4 : 1; }
+
+template <int MB, int NB>
+__device__ __forceinline__ void wgrad_block(const WParams &p, const WDesc &g, int local, int lane)
+{
+    const int r = lane & 31, h = lane >> 5;
+    const int nblk = g.ni_tiles / NB, mi0 = (local / nblk) * MB, ni0 = (local % nblk) * NB;
+    const int64_t chunk = blockIdx.y, k0 = chunk * p.chunk_rows;
+    const int64_t k1 = k0 + p.chunk_rows < p.rows_pad ? k0 + p.chunk_rows : p.rows_pad;
+    const __bf16 *ap = g.a + (size_t)(32 * mi0 + r) * (size_t)p.ld + 8 * h;
+    const __bf16 *dp = g.d + (size_t)(32 * ni0 + r) * (size_t)p.ld + 8 * h;
+    const size_t tile_stride = (size_t)32 * (size_t)p.ld;
+    f32x16 acc[MB][NB];
+#pragma unroll
+    for (int j = 0; j < NB; j++)
+#pragma unroll
+        for (int e = 0; e < 16; e++)
+#pragma unroll
+            for (int i = 0; i < MB; i++) acc[i][j][e] = 0.f;
+    for (int64_t k = k0; k < k1; k += 16) {
+        bf16x8 A[MB], B[NB];
+#pragma unroll
+        for (int i = 0; i < MB; i++) A[i] = as_frag(*reinterpret_cast<const uint4 *>(ap + i * tile_stride + k));
+#pragma unroll
+        for (int j = 0; j < NB; j++) B[j] = as_frag(*reinterpret_cast<const uint4 *>(dp + j * tile_stride + k));
+#pragma unroll
+        for (int j = 0; j < NB; j++)
+#pragma unroll
+            for (int i = 0; i < MB; i++) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(A[i], B[j], acc[i][j], 0, 0, 0);
+    }
+    const int in_p = 32 * g.mi_tiles, out_p = 32 * g.ni_tiles;
+    float *dst = g.part + (size_t)chunk * (size_t)in_p * out_p;
+#pragma unroll
+    for (int i = 0; i < MB; i++)
+#pragma unroll
+        for (int j = 0; j < NB; j++)
+#pragma unroll
+            for (int e = 0; e < 16; e++)
+                dst[(size_t)(32 * (mi0 + i) + (e & 3) + 8 * (e >> 2) + 4 * h) * out_p + 32 * (ni0 + j) + r] = acc[i][j][e];
+}
+
+// the bias gradients of NB output tiles: the column sums of d as one MFMA per tile against a fragment of ones (every row of the
+// product holds them; row 0 is stored)
+template <int NB>
+__device__ __forceinline__ void wgrad_bias(const WParams &p, const WDesc &g, int blk, int lane)
+{
+    const int r = lane & 31, h = lane >> 5, ni0 = blk * NB;
+    const int64_t chunk = blockIdx.y, k0 = chunk * p.chunk_rows;
+    const int64_t k1 = k0 + p.chunk_rows < p.rows_pad ? k0 + p.chunk_rows : p.rows_pad;
+    const __bf16 *dp = g.d + (size_t)(32 * ni0 + r) * (size_t)p.ld + 8 * h;
+    const size_t tile_stride = (size_t)32 * (size_t)p.ld;
+    f32x16 bacc[NB];
+#pragma unroll
+    for (int j = 0; j < NB; j++)
+#pragma unroll
+        for (int e = 0; e < 16; e++) bacc[j][e] = 0.f;
+    bf16x8 ones;
+#pragma unroll
+    for (int j = 0; j < 8; j++) ones[j] = (__bf16)1.f;
+    for (int64_t k = k0; k < k1; k += 16) {
+#pragma unroll
+        for (int j = 0; j < NB; j++)
+            bacc[j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ones, as_frag(*reinterpret_cast<const uint4 *>(dp + j * tile_stride + k)), bacc[j], 0, 0, 0);
+    }
+    if (h == 0) {
+#pragma unroll
+        for (int j = 0; j < NB; j++) g.bpart[(size_t)chunk * 32 * g.ni_tiles + 32 * (ni0 + j) + r] = bacc[j][0];
+    }
+}
+
+__global__ __launch_bounds__(BLOCK) void wgrad_kernel(const WParams p)
+{
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int task = blockIdx.x * WAVES + wave;
+    if (task >= p.ntask) return;
+    int gi = 0;
+#pragma unroll
+    for (int i = 1; i < 6; i++) gi = task >= p.g[i].first_task ? i : gi;
+    const WDesc g = p.g[gi];
+    const int local = task - g.first_task, mb = wgrad_mb(g.mi_tiles), nb = wgrad_nb(g.ni_tiles);      // (wave-uniform)
+    if (local >= g.nmain) {                                                           // behind a product's blocks: its bias tasks
+        if (nb == 4) wgrad_bias<4>(p, g, local - g.nmain, lane);
+        else wgrad_bias<1>(p, g, local - g.nmain, lane);
+    } else if (mb == 2 && nb == 4) wgrad_block<2, 4>(p, g, local, lane);
+    else if (nb == 4) wgrad_block<1, 4>(p, g, local, lane);
+    else if (mb == 2) wgrad_block<2, 1>(p, g, local, lane);
+    else wgrad_block<1, 1>(p, g, local, lane);
+}
+
+// ---------------------------------------------------------------- the natural-layout arrays
+struct ADesc {
+    int32_t off, nin, nout, out_p, in_p, is_bias;            // [nin][nout] at `off` of the flat arrays (a bias: nin = 1)
+    const float *part;                                       // chunk partials ([chunk][in_p][out_p] / [chunk][out_p])
+    // repack targets: a weight goes as bf16 into the forward fragments and, layers 2 and 3, the backward ones; a bias as f32
+    uint16_t *fwd, *bwd;
+    float *bias;
+    int32_t fwd_ks, fwd_perm, bwd_ks, bwd_perm;
+};
+struct AParams {
+    ADesc a[NARR];
+    int32_t total, nchunks;
+    float scale;
+    float *w, *g, *m, *v;
+    const float4 *tile_part;
+    int64_t tiles;
+    float *stats;
+    double count;
+    float vf_coeff, ent_coeff, kl_coeff;
+    int32_t adam, want_stats;
+    float beta1, omb1, beta2, omb2, step_size, bc2_sqrt, eps;
+};
+
+__device__ __forceinline__ int find_array(const AParams &p, int e)
+{
+    int ai = 0;
+#pragma unroll
+    for (int i = 1; i < NARR; i++) ai = e >= p.a[i].off ? i : ai;
+    return ai;
+}
+
+__global__ __launch_bounds__(256) void reduce_kernel(const AParams p)
+{
+    const int e = blockIdx.x * 256 + threadIdx.x;
+    if (e < p.total) {
+        const int ai = find_array(p, e);
+        const ADesc d = p.a[ai];
+        const int idx = e - d.off, k = idx / d.nout, o = idx - k * d.nout;
+        const size_t stride = d.is_bias ? (size_t)d.out_p : (size_t)d.in_p * d.out_p, at = (size_t)k * d.out_p + o;
+        float s = 0.f;
+        for (int c = 0; c < p.nchunks; c++) s += d.part[c * stride + at];             // chunk order
+        p.g[e] = s * p.scale;
+    }
+    if (p.want_stats && blockIdx.x == 0) {
+        // the five statistics: 256 fixed ranges of tiles, then the 256 sums in order.  Summed in double: a mean over millions of rows
+        // averages the bf16 roundings away, and what is left of the error would be the f32 rounding of this one sum
+        __shared__ double sh[256][4];
+        const int64_t per = (p.tiles + 255) / 256, lo = threadIdx.x * per, hi = lo + per < p.tiles ? lo + per : p.tiles;
+        double s0 = 0., s1 = 0., s2 = 0., s3 = 0.;
+        for (int64_t t = lo; t < hi; t++) {
+            const float4 v = p.tile_part[t];
+            s0 += v.x; s1 += v.y; s2 += v.z; s3 += v.w;
+        }
+        sh[threadIdx.x][0] = s0; sh[threadIdx.x][1] = s1; sh[threadIdx.x][2] = s2; sh[threadIdx.x][3] = s3;
+        __syncthreads();
+        if (threadIdx.x == 0) {
+            double t0 = 0., t1 = 0., t2 = 0., t3 = 0.;
+            for (int i = 0; i < 256; i++) { t0 += sh[i][0]; t1 += sh[i][1]; t2 += sh[i][2]; t3 += sh[i][3]; }
+            const double inv = p.count > 0. ? 1.0 / p.count : 0.0;
+            const float pol = (float)(-t0 * inv), kl = (float)(t1 * inv), ent = (float)(t2 * inv), vfl = (float)(t3 * inv);
+            p.stats[0] = pol + p.kl_coeff * kl + p.vf_coeff * vfl - p.ent_coeff * ent;
+            p.stats[1] = pol; p.stats[2] = vfl; p.stats[3] = kl; p.stats[4] = ent;
+        }
+    }
+}
+
+__device__ __forceinline__ uint16_t bf16_rne_dev(float f)                             // dactor::bf16_rne, on the device
+{
+    const uint32_t u = __float_as_uint(f);
+    if ((u & 0x7FFFFFFFu) > 0x7F800000u) return (uint16_t)((u >> 16) | 0x40u);
+    return (uint16_t)((u + 0x7FFFu + ((u >> 16) & 1u)) >> 16);
+}
+
+// where pack() puts input k, output o
+__device__ __forceinline__ size_t pack_index(int k, int o, int ksteps, int permuted)
+{
+    const int m = o >> 5, r = o & 31, ks = k >> 4, kk = k & 15;
+    const int h = permuted ? (kk & 7) >> 2 : kk >> 3, j = permuted ? 4 * (kk >> 3) + (kk & 3) : kk & 7;
+    return (((size_t)m * ksteps + ks) * 64 + 32 * h + r) * 8 + j;
+}
+
+__global__ __launch_bounds__(256) void adam_kernel(const AParams p)
+{
+#pragma clang fp contract(off)
+    const int e = blockIdx.x * 256 + threadIdx.x;
+    if (e >= p.total) return;
+    float w = p.w[e];
+    if (p.adam) {                                                                    // adam_reference: every operation rounded on its own
+        const float g = p.g[e];
+        const float m = p.m[e] * p.beta1 + g * p.omb1;
+        const float v = p.v[e] * p.beta2 + (g * g) * p.omb2;
+        const float denom = sqrtf(v) / p.bc2_sqrt + p.eps;
+        w = w - p.step_size * (m / denom);
+        p.m[e] = m; p.v[e] = v; p.w[e] = w;
+    }
+    const int ai = find_array(p, e);
+    const ADesc d = p.a[ai];
+    const int idx = e - d.off;
+    if (d.is_bias) {
+        d.bias[idx] = w;
+        return;
+    }
+    const int k = idx / d.nout, o = idx - k * d.nout;
+    const uint16_t q = bf16_rne_dev(w);
+    d.fwd[pack_index(k, o, d.fwd_ks, d.fwd_perm)] = q;
+    if (d.bwd) d.bwd[pack_index(o, k, d.bwd_ks, d.bwd_perm)] = q;                     // the other orientation: W^T
+}
+
+}  // namespace dlearn
+
+struct dcomp_learner {
+    dcomp_actor *a;
+    int64_t max_rows, ld, step;
+    int32_t device, total;
+    float beta1, beta2, eps;
+    void *mem;
+    float *w, *g, *m, *v;
+    dlearn::LParams lp;                   // the handle's part of the kernel arguments
+    dlearn::WParams wp;
+    dlearn::AParams ap;
+    int32_t off[dlearn::NARR], len[dlearn::NARR];
+};
+
+static int lfail(int code, const char *fmt, ...) __attribute__((format(printf, 2, 3)));
+static int lfail(int code, const char *fmt, ...)
+{
+    char buf[512];
+    va_list ap;
+    va_start(ap, fmt);
+    vsnprintf(buf, sizeof(buf), fmt, ap);
+    va_end(ap);
+    return dcomp::report(code, buf);
+}
+#define LEARNER_HIP_TRY(expr)                                                                        \
+    do {                                                                                             \
+        hipError_t e_ = (expr);                                                                      \
+        if (e_ != hipSuccess) return lfail(DCOMP_EHIP, "%s failed: %s", #expr, hipGetErrorString(e_)); \
+    } while (0)
+
+static const char *const ARRAY_NAMES[dlearn::NARR] = {"w1", "b1", "w2", "b2", "w3", "b3", "vw1", "vb1", "vw2", "vb2", "wv", "bv"};
+
+static void members(const dcomp_learner_arrays *s, float *(&out)[dlearn::NARR])
+{
+    float *m[dlearn::NARR] = {s->w1, s->b1, s->w2, s->b2, s->w3, s->b3, s->vw1, s->vb1, s->vw2, s->vb2, s->wv, s->bv};
+    for (int i = 0; i < dlearn::NARR; i++) out[i] = m[i];
+}
+
+// struct size and, with `all`, every member non-NULL
+static int check_arrays(const char *fn, const char *what, const dcomp_learner_arrays *s, bool all)
+{
+    if (!s) return lfail(DCOMP_EINVAL, "%s: %s must not be NULL", fn, what);
+    if (s->struct_size != (int32_t)sizeof(dcomp_learner_arrays))
+        return lfail(DCOMP_EABI, "%s: caller's dcomp_learner_arrays has %d bytes, the library's %d", fn, s->struct_size, (int)sizeof(dcomp_learner_arrays));
+    if (all) {
+        float *m[dlearn::NARR];
+        members(s, m);
+        for (int i = 0; i < dlearn::NARR; i++)
+            if (!m[i]) return lfail(DCOMP_EINVAL, "%s: %s.%s is NULL", fn, what, ARRAY_NAMES[i]);
+    }
+    return DCOMP_OK;
+}
+
+static void launch_adam(dcomp_learner *l, bool adam, float lr, hipStream_t stream)
+{
+    dlearn::AParams ap = l->ap;
+    ap.adam = adam;
+    if (adam) {
+        const double t = (double)(l->step + 1);
+        ap.beta1 = l->beta1; ap.beta2 = l->beta2; ap.eps = l->eps;
+        ap.omb1 = (float)(1.0 - (double)l->beta1); ap.omb2 = (float)(1.0 - (double)l->beta2);
+        ap.step_size = (float)((double)lr / (1.0 - std::pow((double)l->beta1, t)));
+        ap.bc2_sqrt = (float)std::sqrt(1.0 - std::pow((double)l->beta2, t));
+    }
+    hipLaunchKernelGGL(dlearn::adam_kernel, dim3((l->total + 255) / 256), dim3(256), 0, stream, ap);
+}
+
+extern "C" int dcomp_learner_create(dcomp_actor *a, const dcomp_learner_cfg *cfg, dcomp_learner **out)
+{
+    using namespace dlearn;
+    const char *fn = "dcomp_learner_create";
+    if (out) *out = nullptr;
+    if (!a || !cfg || !out) return lfail(DCOMP_EINVAL, "%s: actor, cfg and out must not be NULL", fn);
+    if (cfg->struct_size != (int32_t)sizeof(dcomp_learner_cfg))
+        return lfail(DCOMP_EABI, "%s: caller's dcomp_learner_cfg has %d bytes, the library's %d", fn, cfg->struct_size, (int)sizeof(dcomp_learner_cfg));
+    if (cfg->value_shared == 1) return lfail(DCOMP_EUNSUPPORTED, "%s: the shared value function (vf_share_layers=True) is not supported: the learner needs a value trunk of its own", fn);
+    if (cfg->value_shared != 0) return lfail(DCOMP_EINVAL, "%s: value_shared %d is neither 0 nor 1", fn, cfg->value_shared);
+    if (cfg->max_rows < 1 || cfg->max_rows > (1ll << 28)) return lfail(DCOMP_EINVAL, "%s: max_rows %lld outside [1, 2^28]", fn, (long long)cfg->max_rows);
+    if (!(cfg->beta1 >= 0.f && cfg->beta1 < 1.f) || !(cfg->beta2 >= 0.f && cfg->beta2 < 1.f)) return lfail(DCOMP_EINVAL, "%s: beta1 %g / beta2 %g outside [0, 1)", fn, cfg->beta1, cfg->beta2);
+    if (!(cfg->eps > 0.f)) return lfail(DCOMP_EINVAL, "%s: eps %g must be > 0", fn, cfg->eps);
+    if (int rc = check_arrays(fn, "cfg.weights", cfg->weights, true)) return rc;
+    // the handle, from here on
+    if (a->value == 2) return lfail(DCOMP_EUNSUPPORTED, "%s: the actor's value function is shared (vf_share_layers=True): the learner needs a value trunk of its own", fn);
+    if (a->value != 1) return lfail(DCOMP_EINVAL, "%s: the actor has no value trunk (dcomp_actor_set_value with shared = 0)", fn);
+
+    const int H = a->hidden, Hp = 32 * a->mt, KS2 = 2 * a->mt, K1 = a->K1, N3 = a->N3, NT3 = a->NT3;
+    const int K1pp = (K1 + 31) & ~31, N3p = 32 * NT3;
+    dcomp_learner *l = new dcomp_learner();
+    memset(l, 0, sizeof(*l));
+    l->a = a; l->max_rows = cfg->max_rows;
+    // the row stride of the [width][rows] workspaces: whole tiles, + 128 bytes so that a power-of-two batch does not put the 32 rows a
+    // wgrad operand load touches into one memory channel
+    l->ld = ((cfg->max_rows + 31) & ~(int64_t)31) + 64;
+    l->beta1 = cfg->beta1; l->beta2 = cfg->beta2; l->eps = cfg->eps;
+    const int nin[NARR] = {K1, 1, H, 1, H, 1, K1, 1, H, 1, H, 1}, nout[NARR] = {H, H, H, H, N3, N3, H, H, H, H, 1, 1};
+    int total = 0;
+    for (int i = 0; i < NARR; i++) { l->off[i] = total; l->len[i] = nin[i] * nout[i]; total += l->len[i]; }
+    l->total = total;
+
+    // one allocation: flat f32 arrays | backward fragments | activation / delta workspaces | walk and statistics workspaces | partials
+    auto up = [](size_t v) { return (v + 255) & ~(size_t)255; };
+    size_t at = 0;
+    auto take = [&](size_t bytes) { const size_t o = at; at = up(at + bytes); return o; };
+    const size_t o_flat = take((size_t)4 * total * 4);
+    const size_t n_w2b = (size_t)a->mt * KS2 * 512, n_w3b = (size_t)a->mt * 2 * NT3 * 512, n_vw3b = (size_t)a->mt * 2 * 512;
+    const size_t o_w2b = take(n_w2b * 2), o_w3b = take(n_w3b * 2), o_vw2b = take(n_w2b * 2), o_vw3b = take(n_vw3b * 2);
+    const size_t zero_end = at;                                                      // (zeroed up to here and over X: padding must read as zero)
+    const size_t ld = (size_t)l->ld;
+    const size_t o_X = take((size_t)K1pp * ld * 2);
+    size_t o_H[8];
+    for (int i = 0; i < 8; i++) o_H[i] = take((size_t)Hp * ld * 2);
+    const size_t o_D3 = take((size_t)N3p * ld * 2), o_VD3 = take((size_t)32 * ld * 2);
+    const size_t o_head = take((size_t)cfg->max_rows * a->heads * 16), o_tpart = take((ld / 32) * 16);      // (ld / 32 >= the tiles of max_rows)
+    const int in_p[6] = {K1pp, Hp, Hp, K1pp, Hp, Hp}, out_p[6] = {Hp, Hp, N3p, Hp, Hp, 32};
+    size_t o_part[6], o_bpart[6];
+    for (int i = 0; i < 6; i++) { o_part[i] = take((size_t)MAX_CHUNKS * in_p[i] * out_p[i] * 4); o_bpart[i] = take((size_t)MAX_CHUNKS * out_p[i] * 4); }
+    const size_t bytes = at;
+
+    hipError_t e = hipGetDevice(&l->device);
+    if (e == hipSuccess && l->device != a->device) {
+        const int dev = l->device;
+        delete l;
+        return lfail(DCOMP_EINVAL, "%s: the actor lives on device %d, the calling thread's current device is %d", fn, a->device, dev);
+    }
+    if (e == hipSuccess) e = hipMalloc(&l->mem, bytes);
+    unsigned char *d = static_cast<unsigned char *>(l->mem);
+    if (e == hipSuccess) e = hipMemset(d, 0, zero_end);
+    if (e == hipSuccess) e = hipMemset(d + o_X, 0, (size_t)K1pp * ld * 2);
+    float *src[NARR];
+    members(cfg->weights, src);
+    l->w = reinterpret_cast<float *>(d + o_flat); l->g = l->w + total; l->m = l->g + total; l->v = l->m + total;
+    for (int i = 0; i < NARR && e == hipSuccess; i++) e = hipMemcpy(l->w + l->off[i], src[i], (size_t)l->len[i] * 4, hipMemcpyHostToDevice);
+    if (e != hipSuccess) {
+        if (l->mem) (void)hipFree(l->mem);
+        delete l;
+        return lfail(DCOMP_EHIP, "%s: %s (%zu bytes of device memory for max_rows %lld)", fn, hipGetErrorString(e), bytes, (long long)cfg->max_rows);
+    }
+
+    LParams &p = l->lp;
+    p.w1 = a->w1; p.w2 = a->w2; p.w3 = a->w3; p.vw1 = a->vw1; p.vw2 = a->vw2; p.vw3 = a->vw3;
+    p.b1 = a->b1; p.b2 = a->b2; p.b3 = a->b3; p.vb1 = a->vb1; p.vb2 = a->vb2; p.vb3 = a->vb3;
+    p.w2b = reinterpret_cast<const uint4 *>(d + o_w2b); p.w3b = reinterpret_cast<const uint4 *>(d + o_w3b);
+    p.vw2b = reinterpret_cast<const uint4 *>(d + o_vw2b); p.vw3b = reinterpret_cast<const uint4 *>(d + o_vw3b);
+    auto bf = [&](size_t o) { return reinterpret_cast<__bf16 *>(d + o); };
+    p.X = bf(o_X); p.H1 = bf(o_H[0]); p.H2 = bf(o_H[1]); p.D1 = bf(o_H[2]); p.D2 = bf(o_H[3]);
+    p.VH1 = bf(o_H[4]); p.VH2 = bf(o_H[5]); p.VD1 = bf(o_H[6]); p.VD2 = bf(o_H[7]); p.D3 = bf(o_D3); p.VD3 = bf(o_VD3);
+    p.headws = reinterpret_cast<float4 *>(d + o_head); p.part = reinterpret_cast<float4 *>(d + o_tpart);
+    p.ld = l->ld; p.K1 = K1; p.K1p = a->K1p; p.XS = a->XS; p.N3 = N3; p.NT3 = NT3; p.heads = a->heads; p.B = a->B; p.U = a->U;
+    p.multi = a->kind == DCOMP_MULTI; p.lds_per_wave = a->lds_per_wave;
+
+    WParams &w = l->wp;
+    const __bf16 *wa[6] = {p.X, p.H1, p.H2, p.X, p.VH1, p.VH2}, *wd[6] = {p.D1, p.D2, p.D3, p.VD1, p.VD2, p.VD3};
+    int ntask = 0;
+    for (int i = 0; i < 6; i++) {
+        w.g[i].a = wa[i]; w.g[i].d = wd[i];
+        w.g[i].part = reinterpret_cast<float *>(d + o_part[i]); w.g[i].bpart = reinterpret_cast<float *>(d + o_bpart[i]);
+        w.g[i].mi_tiles = in_p[i] / 32; w.g[i].ni_tiles = out_p[i] / 32; w.g[i].first_task = ntask;
+        w.g[i].nmain = (w.g[i].mi_tiles / wgrad_mb(w.g[i].mi_tiles)) * (w.g[i].ni_tiles / wgrad_nb(w.g[i].ni_tiles));
+        ntask += w.g[i].nmain + w.g[i].ni_tiles / wgrad_nb(w.g[i].ni_tiles);
+    }
+    w.ld = l->ld; w.ntask = ntask;
+
+    AParams &ap = l->ap;
+    ap.total = total; ap.w = l->w; ap.g = l->g; ap.m = l->m; ap.v = l->v; ap.tile_part = p.part;
+    auto u16 = [](const void *q) { return reinterpret_cast<uint16_t *>(const_cast<void *>(q)); };
+    auto f32 = [](const float *q) { return const_cast<float *>(q); };
+    for (int i = 0; i < NARR; i++) {
+        ADesc &x = ap.a[i];
+        const int layer = i / 2;                                                     // 0 ... 5: the weight-gradient products
+        x.off = l->off[i]; x.nin = nin[i]; x.nout = nout[i]; x.in_p = in_p[layer]; x.out_p = out_p[layer]; x.is_bias = i & 1;
+        x.part = (i & 1) ? w.g[layer].bpart : w.g[layer].part;
+    }
+    ap.a[0].fwd = u16(a->w1); ap.a[0].fwd_ks = a->K1p / 16; ap.a[0].fwd_perm = 0;
+    ap.a[2].fwd = u16(a->w2); ap.a[2].fwd_ks = KS2; ap.a[2].fwd_perm = 1; ap.a[2].bwd = u16(p.w2b); ap.a[2].bwd_ks = KS2; ap.a[2].bwd_perm = 1;
+    ap.a[4].fwd = u16(a->w3); ap.a[4].fwd_ks = KS2; ap.a[4].fwd_perm = 1; ap.a[4].bwd = u16(p.w3b); ap.a[4].bwd_ks = 2 * NT3; ap.a[4].bwd_perm = 0;
+    ap.a[6].fwd = u16(a->vw1); ap.a[6].fwd_ks = a->K1p / 16; ap.a[6].fwd_perm = 0;
+    ap.a[8].fwd = u16(a->vw2); ap.a[8].fwd_ks = KS2; ap.a[8].fwd_perm = 1; ap.a[8].bwd = u16(p.vw2b); ap.a[8].bwd_ks = KS2; ap.a[8].bwd_perm = 1;
+    ap.a[10].fwd = u16(a->vw3); ap.a[10].fwd_ks = KS2; ap.a[10].fwd_perm = 1; ap.a[10].bwd = u16(p.vw3b); ap.a[10].bwd_ks = 2; ap.a[10].bwd_perm = 0;
+    ap.a[1].bias = f32(a->b1); ap.a[3].bias = f32(a->b2); ap.a[5].bias = f32(a->b3);
+    ap.a[7].bias = f32(a->vb1); ap.a[9].bias = f32(a->vb2); ap.a[11].bias = f32(a->vb3);
+
+    launch_adam(l, false, 0.f, nullptr);                                             // the backward fragments (and the forward ones, again) from the masters
+    e = hipGetLastError();
+    if (e == hipSuccess) e = hipDeviceSynchronize();
+    if (e != hipSuccess) {
+        (void)hipFree(l->mem);
+        delete l;
+        return lfail(DCOMP_EHIP, "%s: %s", fn, hipGetErrorString(e));
+    }
+    *out = l;
+    return DCOMP_OK;
+}
+
+extern "C" int dcomp_learner_destroy(dcomp_learner *l)
+{
+    if (!l) return DCOMP_OK;
+    const hipError_t e = hipFree(l->mem);
+    delete l;
+    return e == hipSuccess ? DCOMP_OK : lfail(DCOMP_EHIP, "dcomp_learner_destroy: hipFree failed: %s", hipGetErrorString(e));
+}
+
+// dcomp_learner_grads (evaluate = false) and dcomp_learner_evaluate: every check on the host first
+static int learner_launch(const char *fn, bool evaluate, dcomp_learner *l, const dcomp_ppo_batch *b, const dcomp_ppo_hyper *hy, float *stats, void *stream)
+{
+    using namespace dlearn;
+    if (!l || !b) return lfail(DCOMP_EINVAL, "%s: handle and batch must not be NULL", fn);
+    if (b->struct_size != (int32_t)sizeof(dcomp_ppo_batch))
+        return lfail(DCOMP_EABI, "%s: caller's dcomp_ppo_batch has %d bytes, the library's %d", fn, b->struct_size, (int)sizeof(dcomp_ppo_batch));
+    if (!evaluate) {
+        if (!hy) return lfail(DCOMP_EINVAL, "%s: hyper must not be NULL", fn);
+        if (hy->struct_size != (int32_t)sizeof(dcomp_ppo_hyper))
+            return lfail(DCOMP_EABI, "%s: caller's dcomp_ppo_hyper has %d bytes, the library's %d", fn, hy->struct_size, (int)sizeof(dcomp_ppo_hyper));
+        if (!stats) return lfail(DCOMP_EINVAL, "%s: stats_dev must not be NULL", fn);
+        if (!(hy->clip_param >= 0.f) || !(hy->vf_clip_param >= 0.f)) return lfail(DCOMP_EINVAL, "%s: clip_param %g / vf_clip_param %g must be >= 0", fn, hy->clip_param, hy->vf_clip_param);
+    }
+    if (b->obs_format == DCOMP_ACTOR_COMPACT) return lfail(DCOMP_EUNSUPPORTED, "%s: the compact record is not supported as learner input: pass observation rows", fn);
+    if (b->obs_format != DCOMP_ACTOR_ROWS) return lfail(DCOMP_EINVAL, "%s: unknown obs_format %d", fn, b->obs_format);
+    if (!b->obs) return lfail(DCOMP_EINVAL, "%s: batch.obs must not be NULL", fn);
+    const bool upstream = b->dlogits || b->dvalue;
+    if (evaluate) {
+        if (!b->actions) return lfail(DCOMP_EINVAL, "%s: batch.actions must not be NULL", fn);
+        if (!b->logp && !b->entropy && !b->vf) return lfail(DCOMP_EINVAL, "%s: none of batch.logp / entropy / vf is given: nothing to write", fn);
+        if (upstream) return lfail(DCOMP_EINVAL, "%s: upstream gradients (batch.dlogits / dvalue) belong to dcomp_learner_grads", fn);
+    } else if (upstream) {
+        if (!b->dlogits || !b->dvalue) return lfail(DCOMP_EINVAL, "%s: batch.dlogits and batch.dvalue come together: one of them is NULL", fn);
+    } else if (!b->actions || !b->old_logp || !b->old_logits || !b->advantages || !b->value_targets || !b->old_vf) {
+        return lfail(DCOMP_EINVAL, "%s: a pointer of batch.actions / old_logp / old_logits / advantages / value_targets / old_vf is NULL", fn);
+    }
+    if (b->rows < 1) return lfail(DCOMP_EINVAL, "%s: rows %lld < 1", fn, (long long)b->rows);
+    // the handle, from here on
+    if (b->rows > l->max_rows) return lfail(DCOMP_EINVAL, "%s: rows %lld > max_rows %lld of the handle", fn, (long long)b->rows, (long long)l->max_rows);
+    const dcomp_actor *a = l->a;
+    if (b->num_active < 0 || b->num_active > a->U) return lfail(DCOMP_EINVAL, "%s: num_active %d outside [0, %d]", fn, b->num_active, a->U);
+
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    LParams p = l->lp;
+    p.obs = b->obs; p.actions = b->actions; p.old_logp = b->old_logp; p.old_logits = b->old_logits; p.adv = b->advantages;
+    p.vtarg = b->value_targets; p.old_vf = b->old_vf;
+    p.o_logp = b->logp; p.o_ent = b->entropy; p.o_kl = b->kl; p.o_vf = b->vf; p.o_ratio = b->ratio;
+    p.up_dlogits = b->dlogits; p.up_dvalue = b->dvalue;
+    p.rows = b->rows; p.tiles = (b->rows + TILE - 1) / TILE; p.num_active = b->num_active;
+    p.fwd_only = evaluate; p.upstream = upstream;
+    if (hy) { p.clip = hy->clip_param; p.vf_clip = hy->vf_clip_param; p.vf_coeff = hy->vf_loss_coeff; p.ent_coeff = hy->entropy_coeff; p.kl_coeff = hy->kl_coeff; }
+    const int64_t want = (p.tiles + WAVES - 1) / WAVES;
+    const int grid = (int)(want < a->max_blocks ? want : a->max_blocks);
+    hipLaunchKernelGGL(pick(a->mt, a->relu != 0), dim3(grid), dim3(BLOCK), (size_t)a->lds_per_wave * WAVES, s, p);
+    LEARNER_HIP_TRY(hipGetLastError());
+    if (evaluate) return DCOMP_OK;
+
+    // the row split of the weight gradients: a function of the row count alone
+    WParams w = l->wp;
+    w.rows_pad = p.tiles * TILE;
+    const int64_t mult = (w.rows_pad + (int64_t)CHUNK_UNIT * MAX_CHUNKS - 1) / ((int64_t)CHUNK_UNIT * MAX_CHUNKS);
+    w.chunk_rows = CHUNK_UNIT * mult;
+    const int nchunks = (int)((w.rows_pad + w.chunk_rows - 1) / w.chunk_rows);
+    hipLaunchKernelGGL(wgrad_kernel, dim3((w.ntask + WAVES - 1) / WAVES, nchunks), dim3(BLOCK), 0, s, w);
+    LEARNER_HIP_TRY(hipGetLastError());
+
+    AParams ap = l->ap;
+    ap.nchunks = nchunks; ap.tiles = p.tiles; ap.stats = stats; ap.want_stats = 1;
+    const int64_t counted = a->kind == DCOMP_MULTI ? (b->rows / a->U) * b->num_active + (b->rows % a->U < b->num_active ? b->rows % a->U : b->num_active) : b->rows;
+    ap.count = upstream ? 0. : (double)counted;
+    ap.scale = upstream ? 1.f : (counted > 0 ? (float)(1.0 / (double)counted) : 0.f);
+    ap.vf_coeff = p.vf_coeff; ap.ent_coeff = p.ent_coeff; ap.kl_coeff = p.kl_coeff;
+    hipLaunchKernelGGL(reduce_kernel, dim3((l->total + 255) / 256), dim3(256), 0, s, ap);
+    LEARNER_HIP_TRY(hipGetLastError());
+    return DCOMP_OK;
+}
+
+extern "C" int dcomp_learner_grads(dcomp_learner *l, const dcomp_ppo_batch *b, const dcomp_ppo_hyper *hy, float *stats_dev, void *stream)
+{
+    return learner_launch("dcomp_learner_grads", false, l, b, hy, stats_dev, stream);
+}
+
+extern "C" int dcomp_learner_evaluate(dcomp_learner *l, const dcomp_ppo_batch *b, void *stream)
+{
+    return learner_launch("dcomp_learner_evaluate", true, l, b, nullptr, nullptr, stream);
+}
+
+extern "C" int dcomp_learner_apply(dcomp_learner *l, float lr, void *stream)
+{
+    if (!l) return lfail(DCOMP_EINVAL, "dcomp_learner_apply: handle must not be NULL");
+    if (!(lr >= 0.f) || !std::isfinite(lr)) return lfail(DCOMP_EINVAL, "dcomp_learner_apply: lr %g is not a finite number >= 0", lr);
+    launch_adam(l, true, lr, static_cast<hipStream_t>(stream));
+    LEARNER_HIP_TRY(hipGetLastError());
+    l->step++;
+    return DCOMP_OK;
+}
+
+extern "C" int dcomp_learner_read(dcomp_learner *l, int32_t which, const dcomp_learner_arrays *dst, int64_t *step, void *stream)
+{
+    const char *fn = "dcomp_learner_read";
+    if (!l) return lfail(DCOMP_EINVAL, "%s: handle must not be NULL", fn);
+    if (which < DCOMP_LEARNER_WEIGHTS || which > DCOMP_LEARNER_ADAM_V) return lfail(DCOMP_EINVAL, "%s: which %d is not one of DCOMP_LEARNER_*", fn, which);
+    if (int rc = check_arrays(fn, "dst", dst, false)) return rc;
+    const float *src = which == DCOMP_LEARNER_WEIGHTS ? l->w : which == DCOMP_LEARNER_GRADS ? l->g : which == DCOMP_LEARNER_ADAM_M ? l->m : l->v;
+    LEARNER_HIP_TRY(hipStreamSynchronize(static_cast<hipStream_t>(stream)));
+    float *m[dlearn::NARR];
+    members(dst, m);
+    for (int i = 0; i < dlearn::NARR; i++)
+        if (m[i]) LEARNER_HIP_TRY(hipMemcpy(m[i], src + l->off[i], (size_t)l->len[i] * 4, hipMemcpyDeviceToHost));
+    if (step) *step = l->step;
+    return DCOMP_OK;
+}
+
+extern "C" int dcomp_learner_load_state(dcomp_learner *l, const dcomp_learner_arrays *weights, const dcomp_learner_arrays *adam_m,
+                                        const dcomp_learner_arrays *adam_v, int64_t step, void *stream)
+{
+    const char *fn = "dcomp_learner_load_state";
+    if (!l) return lfail(DCOMP_EINVAL, "%s: handle must not be NULL", fn);
+    if (int rc = check_arrays(fn, "weights", weights, true)) return rc;
+    if (int rc = check_arrays(fn, "adam_m", adam_m, true)) return rc;
+    if (int rc = check_arrays(fn, "adam_v", adam_v, true)) return rc;
+    if (step < 0) return lfail(DCOMP_EINVAL, "%s: step %lld < 0", fn, (long long)step);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    LEARNER_HIP_TRY(hipStreamSynchronize(s));
+    const dcomp_learner_arrays *from[3] = {weights, adam_m, adam_v};
+    float *to[3] = {l->w, l->m, l->v};
+    for (int k = 0; k < 3; k++) {
+        float *m[dlearn::NARR];
+        members(from[k], m);
+        for (int i = 0; i < dlearn::NARR; i++) LEARNER_HIP_TRY(hipMemcpy(to[k] + l->off[i], m[i], (size_t)l->len[i] * 4, hipMemcpyHostToDevice));
+    }
+    l->step = step;
+    launch_adam(l, false, 0.f, s);
+    LEARNER_HIP_TRY(hipGetLastError());
+    return DCOMP_OK;
+}

@@ -1,0 +1,444 @@
+"""The PPO learner of the fcnet policy on the device (include/dcomp_learner.h): loss, backward pass and Adam on the train batch
+``sampler.collect`` leaves in HBM, writing the new weights straight into the actor's handle.
+
+    actor = FcnetActor('multi', U, B, weights, value_weights=value_weights)        # a value trunk of its own
+    learner = PPOLearner(actor, lr=5e-5, max_rows=rows_per_minibatch)
+    for _ in range(iters):
+        batch = collect(env, actor, num_steps=50, gamma=0.99, lam=0.95, dist_inputs=True)
+        stats = learner.update(batch, num_sgd_iter=30, minibatch_rows=rows_per_minibatch)
+    rllib_weights = learner.to_rllib_weights()
+
+Supported: ``multi`` and ``central``, tanh and relu, every hidden width the actor takes, the value function as a trunk of its own
+(``vf_share_layers=False``, PPO's default).  The shared value function and the compact record as learner input are refused
+(NotImplementedError); envs with UE arrival are refused by ``collect`` already.
+
+The arithmetic is the specification, spelled out here in torch / numpy on the CPU: ``ppo_loss_reference`` (RLlib's
+ppo_surrogate_loss and its gradients, as the float64 model and as the bf16 chain the kernels implement) and ``adam_reference``
+(torch.optim.Adam as pinned float32 operations)."""
+import ctypes
+import math
+
+import numpy as np
+import torch
+
+from . import _lib
+from .actor import FcnetActor, _bf16
+
+ARRAYS = _lib.LEARNER_ARRAYS
+_POLICY, _VALUE = ARRAYS[:6], ARRAYS[6:]
+_VALUE_KEYS = ('w1', 'b1', 'w2', 'b2', 'wv', 'bv')            # FcnetActor.value_weights' names of vw1 ... bv
+DEFAULT_HYPER = {'clip_param': 0.3, 'vf_clip_param': 10.0, 'vf_loss_coeff': 1.0, 'entropy_coeff': 0.0, 'kl_coeff': 0.2}
+STATS = _lib.PPO_STATS
+
+
+def join_weights(weights, value_weights, dtype=np.float32):
+    """The twelve arrays of a learner from FcnetActor.weights and FcnetActor.value_weights (a trunk of its own)."""
+    out = {n: np.asarray(weights[n], dtype=dtype) for n in _POLICY}
+    out.update({a: np.asarray(value_weights[k], dtype=dtype).reshape(-1) if k in ('wv', 'bv') else np.asarray(value_weights[k], dtype=dtype)
+                for a, k in zip(_VALUE, _VALUE_KEYS)})
+    return out
+
+
+def split_weights(arrays):
+    """The inverse of join_weights: (weights, value_weights)."""
+    return {n: arrays[n] for n in _POLICY}, {k: arrays[a] for a, k in zip(_VALUE, _VALUE_KEYS)}
+
+
+def _act(activation):
+    return torch.tanh if activation == 'tanh' else torch.relu
+
+
+def _dact(activation, h):
+    """The activation's derivative from its OUTPUT h (the stored activation): tanh 1 - h^2, relu h > 0."""
+    return 1 - h * h if activation == 'tanh' else (h > 0).to(h.dtype)
+
+
+def _row_terms(logits, v, b, hy):
+    """Per-row terms of RLlib's ppo_surrogate_loss on the heads that count.  logits [R, heads, A], v [R]; b: actions [R, heads]
+    (int64), old_logp [R, heads], old_logits [R, heads, A], advantages, value_targets, old_vf [R]."""
+    lsm = torch.log_softmax(logits, -1)
+    lso = torch.log_softmax(b['old_logits'], -1)
+    p, po = lsm.exp(), lso.exp()
+    logp_h = lsm.gather(-1, b['actions'].unsqueeze(-1)).squeeze(-1)
+    logp = logp_h.sum(1)
+    ratio = (logp - b['old_logp'].sum(1)).exp()
+    adv = b['advantages']
+    s1, s2 = adv * ratio, adv * ratio.clamp(1 - hy['clip_param'], 1 + hy['clip_param'])
+    ent_h = -(p * lsm).sum(-1)
+    kl = (po * (lso - lsm)).sum(-1).sum(1)
+    d1 = v - b['value_targets']
+    d2 = b['old_vf'] + (v - b['old_vf']).clamp(-hy['vf_clip_param'], hy['vf_clip_param']) - b['value_targets']
+    return {'logp_h': logp_h, 'ratio': ratio, 's1': s1, 's2': s2, 'surr': torch.minimum(s1, s2), 'kl': kl, 'ent_h': ent_h, 'ent': ent_h.sum(1),
+            'd1': d1, 'd2': d2, 'vf_loss': torch.maximum(d1 * d1, d2 * d2), 'p': p, 'po': po, 'lsm': lsm}
+
+
+def ppo_loss_reference(weights, value_weights, batch, hyper=None, activation='tanh', form='float64', round_weights=True):
+    """RLlib's ppo_surrogate_loss and its gradients with respect to the twelve arrays, on the CPU.
+
+    weights / value_weights: FcnetActor.weights / .value_weights (a value trunk of its own).  batch: a dict of arrays -- obs
+    [rows, inputs], actions [rows, heads], old_logp [rows, heads], old_logits [rows, logits], advantages, value_targets, old_vf
+    [rows]; optional num_active with num_ue (multi: rows whose slot row % num_ue is >= num_active contribute nothing and are not
+    counted; central: heads >= num_active are left out of logp, kl and the entropy); optional dlogits [rows, logits] with dvalue
+    [rows]: upstream gradients used instead of the loss's (no statistics, no 1 / N).  hyper: clip_param, vf_clip_param,
+    vf_loss_coeff, entropy_coeff, kl_coeff (RLlib's defaults where absent).
+
+    Per counted row: logp = sum over heads of log_softmax(logits_head)[action]; ratio = exp(logp - sum old_logp); surr =
+    min(adv ratio, adv clip(ratio, 1 - eps, 1 + eps)); kl = sum KL(old || new); ent = sum H(new); vf_loss = max((v - vt)^2,
+    (old_v + clip(v - old_v, +-vf_clip) - vt)^2); loss = mean(-surr + kl_coeff kl + vf_loss_coeff vf_loss - entropy_coeff ent).
+
+    form='float64': the model.  Weights and inputs rounded to bf16 as in reference_logits_of(form='float64'), everything else in
+    float64, gradients from autograd.  (round_weights=False, float64 only: the weights are taken as they come, in float64 -- for
+    finite differences of the model's own loss, which must be able to move a weight by less than a bf16 step.)
+    form='bf16': the chain the kernels implement, by hand.  Forward = reference_logits_of / reference_value_of(form='bf16'); per-row
+    terms, dlogits and dv in f32; backward matrix products with bf16 operands (dlogits, dA2 = (dlogits W3^T) * act'(h2), dA1,
+    each rounded to bf16 where it becomes an operand; act' from the stored bf16 h) and f32 sums; dW = a^T d; db = column sums of
+    the bf16 d; the 1 / N of the mean once, in f32, after the sum over rows.
+
+    Returns (stats, grads, rows): stats total_loss, policy_loss (= -mean surr), vf_loss, kl, entropy; grads the twelve arrays
+    (numpy); rows the per-row tensors logp [rows, heads], ratio, surr, kl, entropy, vf_loss, vf, and which of the two branches of
+    surr / vf_loss each row took (clipped, vf_clipped) -- rows that do not count hold zeros."""
+    if form not in ('float64', 'bf16'):
+        raise ValueError("form is 'bf16' or 'float64'")
+    hy = dict(DEFAULT_HYPER)
+    hy.update(hyper or {})
+    dt = torch.float64 if form == 'float64' else torch.float32
+    if not round_weights and form != 'float64':
+        raise ValueError("round_weights=False goes with form='float64'")
+    arrays = join_weights(weights, value_weights, np.float32 if round_weights else np.float64)
+    nin, H = arrays['w1'].shape
+    N3 = arrays['w3'].shape[1]
+    upstream = batch.get('dlogits') is not None
+    obs = np.asarray(batch['obs'], dtype=np.float32).reshape(-1, nin)
+    R = obs.shape[0]
+    if upstream:
+        heads = 1
+    else:
+        actions = torch.as_tensor(np.asarray(batch['actions']).astype(np.int64)).reshape(R, -1)
+        heads = actions.shape[1]
+    A = N3 // heads
+    na, U = batch.get('num_active'), batch.get('num_ue')
+    live = np.ones(R, dtype=bool)
+    head_count = heads
+    if na is not None:
+        if heads == 1 and U is not None:                                   # multi: whole rows drop out
+            live = (np.arange(R) % int(U)) < int(na)
+        elif heads > 1:
+            head_count = int(na)
+    idx = torch.as_tensor(np.nonzero(live)[0])
+    N = int(live.sum())
+    act = _act(activation)
+
+    x = _bf16(torch.as_tensor(obs[live])).to(dt)
+    leaf = {}
+    for n in ARRAYS:
+        t = torch.as_tensor(arrays[n])
+        t = (_bf16(t) if round_weights and n[-2] == 'w' else t).to(dt)
+        leaf[n] = t.clone().requires_grad_(form == 'float64')
+    rnd = (lambda t: t) if form == 'float64' else _bf16
+
+    def trunk(w1, b1, w2, b2):
+        h1 = rnd(act(x @ leaf[w1] + leaf[b1]))
+        h2 = rnd(act(h1 @ leaf[w2] + leaf[b2]))
+        return h1, h2
+    h1, h2 = trunk('w1', 'b1', 'w2', 'b2')
+    logits = h2 @ leaf['w3'] + leaf['b3']
+    g1, g2 = trunk('vw1', 'vb1', 'vw2', 'vb2')
+    v = g2 @ leaf['wv'] + leaf['bv'][0]
+
+    stats = {n: 0.0 for n in STATS}
+    rows = {}
+    if upstream:
+        dl = torch.as_tensor(np.asarray(batch['dlogits'], dtype=np.float32).reshape(R, N3)[live]).to(dt)
+        dv = torch.as_tensor(np.asarray(batch['dvalue'], dtype=np.float32).reshape(R)[live]).to(dt)
+        scale = 1.0
+        if form == 'float64':
+            ((logits * dl).sum() + (v * dv).sum()).backward()
+    else:
+        hc = head_count
+        f = lambda k, shape: torch.as_tensor(np.asarray(batch[k], dtype=np.float32).reshape(shape)[live]).to(dt)      # noqa: E731
+        b = {'actions': actions[idx][:, :hc], 'old_logp': f('old_logp', (R, heads))[:, :hc], 'old_logits': f('old_logits', (R, heads, A))[:, :hc],
+             'advantages': f('advantages', (R,)), 'value_targets': f('value_targets', (R,)), 'old_vf': f('old_vf', (R,))}
+        lg = logits.reshape(N, heads, A)[:, :hc]
+        t = _row_terms(lg, v, b, hy)
+        scale = 1.0 / N if N else 0.0
+        pol, kl, ent, vfl = -t['surr'].sum() * scale, t['kl'].sum() * scale, t['ent'].sum() * scale, t['vf_loss'].sum() * scale
+        total = pol + hy['kl_coeff'] * kl + hy['vf_loss_coeff'] * vfl - hy['entropy_coeff'] * ent
+        stats = {n: float(t_.detach()) for n, t_ in zip(STATS, (total, pol, vfl, kl, ent))}
+        full = lambda src, shape: torch.zeros(shape, dtype=dt).index_copy_(0, idx, src.detach())      # noqa: E731
+        logp_full = torch.zeros((R, heads), dtype=dt)
+        logp_full[idx, :hc] = t['logp_h'].detach()
+        rows = {'logp': logp_full, 'ratio': full(t['ratio'], (R,)), 'surr': full(t['surr'], (R,)), 'kl': full(t['kl'], (R,)),
+                'entropy': full(t['ent'], (R,)), 'vf_loss': full(t['vf_loss'], (R,)),
+                'clipped': full((t['s2'] < t['s1']).to(dt), (R,)), 'vf_clipped': full((t['d2'] * t['d2'] > t['d1'] * t['d1']).to(dt), (R,))}
+        if form == 'float64':
+            total.backward()
+        else:
+            c_lp = torch.where(t['s1'] <= t['s2'], -t['s1'], torch.zeros_like(t['s1']))
+            onehot = torch.zeros_like(t['p']).scatter_(-1, b['actions'].unsqueeze(-1), 1.0)
+            d = c_lp[:, None, None] * (onehot - t['p']) + hy['kl_coeff'] * (t['p'] - t['po']) \
+                + hy['entropy_coeff'] * (t['p'] * (t['lsm'] + t['ent_h'].unsqueeze(-1)))
+            dl = torch.zeros((N, heads, A), dtype=dt)
+            dl[:, :hc] = d
+            dl = dl.reshape(N, N3)
+            l1, l2 = t['d1'] * t['d1'], t['d2'] * t['d2']
+            inside = ((v - b['old_vf']).abs() < hy['vf_clip_param']).to(dt)
+            dv = hy['vf_loss_coeff'] * torch.where(l1 >= l2, 2 * t['d1'], 2 * t['d2'] * inside)
+    rows['vf'] = torch.zeros(R, dtype=dt).index_copy_(0, idx, v.detach())
+
+    if form == 'float64':
+        grads = {n: (leaf[n].grad if leaf[n].grad is not None else torch.zeros_like(leaf[n])).numpy() for n in ARRAYS}
+        return stats, grads, rows
+
+    def backward(a0, a1, a2, w2, w3, d3):
+        """dW1, db1, dW2, db2, dW3, db3 of one trunk: a0 = x, a1 = h1, a2 = h2 (bf16 values), d3 = the f32 delta of the output."""
+        d3 = _bf16(d3)
+        dA2 = _bf16((d3 @ w3.t()) * _dact(activation, a2))
+        dA1 = _bf16((dA2 @ w2.t()) * _dact(activation, a1))
+        s = np.float32(scale)
+        return [(g * s).numpy() for g in (a0.t() @ dA1, dA1.sum(0), a1.t() @ dA2, dA2.sum(0), a2.t() @ d3, d3.sum(0))]
+    with torch.no_grad():
+        gp = backward(x, h1, h2, leaf['w2'], leaf['w3'], dl)
+        gv = backward(x, g1, g2, leaf['vw2'], leaf['wv'].reshape(H, 1), dv.reshape(N, 1))
+    grads = dict(zip(_POLICY, gp))
+    grads.update(dict(zip(_VALUE, gv)))
+    grads['wv'] = grads['wv'].reshape(-1)
+    return stats, grads, rows
+
+
+def adam_constants(t, lr, beta1=0.9, beta2=0.999, eps=1e-8):
+    """The f32 scalars of step t (1, 2, ...): the bias corrections 1 - beta^t are computed in double from the f32 betas."""
+    f = np.float32
+    b1, b2 = float(f(beta1)), float(f(beta2))
+    return {'beta1': f(beta1), 'omb1': f(1.0 - b1), 'beta2': f(beta2), 'omb2': f(1.0 - b2),
+            'step_size': f(float(f(lr)) / (1.0 - b1 ** int(t))), 'bc2_sqrt': f(math.sqrt(1.0 - b2 ** int(t))), 'eps': f(eps)}
+
+
+def adam_reference(w, g, m, v, t, lr, beta1=0.9, beta2=0.999, eps=1e-8):
+    """torch.optim.Adam's update (no weight decay, no amsgrad) as numpy float32 operations, each rounded on its own, in this
+    order -- what the kernel computes bit for bit.  t: the step being taken (1 for the first).  Returns (w, m, v)."""
+    c = adam_constants(t, lr, beta1, beta2, eps)
+    w, g, m, v = (np.asarray(a, dtype=np.float32) for a in (w, g, m, v))
+    m = m * c['beta1'] + g * c['omb1']
+    v = v * c['beta2'] + (g * g) * c['omb2']
+    denom = np.sqrt(v) / c['bc2_sqrt'] + c['eps']
+    w = w - c['step_size'] * (m / denom)
+    return w, m, v
+
+
+def adapt_kl_coeff(kl_coeff, kl, kl_target):
+    """RLlib's update_kl: x 1.5 above twice the target, x 0.5 below half of it."""
+    if kl > 2.0 * kl_target:
+        return kl_coeff * 1.5
+    if kl < 0.5 * kl_target:
+        return kl_coeff * 0.5
+    return kl_coeff
+
+
+def to_rllib_weights(arrays, prefix='default_policy/'):
+    """The twelve arrays under RLlib's fcnet names (kernels [in][out], value_out's kernel [hidden][1]): the inverse of
+    FcnetActor.map_rllib_weights / map_rllib_value_weights."""
+    names = {'w1': 'fc_1/kernel', 'b1': 'fc_1/bias', 'w2': 'fc_2/kernel', 'b2': 'fc_2/bias', 'w3': 'fc_out/kernel', 'b3': 'fc_out/bias',
+             'vw1': 'fc_value_1/kernel', 'vb1': 'fc_value_1/bias', 'vw2': 'fc_value_2/kernel', 'vb2': 'fc_value_2/bias',
+             'wv': 'value_out/kernel', 'bv': 'value_out/bias'}
+    out = {prefix + names[n]: np.array(arrays[n], dtype=np.float32) for n in ARRAYS}
+    out[prefix + 'value_out/kernel'] = out[prefix + 'value_out/kernel'].reshape(-1, 1)
+    return out
+
+
+def _arrays_struct(arrays):
+    """A dcomp_learner_arrays over the numpy arrays of a dict (which must stay alive while the struct is in use)."""
+    fp = ctypes.POINTER(ctypes.c_float)
+    return _lib.DcompLearnerArrays(ctypes.sizeof(_lib.DcompLearnerArrays), 0, *[arrays[n].ctypes.data_as(fp) for n in ARRAYS])
+
+
+class PPOLearner:
+    """PPO on the device for the policy an FcnetActor runs; every update lands in the actor's own handle."""
+
+    def __init__(self, actor, lr=5e-5, clip_param=0.3, vf_clip_param=10.0, vf_loss_coeff=1.0, entropy_coeff=0.0, kl_coeff=0.2, kl_target=0.01,
+                 max_rows=65536, betas=(0.9, 0.999), eps=1e-8):
+        self._h = None
+        if not isinstance(actor, FcnetActor):
+            raise ValueError("actor must be an FcnetActor")
+        if actor.value_weights is None:
+            raise ValueError("the actor has no value function (set_value): PPO needs one")
+        if actor.value_shared:
+            raise NotImplementedError("the shared value function (vf_share_layers=True) is not supported: the learner needs a value trunk of its own")
+        self.actor, self.device, self._L = actor, actor.device, actor._L
+        self.lr, self.kl_target = float(lr), float(kl_target)
+        self.hyper = {'clip_param': float(clip_param), 'vf_clip_param': float(vf_clip_param), 'vf_loss_coeff': float(vf_loss_coeff),
+                      'entropy_coeff': float(entropy_coeff), 'kl_coeff': float(kl_coeff)}
+        self.max_rows = int(max_rows)
+        self.betas, self.eps = (float(betas[0]), float(betas[1])), float(eps)
+        self.shapes = {n: a.shape for n, a in join_weights(actor.weights, actor.value_weights).items()}
+        host = {n: np.ascontiguousarray(a) for n, a in join_weights(actor.weights, actor.value_weights).items()}
+        arr = _arrays_struct(host)
+        cfg = _lib.DcompLearnerCfg(ctypes.sizeof(_lib.DcompLearnerCfg), 0, self.max_rows, self.betas[0], self.betas[1], self.eps, 0, ctypes.pointer(arr))
+        h = ctypes.c_void_p()
+        with torch.cuda.device(self.device):
+            _lib.check(self._L.dcomp_learner_create(actor._h, ctypes.byref(cfg), ctypes.byref(h)))
+        self._h = h
+        self._mb = {}
+        self.step = 0
+
+    def __del__(self):
+        h = getattr(self, '_h', None)
+        if h is not None and h.value:
+            self._L.dcomp_learner_destroy(h)
+            self._h = None
+
+    # ------------------------------------------------------------------ the kernels
+    def _rows(self, obs):
+        a = self.actor
+        if not isinstance(obs, torch.Tensor) or obs.numel() == 0 or obs.numel() % a.num_in:
+            raise ValueError(f"obs must hold a whole number of rows of {a.num_in} elements")
+        rows = obs.numel() // a.num_in
+        a._check(obs, torch.float32, rows * a.num_in, 'obs')
+        if rows > self.max_rows:
+            raise ValueError(f"{rows} rows > max_rows {self.max_rows} of the learner")
+        return rows
+
+    def _batch(self, obs, rows, num_active, tensors):
+        """dcomp_ppo_batch over checked tensors: tensors maps a field to (tensor or None, dtype, elements per row)."""
+        a = self.actor
+        ptr = {}
+        for name, (t, dtype, per_row) in tensors.items():
+            if t is not None:
+                a._check(t, dtype, rows * per_row, name)
+            ptr[name] = t.data_ptr() if t is not None else None
+        order = ('actions', 'old_logp', 'old_logits', 'advantages', 'value_targets', 'old_vf', 'logp', 'entropy', 'kl', 'vf', 'ratio', 'dlogits', 'dvalue')
+        return _lib.DcompPpoBatch(ctypes.sizeof(_lib.DcompPpoBatch), _lib.ACTOR_ROWS, rows, a.U if num_active is None else int(num_active), 0,
+                                  obs.data_ptr(), *[ptr.get(n) for n in order])
+
+    def grads(self, obs, actions=None, old_logp=None, old_logits=None, advantages=None, value_targets=None, old_vf=None, *, num_active=None,
+              logp=None, entropy=None, kl=None, vf=None, ratio=None, dlogits=None, dvalue=None, stats=None):
+        """The loss statistics (a float32 [5] device tensor: total_loss, policy_loss, vf_loss, kl, entropy) and the gradients of all
+        twelve arrays into the handle, from one (mini)batch of device tensors: obs float32 [rows, inputs], actions uint8 [rows,
+        heads], old_logp [rows, heads], old_logits [rows, logits], advantages / value_targets / old_vf [rows].  logp ... ratio:
+        optional per-row outputs.  dlogits [rows, logits] with dvalue [rows]: upstream gradients used instead of the loss's (the
+        gradients are then plain sums over the rows, the statistics zero).  Nothing synchronises."""
+        a = self.actor
+        rows = self._rows(obs)
+        f32, h, n3 = torch.float32, a.heads, a.num_logits
+        b = self._batch(obs, rows, num_active, {
+            'actions': (actions, torch.uint8, h), 'old_logp': (old_logp, f32, h), 'old_logits': (old_logits, f32, n3), 'advantages': (advantages, f32, 1),
+            'value_targets': (value_targets, f32, 1), 'old_vf': (old_vf, f32, 1), 'logp': (logp, f32, h), 'entropy': (entropy, f32, 1), 'kl': (kl, f32, 1),
+            'vf': (vf, f32, 1), 'ratio': (ratio, f32, 1), 'dlogits': (dlogits, f32, n3), 'dvalue': (dvalue, f32, 1)})
+        if stats is None:
+            stats = torch.zeros(_lib.PPO_NUM_STATS, dtype=f32, device=self.device)
+        a._check(stats, f32, _lib.PPO_NUM_STATS, 'stats')
+        hy = _lib.DcompPpoHyper(ctypes.sizeof(_lib.DcompPpoHyper), *[self.hyper[n] for n in ('clip_param', 'vf_clip_param', 'vf_loss_coeff', 'entropy_coeff', 'kl_coeff')])
+        with torch.cuda.device(self.device):
+            _lib.check(self._L.dcomp_learner_grads(self._h, ctypes.byref(b), ctypes.byref(hy), ctypes.c_void_p(stats.data_ptr()), a._stream()))
+        return stats
+
+    def evaluate(self, obs, actions, *, num_active=None):
+        """logp [rows, heads] of the GIVEN actions, the entropy [rows] and the value predictions [rows] under the current weights."""
+        a = self.actor
+        rows = self._rows(obs)
+        f32 = torch.float32
+        logp = torch.empty((rows, a.heads), dtype=f32, device=self.device)
+        entropy, vf = torch.empty(rows, dtype=f32, device=self.device), torch.empty(rows, dtype=f32, device=self.device)
+        b = self._batch(obs, rows, num_active, {'actions': (actions, torch.uint8, a.heads), 'logp': (logp, f32, a.heads), 'entropy': (entropy, f32, 1),
+                                                'vf': (vf, f32, 1)})
+        with torch.cuda.device(self.device):
+            _lib.check(self._L.dcomp_learner_evaluate(self._h, ctypes.byref(b), a._stream()))
+        return logp, entropy, vf
+
+    def apply(self, lr=None):
+        """One Adam step on the gradients of the last grads(); the actor's next launch runs the new weights."""
+        with torch.cuda.device(self.device):
+            _lib.check(self._L.dcomp_learner_apply(self._h, float(self.lr if lr is None else lr), self.actor._stream()))
+
+    # ------------------------------------------------------------------ host copies
+    def read(self, which='weights'):
+        """The twelve arrays of the master weights ('weights'), the gradients ('grads') or Adam's moments ('m', 'v') as numpy."""
+        code = {'weights': _lib.LEARNER_WEIGHTS, 'grads': _lib.LEARNER_GRADS, 'm': _lib.LEARNER_ADAM_M, 'v': _lib.LEARNER_ADAM_V}[which]
+        out = {n: np.empty(self.shapes[n], dtype=np.float32) for n in ARRAYS}
+        step = ctypes.c_int64()
+        with torch.cuda.device(self.device):
+            _lib.check(self._L.dcomp_learner_read(self._h, code, ctypes.byref(_arrays_struct(out)), ctypes.byref(step), self.actor._stream()))
+        self.step = int(step.value)
+        return out
+
+    def get_weights(self):
+        """(weights, value_weights) as FcnetActor takes them; also refreshes actor.weights / actor.value_weights, which the
+        actor's reference_* methods read."""
+        w, vw = split_weights(self.read('weights'))
+        self.actor.weights, self.actor.value_weights = w, vw
+        return w, vw
+
+    def to_rllib_weights(self, prefix='default_policy/'):
+        return to_rllib_weights(self.read('weights'), prefix)
+
+    def state_dict(self):
+        return {'weights': self.read('weights'), 'm': self.read('m'), 'v': self.read('v'), 'step': self.step, 'kl_coeff': self.hyper['kl_coeff'], 'lr': self.lr}
+
+    def load_state_dict(self, state):
+        host = {}
+        for k in ('weights', 'm', 'v'):
+            host[k] = {n: np.ascontiguousarray(np.asarray(state[k][n], dtype=np.float32)) for n in ARRAYS}
+            for n in ARRAYS:
+                if host[k][n].shape != self.shapes[n]:
+                    raise ValueError(f"{k}[{n!r}] has shape {host[k][n].shape}, expected {self.shapes[n]}")
+        with torch.cuda.device(self.device):
+            _lib.check(self._L.dcomp_learner_load_state(self._h, ctypes.byref(_arrays_struct(host['weights'])), ctypes.byref(_arrays_struct(host['m'])),
+                                                        ctypes.byref(_arrays_struct(host['v'])), int(state['step']), self.actor._stream()))
+        self.hyper['kl_coeff'], self.lr = float(state['kl_coeff']), float(state['lr'])
+        self.actor.weights, self.actor.value_weights = split_weights(host['weights'])
+
+    # ------------------------------------------------------------------ the training step
+    def update(self, batch, num_sgd_iter=30, minibatch_rows=None, seed=0, num_active=None):
+        """PPO's SGD phase on one collect(..., dist_inputs=True) batch: the batch is flattened to rows, the advantages are
+        standardised over the batch (RLlib: (a - mean) / max(1e-4, std)), and per iteration a seeded device permutation splits the
+        rows into minibatches of minibatch_rows (default: the whole batch) gathered into buffers allocated once; each gets grads +
+        apply.  Afterwards the mean KL of the last iteration is read (the one synchronisation) and kl_coeff adapted by RLlib's rule.
+        num_active: listed UEs where fewer than the env's slots (multi: the other rows are dropped before the split).
+        Returns the last iteration's mean statistics and the new kl_coeff."""
+        a = self.actor
+        if 'action_dist_inputs' not in batch:
+            raise ValueError("the batch has no action_dist_inputs: collect(..., dist_inputs=True)")
+        if 'obs' not in batch:
+            raise NotImplementedError("the compact record is not supported as learner input: collect(..., compact=False)")
+        multi = a.kind == _lib.MULTI
+        src = {'obs': batch['obs'].reshape(-1, a.num_in), 'actions': batch['actions'].reshape(-1, a.heads),
+               'old_logp': batch['action_logp'].reshape(-1, a.heads), 'old_logits': batch['action_dist_inputs'].reshape(-1, a.num_logits),
+               'advantages': batch['advantages'].reshape(-1), 'value_targets': batch['value_targets'].reshape(-1), 'old_vf': batch['vf_preds'].reshape(-1)}
+        N = src['obs'].shape[0]
+        if any(t.shape[0] != N for t in src.values()):
+            raise ValueError("the batch's tensors disagree about the number of rows")
+        kernel_active = None
+        if num_active is not None and int(num_active) < a.U:
+            if multi:
+                keep = torch.nonzero(torch.arange(N, device=self.device) % a.U < int(num_active)).reshape(-1)
+                src = {k: t.index_select(0, keep) for k, t in src.items()}
+                N = int(keep.numel())
+            else:
+                kernel_active = int(num_active)
+        adv = src['advantages']
+        src['advantages'] = (adv - adv.mean()) / adv.std(unbiased=False).clamp_min(1e-4)
+        mb = N if minibatch_rows is None else min(int(minibatch_rows), N)
+        if mb > self.max_rows:
+            raise ValueError(f"minibatches of {mb} rows > max_rows {self.max_rows} of the learner")
+        if mb not in self._mb:
+            self._mb = {mb: {k: torch.empty((mb,) + tuple(t.shape[1:]), dtype=t.dtype, device=self.device) for k, t in src.items()}}
+        buf = self._mb[mb]
+        starts = list(range(0, N, mb))
+        stats = torch.zeros((len(starts), _lib.PPO_NUM_STATS), dtype=torch.float32, device=self.device)
+        gen = torch.Generator(device=self.device)
+        gen.manual_seed(int(seed))
+        for _ in range(int(num_sgd_iter)):
+            perm = torch.randperm(N, generator=gen, device=self.device)
+            for i, s in enumerate(starts):
+                idx = perm[s:s + mb]
+                n = int(idx.numel())
+                view = {k: t[:n] for k, t in buf.items()}
+                for k in src:
+                    torch.index_select(src[k], 0, idx, out=view[k])
+                self.grads(view['obs'], view['actions'], view['old_logp'], view['old_logits'], view['advantages'], view['value_targets'], view['old_vf'],
+                           num_active=kernel_active, stats=stats[i])
+                self.apply()
+        mean = stats.mean(0).cpu().numpy()
+        out = {n: float(mean[i]) for i, n in enumerate(STATS)}
+        self.hyper['kl_coeff'] = adapt_kl_coeff(self.hyper['kl_coeff'], out['kl'], self.kl_target)
+        out['kl_coeff'] = self.hyper['kl_coeff']
+        return out

@@ -9,7 +9,8 @@ What an RLlib rollout worker does per env and step -- compute_action, env.step, 
 
 Per step two launches (the actor with its value function, the env step writing straight into the next slot of the buffers), after
 the loop one value-only launch for the bootstrap and one for the advantages.  With Philox draws nothing synchronises and nothing is
-allocated per step.  The PPO loss and the optimiser are not part of this package.
+allocated per step.  The PPO loss and the optimiser read the batch where it lies: deepcomp_amd.learner.PPOLearner.update (which needs
+``dist_inputs=True``: the logits the actions were drawn from, for the KL term).
 """
 import ctypes
 
@@ -85,7 +86,7 @@ def _codec(env):
     return _CODECS[key]
 
 
-def buffers(env, actor, num_steps, compact=False):
+def buffers(env, actor, num_steps, compact=False, dist_inputs=False):
     """The device buffers of a num_steps batch, allocated once."""
     T, E, U, dev = int(num_steps), env.E, env.U, env.device
     rows = E * U if env.kind == _lib.MULTI else E
@@ -98,6 +99,8 @@ def buffers(env, actor, num_steps, compact=False):
         b['new_obs_last'] = torch.zeros_like(env.obs)
     b['actions'] = torch.zeros((T, E, U), dtype=torch.uint8, device=dev)
     b['action_logp'] = torch.zeros((T, rows, actor.heads), dtype=torch.float32, device=dev)
+    if dist_inputs:
+        b['action_dist_inputs'] = torch.zeros((T, rows, actor.num_logits), dtype=torch.float32, device=dev)
     for name in ('vf_preds', 'rewards', 'advantages', 'value_targets'):
         b[name] = torch.zeros((T, rows), dtype=torch.float32, device=dev)
     b['dones'] = torch.zeros(T, dtype=torch.uint8, device=dev)
@@ -105,12 +108,13 @@ def buffers(env, actor, num_steps, compact=False):
     return b
 
 
-def collect(env, actor, num_steps, gamma=0.99, lam=1.0, sample=True, compact=False, out=None):
+def collect(env, actor, num_steps, gamma=0.99, lam=1.0, sample=True, compact=False, out=None, dist_inputs=False):
     """num_steps steps of `env` driven by `actor` (which needs a value function) as one PPO train batch: a dict of device tensors
     under RLlib's SampleBatch names -- obs [T, ...] (compact=True: obs_compact [T, E, words], the record of env.step_compact),
     actions [T, E, U] uint8, action_logp [T, rows, heads], vf_preds / rewards / advantages / value_targets [T, rows], dones [T]
     uint8 (the env batch runs in lock-step) and new_obs_last, the observation after step T-1 (last_vf [rows] holds its value, the
-    bootstrap, where the batch ended inside an episode).
+    bootstrap, where the batch ended inside an episode).  dist_inputs=True adds action_dist_inputs [T, rows, logits], the logits the
+    actions were drawn from (what PPO's KL term needs).
 
     The batch starts from env.obs -- the observation of the caller's reset() / step(), or of the previous collect() -- and from a
     reset of its own where the env has never been reset; it leaves new_obs_last in env.obs, so batches follow each other (and the
@@ -131,9 +135,10 @@ def collect(env, actor, num_steps, gamma=0.99, lam=1.0, sample=True, compact=Fal
     if compact and env.kind != _lib.MULTI:
         raise NotImplementedError("compact observation records exist for multi-agent observations only")
     key = 'obs_compact' if compact else 'obs'
-    b = out if out is not None else buffers(env, actor, T, compact)
-    if not isinstance(b, dict) or key not in b or b[key].shape[0] != T or b['actions'].shape != (T, env.E, env.U):
-        raise ValueError(f"out must be the dict of a collect() call with the same env shape, num_steps and compact={compact}")
+    b = out if out is not None else buffers(env, actor, T, compact, dist_inputs)
+    if not isinstance(b, dict) or key not in b or b[key].shape[0] != T or b['actions'].shape != (T, env.E, env.U) or \
+            (dist_inputs and 'action_dist_inputs' not in b):
+        raise ValueError(f"out must be the dict of a collect() call with the same env shape, num_steps, compact={compact} and dist_inputs")
     obs, last = b[key], b['new_obs_last']
     reset_into = env.reset_compact if compact else env.reset_into
 
@@ -147,7 +152,8 @@ def collect(env, actor, num_steps, gamma=0.99, lam=1.0, sample=True, compact=Fal
     b['dones'].zero_()
     done = False
     for t in range(T):
-        actor.act(env, sample=sample, obs=obs[t], compact=compact, out=b['actions'][t], logp=b['action_logp'][t], vf=b['vf_preds'][t])
+        actor.act(env, sample=sample, obs=obs[t], compact=compact, out=b['actions'][t], logp=b['action_logp'][t], vf=b['vf_preds'][t],
+                  logits=b['action_dist_inputs'][t] if dist_inputs else None)
         nxt = obs[t + 1] if t + 1 < T else last
         if compact:
             env.step_compact(b['actions'][t], nxt, b['rewards'][t])

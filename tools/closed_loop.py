@@ -6,6 +6,7 @@ this only shows where the time goes once the env runs at ~10^8-10^9 env-steps/s.
 
     python tools/closed_loop.py [--envs 65536] [--steps 200] [--dtype bf16] [--kind multi] [--actor hip [--compact]]
     python tools/closed_loop.py --collect 50 [--envs 65536] [--kind multi] [--compact] [--shared-value]
+    python tools/closed_loop.py --train 3 [--train-steps 5] [--sgd-iters 2] [--minibatch ROWS] [--envs 65536] [--kind multi]
 
 --actor torch (default): the actor as torch ops (bf16 matmuls, Gumbel-max through torch.rand).  --actor hip: the same weights in
 deepcomp_amd.actor.FcnetActor -- one HIP kernel from observation tensor to action tensor -- and BOTH loops are timed in this
@@ -16,6 +17,10 @@ process, one after the other on the same env.  --compact (multi-agent, hip): the
 the bootstrap value, dcomp_gae) against the same loop with the HIP actor but the value network as torch ops (bf16 matmuls) and GAE
 as a torch loop over t: what a user had before the value function moved into the kernel.  Both are timed in this process,
 interleaved, --steps / T batches each.
+
+--train ITERS: the whole PPO loop in this process -- sampler.collect(dist_inputs=True) then deepcomp_amd.learner.PPOLearner.update --
+printing the mean reward and the five loss statistics per iteration; then the time of grads + apply per minibatch (HIP events over
+back-to-back launches) next to the same network and loss under torch autograd with bf16 autocast and torch.optim.Adam, interleaved.
 """
 import argparse
 import sys
@@ -40,8 +45,12 @@ ap.add_argument('--actor', default='torch', choices=['torch', 'hip'])
 ap.add_argument('--compact', action='store_true', help='hip actor, multi-agent: the env writes only the compact record and the actor reads it')
 ap.add_argument('--collect', type=int, default=0, metavar='T', help='time sampler.collect of T-step batches against the torch-value + torch-GAE loop')
 ap.add_argument('--shared-value', action='store_true', help='--collect: value_out on the actor\'s second hidden layer (vf_share_layers)')
+ap.add_argument('--train', type=int, default=0, metavar='ITERS', help='collect -> PPOLearner.update, ITERS times, then time grads + apply against torch autograd')
+ap.add_argument('--train-steps', type=int, default=5, help='--train: steps per collected batch')
+ap.add_argument('--sgd-iters', type=int, default=2, help='--train: SGD iterations per batch')
+ap.add_argument('--minibatch', type=int, default=0, help='--train: rows per minibatch (default: one step\'s rows)')
 a = ap.parse_args()
-if a.collect:
+if a.collect or a.train:
     a.actor = 'hip'
 if a.compact and (a.actor != 'hip' or a.kind != 'multi'):
     ap.error('--compact needs --actor hip and --kind multi')
@@ -141,8 +150,89 @@ def collect_mode(T):
     env.check()
 
 
+def train_mode(iters):
+    from deepcomp_amd.learner import PPOLearner, STATS
+    from deepcomp_amd.sampler import collect
+    T = a.train_steps
+    host_v = FcnetActor.random_value_weights(a.kind, U, B, 256, seed=0)
+    hip.set_value(host_v)
+    rows = E * U if multi else E
+    mb = a.minibatch or rows
+    learner = PPOLearner(hip, lr=5e-5, max_rows=mb)
+    env.reset()
+    buf = None
+    print(f'{E} envs x {U} UE x {B} BS ({a.kind}), 2x256 tanh + value trunk, batches of T = {T} ({T * rows} rows), {a.sgd_iters} SGD iterations, minibatches of {mb}')
+    for it in range(iters):
+        buf = collect(env, hip, T, 0.99, 0.95, out=buf, dist_inputs=True)
+        st = learner.update(buf, num_sgd_iter=a.sgd_iters, minibatch_rows=mb, seed=it)
+        print(f'iter {it}: mean reward {float(buf["rewards"].mean()):+.4f}  ' + '  '.join(f'{n} {st[n]:+.5f}' for n in STATS) + f'  kl_coeff {st["kl_coeff"]:.3f}')
+
+    # ---- grads + apply on one minibatch against torch autograd (bf16 autocast) + torch.optim.Adam on the same network and loss
+    f = lambda k, w: buf[k].reshape(-1, w)[:mb].contiguous()             # noqa: E731
+    obs, act = f('obs', D), f('actions', heads)
+    olp, ologits = f('action_logp', heads), f('action_dist_inputs', heads * (B + 1))
+    adv, vt, ovf = (buf[k].reshape(-1)[:mb].contiguous() for k in ('advantages', 'value_targets', 'vf_preds'))
+    stats = torch.zeros(5, device=dev)
+
+    def hip_step():
+        learner.grads(obs, act, olp, ologits, adv, vt, ovf, stats=stats)
+        learner.apply()
+
+    names = ('w1', 'b1', 'w2', 'b2', 'w3', 'b3')
+    P = {n: torch.from_numpy(host_w[n]).to(dev).requires_grad_() for n in names}
+    V = {n: torch.from_numpy(host_v[n]).to(dev).requires_grad_() for n in ('w1', 'b1', 'w2', 'b2', 'wv', 'bv')}
+    opt = torch.optim.Adam(list(P.values()) + list(V.values()), lr=5e-5)
+    act_l = act.long().unsqueeze(-1)
+    hy = learner.hyper
+
+    def torch_step():
+        opt.zero_grad(set_to_none=True)
+        with torch.autocast('cuda', dtype=torch.bfloat16):
+            h = torch.tanh(torch.addmm(P['b2'], torch.tanh(torch.addmm(P['b1'], obs, P['w1'])), P['w2']))
+            logits = torch.addmm(P['b3'], h, P['w3'])
+            g = torch.tanh(torch.addmm(V['b2'], torch.tanh(torch.addmm(V['b1'], obs, V['w1'])), V['w2']))
+            v = (g @ V['wv'].unsqueeze(-1)).squeeze(-1)
+        v = v.float() + V['bv']
+        lsm = torch.log_softmax(logits.float().view(mb, heads, B + 1), -1)
+        lso = torch.log_softmax(ologits.view(mb, heads, B + 1), -1)
+        ratio = (lsm.gather(-1, act_l).squeeze(-1).sum(1) - olp.sum(1)).exp()
+        surr = torch.minimum(adv * ratio, adv * ratio.clamp(1 - hy['clip_param'], 1 + hy['clip_param']))
+        kl = (lso.exp() * (lso - lsm)).sum((1, 2))
+        ent = -(lsm.exp() * lsm).sum((1, 2))
+        vc = ovf + (v - ovf).clamp(-hy['vf_clip_param'], hy['vf_clip_param'])
+        vfl = torch.maximum((v - vt) ** 2, (vc - vt) ** 2)
+        (-surr + hy['kl_coeff'] * kl + hy['vf_loss_coeff'] * vfl - hy['entropy_coeff'] * ent).mean().backward()
+        opt.step()
+
+    def timed(fn, n):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        torch.cuda.synchronize()
+        e0.record()
+        for _ in range(n):
+            fn()
+        e1.record()
+        torch.cuda.synchronize()
+        return e0.elapsed_time(e1) * 1e3 / n
+
+    n = max(3, min(50, a.steps))
+    for fn in (hip_step, torch_step):
+        timed(fn, 2)
+    res = {'hip': [], 'torch': []}
+    for _ in range(3):                                  # interleaved: drift of the clocks shows as spread, not as a difference
+        res['hip'].append(timed(hip_step, n))
+        res['torch'].append(timed(torch_step, n))
+    print(f'one minibatch of {mb} rows, {n} back-to-back steps per timing, HIP events')
+    print('PPOLearner grads + apply                      : ' + ' / '.join(f'{t:.0f}' for t in res['hip']) + ' us')
+    print('torch autograd (bf16 autocast) + Adam         : ' + ' / '.join(f'{t:.0f}' for t in res['torch']) + ' us')
+    print(f'torch / PPOLearner: {min(res["torch"]) / min(res["hip"]):.2f} x')
+    env.check()
+
+
 if a.collect:
     collect_mode(a.collect)
+    sys.exit(0)
+if a.train:
+    train_mode(a.train)
     sys.exit(0)
 packed = torch.zeros((E, env.compact_words), dtype=torch.int32, device=dev) if a.compact else None
 act_buf = torch.zeros((E, U), dtype=torch.uint8, device=dev)
