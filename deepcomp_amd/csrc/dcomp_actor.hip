@@ -31,20 +31,21 @@
 //   - VF = 2, value_out on the actor's h2: one more column behind the last head in the packed W3; the row walk never sees it
 //   - the value-only call (action == NULL) runs the value sweep alone (VF = 1) / the one output tile that holds the column (VF = 2)
 // VF = 0 is what dcomp_actor_actions launches, with or without a value function attached.
+//
+// This file has the actor's own: the staging of observation rows and compact records (the fetch it hands to layer1), the ring that
+// streams the weights of layers 2 and 3, the row walk with its draws, and the entry points.  The pieces the learner's kernel runs
+// too -- layer 1, the hidden fragments, the logit tile, the log-sum-exp step -- the fragment layout, the net description (Net) and
+// the host helpers are in dcomp_actor_impl.h.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
-#include <cstdarg>
 #include <cstdint>
-#include <cstdio>
 #include <cstring>
 #include <vector>
 
 #define DCOMP_BUILDING_LIBRARY 1
 #include "../../include/dcomp.h"
-#include "dcomp_actor_impl.h"       // fragment helpers, pack(), struct dcomp_actor: shared with dcomp_learner.hip
-
-namespace dcomp { int report(int code, const char *msg); }       // dcomp_api.hip: the thread's dcomp_last_error() text
+#include "dcomp_actor_impl.h"       // the forward-pass helpers, the fragment layout, Net and struct dcomp_actor, fail / HIP_TRY: shared with dcomp_learner.hip
 
 namespace dactor {
 
@@ -59,14 +60,10 @@ struct Params {
     const void *obs;
     uint8_t *action;
     float *logits, *logp, *vf;
-    const uint4 *w1, *w2, *w3;        // packed bf16 fragments [m tile][k step][lane] x 8 elements
-    const float *b1, *b2, *b3;        // padded with zeros to the padded widths
-    const uint4 *vw1, *vw2, *vw3;     // VF = 1: the value trunk, packed like the actor's; vw3 = value_out as ONE output tile, column 0
-    const float *vb1, *vb2, *vb3;
+    Net net;                          // the handle's; VF = 2: pi.w3 / pi.b3, NT3 and N3 are the output tiles this call walks (actor_launch)
     int64_t rows, tiles, row_base;
-    int32_t K1, K1p, XS, N3, NT3, heads, B, U, num_active, multi, compact, sample;
+    int32_t num_active, compact, sample;
     uint32_t step, seed_lo, seed_hi;
-    int32_t lds_per_wave;
     int32_t vcol, policy;             // VF = 2: the value's column of the packed W3; policy = 0: the value-only call
 };
 
@@ -90,12 +87,12 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(2, 2))) v
     extern __shared__ uint4 lds4[];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, r = lane & 31, h = lane >> 5;
     const uint32_t lane16 = (uint32_t)lane * 16u;
-    unsigned char *base = reinterpret_cast<unsigned char *>(lds4) + (size_t)wave * p.lds_per_wave;
+    const Net &n = p.net;
+    unsigned char *base = reinterpret_cast<unsigned char *>(lds4) + (size_t)wave * n.lds_per_wave;
     __bf16 *xs = reinterpret_cast<__bf16 *>(base);                                   // [32][XS] bf16: the chunk of the tile's rows
-    float *lt = reinterpret_cast<float *>(base + (size_t)TILE * p.XS * 2);           // [32][LT] f32: 32 logits of every row
+    float *lt = reinterpret_cast<float *>(base + (size_t)TILE * n.XS * 2);           // [32][LT] f32: 32 logits of every row
     uint32_t *ri = reinterpret_cast<uint32_t *>(lt + TILE * LT);                     // [32][4]: compact record of row r: word offset lo, hi | listed | UE slot
-    const int XS = p.XS, K1 = p.K1, B = p.B, U = p.U, NA = B + 1;
-    const int KS1 = p.K1p >> 4;
+    const int XS = n.XS, K1 = n.K1, B = n.B, U = n.U, NA = B + 1;
     constexpr int KS2 = 2 * MT;                                  // k steps of layers 2 and 3
     constexpr int D = KS2 < 8 ? KS2 : 8;                         // weight fragments in flight (32 registers at most)
     constexpr int Q2 = MT * KS2;                                 // MFMAs of layer 2
@@ -109,7 +106,7 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(2, 2))) v
         const int64_t myrow = row0 + r;                                              // the decision row on this lane
         const bool have = r < nrow;
         int slot = 0;                                                                // multi-agent: the row's UE slot
-        if (p.multi && have) slot = (int)(myrow % U);
+        if (n.multi && have) slot = (int)(myrow % U);
         if (p.compact) {
             if (lane < TILE) {
                 uint32_t lo = 0, hi = 0, listed = 0;
@@ -129,56 +126,30 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(2, 2))) v
 #pragma nounroll
         for (int sweep = (VF == 1 && !p.policy) ? 1 : 0; sweep < (VF == 1 ? 2 : 1); sweep++) {
         const bool val = VF == 1 && sweep != 0;
-        const uint4 *w1 = val ? p.vw1 : p.w1, *w2 = val ? p.vw2 : p.w2, *w3 = val ? p.vw3 : p.w3;
-        const float *b1 = val ? p.vb1 : p.b1, *b2 = val ? p.vb2 : p.b2, *b3 = val ? p.vb3 : p.b3;
-        const int NT3 = val ? 1 : p.NT3, N3 = val ? 0 : p.N3;                        // (the value trunk has no logits to walk or store)
+        const Trunk t = select_trunk(n, val);
+        const int NT3 = val ? 1 : n.NT3, N3 = val ? 0 : n.N3;                        // (the value trunk has no logits to walk or store)
         const int vcol = VF == 0 ? -1 : VF == 1 ? (val ? 0 : -1) : p.vcol;
-        const bool staged = val && p.policy && p.K1p <= KC;                          // the policy sweep left the bf16 rows in LDS
+        const bool staged = val && p.policy && n.K1p <= KC;                          // the policy sweep left the bf16 rows in LDS
 
         // ---- layer 1: acc[m] = W1^T (units 32m ...) x X^T, the inputs in chunks through LDS
         f32x16 acc[MT];
-#pragma unroll
-        for (int m = 0; m < MT; m++)
-#pragma unroll
-            for (int i = 0; i < 16; i++) acc[m][i] = 0.f;
-        uint4 wq1[MT];                                                               // layer 1's weights, one k step ahead
-#pragma unroll
-        for (int m = 0; m < MT; m++) wq1[m] = load_frag(w1, (size_t)m * KS1, lane16);
-        for (int k0 = 0; k0 < p.K1p; k0 += KC) {
-            const int kc = p.K1p - k0 < KC ? p.K1p - k0 : KC;                        // a multiple of 16
-            const uint32_t magic = (uint32_t)(0x100000000ull / (uint32_t)kc) + 1u;   // f / kc = umulhi(f, magic): f < 2^14, f kc < 2^32
-            const int nf = staged ? 0 : TILE * kc;
-#pragma unroll 4
-            for (int f = lane; f < nf; f += 64) {
-                const int rr = (int)__umulhi((uint32_t)f, magic), c = f - rr * kc, k = k0 + c;
-                float v = 0.f;
-                if (rr < nrow && k < K1) {
-                    if (!p.compact) {
-                        v = rowsf[(size_t)(row0 + rr) * K1 + k];
-                    } else {
-                        const uint64_t off = (uint64_t)ri[rr * 4] | ((uint64_t)ri[rr * 4 + 1] << 32);
-                        if (k < B) v = (float)((cwords[off + B + 1 + (k >> 5)] >> (k & 31)) & 1u);      // connected
-                        else if (k < 2 * B) v = __uint_as_float(cwords[off + (k - B)]);                // dr
-                        else if (k < 4 * B) v = ri[rr * 4 + 2] ? __uint_as_float(cwords[off + (uint64_t)(U - (int)ri[rr * 4 + 3]) * CW + (k - 2 * B)]) : 0.f;
-                        else v = __uint_as_float(cwords[off + B]);                                    // utility
-                    }
-                }
-                xs[rr * XS + c] = (__bf16)v;
-            }
-            wave_fence();
-            for (int s = 0; s < (kc >> 4); s++) {
-                const bf16x8 b = as_frag(*reinterpret_cast<const uint4 *>(xs + r * XS + 16 * s + 8 * h));
-                const int ksn = (k0 >> 4) + s + 1 < KS1 ? (k0 >> 4) + s + 1 : KS1 - 1;          // (the last step re-reads itself)
-                uint4 nx[MT];
-#pragma unroll
-                for (int m = 0; m < MT; m++) nx[m] = load_frag(w1, (size_t)m * KS1 + ksn, lane16);
-#pragma unroll
-                for (int m = 0; m < MT; m++) acc[m] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(as_frag(wq1[m]), b, acc[m], 0, 0, 0);
-#pragma unroll
-                for (int m = 0; m < MT; m++) wq1[m] = nx[m];
-            }
-            wave_fence();
-        }
+        layer1<MT>(acc, t.w1, n.K1p, xs, XS, lane, lane16, staged,
+                   [&](int rr, int k) {
+                       float v = 0.f;
+                       if (rr < nrow && k < K1) {
+                           if (!p.compact) {
+                               v = rowsf[(size_t)(row0 + rr) * K1 + k];
+                           } else {
+                               const uint64_t off = (uint64_t)ri[rr * 4] | ((uint64_t)ri[rr * 4 + 1] << 32);
+                               if (k < B) v = (float)((cwords[off + B + 1 + (k >> 5)] >> (k & 31)) & 1u);      // connected
+                               else if (k < 2 * B) v = __uint_as_float(cwords[off + (k - B)]);                // dr
+                               else if (k < 4 * B) v = ri[rr * 4 + 2] ? __uint_as_float(cwords[off + (uint64_t)(U - (int)ri[rr * 4 + 3]) * CW + (k - 2 * B)]) : 0.f;
+                               else v = __uint_as_float(cwords[off + B]);                                    // utility
+                           }
+                       }
+                       return v;
+                   },
+                   [](int, int) {});
 
         // ---- h1 = bf16(act(. + b1)) as the B fragments of layer 2 (whose first weights are on their way meanwhile)
         // The weights of layers 2 and 3 come through a ring of D fragments, D MFMAs ahead of their use: fragment q is loaded into
@@ -186,15 +157,9 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(2, 2))) v
         // hoists every load of a layer to its top -- 512 registers and spills.)
         uint4 ring[D];
 #pragma unroll
-        for (int i = 0; i < D; i++) ring[i] = load_frag(w2, i, lane16);
+        for (int i = 0; i < D; i++) ring[i] = load_frag(t.w2, i, lane16);
         bf16x8 h1[MT][2];
-#pragma unroll
-        for (int t = 0; t < MT; t++) {
-            h1[t][0] = next_fragment<RELU>(acc[t], 0, b1 + 32 * t + 4 * h);
-            h1[t][1] = next_fragment<RELU>(acc[t], 1, b1 + 32 * t + 4 * h);
-            asm volatile("" : "+v"(h1[t][0]), "+v"(h1[t][1]));
-            __builtin_amdgcn_sched_barrier(0);                   // (tile by tile: 16 registers become 8, not every bias load first)
-        }
+        hidden_fragments<MT, RELU>(acc, t.b1, h, h1);
 
         // ---- layer 2, one tile of 32 units at a time
         bf16x8 h2[MT][2];
@@ -208,11 +173,11 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(2, 2))) v
                 for (int ks = 0; ks < KS2; ks++) {
                     const int q = m * KS2 + ks;
                     a2 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(as_frag(ring[q % D]), h1[ks >> 1][ks & 1], a2, 0, 0, 0);
-                    ring[q % D] = q + D < Q2 ? load_frag(w2, q + D, lane16) : load_frag(w3, q + D - Q2, lane16);   // behind layer 2: layer 3's first
+                    ring[q % D] = q + D < Q2 ? load_frag(t.w2, q + D, lane16) : load_frag(t.w3, q + D - Q2, lane16);   // behind layer 2: layer 3's first
                     __builtin_amdgcn_sched_barrier(0);
                 }
-                h2[m][0] = next_fragment<RELU>(a2, 0, b2 + 32 * m + 4 * h);
-                h2[m][1] = next_fragment<RELU>(a2, 1, b2 + 32 * m + 4 * h);
+                h2[m][0] = next_fragment<RELU>(a2, 0, t.b2 + 32 * m + 4 * h);
+                h2[m][1] = next_fragment<RELU>(a2, 1, t.b2 + 32 * m + 4 * h);
                 asm volatile("" : "+v"(h2[m][0]), "+v"(h2[m][1]));       // converted HERE: sunk towards layer 3, the 16 raw floats stay live instead of 8 registers
                 __builtin_amdgcn_sched_barrier(0);
             }
@@ -231,10 +196,12 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(2, 2))) v
             for (int ks = 0; ks < KS2; ks++) {
                 a3 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(as_frag(ring[ks % D]), h2[ks >> 1][ks & 1], a3, 0, 0, 0);      // (Q2 and KS2 are multiples of D)
                 const int f = nt * KS2 + ks + D;
-                ring[ks % D] = load_frag(w3, f < NT3 * KS2 ? f : 0, lane16);                // (behind the last: any valid one)
+                ring[ks % D] = load_frag(t.w3, f < NT3 * KS2 ? f : 0, lane16);                // (behind the last: any valid one)
                 __builtin_amdgcn_sched_barrier(0);
             }
-            const float *bias = b3 + 32 * nt + 4 * h;
+            // (put_logit_tile, written out: through the shared function the allocator reloads spilled scalars inside layer 1's staging
+            // loop and the compact-record loop runs 0.7 % slower, profiles/r10_fcnet_refactor.txt)
+            const float *bias = t.b3 + 32 * nt + 4 * h;
 #pragma unroll
             for (int g = 0; g < 4; g++) {
                 const float4 bv = *reinterpret_cast<const float4 *>(bias + 8 * g);
@@ -257,13 +224,12 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(2, 2))) v
                     if (a == 0) first_l = x;
                     if (y > best_y) { best_y = y; best_a = a; best_l = x; }       // strict: the FIRST maximum
                     if (p.logp) {
-                        const float m2 = fmaxf(mx, x);
-                        sm = sm * expf(mx - m2) + expf(x - m2);
-                        mx = m2;
+                        float e1, e2;
+                        lse_push(x, mx, sm, e1, e2);
                     }
                     if (++a == NA) {
-                        const bool off = (p.multi ? slot : hd) >= p.num_active;    // unlisted slot / head: action 0
-                        const size_t at = (size_t)myrow * p.heads + hd;
+                        const bool off = (n.multi ? slot : hd) >= p.num_active;    // unlisted slot / head: action 0
+                        const size_t at = (size_t)myrow * n.heads + hd;
                         p.action[at] = (uint8_t)(off ? 0 : best_a);
                         if (p.logp) p.logp[at] = (off ? first_l : best_l) - (mx + logf(sm));
                         a = 0; hd++;
@@ -290,12 +256,7 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(2, 2))) v
 typedef void (*kernel_fn)(const Params);
 template <int VF> static kernel_fn pick_width(int mt, bool relu)
 {
-    switch (mt) {
-    case 1: return relu ? actor_kernel<1, true, VF> : actor_kernel<1, false, VF>;
-    case 2: return relu ? actor_kernel<2, true, VF> : actor_kernel<2, false, VF>;
-    case 4: return relu ? actor_kernel<4, true, VF> : actor_kernel<4, false, VF>;
-    default: return relu ? actor_kernel<8, true, VF> : actor_kernel<8, false, VF>;
-    }
+    return pick_shape(mt, relu, [](auto s) -> kernel_fn { return actor_kernel<decltype(s)::MT, decltype(s)::RELU, VF>; });
 }
 static kernel_fn pick(int mt, bool relu, int vf)
 {
@@ -341,85 +302,56 @@ __global__ __launch_bounds__(256) void gae_kernel(const GaeParams g)
 }  // namespace dactor
 
 
-static int afail(int code, const char *fmt, ...) __attribute__((format(printf, 2, 3)));
-static int afail(int code, const char *fmt, ...)
-{
-    char buf[512];
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(buf, sizeof(buf), fmt, ap);
-    va_end(ap);
-    return dcomp::report(code, buf);
-}
-#define ACTOR_HIP_TRY(expr)                                                                          \
-    do {                                                                                             \
-        hipError_t e_ = (expr);                                                                      \
-        if (e_ != hipSuccess) return afail(DCOMP_EHIP, "%s failed: %s", #expr, hipGetErrorString(e_)); \
-    } while (0)
-
 extern "C" int dcomp_actor_create(const dcomp_actor_cfg *cfg, dcomp_actor **out)
 {
     using namespace dactor;
     if (out) *out = nullptr;
-    if (!cfg || !out) return afail(DCOMP_EINVAL, "dcomp_actor_create: cfg and out must not be NULL");
+    if (!cfg || !out) return fail(DCOMP_EINVAL, "dcomp_actor_create: cfg and out must not be NULL");
     if (cfg->struct_size != (int32_t)sizeof(dcomp_actor_cfg))
-        return afail(DCOMP_EABI, "dcomp_actor_create: caller's dcomp_actor_cfg has %d bytes, the library's %d", cfg->struct_size, (int)sizeof(dcomp_actor_cfg));
+        return fail(DCOMP_EABI, "dcomp_actor_create: caller's dcomp_actor_cfg has %d bytes, the library's %d", cfg->struct_size, (int)sizeof(dcomp_actor_cfg));
     // host-only validation first: nothing below touches HIP before the arguments are known to be good
-    if (cfg->obs_kind != DCOMP_MULTI && cfg->obs_kind != DCOMP_CENTRAL) return afail(DCOMP_EINVAL, "dcomp_actor_create: obs_kind %d is neither DCOMP_CENTRAL nor DCOMP_MULTI", cfg->obs_kind);
-    if (cfg->num_ue < 1 || cfg->num_bs < 1) return afail(DCOMP_EINVAL, "dcomp_actor_create: num_ue %d / num_bs %d must be >= 1", cfg->num_ue, cfg->num_bs);
-    if (cfg->hidden < 32 || cfg->hidden % 32) return afail(DCOMP_EINVAL, "dcomp_actor_create: hidden %d is not a multiple of 32 >= 32", cfg->hidden);
-    if (cfg->activation != DCOMP_ACT_TANH && cfg->activation != DCOMP_ACT_RELU) return afail(DCOMP_EINVAL, "dcomp_actor_create: unknown activation %d", cfg->activation);
-    if (!cfg->w1 || !cfg->b1 || !cfg->w2 || !cfg->b2 || !cfg->w3 || !cfg->b3) return afail(DCOMP_EINVAL, "dcomp_actor_create: a weight or bias pointer is NULL");
-    if (cfg->num_bs > DCOMP_MAX_BS) return afail(DCOMP_EUNSUPPORTED, "dcomp_actor_create: num_bs %d > %d", cfg->num_bs, DCOMP_MAX_BS);
-    if (cfg->num_ue > DCOMP_MAX_UE) return afail(DCOMP_EUNSUPPORTED, "dcomp_actor_create: num_ue %d > %d", cfg->num_ue, DCOMP_MAX_UE);
-    if (cfg->hidden > DCOMP_ACTOR_MAX_HIDDEN) return afail(DCOMP_EUNSUPPORTED, "dcomp_actor_create: hidden %d > %d", cfg->hidden, DCOMP_ACTOR_MAX_HIDDEN);
+    if (cfg->obs_kind != DCOMP_MULTI && cfg->obs_kind != DCOMP_CENTRAL) return fail(DCOMP_EINVAL, "dcomp_actor_create: obs_kind %d is neither DCOMP_CENTRAL nor DCOMP_MULTI", cfg->obs_kind);
+    if (cfg->num_ue < 1 || cfg->num_bs < 1) return fail(DCOMP_EINVAL, "dcomp_actor_create: num_ue %d / num_bs %d must be >= 1", cfg->num_ue, cfg->num_bs);
+    if (cfg->hidden < 32 || cfg->hidden % 32) return fail(DCOMP_EINVAL, "dcomp_actor_create: hidden %d is not a multiple of 32 >= 32", cfg->hidden);
+    if (cfg->activation != DCOMP_ACT_TANH && cfg->activation != DCOMP_ACT_RELU) return fail(DCOMP_EINVAL, "dcomp_actor_create: unknown activation %d", cfg->activation);
+    if (!cfg->w1 || !cfg->b1 || !cfg->w2 || !cfg->b2 || !cfg->w3 || !cfg->b3) return fail(DCOMP_EINVAL, "dcomp_actor_create: a weight or bias pointer is NULL");
+    if (cfg->num_bs > DCOMP_MAX_BS) return fail(DCOMP_EUNSUPPORTED, "dcomp_actor_create: num_bs %d > %d", cfg->num_bs, DCOMP_MAX_BS);
+    if (cfg->num_ue > DCOMP_MAX_UE) return fail(DCOMP_EUNSUPPORTED, "dcomp_actor_create: num_ue %d > %d", cfg->num_ue, DCOMP_MAX_UE);
+    if (cfg->hidden > DCOMP_ACTOR_MAX_HIDDEN) return fail(DCOMP_EUNSUPPORTED, "dcomp_actor_create: hidden %d > %d", cfg->hidden, DCOMP_ACTOR_MAX_HIDDEN);
     const bool multi = cfg->obs_kind == DCOMP_MULTI;
     const int U = cfg->num_ue, B = cfg->num_bs, H = cfg->hidden;
     const int K1 = multi ? 4 * B + 1 : U * (2 * B + 1), heads = multi ? 1 : U, N3 = heads * (B + 1);
-    if (K1 > DCOMP_ACTOR_MAX_IN) return afail(DCOMP_EUNSUPPORTED, "dcomp_actor_create: a central row of %d x %d has %d inputs > %d", U, B, K1, DCOMP_ACTOR_MAX_IN);
-    if (N3 > DCOMP_ACTOR_MAX_LOGITS) return afail(DCOMP_EUNSUPPORTED, "dcomp_actor_create: a central row of %d x %d has %d logits > %d", U, B, N3, DCOMP_ACTOR_MAX_LOGITS);
+    if (K1 > DCOMP_ACTOR_MAX_IN) return fail(DCOMP_EUNSUPPORTED, "dcomp_actor_create: a central row of %d x %d has %d inputs > %d", U, B, K1, DCOMP_ACTOR_MAX_IN);
+    if (N3 > DCOMP_ACTOR_MAX_LOGITS) return fail(DCOMP_EUNSUPPORTED, "dcomp_actor_create: a central row of %d x %d has %d logits > %d", U, B, N3, DCOMP_ACTOR_MAX_LOGITS);
 
     dcomp_actor *a = new dcomp_actor();
-    a->kind = cfg->obs_kind; a->U = U; a->B = B; a->hidden = H;
+    Net &n = a->net;
+    n.multi = multi; n.U = U; n.B = B; a->hidden = H;
     a->mt = H <= 32 ? 1 : H <= 64 ? 2 : H <= 128 ? 4 : 8;
     a->relu = cfg->activation == DCOMP_ACT_RELU;
-    a->K1 = K1; a->K1p = (K1 + 15) & ~15; a->N3 = N3; a->NT3 = (N3 + 31) / 32; a->heads = heads;
-    const int kcp = a->K1p < KC ? a->K1p : KC;
-    a->XS = kcp + 8;                                         // row stride = an odd number of 16-byte slots: 16 rows, 16 slots
-    a->lds_per_wave = TILE * a->XS * 2 + TILE * LT * 4 + TILE * 16;
+    n.K1 = K1; n.K1p = (K1 + 15) & ~15; n.N3 = N3; n.NT3 = (N3 + 31) / 32; n.heads = heads;
+    const int kcp = n.K1p < KC ? n.K1p : KC;
+    n.XS = kcp + 8;                                          // row stride = an odd number of 16-byte slots: 16 rows, 16 slots
+    n.lds_per_wave = TILE * n.XS * 2 + TILE * LT * 4 + TILE * 16;
     const int Hp = 32 * a->mt, KS2 = 2 * a->mt;
     std::vector<uint16_t> p1, p2, p3;
-    pack(p1, cfg->w1, K1, H, a->K1p / 16, a->mt, false);
+    pack(p1, cfg->w1, K1, H, n.K1p / 16, a->mt, false);
     pack(p2, cfg->w2, H, H, KS2, a->mt, true);
-    pack(p3, cfg->w3, H, N3, KS2, a->NT3, true);
-    std::vector<float> bias((size_t)2 * Hp + 32 * a->NT3, 0.f);
+    pack(p3, cfg->w3, H, N3, KS2, n.NT3, true);
+    std::vector<float> bias((size_t)2 * Hp + 32 * n.NT3, 0.f);
     memcpy(bias.data(), cfg->b1, sizeof(float) * H);
     memcpy(bias.data() + Hp, cfg->b2, sizeof(float) * H);
     memcpy(bias.data() + 2 * Hp, cfg->b3, sizeof(float) * N3);
-    auto up = [](size_t v) { return (v + 255) & ~(size_t)255; };
-    const size_t o1 = 0, o2 = up(o1 + p1.size() * 2), o3 = up(o2 + p2.size() * 2), ob = up(o3 + p3.size() * 2), total = ob + bias.size() * 4;
-    std::vector<unsigned char> img(total, 0);
-    memcpy(img.data() + o1, p1.data(), p1.size() * 2);
-    memcpy(img.data() + o2, p2.data(), p2.size() * 2);
-    memcpy(img.data() + o3, p3.data(), p3.size() * 2);
-    memcpy(img.data() + ob, bias.data(), bias.size() * 4);
 
     hipError_t e = hipGetDevice(&a->device);
     int cus = 0;
     if (e == hipSuccess) e = hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, a->device);
-    if (e == hipSuccess) e = hipMalloc(&a->dev_mem, total);
-    if (e == hipSuccess) {
-        e = hipMemcpy(a->dev_mem, img.data(), total, hipMemcpyHostToDevice);
-        if (e != hipSuccess) (void)hipFree(a->dev_mem);
-    }
+    if (e == hipSuccess) e = upload_image(p1, p2, p3, bias, Hp, &a->dev_mem, &n.pi);
     if (e != hipSuccess) {
         delete a;
-        return afail(DCOMP_EHIP, "dcomp_actor_create: %s", hipGetErrorString(e));
+        return fail(DCOMP_EHIP, "dcomp_actor_create: %s", hipGetErrorString(e));
     }
     a->max_blocks = (cus > 0 ? cus : 256) * 2;               // two workgroups of four waves per CU: two waves per SIMD
-    unsigned char *d = static_cast<unsigned char *>(a->dev_mem);
-    a->w1 = reinterpret_cast<const uint4 *>(d + o1); a->w2 = reinterpret_cast<const uint4 *>(d + o2); a->w3 = reinterpret_cast<const uint4 *>(d + o3);
-    a->b1 = reinterpret_cast<const float *>(d + ob); a->b2 = a->b1 + Hp; a->b3 = a->b2 + Hp;
     *out = a;
     return DCOMP_OK;
 }
@@ -433,56 +365,52 @@ extern "C" int dcomp_actor_destroy(dcomp_actor *a)
         if (e == hipSuccess) e = e2;
     }
     delete a;
-    return e == hipSuccess ? DCOMP_OK : afail(DCOMP_EHIP, "dcomp_actor_destroy: hipFree failed: %s", hipGetErrorString(e));
+    return e == hipSuccess ? DCOMP_OK : fail(DCOMP_EHIP, "dcomp_actor_destroy: hipFree failed: %s", hipGetErrorString(e));
 }
 
 // dcomp_actor_actions (vf_call = false) and dcomp_actor_actions_v: every check on the host first, then ONE launch
 static int actor_launch(const char *fn, bool vf_call, dcomp_actor *a, const dcomp_actor_run *r, const void *obs, uint8_t *action, float *vf, void *stream)
 {
     using namespace dactor;
-    if (!a || !r) return afail(DCOMP_EINVAL, "%s: handle and run must not be NULL", fn);
+    if (!a || !r) return fail(DCOMP_EINVAL, "%s: handle and run must not be NULL", fn);
     if (r->struct_size != (int32_t)sizeof(dcomp_actor_run))
-        return afail(DCOMP_EABI, "%s: caller's dcomp_actor_run has %d bytes, the library's %d", fn, r->struct_size, (int)sizeof(dcomp_actor_run));
-    if (r->obs_format != DCOMP_ACTOR_ROWS && r->obs_format != DCOMP_ACTOR_COMPACT) return afail(DCOMP_EINVAL, "%s: unknown obs_format %d", fn, r->obs_format);
-    if (r->obs_format == DCOMP_ACTOR_COMPACT && a->kind != DCOMP_MULTI)
-        return afail(DCOMP_EUNSUPPORTED, "%s: the compact record exists for multi-agent observations only", fn);
+        return fail(DCOMP_EABI, "%s: caller's dcomp_actor_run has %d bytes, the library's %d", fn, r->struct_size, (int)sizeof(dcomp_actor_run));
+    if (r->obs_format != DCOMP_ACTOR_ROWS && r->obs_format != DCOMP_ACTOR_COMPACT) return fail(DCOMP_EINVAL, "%s: unknown obs_format %d", fn, r->obs_format);
+    if (r->obs_format == DCOMP_ACTOR_COMPACT && !a->net.multi)
+        return fail(DCOMP_EUNSUPPORTED, "%s: the compact record exists for multi-agent observations only", fn);
     if (!vf_call) {
-        if (!obs || !action) return afail(DCOMP_EINVAL, "%s: obs and action must not be NULL", fn);
+        if (!obs || !action) return fail(DCOMP_EINVAL, "%s: obs and action must not be NULL", fn);
     } else {
-        if (!obs) return afail(DCOMP_EINVAL, "%s: obs must not be NULL", fn);
-        if (!vf) return afail(DCOMP_EINVAL, "%s: vf must not be NULL (dcomp_actor_actions is the call without a value)", fn);
-        if (!action && (r->logits || r->logp)) return afail(DCOMP_EINVAL, "%s: action == NULL is the value-only call: run.logits and run.logp must be NULL", fn);
-        if (!a->value) return afail(DCOMP_EINVAL, "%s: the handle has no value function (dcomp_actor_set_value)", fn);
+        if (!obs) return fail(DCOMP_EINVAL, "%s: obs must not be NULL", fn);
+        if (!vf) return fail(DCOMP_EINVAL, "%s: vf must not be NULL (dcomp_actor_actions is the call without a value)", fn);
+        if (!action && (r->logits || r->logp)) return fail(DCOMP_EINVAL, "%s: action == NULL is the value-only call: run.logits and run.logp must be NULL", fn);
+        if (!a->value) return fail(DCOMP_EINVAL, "%s: the handle has no value function (dcomp_actor_set_value)", fn);
     }
-    if (r->num_envs < 1) return afail(DCOMP_EINVAL, "%s: num_envs %d < 1", fn, r->num_envs);
-    if (r->num_active < 0 || r->num_active > a->U) return afail(DCOMP_EINVAL, "%s: num_active %d outside [0, %d]", fn, r->num_active, a->U);
-    const int64_t rows = a->kind == DCOMP_MULTI ? (int64_t)r->num_envs * a->U : (int64_t)r->num_envs;
+    if (r->num_envs < 1) return fail(DCOMP_EINVAL, "%s: num_envs %d < 1", fn, r->num_envs);
+    if (r->num_active < 0 || r->num_active > a->net.U) return fail(DCOMP_EINVAL, "%s: num_active %d outside [0, %d]", fn, r->num_active, a->net.U);
+    const int64_t rows = a->net.multi ? (int64_t)r->num_envs * a->net.U : (int64_t)r->num_envs;
     if (r->row_base < 0 || r->row_base + rows > 0x100000000ll)
-        return afail(DCOMP_EINVAL, "%s: decision rows %lld ... %lld do not fit the 32-bit draw counter word", fn, (long long)r->row_base,
+        return fail(DCOMP_EINVAL, "%s: decision rows %lld ... %lld do not fit the 32-bit draw counter word", fn, (long long)r->row_base,
                      (long long)(r->row_base + rows - 1));
     const int mode = vf_call ? a->value : 0;
     Params p;
     memset(&p, 0, sizeof(p));
     p.obs = obs; p.action = action; p.logits = r->logits; p.logp = r->logp; p.vf = vf;
-    p.w1 = a->w1; p.w2 = a->w2; p.w3 = a->w3; p.b1 = a->b1; p.b2 = a->b2; p.b3 = a->b3;
+    p.net = a->net;
     p.rows = rows; p.tiles = (rows + TILE - 1) / TILE; p.row_base = r->row_base;
-    p.K1 = a->K1; p.K1p = a->K1p; p.XS = a->XS; p.N3 = a->N3; p.NT3 = a->NT3; p.heads = a->heads; p.B = a->B; p.U = a->U;
-    p.num_active = r->num_active; p.multi = a->kind == DCOMP_MULTI; p.compact = r->obs_format == DCOMP_ACTOR_COMPACT; p.sample = r->sample != 0;
+    p.num_active = r->num_active; p.compact = r->obs_format == DCOMP_ACTOR_COMPACT; p.sample = r->sample != 0;
     p.step = r->step; p.seed_lo = (uint32_t)r->seed; p.seed_hi = (uint32_t)(r->seed >> 32);
-    p.lds_per_wave = a->lds_per_wave;
     p.policy = action != nullptr; p.vcol = -1;
-    if (mode == 1) {
-        p.vw1 = a->vw1; p.vw2 = a->vw2; p.vw3 = a->vw3; p.vb1 = a->vb1; p.vb2 = a->vb2; p.vb3 = a->vb3;
-    } else if (mode == 2) {
+    if (mode == 2) {
         const int first = p.policy ? 0 : a->NT3v - 1;        // value only: the one output tile that holds the value's column, no logits
-        p.w3 = a->vw3 + (size_t)first * 2 * a->mt * 64; p.b3 = a->vb3 + 32 * first;
-        p.NT3 = a->NT3v - first; p.vcol = a->N3 - 32 * first;
-        if (!p.policy) p.N3 = 0;
+        p.net.pi.w3 = a->net.vf.w3 + (size_t)first * 2 * a->mt * 64; p.net.pi.b3 = a->net.vf.b3 + 32 * first;
+        p.net.NT3 = a->NT3v - first; p.vcol = a->net.N3 - 32 * first;
+        if (!p.policy) p.net.N3 = 0;
     }
     const int64_t want = (p.tiles + WAVES - 1) / WAVES;
     const int grid = (int)(want < a->max_blocks ? want : a->max_blocks);
-    hipLaunchKernelGGL(pick(a->mt, a->relu != 0, mode), dim3(grid), dim3(BLOCK), (size_t)a->lds_per_wave * WAVES, static_cast<hipStream_t>(stream), p);
-    ACTOR_HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(pick(a->mt, a->relu != 0, mode), dim3(grid), dim3(BLOCK), (size_t)a->net.lds_per_wave * WAVES, static_cast<hipStream_t>(stream), p);
+    HIP_TRY(hipGetLastError());
     return DCOMP_OK;
 }
 
@@ -499,21 +427,22 @@ extern "C" int dcomp_actor_actions_v(dcomp_actor *a, const dcomp_actor_run *r, c
 extern "C" int dcomp_actor_set_value(dcomp_actor *a, const dcomp_actor_value_cfg *cfg)
 {
     using namespace dactor;
-    if (!a || !cfg) return afail(DCOMP_EINVAL, "dcomp_actor_set_value: handle and cfg must not be NULL");
+    if (!a || !cfg) return fail(DCOMP_EINVAL, "dcomp_actor_set_value: handle and cfg must not be NULL");
     if (cfg->struct_size != (int32_t)sizeof(dcomp_actor_value_cfg))
-        return afail(DCOMP_EABI, "dcomp_actor_set_value: caller's dcomp_actor_value_cfg has %d bytes, the library's %d", cfg->struct_size, (int)sizeof(dcomp_actor_value_cfg));
-    if (cfg->shared != 0 && cfg->shared != 1) return afail(DCOMP_EINVAL, "dcomp_actor_set_value: shared %d is neither 0 nor 1", cfg->shared);
-    if (!cfg->wv || !cfg->bv) return afail(DCOMP_EINVAL, "dcomp_actor_set_value: wv or bv is NULL");
+        return fail(DCOMP_EABI, "dcomp_actor_set_value: caller's dcomp_actor_value_cfg has %d bytes, the library's %d", cfg->struct_size, (int)sizeof(dcomp_actor_value_cfg));
+    if (cfg->shared != 0 && cfg->shared != 1) return fail(DCOMP_EINVAL, "dcomp_actor_set_value: shared %d is neither 0 nor 1", cfg->shared);
+    if (!cfg->wv || !cfg->bv) return fail(DCOMP_EINVAL, "dcomp_actor_set_value: wv or bv is NULL");
     const bool any = cfg->w1 || cfg->b1 || cfg->w2 || cfg->b2, all = cfg->w1 && cfg->b1 && cfg->w2 && cfg->b2;
-    if (cfg->shared && any) return afail(DCOMP_EINVAL, "dcomp_actor_set_value: shared = 1 takes value_out only: the trunk pointers w1 ... b2 must be NULL");
-    if (!cfg->shared && !all) return afail(DCOMP_EINVAL, "dcomp_actor_set_value: shared = 0 needs the value trunk: a pointer of w1 ... b2 is NULL");
-    if (a->value) return afail(DCOMP_EINVAL, "dcomp_actor_set_value: the handle has a value function already (once per handle)");
+    if (cfg->shared && any) return fail(DCOMP_EINVAL, "dcomp_actor_set_value: shared = 1 takes value_out only: the trunk pointers w1 ... b2 must be NULL");
+    if (!cfg->shared && !all) return fail(DCOMP_EINVAL, "dcomp_actor_set_value: shared = 0 needs the value trunk: a pointer of w1 ... b2 is NULL");
+    if (a->value) return fail(DCOMP_EINVAL, "dcomp_actor_set_value: the handle has a value function already (once per handle)");
 
     int dev = -1;
     hipError_t e = hipGetDevice(&dev);
-    if (e == hipSuccess && dev != a->device) return afail(DCOMP_EINVAL, "dcomp_actor_set_value: the handle lives on device %d, the calling thread's current device is %d", a->device, dev);
-    if (e != hipSuccess) return afail(DCOMP_EHIP, "dcomp_actor_set_value: %s", hipGetErrorString(e));
+    if (e == hipSuccess && dev != a->device) return fail(DCOMP_EINVAL, "dcomp_actor_set_value: the handle lives on device %d, the calling thread's current device is %d", a->device, dev);
+    if (e != hipSuccess) return fail(DCOMP_EHIP, "dcomp_actor_set_value: %s", hipGetErrorString(e));
 
+    const Net &n = a->net;
     const int H = a->hidden, Hp = 32 * a->mt, KS2 = 2 * a->mt;
     const size_t frag = (size_t)KS2 * 64 * 8;                // bf16 elements of one output tile of a hidden -> out layer
     std::vector<uint16_t> p1, p2, p3;
@@ -522,22 +451,16 @@ extern "C" int dcomp_actor_set_value(dcomp_actor *a, const dcomp_actor_value_cfg
     if (cfg->shared) {
         // the actor's packed W3 (read back from the handle's device memory) with one more column: output N3 = lane r = N3 % 32 of
         // tile N3 / 32 (a new tile when N3 % 32 == 0)
-        nt3v = a->N3 / 32 + 1;
+        nt3v = n.N3 / 32 + 1;
         p3.assign((size_t)nt3v * frag, 0);
         bias.assign((size_t)32 * nt3v, 0.f);
-        ACTOR_HIP_TRY(hipMemcpy(p3.data(), a->w3, (size_t)a->NT3 * frag * 2, hipMemcpyDeviceToHost));
-        ACTOR_HIP_TRY(hipMemcpy(bias.data(), a->b3, sizeof(float) * 32 * a->NT3, hipMemcpyDeviceToHost));
-        const int m = a->N3 / 32, rr = a->N3 % 32;
-        for (int ks = 0; ks < KS2; ks++)
-            for (int hh = 0; hh < 2; hh++)
-                for (int j = 0; j < 8; j++) {
-                    const int k = 16 * ks + 8 * (j >> 2) + 4 * hh + (j & 3);
-                    if (k < H) p3[(((size_t)m * KS2 + ks) * 64 + 32 * hh + rr) * 8 + j] = bf16_rne(cfg->wv[k]);
-                }
-        bias[a->N3] = cfg->bv[0];
+        HIP_TRY(hipMemcpy(p3.data(), n.pi.w3, (size_t)n.NT3 * frag * 2, hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(bias.data(), n.pi.b3, sizeof(float) * 32 * n.NT3, hipMemcpyDeviceToHost));
+        for (int k = 0; k < H; k++) p3[pack_index(k, n.N3, KS2, true)] = bf16_rne(cfg->wv[k]);
+        bias[n.N3] = cfg->bv[0];
     } else {
         nt3v = 1;
-        pack(p1, cfg->w1, a->K1, H, a->K1p / 16, a->mt, false);
+        pack(p1, cfg->w1, n.K1, H, n.K1p / 16, a->mt, false);
         pack(p2, cfg->w2, H, H, KS2, a->mt, true);
         pack(p3, cfg->wv, H, 1, KS2, 1, true);
         bias.assign((size_t)2 * Hp + 32, 0.f);
@@ -545,27 +468,12 @@ extern "C" int dcomp_actor_set_value(dcomp_actor *a, const dcomp_actor_value_cfg
         memcpy(bias.data() + Hp, cfg->b2, sizeof(float) * H);
         bias[2 * Hp] = cfg->bv[0];
     }
-    auto up = [](size_t v) { return (v + 255) & ~(size_t)255; };
-    const size_t o1 = 0, o2 = up(o1 + p1.size() * 2), o3 = up(o2 + p2.size() * 2), ob = up(o3 + p3.size() * 2), total = ob + bias.size() * 4;
-    std::vector<unsigned char> img(total, 0);
-    if (!p1.empty()) memcpy(img.data() + o1, p1.data(), p1.size() * 2);
-    if (!p2.empty()) memcpy(img.data() + o2, p2.data(), p2.size() * 2);
-    memcpy(img.data() + o3, p3.data(), p3.size() * 2);
-    memcpy(img.data() + ob, bias.data(), bias.size() * 4);
-
+    // shared: no hidden biases in the image, b3 at its start
     void *mem = nullptr;
-    e = hipMalloc(&mem, total);
-    if (e == hipSuccess) {
-        e = hipMemcpy(mem, img.data(), total, hipMemcpyHostToDevice);
-        if (e != hipSuccess) (void)hipFree(mem);
-    }
-    if (e != hipSuccess) return afail(DCOMP_EHIP, "dcomp_actor_set_value: %s", hipGetErrorString(e));
-    unsigned char *d = static_cast<unsigned char *>(mem);
+    e = upload_image(p1, p2, p3, bias, cfg->shared ? 0 : Hp, &mem, &a->net.vf);
+    if (e != hipSuccess) return fail(DCOMP_EHIP, "dcomp_actor_set_value: %s", hipGetErrorString(e));
     a->value_mem = mem;
-    a->vw1 = reinterpret_cast<const uint4 *>(d + o1); a->vw2 = reinterpret_cast<const uint4 *>(d + o2); a->vw3 = reinterpret_cast<const uint4 *>(d + o3);
-    const float *b = reinterpret_cast<const float *>(d + ob);
-    if (cfg->shared) { a->vb1 = a->vb2 = nullptr; a->vb3 = b; }
-    else { a->vb1 = b; a->vb2 = b + Hp; a->vb3 = b + 2 * Hp; }
+    if (cfg->shared) a->net.vf.b1 = a->net.vf.b2 = nullptr;
     a->NT3v = nt3v;
     a->value = cfg->shared ? 2 : 1;
     return DCOMP_OK;
@@ -574,20 +482,20 @@ extern "C" int dcomp_actor_set_value(dcomp_actor *a, const dcomp_actor_value_cfg
 extern "C" int dcomp_gae(const dcomp_gae_args *g, void *stream)
 {
     using namespace dactor;
-    if (!g) return afail(DCOMP_EINVAL, "dcomp_gae: args must not be NULL");
+    if (!g) return fail(DCOMP_EINVAL, "dcomp_gae: args must not be NULL");
     if (g->struct_size != (int32_t)sizeof(dcomp_gae_args))
-        return afail(DCOMP_EABI, "dcomp_gae: caller's dcomp_gae_args has %d bytes, the library's %d", g->struct_size, (int)sizeof(dcomp_gae_args));
-    if (!g->reward || !g->vf || !g->advantages || !g->value_targets) return afail(DCOMP_EINVAL, "dcomp_gae: reward, vf, advantages and value_targets must not be NULL");
-    if (g->num_steps < 1) return afail(DCOMP_EINVAL, "dcomp_gae: num_steps %d < 1", g->num_steps);
-    if (g->num_rows < 1) return afail(DCOMP_EINVAL, "dcomp_gae: num_rows %lld < 1", (long long)g->num_rows);
+        return fail(DCOMP_EABI, "dcomp_gae: caller's dcomp_gae_args has %d bytes, the library's %d", g->struct_size, (int)sizeof(dcomp_gae_args));
+    if (!g->reward || !g->vf || !g->advantages || !g->value_targets) return fail(DCOMP_EINVAL, "dcomp_gae: reward, vf, advantages and value_targets must not be NULL");
+    if (g->num_steps < 1) return fail(DCOMP_EINVAL, "dcomp_gae: num_steps %d < 1", g->num_steps);
+    if (g->num_rows < 1) return fail(DCOMP_EINVAL, "dcomp_gae: num_rows %lld < 1", (long long)g->num_rows);
     if (g->num_rows >= (1ll << 40) || (int64_t)g->num_steps * g->num_rows >= (1ll << 40))
-        return afail(DCOMP_EINVAL, "dcomp_gae: num_steps x num_rows = %d x %lld is 2^40 elements or more", g->num_steps, (long long)g->num_rows);
+        return fail(DCOMP_EINVAL, "dcomp_gae: num_steps x num_rows = %d x %lld is 2^40 elements or more", g->num_steps, (long long)g->num_rows);
     GaeParams k;
     k.reward = g->reward; k.vf = g->vf; k.last_vf = g->last_vf; k.end = g->end; k.adv = g->advantages; k.target = g->value_targets;
     k.R = g->num_rows; k.T = g->num_steps; k.gamma = g->gamma; k.lambda = g->lambda;
     const int64_t want = (g->num_rows + 255) / 256;
     const int grid = (int)(want < (1 << 20) ? want : (1 << 20));          // (beyond: the kernel strides over the columns)
     hipLaunchKernelGGL(gae_kernel, dim3(grid), dim3(256), 0, static_cast<hipStream_t>(stream), k);
-    ACTOR_HIP_TRY(hipGetLastError());
+    HIP_TRY(hipGetLastError());
     return DCOMP_OK;
 }

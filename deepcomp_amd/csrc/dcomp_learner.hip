@@ -3,9 +3,11 @@
 // Four kernels per minibatch, all deterministic (no floating-point atomics; every sum has an order fixed by the row count):
 //   learner_kernel   forward + loss + backward-data.  The shape of actor_kernel: a wavefront owns 32 decision rows on its lanes and
 //                    runs layers 1-3 transposed on v_mfma_f32_32x32x16_bf16, the logits pass through the [32][33] LDS tile and lane r
-//                    walks row r's columns -- with the GIVEN action, and the same online log-sum-exp in the same order, so at unchanged
-//                    weights logp is what the actor wrote, bit for bit.  A second walk over the recomputed logits writes dlogits back
-//                    into the tile.  Backward stays transposed: dH2^T = W3 dlogits^T, dH1^T = W2 dA2^T with the weights as the A
+//                    walks row r's columns -- with the GIVEN action.  Layer 1, the hidden fragments, the logit tile and the online
+//                    log-sum-exp step are the actor's own functions (dcomp_actor_impl.h), so at unchanged weights logp is what the
+//                    actor wrote, bit for bit; the weights of layers 2 and 3 stream group by group here (tile_dot), not through the
+//                    actor's ring: one wave per SIMD has the registers for whole groups.  A second walk over the recomputed logits
+//                    writes dlogits back into the tile.  Backward stays transposed: dH2^T = W3 dlogits^T, dH1^T = W2 dA2^T with the weights as the A
 //                    operand in the OTHER orientation (a second packed copy, w2b / w3b); the accumulator has the hidden unit in its
 //                    register and the row on its lane exactly like the h fragments, so (.) act'(h) and the bf16 conversion stay in
 //                    registers.  The value trunk is a second sweep.  x, h1, h2, dA1, dA2, dlogits go to HBM as bf16 [width][rows]
@@ -16,24 +18,21 @@
 //   reduce_kernel    sums the chunk partials in chunk order, applies 1 / N once, writes the natural [in][out] gradients; and the
 //                    five statistics from the per-tile sums.
 //   adam_kernel      adam_reference (deepcomp_amd/learner.py) under `#pragma clang fp contract(off)`, then each thread scatters
-//                    its weight as bf16 into the actor handle's packed fragments, in both orientations: the device form of pack().
+//                    its weight as bf16 into the actor handle's packed fragments, in both orientations, where pack_index() (the
+//                    function pack() places its elements with) says.
 // Padded hidden units: the packed copies hold zeros there, forward (h = act(0) = 0) and backward (a zero row of w3b / w2b gives
 // dH = 0), no kernel ever writes a padded entry, and reduce / adam only visit real entries.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
-#include <cstdarg>
 #include <cstdint>
-#include <cstdio>
 #include <cstring>
 #include <vector>
 
 #define DCOMP_BUILDING_LIBRARY 1
 #include "../../include/dcomp.h"
 #include "../../include/dcomp_learner.h"
-#include "dcomp_actor_impl.h"
-
-namespace dcomp { int report(int code, const char *msg); }       // dcomp_api.hip: the thread's dcomp_last_error() text
+#include "dcomp_actor_impl.h"       // the forward-pass helpers, the fragment layout, Net and struct dcomp_actor, fail / HIP_TRY: shared with dcomp_actor.hip
 
 namespace dlearn {
 
@@ -49,14 +48,13 @@ struct LParams {
     const float *old_logp, *old_logits, *adv, *vtarg, *old_vf;
     float *o_logp, *o_ent, *o_kl, *o_vf, *o_ratio;
     const float *up_dlogits, *up_dvalue;
-    const uint4 *w1, *w2, *w3, *vw1, *vw2, *vw3;      // the actor handle's forward fragments
-    const float *b1, *b2, *b3, *vb1, *vb2, *vb3;
+    Net net;                                          // the actor handle's: its forward fragments are the learner's
     const uint4 *w2b, *w3b, *vw2b, *vw3b;             // the backward orientation
     __bf16 *X, *H1, *H2, *D1, *D2, *D3, *VH1, *VH2, *VD1, *VD2, *VD3;    // [width][ld]
     float4 *headws;                                   // [rows][heads]: lse, old lse, entropy of the head
     float4 *part;                                     // [tiles]: sums of surrogate, kl, entropy, vf loss over the tile's counted rows
     int64_t rows, tiles, ld;
-    int32_t K1, K1p, XS, N3, NT3, heads, B, U, num_active, multi, lds_per_wave, fwd_only, upstream;
+    int32_t num_active, fwd_only, upstream;
     float clip, vf_clip, vf_coeff, ent_coeff, kl_coeff;
 };
 
@@ -111,16 +109,6 @@ template <int MT, bool RELU> __device__ __forceinline__ void delta_frags(const f
             }
 }
 
-// one step of actor_kernel's online log-sum-exp (its expression, term for term): the sum rescaled to the new maximum; e1, e2 are
-// the two exponentials, for the sums that ride along
-__device__ __forceinline__ void lse_push(float x, float &mx, float &sm, float &e1, float &e2)
-{
-    const float m2 = fmaxf(mx, x);
-    e1 = expf(mx - m2); e2 = expf(x - m2);
-    sm = sm * e1 + e2;
-    mx = m2;
-}
-
 __device__ __forceinline__ float wave_sum(float v)       // a fixed tree over the 64 lanes
 {
 #pragma unroll
@@ -134,12 +122,12 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(1, 1))) v
     extern __shared__ uint4 lds4[];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, r = lane & 31, h = lane >> 5;
     const uint32_t lane16 = (uint32_t)lane * 16u;
-    unsigned char *base = reinterpret_cast<unsigned char *>(lds4) + (size_t)wave * p.lds_per_wave;
+    const Net &n = p.net;
+    unsigned char *base = reinterpret_cast<unsigned char *>(lds4) + (size_t)wave * n.lds_per_wave;
     __bf16 *xs = reinterpret_cast<__bf16 *>(base);                                   // [32][XS] bf16: the chunk of the tile's rows
-    float *lt = reinterpret_cast<float *>(base + (size_t)TILE * p.XS * 2);           // [32][LT] f32: 32 logits / dlogits of every row
+    float *lt = reinterpret_cast<float *>(base + (size_t)TILE * n.XS * 2);           // [32][LT] f32: 32 logits / dlogits of every row
     uint32_t *ri = reinterpret_cast<uint32_t *>(lt + TILE * LT);                     // [32]: the row is read and counted
-    const int XS = p.XS, K1 = p.K1, U = p.U, NA = p.B + 1;
-    const int KS1 = p.K1p >> 4;
+    const int XS = n.XS, K1 = n.K1, U = n.U, NA = n.B + 1;
     constexpr int KS2 = 2 * MT;
     const int64_t ld = p.ld;
 
@@ -149,7 +137,7 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(1, 1))) v
         const int64_t myrow = row0 + r;                                              // the decision row on this lane
         const bool have = r < nrow;
         // a row beyond the batch, or a multi-agent row of an unlisted slot: computed on zeros, every delta zero, nothing of it read
-        const bool live = have && !(p.multi && (int)(myrow % U) >= p.num_active);
+        const bool live = have && !(n.multi && (int)(myrow % U) >= p.num_active);
         const bool walker = lane < TILE && live;
         const uint32_t voff = (uint32_t)(2 * ((uint64_t)myrow + (uint64_t)(4 * h) * (uint64_t)ld));      // store_frags: this lane's column
         if (lane < TILE) ri[lane] = live ? 1u : 0u;
@@ -160,71 +148,36 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(1, 1))) v
 #pragma nounroll
         for (int sweep = 0; sweep < 2; sweep++) {
         const bool val = sweep != 0;
-        const uint4 *w1 = val ? p.vw1 : p.w1, *w2 = val ? p.vw2 : p.w2, *w3 = val ? p.vw3 : p.w3;
+        const Trunk t = select_trunk(n, val);
         const uint4 *w2b = val ? p.vw2b : p.w2b, *w3b = val ? p.vw3b : p.w3b;
-        const float *b1 = val ? p.vb1 : p.b1, *b2 = val ? p.vb2 : p.b2, *b3 = val ? p.vb3 : p.b3;
         __bf16 *H1 = val ? p.VH1 : p.H1, *H2 = val ? p.VH2 : p.H2, *D1 = val ? p.VD1 : p.D1, *D2 = val ? p.VD2 : p.D2, *D3 = val ? p.VD3 : p.D3;
-        const int NT3 = val ? 1 : p.NT3, N3 = val ? 1 : p.N3;
-        const bool staged = val && p.K1p <= KC;                                      // the policy sweep left the bf16 rows in LDS
+        const int NT3 = val ? 1 : n.NT3, N3 = val ? 1 : n.N3;
+        const bool staged = val && n.K1p <= KC;                                      // the policy sweep left the bf16 rows in LDS
 
-        // ---- layer 1: acc[m] = W1^T (units 32m ...) x X^T, the inputs in chunks through LDS (as actor_kernel)
+        // ---- layer 1, with x as bf16 [input][rows] on the way for dW1 of both trunks
         f32x16 acc[MT];
-#pragma unroll
-        for (int m = 0; m < MT; m++)
-#pragma unroll
-            for (int i = 0; i < 16; i++) acc[m][i] = 0.f;
-        uint4 wq1[MT];
-#pragma unroll
-        for (int m = 0; m < MT; m++) wq1[m] = load_frag(w1, (size_t)m * KS1, lane16);
-        for (int k0 = 0; k0 < p.K1p; k0 += KC) {
-            const int kc = p.K1p - k0 < KC ? p.K1p - k0 : KC;                        // a multiple of 16
-            const uint32_t magic = (uint32_t)(0x100000000ull / (uint32_t)kc) + 1u;   // f / kc = umulhi(f, magic): f < 2^14, f kc < 2^32
-            const int nf = staged ? 0 : TILE * kc;
-#pragma unroll 4
-            for (int f = lane; f < nf; f += 64) {
-                const int rr = (int)__umulhi((uint32_t)f, magic), c = f - rr * kc, k = k0 + c;
-                float v = 0.f;
-                if (ri[rr] && k < K1) v = p.obs[(size_t)(row0 + rr) * K1 + k];
-                xs[rr * XS + c] = (__bf16)v;
-            }
-            wave_fence();
-            if (!val && !p.fwd_only) {                                               // x as bf16 [input][rows] for dW1 of both trunks
-                for (int i = lane; i < kc * TILE; i += 64) {
-                    const int c = i >> 5, rr = i & 31;
-                    p.X[(size_t)(k0 + c) * (size_t)ld + (size_t)(row0 + rr)] = xs[rr * XS + c];
-                }
-            }
-            for (int s = 0; s < (kc >> 4); s++) {
-                const bf16x8 b = as_frag(*reinterpret_cast<const uint4 *>(xs + r * XS + 16 * s + 8 * h));
-                const int ksn = (k0 >> 4) + s + 1 < KS1 ? (k0 >> 4) + s + 1 : KS1 - 1;          // (the last step re-reads itself)
-                uint4 nx[MT];
-#pragma unroll
-                for (int m = 0; m < MT; m++) nx[m] = load_frag(w1, (size_t)m * KS1 + ksn, lane16);
-#pragma unroll
-                for (int m = 0; m < MT; m++) acc[m] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(as_frag(wq1[m]), b, acc[m], 0, 0, 0);
-#pragma unroll
-                for (int m = 0; m < MT; m++) wq1[m] = nx[m];
-            }
-            wave_fence();
-        }
+        layer1<MT>(acc, t.w1, n.K1p, xs, XS, lane, lane16, staged,
+                   [&](int rr, int k) { return ri[rr] && k < K1 ? p.obs[(size_t)(row0 + rr) * K1 + k] : 0.f; },
+                   [&](int k0, int kc) {
+                       if (!val && !p.fwd_only) {
+                           for (int i = lane; i < kc * TILE; i += 64) {
+                               const int c = i >> 5, rr = i & 31;
+                               p.X[(size_t)(k0 + c) * (size_t)ld + (size_t)(row0 + rr)] = xs[rr * XS + c];
+                           }
+                       }
+                   });
 
         bf16x8 h1[MT][2];
-#pragma unroll
-        for (int t = 0; t < MT; t++) {
-            h1[t][0] = next_fragment<RELU>(acc[t], 0, b1 + 32 * t + 4 * h);
-            h1[t][1] = next_fragment<RELU>(acc[t], 1, b1 + 32 * t + 4 * h);
-            asm volatile("" : "+v"(h1[t][0]), "+v"(h1[t][1]));
-            __builtin_amdgcn_sched_barrier(0);
-        }
+        hidden_fragments<MT, RELU>(acc, t.b1, h, h1);
         if (!p.fwd_only) store_frags<MT>(H1, ld, voff, h1);
 
         // ---- layer 2
         bf16x8 h2[MT][2];
 #pragma unroll
         for (int m = 0; m < MT; m++) {
-            const f32x16 a2 = tile_dot<MT>(w2, (size_t)m * KS2, h1, lane16);
-            h2[m][0] = next_fragment<RELU>(a2, 0, b2 + 32 * m + 4 * h);
-            h2[m][1] = next_fragment<RELU>(a2, 1, b2 + 32 * m + 4 * h);
+            const f32x16 a2 = tile_dot<MT>(t.w2, (size_t)m * KS2, h1, lane16);
+            h2[m][0] = next_fragment<RELU>(a2, 0, t.b2 + 32 * m + 4 * h);
+            h2[m][1] = next_fragment<RELU>(a2, 1, t.b2 + 32 * m + 4 * h);
             asm volatile("" : "+v"(h2[m][0]), "+v"(h2[m][1]));
             __builtin_amdgcn_sched_barrier(0);
         }
@@ -236,30 +189,23 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(1, 1))) v
             int hd = 0, a = 0, act = 0;
             float xa = 0.f, mx = -INFINITY, sm = 0.f, tn = 0.f, mo = -INFINITY, so = 0.f;
             for (int nt = 0; nt < NT3; nt++) {
-                const f32x16 a3 = tile_dot<MT>(w3, (size_t)nt * KS2, h2, lane16);
-                const float *bias = b3 + 32 * nt + 4 * h;
-#pragma unroll
-                for (int g = 0; g < 4; g++) {
-                    const float4 bv = *reinterpret_cast<const float4 *>(bias + 8 * g);
-                    float *d = lt + r * LT + 8 * g + 4 * h;
-                    d[0] = a3[4 * g + 0] + bv.x; d[1] = a3[4 * g + 1] + bv.y; d[2] = a3[4 * g + 2] + bv.z; d[3] = a3[4 * g + 3] + bv.w;
-                }
+                put_logit_tile(tile_dot<MT>(t.w3, (size_t)nt * KS2, h2, lane16), t.b3, nt, lt, r, h);
                 wave_fence();
                 if (!val && walker && p.actions) {
                     const int ncol = N3 - 32 * nt < 32 ? N3 - 32 * nt : 32;
                     for (int c = 0; c < ncol; c++) {
                         const float x = lt[r * LT + c];
-                        if (a == 0) act = p.actions[(size_t)myrow * p.heads + hd];
+                        if (a == 0) act = p.actions[(size_t)myrow * n.heads + hd];
                         if (a == act) xa = x;
                         float e1, e2;
                         lse_push(x, mx, sm, e1, e2);
                         tn = tn * e1 + x * e2;
-                        if (p.old_logits) lse_push(p.old_logits[(size_t)myrow * p.N3 + 32 * nt + c], mo, so, e1, e2);
+                        if (p.old_logits) lse_push(p.old_logits[(size_t)myrow * n.N3 + 32 * nt + c], mo, so, e1, e2);
                         if (++a == NA) {
-                            const size_t at = (size_t)myrow * p.heads + hd;
+                            const size_t at = (size_t)myrow * n.heads + hd;
                             const float lse = mx + logf(sm), lp = xa - lse, eh = lse - tn / sm;
                             if (p.o_logp) p.o_logp[at] = lp;
-                            if (p.multi || hd < p.num_active) {
+                            if (n.multi || hd < p.num_active) {
                                 logp_sum += lp; ent_sum += eh;
                                 if (p.old_logp) oldlp_sum += p.old_logp[at];
                             }
@@ -319,17 +265,10 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(1, 1))) v
                 } else if (p.upstream) {
                     for (int i = lane; i < TILE * 32; i += 64) {
                         const int rr = i >> 5, c = i & 31;
-                        lt[rr * LT + c] = ri[rr] && c < ncol ? p.up_dlogits[(size_t)(row0 + rr) * p.N3 + 32 * nt + c] : 0.f;
+                        lt[rr * LT + c] = ri[rr] && c < ncol ? p.up_dlogits[(size_t)(row0 + rr) * n.N3 + 32 * nt + c] : 0.f;
                     }
                 } else {
-                    const f32x16 a3 = tile_dot<MT>(w3, (size_t)nt * KS2, h2, lane16);
-                    const float *bias = b3 + 32 * nt + 4 * h;
-#pragma unroll
-                    for (int g = 0; g < 4; g++) {
-                        const float4 bv = *reinterpret_cast<const float4 *>(bias + 8 * g);
-                        float *d = lt + r * LT + 8 * g + 4 * h;
-                        d[0] = a3[4 * g + 0] + bv.x; d[1] = a3[4 * g + 1] + bv.y; d[2] = a3[4 * g + 2] + bv.z; d[3] = a3[4 * g + 3] + bv.w;
-                    }
+                    put_logit_tile(tile_dot<MT>(t.w3, (size_t)nt * KS2, h2, lane16), t.b3, nt, lt, r, h);
                     wave_fence();
                     if (lane < TILE) {
                         if (!walker) {
@@ -338,13 +277,13 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(1, 1))) v
                             for (int c = 0; c < ncol; c++) {
                                 const float x = lt[r * LT + c];
                                 if (a == 0) {
-                                    hw = p.headws[(size_t)myrow * p.heads + hd];
-                                    act = p.actions[(size_t)myrow * p.heads + hd];
+                                    hw = p.headws[(size_t)myrow * n.heads + hd];
+                                    act = p.actions[(size_t)myrow * n.heads + hd];
                                 }
                                 float dl = 0.f;
-                                if (p.multi || hd < p.num_active) {
+                                if (n.multi || hd < p.num_active) {
                                     const float lpn = x - hw.x, pn = expf(lpn);
-                                    const float lpo = p.old_logits[(size_t)myrow * p.N3 + 32 * nt + c] - hw.y, po = expf(lpo);
+                                    const float lpo = p.old_logits[(size_t)myrow * n.N3 + 32 * nt + c] - hw.y, po = expf(lpo);
                                     kl_sum += po * (lpo - lpn);
                                     dl = c_lp * ((a == act ? 1.f : 0.f) - pn) + p.kl_coeff * (pn - po) + p.ent_coeff * (pn * (lpn + hw.z));
                                 }
@@ -414,12 +353,7 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(1, 1))) v
 typedef void (*learner_fn)(const LParams);
 static learner_fn pick(int mt, bool relu)
 {
-    switch (mt) {
-    case 1: return relu ? learner_kernel<1, true> : learner_kernel<1, false>;
-    case 2: return relu ? learner_kernel<2, true> : learner_kernel<2, false>;
-    case 4: return relu ? learner_kernel<4, true> : learner_kernel<4, false>;
-    default: return relu ? learner_kernel<8, true> : learner_kernel<8, false>;
-    }
+    return pick_shape(mt, relu, [](auto s) -> learner_fn { return learner_kernel<decltype(s)::MT, decltype(s)::RELU>; });
 }
 
 // ---------------------------------------------------------------- weight gradients
@@ -592,21 +526,6 @@ __global__ __launch_bounds__(256) void reduce_kernel(const AParams p)
     }
 }
 
-__device__ __forceinline__ uint16_t bf16_rne_dev(float f)                             // dactor::bf16_rne, on the device
-{
-    const uint32_t u = __float_as_uint(f);
-    if ((u & 0x7FFFFFFFu) > 0x7F800000u) return (uint16_t)((u >> 16) | 0x40u);
-    return (uint16_t)((u + 0x7FFFu + ((u >> 16) & 1u)) >> 16);
-}
-
-// where pack() puts input k, output o
-__device__ __forceinline__ size_t pack_index(int k, int o, int ksteps, int permuted)
-{
-    const int m = o >> 5, r = o & 31, ks = k >> 4, kk = k & 15;
-    const int h = permuted ? (kk & 7) >> 2 : kk >> 3, j = permuted ? 4 * (kk >> 3) + (kk & 3) : kk & 7;
-    return (((size_t)m * ksteps + ks) * 64 + 32 * h + r) * 8 + j;
-}
-
 __global__ __launch_bounds__(256) void adam_kernel(const AParams p)
 {
 #pragma clang fp contract(off)
@@ -629,7 +548,7 @@ __global__ __launch_bounds__(256) void adam_kernel(const AParams p)
         return;
     }
     const int k = idx / d.nout, o = idx - k * d.nout;
-    const uint16_t q = bf16_rne_dev(w);
+    const uint16_t q = bf16_rne(w);
     d.fwd[pack_index(k, o, d.fwd_ks, d.fwd_perm)] = q;
     if (d.bwd) d.bwd[pack_index(o, k, d.bwd_ks, d.bwd_perm)] = q;                     // the other orientation: W^T
 }
@@ -649,22 +568,6 @@ struct dcomp_learner {
     int32_t off[dlearn::NARR], len[dlearn::NARR];
 };
 
-static int lfail(int code, const char *fmt, ...) __attribute__((format(printf, 2, 3)));
-static int lfail(int code, const char *fmt, ...)
-{
-    char buf[512];
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(buf, sizeof(buf), fmt, ap);
-    va_end(ap);
-    return dcomp::report(code, buf);
-}
-#define LEARNER_HIP_TRY(expr)                                                                        \
-    do {                                                                                             \
-        hipError_t e_ = (expr);                                                                      \
-        if (e_ != hipSuccess) return lfail(DCOMP_EHIP, "%s failed: %s", #expr, hipGetErrorString(e_)); \
-    } while (0)
-
 static const char *const ARRAY_NAMES[dlearn::NARR] = {"w1", "b1", "w2", "b2", "w3", "b3", "vw1", "vb1", "vw2", "vb2", "wv", "bv"};
 
 static void members(const dcomp_learner_arrays *s, float *(&out)[dlearn::NARR])
@@ -676,14 +579,14 @@ static void members(const dcomp_learner_arrays *s, float *(&out)[dlearn::NARR])
 // struct size and, with `all`, every member non-NULL
 static int check_arrays(const char *fn, const char *what, const dcomp_learner_arrays *s, bool all)
 {
-    if (!s) return lfail(DCOMP_EINVAL, "%s: %s must not be NULL", fn, what);
+    if (!s) return fail(DCOMP_EINVAL, "%s: %s must not be NULL", fn, what);
     if (s->struct_size != (int32_t)sizeof(dcomp_learner_arrays))
-        return lfail(DCOMP_EABI, "%s: caller's dcomp_learner_arrays has %d bytes, the library's %d", fn, s->struct_size, (int)sizeof(dcomp_learner_arrays));
+        return fail(DCOMP_EABI, "%s: caller's dcomp_learner_arrays has %d bytes, the library's %d", fn, s->struct_size, (int)sizeof(dcomp_learner_arrays));
     if (all) {
         float *m[dlearn::NARR];
         members(s, m);
         for (int i = 0; i < dlearn::NARR; i++)
-            if (!m[i]) return lfail(DCOMP_EINVAL, "%s: %s.%s is NULL", fn, what, ARRAY_NAMES[i]);
+            if (!m[i]) return fail(DCOMP_EINVAL, "%s: %s.%s is NULL", fn, what, ARRAY_NAMES[i]);
     }
     return DCOMP_OK;
 }
@@ -707,20 +610,21 @@ extern "C" int dcomp_learner_create(dcomp_actor *a, const dcomp_learner_cfg *cfg
     using namespace dlearn;
     const char *fn = "dcomp_learner_create";
     if (out) *out = nullptr;
-    if (!a || !cfg || !out) return lfail(DCOMP_EINVAL, "%s: actor, cfg and out must not be NULL", fn);
+    if (!a || !cfg || !out) return fail(DCOMP_EINVAL, "%s: actor, cfg and out must not be NULL", fn);
     if (cfg->struct_size != (int32_t)sizeof(dcomp_learner_cfg))
-        return lfail(DCOMP_EABI, "%s: caller's dcomp_learner_cfg has %d bytes, the library's %d", fn, cfg->struct_size, (int)sizeof(dcomp_learner_cfg));
-    if (cfg->value_shared == 1) return lfail(DCOMP_EUNSUPPORTED, "%s: the shared value function (vf_share_layers=True) is not supported: the learner needs a value trunk of its own", fn);
-    if (cfg->value_shared != 0) return lfail(DCOMP_EINVAL, "%s: value_shared %d is neither 0 nor 1", fn, cfg->value_shared);
-    if (cfg->max_rows < 1 || cfg->max_rows > (1ll << 28)) return lfail(DCOMP_EINVAL, "%s: max_rows %lld outside [1, 2^28]", fn, (long long)cfg->max_rows);
-    if (!(cfg->beta1 >= 0.f && cfg->beta1 < 1.f) || !(cfg->beta2 >= 0.f && cfg->beta2 < 1.f)) return lfail(DCOMP_EINVAL, "%s: beta1 %g / beta2 %g outside [0, 1)", fn, cfg->beta1, cfg->beta2);
-    if (!(cfg->eps > 0.f)) return lfail(DCOMP_EINVAL, "%s: eps %g must be > 0", fn, cfg->eps);
+        return fail(DCOMP_EABI, "%s: caller's dcomp_learner_cfg has %d bytes, the library's %d", fn, cfg->struct_size, (int)sizeof(dcomp_learner_cfg));
+    if (cfg->value_shared == 1) return fail(DCOMP_EUNSUPPORTED, "%s: the shared value function (vf_share_layers=True) is not supported: the learner needs a value trunk of its own", fn);
+    if (cfg->value_shared != 0) return fail(DCOMP_EINVAL, "%s: value_shared %d is neither 0 nor 1", fn, cfg->value_shared);
+    if (cfg->max_rows < 1 || cfg->max_rows > (1ll << 28)) return fail(DCOMP_EINVAL, "%s: max_rows %lld outside [1, 2^28]", fn, (long long)cfg->max_rows);
+    if (!(cfg->beta1 >= 0.f && cfg->beta1 < 1.f) || !(cfg->beta2 >= 0.f && cfg->beta2 < 1.f)) return fail(DCOMP_EINVAL, "%s: beta1 %g / beta2 %g outside [0, 1)", fn, cfg->beta1, cfg->beta2);
+    if (!(cfg->eps > 0.f)) return fail(DCOMP_EINVAL, "%s: eps %g must be > 0", fn, cfg->eps);
     if (int rc = check_arrays(fn, "cfg.weights", cfg->weights, true)) return rc;
     // the handle, from here on
-    if (a->value == 2) return lfail(DCOMP_EUNSUPPORTED, "%s: the actor's value function is shared (vf_share_layers=True): the learner needs a value trunk of its own", fn);
-    if (a->value != 1) return lfail(DCOMP_EINVAL, "%s: the actor has no value trunk (dcomp_actor_set_value with shared = 0)", fn);
+    if (a->value == 2) return fail(DCOMP_EUNSUPPORTED, "%s: the actor's value function is shared (vf_share_layers=True): the learner needs a value trunk of its own", fn);
+    if (a->value != 1) return fail(DCOMP_EINVAL, "%s: the actor has no value trunk (dcomp_actor_set_value with shared = 0)", fn);
 
-    const int H = a->hidden, Hp = 32 * a->mt, KS2 = 2 * a->mt, K1 = a->K1, N3 = a->N3, NT3 = a->NT3;
+    const Net &n = a->net;
+    const int H = a->hidden, Hp = 32 * a->mt, KS2 = 2 * a->mt, K1 = n.K1, N3 = n.N3, NT3 = n.NT3;
     const int K1pp = (K1 + 31) & ~31, N3p = 32 * NT3;
     dcomp_learner *l = new dcomp_learner();
     memset(l, 0, sizeof(*l));
@@ -747,7 +651,7 @@ extern "C" int dcomp_learner_create(dcomp_actor *a, const dcomp_learner_cfg *cfg
     size_t o_H[8];
     for (int i = 0; i < 8; i++) o_H[i] = take((size_t)Hp * ld * 2);
     const size_t o_D3 = take((size_t)N3p * ld * 2), o_VD3 = take((size_t)32 * ld * 2);
-    const size_t o_head = take((size_t)cfg->max_rows * a->heads * 16), o_tpart = take((ld / 32) * 16);      // (ld / 32 >= the tiles of max_rows)
+    const size_t o_head = take((size_t)cfg->max_rows * n.heads * 16), o_tpart = take((ld / 32) * 16);      // (ld / 32 >= the tiles of max_rows)
     const int in_p[6] = {K1pp, Hp, Hp, K1pp, Hp, Hp}, out_p[6] = {Hp, Hp, N3p, Hp, Hp, 32};
     size_t o_part[6], o_bpart[6];
     for (int i = 0; i < 6; i++) { o_part[i] = take((size_t)MAX_CHUNKS * in_p[i] * out_p[i] * 4); o_bpart[i] = take((size_t)MAX_CHUNKS * out_p[i] * 4); }
@@ -757,7 +661,7 @@ extern "C" int dcomp_learner_create(dcomp_actor *a, const dcomp_learner_cfg *cfg
     if (e == hipSuccess && l->device != a->device) {
         const int dev = l->device;
         delete l;
-        return lfail(DCOMP_EINVAL, "%s: the actor lives on device %d, the calling thread's current device is %d", fn, a->device, dev);
+        return fail(DCOMP_EINVAL, "%s: the actor lives on device %d, the calling thread's current device is %d", fn, a->device, dev);
     }
     if (e == hipSuccess) e = hipMalloc(&l->mem, bytes);
     unsigned char *d = static_cast<unsigned char *>(l->mem);
@@ -770,20 +674,18 @@ extern "C" int dcomp_learner_create(dcomp_actor *a, const dcomp_learner_cfg *cfg
     if (e != hipSuccess) {
         if (l->mem) (void)hipFree(l->mem);
         delete l;
-        return lfail(DCOMP_EHIP, "%s: %s (%zu bytes of device memory for max_rows %lld)", fn, hipGetErrorString(e), bytes, (long long)cfg->max_rows);
+        return fail(DCOMP_EHIP, "%s: %s (%zu bytes of device memory for max_rows %lld)", fn, hipGetErrorString(e), bytes, (long long)cfg->max_rows);
     }
 
     LParams &p = l->lp;
-    p.w1 = a->w1; p.w2 = a->w2; p.w3 = a->w3; p.vw1 = a->vw1; p.vw2 = a->vw2; p.vw3 = a->vw3;
-    p.b1 = a->b1; p.b2 = a->b2; p.b3 = a->b3; p.vb1 = a->vb1; p.vb2 = a->vb2; p.vb3 = a->vb3;
+    p.net = n;
     p.w2b = reinterpret_cast<const uint4 *>(d + o_w2b); p.w3b = reinterpret_cast<const uint4 *>(d + o_w3b);
     p.vw2b = reinterpret_cast<const uint4 *>(d + o_vw2b); p.vw3b = reinterpret_cast<const uint4 *>(d + o_vw3b);
     auto bf = [&](size_t o) { return reinterpret_cast<__bf16 *>(d + o); };
     p.X = bf(o_X); p.H1 = bf(o_H[0]); p.H2 = bf(o_H[1]); p.D1 = bf(o_H[2]); p.D2 = bf(o_H[3]);
     p.VH1 = bf(o_H[4]); p.VH2 = bf(o_H[5]); p.VD1 = bf(o_H[6]); p.VD2 = bf(o_H[7]); p.D3 = bf(o_D3); p.VD3 = bf(o_VD3);
     p.headws = reinterpret_cast<float4 *>(d + o_head); p.part = reinterpret_cast<float4 *>(d + o_tpart);
-    p.ld = l->ld; p.K1 = K1; p.K1p = a->K1p; p.XS = a->XS; p.N3 = N3; p.NT3 = NT3; p.heads = a->heads; p.B = a->B; p.U = a->U;
-    p.multi = a->kind == DCOMP_MULTI; p.lds_per_wave = a->lds_per_wave;
+    p.ld = l->ld;
 
     WParams &w = l->wp;
     const __bf16 *wa[6] = {p.X, p.H1, p.H2, p.X, p.VH1, p.VH2}, *wd[6] = {p.D1, p.D2, p.D3, p.VD1, p.VD2, p.VD3};
@@ -807,14 +709,15 @@ extern "C" int dcomp_learner_create(dcomp_actor *a, const dcomp_learner_cfg *cfg
         x.off = l->off[i]; x.nin = nin[i]; x.nout = nout[i]; x.in_p = in_p[layer]; x.out_p = out_p[layer]; x.is_bias = i & 1;
         x.part = (i & 1) ? w.g[layer].bpart : w.g[layer].part;
     }
-    ap.a[0].fwd = u16(a->w1); ap.a[0].fwd_ks = a->K1p / 16; ap.a[0].fwd_perm = 0;
-    ap.a[2].fwd = u16(a->w2); ap.a[2].fwd_ks = KS2; ap.a[2].fwd_perm = 1; ap.a[2].bwd = u16(p.w2b); ap.a[2].bwd_ks = KS2; ap.a[2].bwd_perm = 1;
-    ap.a[4].fwd = u16(a->w3); ap.a[4].fwd_ks = KS2; ap.a[4].fwd_perm = 1; ap.a[4].bwd = u16(p.w3b); ap.a[4].bwd_ks = 2 * NT3; ap.a[4].bwd_perm = 0;
-    ap.a[6].fwd = u16(a->vw1); ap.a[6].fwd_ks = a->K1p / 16; ap.a[6].fwd_perm = 0;
-    ap.a[8].fwd = u16(a->vw2); ap.a[8].fwd_ks = KS2; ap.a[8].fwd_perm = 1; ap.a[8].bwd = u16(p.vw2b); ap.a[8].bwd_ks = KS2; ap.a[8].bwd_perm = 1;
-    ap.a[10].fwd = u16(a->vw3); ap.a[10].fwd_ks = KS2; ap.a[10].fwd_perm = 1; ap.a[10].bwd = u16(p.vw3b); ap.a[10].bwd_ks = 2; ap.a[10].bwd_perm = 0;
-    ap.a[1].bias = f32(a->b1); ap.a[3].bias = f32(a->b2); ap.a[5].bias = f32(a->b3);
-    ap.a[7].bias = f32(a->vb1); ap.a[9].bias = f32(a->vb2); ap.a[11].bias = f32(a->vb3);
+    const Trunk *trunk[2] = {&n.pi, &n.vf};
+    const uint4 *w2b[2] = {p.w2b, p.vw2b}, *w3b[2] = {p.w3b, p.vw3b};
+    for (int t = 0; t < 2; t++) {
+        ADesc *x = ap.a + 6 * t;                                                     // w1 b1 w2 b2 w3 b3 of the trunk
+        x[0].fwd = u16(trunk[t]->w1); x[0].fwd_ks = n.K1p / 16; x[0].fwd_perm = 0;
+        x[2].fwd = u16(trunk[t]->w2); x[2].fwd_ks = KS2; x[2].fwd_perm = 1; x[2].bwd = u16(w2b[t]); x[2].bwd_ks = KS2; x[2].bwd_perm = 1;
+        x[4].fwd = u16(trunk[t]->w3); x[4].fwd_ks = KS2; x[4].fwd_perm = 1; x[4].bwd = u16(w3b[t]); x[4].bwd_ks = t ? 2 : 2 * NT3; x[4].bwd_perm = 0;
+        x[1].bias = f32(trunk[t]->b1); x[3].bias = f32(trunk[t]->b2); x[5].bias = f32(trunk[t]->b3);
+    }
 
     launch_adam(l, false, 0.f, nullptr);                                             // the backward fragments (and the forward ones, again) from the masters
     e = hipGetLastError();
@@ -822,7 +725,7 @@ extern "C" int dcomp_learner_create(dcomp_actor *a, const dcomp_learner_cfg *cfg
     if (e != hipSuccess) {
         (void)hipFree(l->mem);
         delete l;
-        return lfail(DCOMP_EHIP, "%s: %s", fn, hipGetErrorString(e));
+        return fail(DCOMP_EHIP, "%s: %s", fn, hipGetErrorString(e));
     }
     *out = l;
     return DCOMP_OK;
@@ -833,41 +736,42 @@ extern "C" int dcomp_learner_destroy(dcomp_learner *l)
     if (!l) return DCOMP_OK;
     const hipError_t e = hipFree(l->mem);
     delete l;
-    return e == hipSuccess ? DCOMP_OK : lfail(DCOMP_EHIP, "dcomp_learner_destroy: hipFree failed: %s", hipGetErrorString(e));
+    return e == hipSuccess ? DCOMP_OK : fail(DCOMP_EHIP, "dcomp_learner_destroy: hipFree failed: %s", hipGetErrorString(e));
 }
 
 // dcomp_learner_grads (evaluate = false) and dcomp_learner_evaluate: every check on the host first
 static int learner_launch(const char *fn, bool evaluate, dcomp_learner *l, const dcomp_ppo_batch *b, const dcomp_ppo_hyper *hy, float *stats, void *stream)
 {
     using namespace dlearn;
-    if (!l || !b) return lfail(DCOMP_EINVAL, "%s: handle and batch must not be NULL", fn);
+    if (!l || !b) return fail(DCOMP_EINVAL, "%s: handle and batch must not be NULL", fn);
     if (b->struct_size != (int32_t)sizeof(dcomp_ppo_batch))
-        return lfail(DCOMP_EABI, "%s: caller's dcomp_ppo_batch has %d bytes, the library's %d", fn, b->struct_size, (int)sizeof(dcomp_ppo_batch));
+        return fail(DCOMP_EABI, "%s: caller's dcomp_ppo_batch has %d bytes, the library's %d", fn, b->struct_size, (int)sizeof(dcomp_ppo_batch));
     if (!evaluate) {
-        if (!hy) return lfail(DCOMP_EINVAL, "%s: hyper must not be NULL", fn);
+        if (!hy) return fail(DCOMP_EINVAL, "%s: hyper must not be NULL", fn);
         if (hy->struct_size != (int32_t)sizeof(dcomp_ppo_hyper))
-            return lfail(DCOMP_EABI, "%s: caller's dcomp_ppo_hyper has %d bytes, the library's %d", fn, hy->struct_size, (int)sizeof(dcomp_ppo_hyper));
-        if (!stats) return lfail(DCOMP_EINVAL, "%s: stats_dev must not be NULL", fn);
-        if (!(hy->clip_param >= 0.f) || !(hy->vf_clip_param >= 0.f)) return lfail(DCOMP_EINVAL, "%s: clip_param %g / vf_clip_param %g must be >= 0", fn, hy->clip_param, hy->vf_clip_param);
+            return fail(DCOMP_EABI, "%s: caller's dcomp_ppo_hyper has %d bytes, the library's %d", fn, hy->struct_size, (int)sizeof(dcomp_ppo_hyper));
+        if (!stats) return fail(DCOMP_EINVAL, "%s: stats_dev must not be NULL", fn);
+        if (!(hy->clip_param >= 0.f) || !(hy->vf_clip_param >= 0.f)) return fail(DCOMP_EINVAL, "%s: clip_param %g / vf_clip_param %g must be >= 0", fn, hy->clip_param, hy->vf_clip_param);
     }
-    if (b->obs_format == DCOMP_ACTOR_COMPACT) return lfail(DCOMP_EUNSUPPORTED, "%s: the compact record is not supported as learner input: pass observation rows", fn);
-    if (b->obs_format != DCOMP_ACTOR_ROWS) return lfail(DCOMP_EINVAL, "%s: unknown obs_format %d", fn, b->obs_format);
-    if (!b->obs) return lfail(DCOMP_EINVAL, "%s: batch.obs must not be NULL", fn);
+    if (b->obs_format == DCOMP_ACTOR_COMPACT) return fail(DCOMP_EUNSUPPORTED, "%s: the compact record is not supported as learner input: pass observation rows", fn);
+    if (b->obs_format != DCOMP_ACTOR_ROWS) return fail(DCOMP_EINVAL, "%s: unknown obs_format %d", fn, b->obs_format);
+    if (!b->obs) return fail(DCOMP_EINVAL, "%s: batch.obs must not be NULL", fn);
     const bool upstream = b->dlogits || b->dvalue;
     if (evaluate) {
-        if (!b->actions) return lfail(DCOMP_EINVAL, "%s: batch.actions must not be NULL", fn);
-        if (!b->logp && !b->entropy && !b->vf) return lfail(DCOMP_EINVAL, "%s: none of batch.logp / entropy / vf is given: nothing to write", fn);
-        if (upstream) return lfail(DCOMP_EINVAL, "%s: upstream gradients (batch.dlogits / dvalue) belong to dcomp_learner_grads", fn);
+        if (!b->actions) return fail(DCOMP_EINVAL, "%s: batch.actions must not be NULL", fn);
+        if (!b->logp && !b->entropy && !b->vf) return fail(DCOMP_EINVAL, "%s: none of batch.logp / entropy / vf is given: nothing to write", fn);
+        if (upstream) return fail(DCOMP_EINVAL, "%s: upstream gradients (batch.dlogits / dvalue) belong to dcomp_learner_grads", fn);
     } else if (upstream) {
-        if (!b->dlogits || !b->dvalue) return lfail(DCOMP_EINVAL, "%s: batch.dlogits and batch.dvalue come together: one of them is NULL", fn);
+        if (!b->dlogits || !b->dvalue) return fail(DCOMP_EINVAL, "%s: batch.dlogits and batch.dvalue come together: one of them is NULL", fn);
     } else if (!b->actions || !b->old_logp || !b->old_logits || !b->advantages || !b->value_targets || !b->old_vf) {
-        return lfail(DCOMP_EINVAL, "%s: a pointer of batch.actions / old_logp / old_logits / advantages / value_targets / old_vf is NULL", fn);
+        return fail(DCOMP_EINVAL, "%s: a pointer of batch.actions / old_logp / old_logits / advantages / value_targets / old_vf is NULL", fn);
     }
-    if (b->rows < 1) return lfail(DCOMP_EINVAL, "%s: rows %lld < 1", fn, (long long)b->rows);
+    if (b->rows < 1) return fail(DCOMP_EINVAL, "%s: rows %lld < 1", fn, (long long)b->rows);
     // the handle, from here on
-    if (b->rows > l->max_rows) return lfail(DCOMP_EINVAL, "%s: rows %lld > max_rows %lld of the handle", fn, (long long)b->rows, (long long)l->max_rows);
+    if (b->rows > l->max_rows) return fail(DCOMP_EINVAL, "%s: rows %lld > max_rows %lld of the handle", fn, (long long)b->rows, (long long)l->max_rows);
     const dcomp_actor *a = l->a;
-    if (b->num_active < 0 || b->num_active > a->U) return lfail(DCOMP_EINVAL, "%s: num_active %d outside [0, %d]", fn, b->num_active, a->U);
+    const int U = a->net.U;
+    if (b->num_active < 0 || b->num_active > U) return fail(DCOMP_EINVAL, "%s: num_active %d outside [0, %d]", fn, b->num_active, U);
 
     hipStream_t s = static_cast<hipStream_t>(stream);
     LParams p = l->lp;
@@ -880,8 +784,8 @@ static int learner_launch(const char *fn, bool evaluate, dcomp_learner *l, const
     if (hy) { p.clip = hy->clip_param; p.vf_clip = hy->vf_clip_param; p.vf_coeff = hy->vf_loss_coeff; p.ent_coeff = hy->entropy_coeff; p.kl_coeff = hy->kl_coeff; }
     const int64_t want = (p.tiles + WAVES - 1) / WAVES;
     const int grid = (int)(want < a->max_blocks ? want : a->max_blocks);
-    hipLaunchKernelGGL(pick(a->mt, a->relu != 0), dim3(grid), dim3(BLOCK), (size_t)a->lds_per_wave * WAVES, s, p);
-    LEARNER_HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(pick(a->mt, a->relu != 0), dim3(grid), dim3(BLOCK), (size_t)a->net.lds_per_wave * WAVES, s, p);
+    HIP_TRY(hipGetLastError());
     if (evaluate) return DCOMP_OK;
 
     // the row split of the weight gradients: a function of the row count alone
@@ -891,16 +795,16 @@ static int learner_launch(const char *fn, bool evaluate, dcomp_learner *l, const
     w.chunk_rows = CHUNK_UNIT * mult;
     const int nchunks = (int)((w.rows_pad + w.chunk_rows - 1) / w.chunk_rows);
     hipLaunchKernelGGL(wgrad_kernel, dim3((w.ntask + WAVES - 1) / WAVES, nchunks), dim3(BLOCK), 0, s, w);
-    LEARNER_HIP_TRY(hipGetLastError());
+    HIP_TRY(hipGetLastError());
 
     AParams ap = l->ap;
     ap.nchunks = nchunks; ap.tiles = p.tiles; ap.stats = stats; ap.want_stats = 1;
-    const int64_t counted = a->kind == DCOMP_MULTI ? (b->rows / a->U) * b->num_active + (b->rows % a->U < b->num_active ? b->rows % a->U : b->num_active) : b->rows;
+    const int64_t counted = a->net.multi ? (b->rows / U) * b->num_active + (b->rows % U < b->num_active ? b->rows % U : b->num_active) : b->rows;
     ap.count = upstream ? 0. : (double)counted;
     ap.scale = upstream ? 1.f : (counted > 0 ? (float)(1.0 / (double)counted) : 0.f);
     ap.vf_coeff = p.vf_coeff; ap.ent_coeff = p.ent_coeff; ap.kl_coeff = p.kl_coeff;
     hipLaunchKernelGGL(reduce_kernel, dim3((l->total + 255) / 256), dim3(256), 0, s, ap);
-    LEARNER_HIP_TRY(hipGetLastError());
+    HIP_TRY(hipGetLastError());
     return DCOMP_OK;
 }
 
@@ -916,10 +820,10 @@ extern "C" int dcomp_learner_evaluate(dcomp_learner *l, const dcomp_ppo_batch *b
 
 extern "C" int dcomp_learner_apply(dcomp_learner *l, float lr, void *stream)
 {
-    if (!l) return lfail(DCOMP_EINVAL, "dcomp_learner_apply: handle must not be NULL");
-    if (!(lr >= 0.f) || !std::isfinite(lr)) return lfail(DCOMP_EINVAL, "dcomp_learner_apply: lr %g is not a finite number >= 0", lr);
+    if (!l) return fail(DCOMP_EINVAL, "dcomp_learner_apply: handle must not be NULL");
+    if (!(lr >= 0.f) || !std::isfinite(lr)) return fail(DCOMP_EINVAL, "dcomp_learner_apply: lr %g is not a finite number >= 0", lr);
     launch_adam(l, true, lr, static_cast<hipStream_t>(stream));
-    LEARNER_HIP_TRY(hipGetLastError());
+    HIP_TRY(hipGetLastError());
     l->step++;
     return DCOMP_OK;
 }
@@ -927,15 +831,15 @@ extern "C" int dcomp_learner_apply(dcomp_learner *l, float lr, void *stream)
 extern "C" int dcomp_learner_read(dcomp_learner *l, int32_t which, const dcomp_learner_arrays *dst, int64_t *step, void *stream)
 {
     const char *fn = "dcomp_learner_read";
-    if (!l) return lfail(DCOMP_EINVAL, "%s: handle must not be NULL", fn);
-    if (which < DCOMP_LEARNER_WEIGHTS || which > DCOMP_LEARNER_ADAM_V) return lfail(DCOMP_EINVAL, "%s: which %d is not one of DCOMP_LEARNER_*", fn, which);
+    if (!l) return fail(DCOMP_EINVAL, "%s: handle must not be NULL", fn);
+    if (which < DCOMP_LEARNER_WEIGHTS || which > DCOMP_LEARNER_ADAM_V) return fail(DCOMP_EINVAL, "%s: which %d is not one of DCOMP_LEARNER_*", fn, which);
     if (int rc = check_arrays(fn, "dst", dst, false)) return rc;
     const float *src = which == DCOMP_LEARNER_WEIGHTS ? l->w : which == DCOMP_LEARNER_GRADS ? l->g : which == DCOMP_LEARNER_ADAM_M ? l->m : l->v;
-    LEARNER_HIP_TRY(hipStreamSynchronize(static_cast<hipStream_t>(stream)));
+    HIP_TRY(hipStreamSynchronize(static_cast<hipStream_t>(stream)));
     float *m[dlearn::NARR];
     members(dst, m);
     for (int i = 0; i < dlearn::NARR; i++)
-        if (m[i]) LEARNER_HIP_TRY(hipMemcpy(m[i], src + l->off[i], (size_t)l->len[i] * 4, hipMemcpyDeviceToHost));
+        if (m[i]) HIP_TRY(hipMemcpy(m[i], src + l->off[i], (size_t)l->len[i] * 4, hipMemcpyDeviceToHost));
     if (step) *step = l->step;
     return DCOMP_OK;
 }
@@ -944,22 +848,22 @@ extern "C" int dcomp_learner_load_state(dcomp_learner *l, const dcomp_learner_ar
                                         const dcomp_learner_arrays *adam_v, int64_t step, void *stream)
 {
     const char *fn = "dcomp_learner_load_state";
-    if (!l) return lfail(DCOMP_EINVAL, "%s: handle must not be NULL", fn);
+    if (!l) return fail(DCOMP_EINVAL, "%s: handle must not be NULL", fn);
     if (int rc = check_arrays(fn, "weights", weights, true)) return rc;
     if (int rc = check_arrays(fn, "adam_m", adam_m, true)) return rc;
     if (int rc = check_arrays(fn, "adam_v", adam_v, true)) return rc;
-    if (step < 0) return lfail(DCOMP_EINVAL, "%s: step %lld < 0", fn, (long long)step);
+    if (step < 0) return fail(DCOMP_EINVAL, "%s: step %lld < 0", fn, (long long)step);
     hipStream_t s = static_cast<hipStream_t>(stream);
-    LEARNER_HIP_TRY(hipStreamSynchronize(s));
+    HIP_TRY(hipStreamSynchronize(s));
     const dcomp_learner_arrays *from[3] = {weights, adam_m, adam_v};
     float *to[3] = {l->w, l->m, l->v};
     for (int k = 0; k < 3; k++) {
         float *m[dlearn::NARR];
         members(from[k], m);
-        for (int i = 0; i < dlearn::NARR; i++) LEARNER_HIP_TRY(hipMemcpy(to[k] + l->off[i], m[i], (size_t)l->len[i] * 4, hipMemcpyHostToDevice));
+        for (int i = 0; i < dlearn::NARR; i++) HIP_TRY(hipMemcpy(to[k] + l->off[i], m[i], (size_t)l->len[i] * 4, hipMemcpyHostToDevice));
     }
     l->step = step;
     launch_adam(l, false, 0.f, s);
-    LEARNER_HIP_TRY(hipGetLastError());
+    HIP_TRY(hipGetLastError());
     return DCOMP_OK;
 }
