@@ -131,6 +131,17 @@ class DcompPpoBatch(ctypes.Structure):
                                                'logp', 'entropy', 'kl', 'vf', 'ratio', 'dlogits', 'dvalue')]
 
 
+# include/dcomp_learner_indexed.h: minibatches through a row index into the whole sample batch, rows or compact record
+SGD_EXPORTS = ['dcomp_sgd_grads', 'dcomp_sgd_evaluate']
+
+
+class DcompSgdBatch(ctypes.Structure):
+    _fields_ = [('struct_size', ctypes.c_int32), ('obs_format', ctypes.c_int32), ('rows', ctypes.c_int64), ('source_rows', ctypes.c_int64),
+                ('index', ctypes.c_void_p), ('num_active', ctypes.c_int32), ('reserved', ctypes.c_int32)] + \
+               [(n, ctypes.c_void_p) for n in ('obs', 'actions', 'old_logp', 'old_logits', 'advantages', 'value_targets', 'old_vf',
+                                               'dlogits', 'dvalue', 'logp', 'entropy', 'kl', 'vf', 'ratio')]
+
+
 class DcompPpoHyper(ctypes.Structure):
     _fields_ = [('struct_size', ctypes.c_int32), ('clip_param', ctypes.c_float), ('vf_clip_param', ctypes.c_float),
                 ('vf_loss_coeff', ctypes.c_float), ('entropy_coeff', ctypes.c_float), ('kl_coeff', ctypes.c_float)]
@@ -226,6 +237,11 @@ def load():
         L.dcomp_learner_read.argtypes = [vp, i32, ap, ctypes.POINTER(i64), vp]
         L.dcomp_learner_load_state.argtypes = [vp, ap, ap, ap, i64, vp]
         for name in LEARNER_EXPORTS:
+            getattr(L, name)
+    if hasattr(L, 'dcomp_sgd_grads') or not os.environ.get('DCOMP_LIB'):
+        L.dcomp_sgd_grads.argtypes = [vp, ctypes.POINTER(DcompSgdBatch), ctypes.POINTER(DcompPpoHyper), vp, vp]
+        L.dcomp_sgd_evaluate.argtypes = [vp, ctypes.POINTER(DcompSgdBatch), vp]
+        for name in SGD_EXPORTS:
             getattr(L, name)
     for name in EXPORTS:
         getattr(L, name)

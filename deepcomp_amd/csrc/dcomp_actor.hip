@@ -51,11 +51,6 @@ namespace dactor {
 
 constexpr uint32_t DRAW_TAG = 0x00AC7012u;
 
-// the compact record of one env-step (dcomp_fragment.h, whose kernels live in the API object): U x { dr[B] | utility | connection
-// mask word(s) } then ues_at_bs[B] | util_at_bs[B]
-__host__ __device__ inline int ue_words(int B) { return B + 1 + (B > 32 ? 2 : 1); }
-__host__ __device__ inline int env_words(int U, int B) { return U * ue_words(B) + 2 * B; }
-
 struct Params {
     const void *obs;
     uint8_t *action;
@@ -113,9 +108,7 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(2, 2))) v
                 if (have) {
                     const int64_t env = myrow / U;
                     const uint64_t off = (uint64_t)env * (uint64_t)env_words(U, B) + (uint64_t)slot * CW;
-                    uint32_t any = 0;
-                    for (int b = 0; b < B; b++) any |= cwords[off + b] & 0x7FFFFFFFu;          // listed <=> some dr entry is non-zero
-                    lo = (uint32_t)off; hi = (uint32_t)(off >> 32); listed = any != 0u;
+                    lo = (uint32_t)off; hi = (uint32_t)(off >> 32); listed = compact_listed(cwords, off, B);
                 }
                 ri[lane * 4 + 0] = lo; ri[lane * 4 + 1] = hi; ri[lane * 4 + 2] = listed; ri[lane * 4 + 3] = (uint32_t)slot;
             }
@@ -141,10 +134,7 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(2, 2))) v
                                v = rowsf[(size_t)(row0 + rr) * K1 + k];
                            } else {
                                const uint64_t off = (uint64_t)ri[rr * 4] | ((uint64_t)ri[rr * 4 + 1] << 32);
-                               if (k < B) v = (float)((cwords[off + B + 1 + (k >> 5)] >> (k & 31)) & 1u);      // connected
-                               else if (k < 2 * B) v = __uint_as_float(cwords[off + (k - B)]);                // dr
-                               else if (k < 4 * B) v = ri[rr * 4 + 2] ? __uint_as_float(cwords[off + (uint64_t)(U - (int)ri[rr * 4 + 3]) * CW + (k - 2 * B)]) : 0.f;
-                               else v = __uint_as_float(cwords[off + B]);                                    // utility
+                               v = compact_input(cwords, off, ri + rr * 4 + 2, k, B, U, CW);
                            }
                        }
                        return v;

@@ -5,6 +5,8 @@
 //     (put_logit_tile; actor_kernel has it written out, see there) and the online log-sum-exp step (lse_push).  The streaming of
 //     the layer-2 and layer-3 weights is NOT here:
 //     the actor's ring across the layer boundary and the learner's group-by-group loads are tuned against different register budgets
+//   - the compact record as a kernel's input: its word counts (ue_words, env_words) and the decode of one input of one row
+//     (compact_listed, compact_input)
 //   - the packed-fragment layout: pack_index() is the permutation and bf16_rne() the rounding, on the host (pack) and on the device
 //     (the learner's Adam kernel)
 //   - the description of the net (Trunk, Net) that the handle holds and both kernels' arguments embed
@@ -99,6 +101,32 @@ __device__ __forceinline__ bf16x8 as_frag(uint4 v)
     union { uint4 u; bf16x8 f; } c;
     c.u = v;
     return c.f;
+}
+
+// the compact record of one env-step (dcomp_fragment.h, whose kernels live in the API object): U x { dr[B] | utility | connection
+// mask word(s) } then ues_at_bs[B] | util_at_bs[B]
+__host__ __device__ inline int ue_words(int B) { return B + 1 + (B > 32 ? 2 : 1); }
+__host__ __device__ inline int env_words(int U, int B) { return U * ue_words(B) + 2 * B; }
+
+// a UE's record at word offset off: listed <=> some dr entry is non-zero
+__device__ __forceinline__ uint32_t compact_listed(const uint32_t *cwords, uint64_t off, int B)
+{
+    uint32_t any = 0;
+    for (int b = 0; b < B; b++) any |= cwords[off + b] & 0x7FFFFFFFu;
+    return any != 0u;
+}
+
+// input k (< 4B + 1) of the observation row of the UE whose record is at word offset off, as dcomp_unpack_fragment would have
+// written it: connection bits, dr, the per-env block behind the last UE's record (zeros for an unlisted UE), utility.
+// ls: the row's two words listed | UE slot (read only where the per-env block is).  CW = ue_words(B).
+__device__ __forceinline__ float compact_input(const uint32_t *cwords, uint64_t off, const uint32_t *ls, int k, int B, int U, int CW)
+{
+    float v;
+    if (k < B) v = (float)((cwords[off + B + 1 + (k >> 5)] >> (k & 31)) & 1u);      // connected
+    else if (k < 2 * B) v = __uint_as_float(cwords[off + (k - B)]);                // dr
+    else if (k < 4 * B) v = ls[0] ? __uint_as_float(cwords[off + (uint64_t)(U - (int)ls[1]) * CW + (k - 2 * B)]) : 0.f;
+    else v = __uint_as_float(cwords[off + B]);                                    // utility
+    return v;
 }
 
 // Layer 1: acc[m] = W1^T (units 32m ...) x X^T, the K1p inputs in chunks of <= KC through the wave's LDS slice xs [32][XS] bf16.

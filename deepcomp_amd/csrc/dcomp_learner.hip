@@ -1,4 +1,5 @@
-// dcomp_learner.hip -- the PPO learner of the fcnet a dcomp_actor runs (include/dcomp_learner.h): loss, backward pass and Adam.
+// dcomp_learner.hip -- the PPO learner of the fcnet a dcomp_actor runs (include/dcomp_learner.h): loss, backward pass and Adam; and
+// its minibatches picked through a row index out of a whole sample batch, rows or compact record (include/dcomp_learner_indexed.h).
 //
 // Four kernels per minibatch, all deterministic (no floating-point atomics; every sum has an order fixed by the row count):
 //   learner_kernel   forward + loss + backward-data.  The shape of actor_kernel: a wavefront owns 32 decision rows on its lanes and
@@ -27,11 +28,13 @@
 #include <cmath>
 #include <cstdint>
 #include <cstring>
+#include <type_traits>
 #include <vector>
 
 #define DCOMP_BUILDING_LIBRARY 1
 #include "../../include/dcomp.h"
 #include "../../include/dcomp_learner.h"
+#include "../../include/dcomp_learner_indexed.h"
 #include "dcomp_actor_impl.h"       // the forward-pass helpers, the fragment layout, Net and struct dcomp_actor, fail / HIP_TRY: shared with dcomp_actor.hip
 
 namespace dlearn {
@@ -57,6 +60,15 @@ struct LParams {
     int32_t num_active, fwd_only, upstream;
     float clip, vf_clip, vf_coeff, ent_coeff, kl_coeff;
 };
+// the arguments of the indexed instantiations (dcomp_learner_indexed.h): position i of the minibatch reads source row index[i]
+// (NULL: i) of a sample batch of source_rows rows; compact: obs is the record of source_rows / U envs
+struct IParams : LParams {
+    const int32_t *index;
+    int64_t source_rows;
+    int32_t compact;
+};
+
+constexpr uint32_t NO_ROW = 0xFFFFFFFFu;  // ri of a position that reads nothing (a valid source row is < 2^31)
 
 // one output tile of a hidden -> out layer: sum over the 2 MT k steps of fragments first ... of w with the B fragments b
 template <int MT> __device__ __forceinline__ f32x16 tile_dot(const uint4 *w, size_t first, const bf16x8 (&b)[MT][2], uint32_t lane16)
@@ -109,6 +121,13 @@ template <int MT, bool RELU> __device__ __forceinline__ void delta_frags(const f
             }
 }
 
+// the source row of the position on this lane: IDX, what the tile's resolve step left in ri (read from LDS at every use: not a
+// register held across the sweeps); otherwise the position itself
+template <bool IDX> __device__ __forceinline__ size_t source_row(const uint32_t *ri, int r, int64_t myrow)
+{
+    return IDX ? (size_t)ri[r * 4] : (size_t)myrow;
+}
+
 __device__ __forceinline__ float wave_sum(float v)       // a fixed tree over the 64 lanes
 {
 #pragma unroll
@@ -116,8 +135,11 @@ __device__ __forceinline__ float wave_sum(float v)       // a fixed tree over th
     return v;
 }
 
-template <int MT, bool RELU>
-__global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(1, 1))) void learner_kernel(const LParams p)
+// IDX: the per-row inputs come from source row index[i] of the whole sample batch, as rows or as the compact record (the indexed
+// entry points); the workspaces, the partials and the per-row outputs stay at minibatch position i.  A template parameter: the
+// instantiations without it are the kernel as it was.
+template <int MT, bool RELU, bool IDX>
+__global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(1, 1))) void learner_kernel(const std::conditional_t<IDX, IParams, LParams> p)
 {
     extern __shared__ uint4 lds4[];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, r = lane & 31, h = lane >> 5;
@@ -126,8 +148,11 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(1, 1))) v
     unsigned char *base = reinterpret_cast<unsigned char *>(lds4) + (size_t)wave * n.lds_per_wave;
     __bf16 *xs = reinterpret_cast<__bf16 *>(base);                                   // [32][XS] bf16: the chunk of the tile's rows
     float *lt = reinterpret_cast<float *>(base + (size_t)TILE * n.XS * 2);           // [32][LT] f32: 32 logits / dlogits of every row
-    uint32_t *ri = reinterpret_cast<uint32_t *>(lt + TILE * LT);                     // [32]: the row is read and counted
+    // [32]: the row is read and counted.  IDX: [32][4], position r's source row (NO_ROW: nothing is read) | its env | listed | UE slot
+    uint32_t *ri = reinterpret_cast<uint32_t *>(lt + TILE * LT);
     const int XS = n.XS, K1 = n.K1, U = n.U, NA = n.B + 1;
+    const int B = n.B, CW = ue_words(B);
+    const uint32_t *cwords = reinterpret_cast<const uint32_t *>(p.obs);
     constexpr int KS2 = 2 * MT;
     const int64_t ld = p.ld;
 
@@ -136,12 +161,34 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(1, 1))) v
         const int nrow = (int)(p.rows - row0 < TILE ? p.rows - row0 : TILE);
         const int64_t myrow = row0 + r;                                              // the decision row on this lane
         const bool have = r < nrow;
-        // a row beyond the batch, or a multi-agent row of an unlisted slot: computed on zeros, every delta zero, nothing of it read
-        const bool live = have && !(n.multi && (int)(myrow % U) >= p.num_active);
+        if constexpr (IDX) {
+            // the source row of every position, resolved once per tile; an entry outside the sample batch is never dereferenced
+            if (lane < TILE) {
+                uint32_t src = NO_ROW, env = 0, listed = 0, slot = 0;
+                if (have) {
+                    const int64_t s = p.index ? (int64_t)p.index[myrow] : myrow;
+                    if (s >= 0 && s < p.source_rows) {
+                        src = (uint32_t)s;
+                        if (p.compact) {
+                            env = src / (uint32_t)U; slot = src - env * (uint32_t)U;
+                            listed = compact_listed(cwords, (uint64_t)env * (uint64_t)env_words(U, B) + (uint64_t)slot * CW, B);
+                        }
+                    }
+                }
+                ri[lane * 4 + 0] = src; ri[lane * 4 + 1] = env; ri[lane * 4 + 2] = listed; ri[lane * 4 + 3] = slot;
+            }
+            wave_fence();
+        }
+        // a row beyond the batch, a multi-agent row of an unlisted slot, or (IDX) a position whose index entry is outside the sample
+        // batch: computed on zeros, every delta zero, nothing of it read
+        const bool live = IDX ? have && ri[r * 4] != NO_ROW : have && !(n.multi && (int)(myrow % U) >= p.num_active);
         const bool walker = lane < TILE && live;
         const uint32_t voff = (uint32_t)(2 * ((uint64_t)myrow + (uint64_t)(4 * h) * (uint64_t)ld));      // store_frags: this lane's column
-        if (lane < TILE) ri[lane] = live ? 1u : 0u;
-        wave_fence();
+        if constexpr (!IDX) {
+            if (lane < TILE) ri[lane] = live ? 1u : 0u;
+            wave_fence();
+        }
+
         float s_surr = 0.f, s_kl = 0.f, s_ent = 0.f, s_vfl = 0.f;                     // this row's terms (lanes < 32)
         float c_lp = 0.f;                                                            // d(-surrogate) / d(logp)
 
@@ -157,7 +204,20 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(1, 1))) v
         // ---- layer 1, with x as bf16 [input][rows] on the way for dW1 of both trunks
         f32x16 acc[MT];
         layer1<MT>(acc, t.w1, n.K1p, xs, XS, lane, lane16, staged,
-                   [&](int rr, int k) { return ri[rr] && k < K1 ? p.obs[(size_t)(row0 + rr) * K1 + k] : 0.f; },
+                   [&](int rr, int k) {
+                       if constexpr (IDX) {                                          // at the source row: a float row or a compact record
+                           const uint32_t s = ri[rr * 4];
+                           float v = 0.f;
+                           if (s != NO_ROW && k < K1) {
+                               if (!p.compact) v = p.obs[(size_t)s * K1 + k];
+                               else v = compact_input(cwords, (uint64_t)ri[rr * 4 + 1] * (uint64_t)env_words(U, B) + (uint64_t)ri[rr * 4 + 3] * CW,
+                                                      ri + rr * 4 + 2, k, B, U, CW);
+                           }
+                           return v;
+                       } else {
+                           return ri[rr] && k < K1 ? p.obs[(size_t)(row0 + rr) * K1 + k] : 0.f;
+                       }
+                   },
                    [&](int k0, int kc) {
                        if (!val && !p.fwd_only) {
                            for (int i = lane; i < kc * TILE; i += 64) {
@@ -195,19 +255,19 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(1, 1))) v
                     const int ncol = N3 - 32 * nt < 32 ? N3 - 32 * nt : 32;
                     for (int c = 0; c < ncol; c++) {
                         const float x = lt[r * LT + c];
-                        if (a == 0) act = p.actions[(size_t)myrow * n.heads + hd];
+                        if (a == 0) act = p.actions[source_row<IDX>(ri, r, myrow) * n.heads + hd];
                         if (a == act) xa = x;
                         float e1, e2;
                         lse_push(x, mx, sm, e1, e2);
                         tn = tn * e1 + x * e2;
-                        if (p.old_logits) lse_push(p.old_logits[(size_t)myrow * n.N3 + 32 * nt + c], mo, so, e1, e2);
+                        if (p.old_logits) lse_push(p.old_logits[source_row<IDX>(ri, r, myrow) * n.N3 + 32 * nt + c], mo, so, e1, e2);
                         if (++a == NA) {
                             const size_t at = (size_t)myrow * n.heads + hd;
                             const float lse = mx + logf(sm), lp = xa - lse, eh = lse - tn / sm;
                             if (p.o_logp) p.o_logp[at] = lp;
                             if (n.multi || hd < p.num_active) {
                                 logp_sum += lp; ent_sum += eh;
-                                if (p.old_logp) oldlp_sum += p.old_logp[at];
+                                if (p.old_logp) oldlp_sum += p.old_logp[IDX ? source_row<IDX>(ri, r, myrow) * n.heads + hd : at];
                             }
                             if (!p.fwd_only) p.headws[at] = make_float4(lse, mo + logf(so), eh, 0.f);
                             a = 0; hd++; xa = 0.f;
@@ -222,14 +282,25 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(1, 1))) v
             if (walker && p.o_ent) p.o_ent[myrow] = ent_sum;
             s_ent = walker ? ent_sum : 0.f;
             if (!p.fwd_only && !p.upstream && walker) {
-                const float adv = p.adv[myrow], ratio = expf(logp_sum - oldlp_sum);
+                const float adv = p.adv[source_row<IDX>(ri, r, myrow)], ratio = expf(logp_sum - oldlp_sum);
                 const float s1 = adv * ratio, s2 = adv * fminf(fmaxf(ratio, 1.f - p.clip), 1.f + p.clip);
                 s_surr = fminf(s1, s2);
                 c_lp = s1 <= s2 ? -s1 : 0.f;                                          // d(-min) / d(logp): d(adv ratio) / d(logp) = adv ratio
                 if (p.o_ratio) p.o_ratio[myrow] = ratio;
             }
+            if constexpr (IDX) {
+                if (lane < TILE && have && !live) {                                  // nothing was read: its outputs are zeros
+                    if (p.actions && p.o_logp)
+                        for (int hd = 0; hd < n.heads; hd++) p.o_logp[(size_t)myrow * n.heads + hd] = 0.f;
+                    if (p.o_ent) p.o_ent[myrow] = 0.f;
+                    if (!p.fwd_only && !p.upstream) {
+                        if (p.o_ratio) p.o_ratio[myrow] = 0.f;
+                        if (p.o_kl) p.o_kl[myrow] = 0.f;
+                    }
+                }
+            }
         } else if (lane < TILE && have && p.o_vf) {
-            p.o_vf[myrow] = lt[r * LT];                                              // (the tile of the value sweep is still in LDS)
+            p.o_vf[myrow] = !IDX || live ? lt[r * LT] : 0.f;                         // (the tile of the value sweep is still in LDS)
         }
         if (p.fwd_only) continue;
 
@@ -250,9 +321,9 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(1, 1))) v
                     if (lane < TILE) {
                         float dv = 0.f;
                         if (walker) {
-                            if (p.upstream) dv = p.up_dvalue[myrow];
+                            if (p.upstream) dv = p.up_dvalue[source_row<IDX>(ri, r, myrow)];
                             else {
-                                const float v = lt[r * LT], vt = p.vtarg[myrow], ov = p.old_vf[myrow];
+                                const float v = lt[r * LT], vt = p.vtarg[source_row<IDX>(ri, r, myrow)], ov = p.old_vf[source_row<IDX>(ri, r, myrow)];
                                 const float d1 = v - vt, dc = fminf(fmaxf(v - ov, -p.vf_clip), p.vf_clip), d2 = (ov + dc) - vt;
                                 const float l1 = d1 * d1, l2 = d2 * d2;
                                 s_vfl = fmaxf(l1, l2);
@@ -265,7 +336,8 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(1, 1))) v
                 } else if (p.upstream) {
                     for (int i = lane; i < TILE * 32; i += 64) {
                         const int rr = i >> 5, c = i & 31;
-                        lt[rr * LT + c] = ri[rr] && c < ncol ? p.up_dlogits[(size_t)(row0 + rr) * n.N3 + 32 * nt + c] : 0.f;
+                        if constexpr (IDX) lt[rr * LT + c] = ri[rr * 4] != NO_ROW && c < ncol ? p.up_dlogits[(size_t)ri[rr * 4] * n.N3 + 32 * nt + c] : 0.f;
+                        else lt[rr * LT + c] = ri[rr] && c < ncol ? p.up_dlogits[(size_t)(row0 + rr) * n.N3 + 32 * nt + c] : 0.f;
                     }
                 } else {
                     put_logit_tile(tile_dot<MT>(t.w3, (size_t)nt * KS2, h2, lane16), t.b3, nt, lt, r, h);
@@ -278,12 +350,12 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(1, 1))) v
                                 const float x = lt[r * LT + c];
                                 if (a == 0) {
                                     hw = p.headws[(size_t)myrow * n.heads + hd];
-                                    act = p.actions[(size_t)myrow * n.heads + hd];
+                                    act = p.actions[source_row<IDX>(ri, r, myrow) * n.heads + hd];
                                 }
                                 float dl = 0.f;
                                 if (n.multi || hd < p.num_active) {
                                     const float lpn = x - hw.x, pn = expf(lpn);
-                                    const float lpo = p.old_logits[(size_t)myrow * n.N3 + 32 * nt + c] - hw.y, po = expf(lpo);
+                                    const float lpo = p.old_logits[source_row<IDX>(ri, r, myrow) * n.N3 + 32 * nt + c] - hw.y, po = expf(lpo);
                                     kl_sum += po * (lpo - lpn);
                                     dl = c_lp * ((a == act ? 1.f : 0.f) - pn) + p.kl_coeff * (pn - po) + p.ent_coeff * (pn * (lpn + hw.z));
                                 }
@@ -351,9 +423,14 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(1, 1))) v
 }
 
 typedef void (*learner_fn)(const LParams);
+typedef void (*indexed_fn)(const IParams);
 static learner_fn pick(int mt, bool relu)
 {
-    return pick_shape(mt, relu, [](auto s) -> learner_fn { return learner_kernel<decltype(s)::MT, decltype(s)::RELU>; });
+    return pick_shape(mt, relu, [](auto s) -> learner_fn { return learner_kernel<decltype(s)::MT, decltype(s)::RELU, false>; });
+}
+static indexed_fn pick_indexed(int mt, bool relu)
+{
+    return pick_shape(mt, relu, [](auto s) -> indexed_fn { return learner_kernel<decltype(s)::MT, decltype(s)::RELU, true>; });
 }
 
 // ---------------------------------------------------------------- weight gradients
@@ -739,13 +816,24 @@ extern "C" int dcomp_learner_destroy(dcomp_learner *l)
     return e == hipSuccess ? DCOMP_OK : fail(DCOMP_EHIP, "dcomp_learner_destroy: hipFree failed: %s", hipGetErrorString(e));
 }
 
-// dcomp_learner_grads (evaluate = false) and dcomp_learner_evaluate: every check on the host first
-static int learner_launch(const char *fn, bool evaluate, dcomp_learner *l, const dcomp_ppo_batch *b, const dcomp_ppo_hyper *hy, float *stats, void *stream)
+// One (mini)batch as both surfaces give it: dcomp_ppo_batch (dcomp_learner.h: position i is row i of the pointers) and
+// dcomp_sgd_batch (dcomp_learner_indexed.h: position i is source row index[i] of a whole sample batch, rows or compact record).
+struct BatchView {
+    bool indexed;
+    int32_t obs_format, num_active;
+    int64_t rows, source_rows;
+    const int32_t *index;
+    const void *obs;
+    const uint8_t *actions;
+    const float *old_logp, *old_logits, *advantages, *value_targets, *old_vf;
+    float *logp, *entropy, *kl, *vf, *ratio;
+    const float *dlogits, *dvalue;
+};
+
+// the grads (evaluate = false) and evaluate calls of both surfaces: every check on the host first
+static int learner_launch(const char *fn, bool evaluate, dcomp_learner *l, const BatchView *b, const dcomp_ppo_hyper *hy, float *stats, void *stream)
 {
     using namespace dlearn;
-    if (!l || !b) return fail(DCOMP_EINVAL, "%s: handle and batch must not be NULL", fn);
-    if (b->struct_size != (int32_t)sizeof(dcomp_ppo_batch))
-        return fail(DCOMP_EABI, "%s: caller's dcomp_ppo_batch has %d bytes, the library's %d", fn, b->struct_size, (int)sizeof(dcomp_ppo_batch));
     if (!evaluate) {
         if (!hy) return fail(DCOMP_EINVAL, "%s: hyper must not be NULL", fn);
         if (hy->struct_size != (int32_t)sizeof(dcomp_ppo_hyper))
@@ -753,29 +841,42 @@ static int learner_launch(const char *fn, bool evaluate, dcomp_learner *l, const
         if (!stats) return fail(DCOMP_EINVAL, "%s: stats_dev must not be NULL", fn);
         if (!(hy->clip_param >= 0.f) || !(hy->vf_clip_param >= 0.f)) return fail(DCOMP_EINVAL, "%s: clip_param %g / vf_clip_param %g must be >= 0", fn, hy->clip_param, hy->vf_clip_param);
     }
-    if (b->obs_format == DCOMP_ACTOR_COMPACT) return fail(DCOMP_EUNSUPPORTED, "%s: the compact record is not supported as learner input: pass observation rows", fn);
-    if (b->obs_format != DCOMP_ACTOR_ROWS) return fail(DCOMP_EINVAL, "%s: unknown obs_format %d", fn, b->obs_format);
+    const bool compact = b->indexed && b->obs_format == DCOMP_ACTOR_COMPACT;
+    if (b->obs_format == DCOMP_ACTOR_COMPACT && !b->indexed)
+        return fail(DCOMP_EUNSUPPORTED, "%s: the compact record is not supported as learner input: pass observation rows", fn);
+    if (b->obs_format != DCOMP_ACTOR_ROWS && !compact) return fail(DCOMP_EINVAL, "%s: unknown obs_format %d", fn, b->obs_format);
     if (!b->obs) return fail(DCOMP_EINVAL, "%s: batch.obs must not be NULL", fn);
     const bool upstream = b->dlogits || b->dvalue;
     if (evaluate) {
         if (!b->actions) return fail(DCOMP_EINVAL, "%s: batch.actions must not be NULL", fn);
         if (!b->logp && !b->entropy && !b->vf) return fail(DCOMP_EINVAL, "%s: none of batch.logp / entropy / vf is given: nothing to write", fn);
-        if (upstream) return fail(DCOMP_EINVAL, "%s: upstream gradients (batch.dlogits / dvalue) belong to dcomp_learner_grads", fn);
+        if (upstream) return fail(DCOMP_EINVAL, "%s: upstream gradients (batch.dlogits / dvalue) belong to the grads call", fn);
     } else if (upstream) {
         if (!b->dlogits || !b->dvalue) return fail(DCOMP_EINVAL, "%s: batch.dlogits and batch.dvalue come together: one of them is NULL", fn);
     } else if (!b->actions || !b->old_logp || !b->old_logits || !b->advantages || !b->value_targets || !b->old_vf) {
         return fail(DCOMP_EINVAL, "%s: a pointer of batch.actions / old_logp / old_logits / advantages / value_targets / old_vf is NULL", fn);
     }
     if (b->rows < 1) return fail(DCOMP_EINVAL, "%s: rows %lld < 1", fn, (long long)b->rows);
+    if (b->indexed) {
+        if (b->source_rows < 1 || b->source_rows > 0x7FFFFFFFll)
+            return fail(DCOMP_EINVAL, "%s: source_rows %lld outside [1, 2^31 - 1]", fn, (long long)b->source_rows);
+        if (!b->index && b->rows > b->source_rows)
+            return fail(DCOMP_EINVAL, "%s: without an index position i reads source row i: rows %lld > source_rows %lld", fn, (long long)b->rows, (long long)b->source_rows);
+    }
     // the handle, from here on
     if (b->rows > l->max_rows) return fail(DCOMP_EINVAL, "%s: rows %lld > max_rows %lld of the handle", fn, (long long)b->rows, (long long)l->max_rows);
     const dcomp_actor *a = l->a;
     const int U = a->net.U;
+    if (compact && !a->net.multi) return fail(DCOMP_EUNSUPPORTED, "%s: the compact record exists for multi-agent observations only", fn);
+    if (compact && b->source_rows % U)
+        return fail(DCOMP_EINVAL, "%s: the compact record holds whole envs: source_rows %lld is not a multiple of num_ue %d", fn, (long long)b->source_rows, U);
     if (b->num_active < 0 || b->num_active > U) return fail(DCOMP_EINVAL, "%s: num_active %d outside [0, %d]", fn, b->num_active, U);
+    if (b->indexed && a->net.multi && b->num_active != U)
+        return fail(DCOMP_EINVAL, "%s: num_active %d != num_ue %d: with multi-agent rows select the listed rows through the index (every position counts in 1 / N)", fn, b->num_active, U);
 
     hipStream_t s = static_cast<hipStream_t>(stream);
     LParams p = l->lp;
-    p.obs = b->obs; p.actions = b->actions; p.old_logp = b->old_logp; p.old_logits = b->old_logits; p.adv = b->advantages;
+    p.obs = static_cast<const float *>(b->obs); p.actions = b->actions; p.old_logp = b->old_logp; p.old_logits = b->old_logits; p.adv = b->advantages;
     p.vtarg = b->value_targets; p.old_vf = b->old_vf;
     p.o_logp = b->logp; p.o_ent = b->entropy; p.o_kl = b->kl; p.o_vf = b->vf; p.o_ratio = b->ratio;
     p.up_dlogits = b->dlogits; p.up_dvalue = b->dvalue;
@@ -784,7 +885,14 @@ static int learner_launch(const char *fn, bool evaluate, dcomp_learner *l, const
     if (hy) { p.clip = hy->clip_param; p.vf_clip = hy->vf_clip_param; p.vf_coeff = hy->vf_loss_coeff; p.ent_coeff = hy->entropy_coeff; p.kl_coeff = hy->kl_coeff; }
     const int64_t want = (p.tiles + WAVES - 1) / WAVES;
     const int grid = (int)(want < a->max_blocks ? want : a->max_blocks);
-    hipLaunchKernelGGL(pick(a->mt, a->relu != 0), dim3(grid), dim3(BLOCK), (size_t)a->net.lds_per_wave * WAVES, s, p);
+    if (b->indexed) {
+        IParams ip;
+        static_cast<LParams &>(ip) = p;
+        ip.index = b->index; ip.source_rows = b->source_rows; ip.compact = compact;
+        hipLaunchKernelGGL(pick_indexed(a->mt, a->relu != 0), dim3(grid), dim3(BLOCK), (size_t)a->net.lds_per_wave * WAVES, s, ip);
+    } else {
+        hipLaunchKernelGGL(pick(a->mt, a->relu != 0), dim3(grid), dim3(BLOCK), (size_t)a->net.lds_per_wave * WAVES, s, p);
+    }
     HIP_TRY(hipGetLastError());
     if (evaluate) return DCOMP_OK;
 
@@ -799,7 +907,8 @@ static int learner_launch(const char *fn, bool evaluate, dcomp_learner *l, const
 
     AParams ap = l->ap;
     ap.nchunks = nchunks; ap.tiles = p.tiles; ap.stats = stats; ap.want_stats = 1;
-    const int64_t counted = a->net.multi ? (b->rows / U) * b->num_active + (b->rows % U < b->num_active ? b->rows % U : b->num_active) : b->rows;
+    // the count behind 1 / N, on the host: indexed, every position (the index's contents cannot change it)
+    const int64_t counted = b->indexed || !a->net.multi ? b->rows : (b->rows / U) * b->num_active + (b->rows % U < b->num_active ? b->rows % U : b->num_active);
     ap.count = upstream ? 0. : (double)counted;
     ap.scale = upstream ? 1.f : (counted > 0 ? (float)(1.0 / (double)counted) : 0.f);
     ap.vf_coeff = p.vf_coeff; ap.ent_coeff = p.ent_coeff; ap.kl_coeff = p.kl_coeff;
@@ -808,14 +917,45 @@ static int learner_launch(const char *fn, bool evaluate, dcomp_learner *l, const
     return DCOMP_OK;
 }
 
+// the NULL and struct-size checks of a surface's batch, then its view
+static int ppo_launch(const char *fn, bool evaluate, dcomp_learner *l, const dcomp_ppo_batch *b, const dcomp_ppo_hyper *hy, float *stats, void *stream)
+{
+    if (!l || !b) return fail(DCOMP_EINVAL, "%s: handle and batch must not be NULL", fn);
+    if (b->struct_size != (int32_t)sizeof(dcomp_ppo_batch))
+        return fail(DCOMP_EABI, "%s: caller's dcomp_ppo_batch has %d bytes, the library's %d", fn, b->struct_size, (int)sizeof(dcomp_ppo_batch));
+    const BatchView v = {false, b->obs_format, b->num_active, b->rows, b->rows, nullptr, b->obs, b->actions, b->old_logp, b->old_logits, b->advantages,
+                         b->value_targets, b->old_vf, b->logp, b->entropy, b->kl, b->vf, b->ratio, b->dlogits, b->dvalue};
+    return learner_launch(fn, evaluate, l, &v, hy, stats, stream);
+}
+
+static int sgd_launch(const char *fn, bool evaluate, dcomp_learner *l, const dcomp_sgd_batch *b, const dcomp_ppo_hyper *hy, float *stats, void *stream)
+{
+    if (!l || !b) return fail(DCOMP_EINVAL, "%s: handle and batch must not be NULL", fn);
+    if (b->struct_size != (int32_t)sizeof(dcomp_sgd_batch))
+        return fail(DCOMP_EABI, "%s: caller's dcomp_sgd_batch has %d bytes, the library's %d", fn, b->struct_size, (int)sizeof(dcomp_sgd_batch));
+    const BatchView v = {true, b->obs_format, b->num_active, b->rows, b->source_rows, b->index, b->obs, b->actions, b->old_logp, b->old_logits, b->advantages,
+                         b->value_targets, b->old_vf, b->logp, b->entropy, b->kl, b->vf, b->ratio, b->dlogits, b->dvalue};
+    return learner_launch(fn, evaluate, l, &v, hy, stats, stream);
+}
+
 extern "C" int dcomp_learner_grads(dcomp_learner *l, const dcomp_ppo_batch *b, const dcomp_ppo_hyper *hy, float *stats_dev, void *stream)
 {
-    return learner_launch("dcomp_learner_grads", false, l, b, hy, stats_dev, stream);
+    return ppo_launch("dcomp_learner_grads", false, l, b, hy, stats_dev, stream);
 }
 
 extern "C" int dcomp_learner_evaluate(dcomp_learner *l, const dcomp_ppo_batch *b, void *stream)
 {
-    return learner_launch("dcomp_learner_evaluate", true, l, b, nullptr, nullptr, stream);
+    return ppo_launch("dcomp_learner_evaluate", true, l, b, nullptr, nullptr, stream);
+}
+
+extern "C" int dcomp_sgd_grads(dcomp_learner *l, const dcomp_sgd_batch *b, const dcomp_ppo_hyper *hy, float *stats_dev, void *stream)
+{
+    return sgd_launch("dcomp_sgd_grads", false, l, b, hy, stats_dev, stream);
+}
+
+extern "C" int dcomp_sgd_evaluate(dcomp_learner *l, const dcomp_sgd_batch *b, void *stream)
+{
+    return sgd_launch("dcomp_sgd_evaluate", true, l, b, nullptr, nullptr, stream);
 }
 
 extern "C" int dcomp_learner_apply(dcomp_learner *l, float lr, void *stream)

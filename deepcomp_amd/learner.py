@@ -9,8 +9,11 @@
     rllib_weights = learner.to_rllib_weights()
 
 Supported: ``multi`` and ``central``, tanh and relu, every hidden width the actor takes, the value function as a trunk of its own
-(``vf_share_layers=False``, PPO's default).  The shared value function and the compact record as learner input are refused
-(NotImplementedError); envs with UE arrival are refused by ``collect`` already.
+(``vf_share_layers=False``, PPO's default); ``update`` takes the batch as observation rows or as the compact record
+(``collect(compact=True)``, multi), whose minibatches it picks through a row index (``grads_indexed``): from a compact batch no
+observation row is ever written.  The shared value function is refused (NotImplementedError), and so is the
+compact record by ``grads`` / ``evaluate``, which take a contiguous minibatch of rows; envs with UE arrival are refused by ``collect``
+already.
 
 The arithmetic is the specification, spelled out here in torch / numpy on the CPU: ``ppo_loss_reference`` (RLlib's
 ppo_surrogate_loss and its gradients, as the float64 model and as the bf16 chain the kernels implement) and ``adam_reference``
@@ -297,6 +300,9 @@ class PPOLearner:
             raise ValueError(f"{rows} rows > max_rows {self.max_rows} of the learner")
         return rows
 
+    def _hyper_struct(self):
+        return _lib.DcompPpoHyper(ctypes.sizeof(_lib.DcompPpoHyper), *[self.hyper[n] for n in ('clip_param', 'vf_clip_param', 'vf_loss_coeff', 'entropy_coeff', 'kl_coeff')])
+
     def _batch(self, obs, rows, num_active, tensors):
         """dcomp_ppo_batch over checked tensors: tensors maps a field to (tensor or None, dtype, elements per row)."""
         a = self.actor
@@ -326,9 +332,8 @@ class PPOLearner:
         if stats is None:
             stats = torch.zeros(_lib.PPO_NUM_STATS, dtype=f32, device=self.device)
         a._check(stats, f32, _lib.PPO_NUM_STATS, 'stats')
-        hy = _lib.DcompPpoHyper(ctypes.sizeof(_lib.DcompPpoHyper), *[self.hyper[n] for n in ('clip_param', 'vf_clip_param', 'vf_loss_coeff', 'entropy_coeff', 'kl_coeff')])
         with torch.cuda.device(self.device):
-            _lib.check(self._L.dcomp_learner_grads(self._h, ctypes.byref(b), ctypes.byref(hy), ctypes.c_void_p(stats.data_ptr()), a._stream()))
+            _lib.check(self._L.dcomp_learner_grads(self._h, ctypes.byref(b), ctypes.byref(self._hyper_struct()), ctypes.c_void_p(stats.data_ptr()), a._stream()))
         return stats
 
     def evaluate(self, obs, actions, *, num_active=None):
@@ -342,6 +347,90 @@ class PPOLearner:
                                                 'vf': (vf, f32, 1)})
         with torch.cuda.device(self.device):
             _lib.check(self._L.dcomp_learner_evaluate(self._h, ctypes.byref(b), a._stream()))
+        return logp, entropy, vf
+
+    # ------------------------------------------------------------------ minibatches through a row index (include/dcomp_learner_indexed.h)
+    def _sgd_source(self, source, index):
+        """(obs tensor, obs_format, source rows, minibatch rows) of a flattened sample batch and an index, after their checks."""
+        a = self.actor
+        if not isinstance(source, dict) or ('obs' in source) == ('obs_compact' in source):
+            raise ValueError("source must be a dict that holds either 'obs' or 'obs_compact'")
+        if 'obs' in source:
+            obs, fmt = source['obs'], _lib.ACTOR_ROWS
+            if not isinstance(obs, torch.Tensor) or obs.numel() == 0 or obs.numel() % a.num_in:
+                raise ValueError(f"obs must hold a whole number of rows of {a.num_in} elements")
+            n_src = obs.numel() // a.num_in
+            a._check(obs, torch.float32, n_src * a.num_in, 'obs')
+        else:
+            obs, fmt = source['obs_compact'], _lib.ACTOR_COMPACT
+            n_src = a._batch(obs, True)[1]                                     # (central: NotImplementedError)
+        if n_src > 2 ** 31 - 1:
+            raise ValueError(f"{n_src} source rows > 2^31 - 1")
+        rows = n_src
+        if index is not None:
+            if not isinstance(index, torch.Tensor) or index.numel() == 0:
+                raise ValueError("index must be a non-empty contiguous int32 device tensor")
+            rows = index.numel()
+            a._check(index, torch.int32, rows, 'index')
+        if rows > self.max_rows:
+            raise ValueError(f"{rows} rows > max_rows {self.max_rows} of the learner")
+        return obs, fmt, n_src, rows
+
+    def _sgd_batch(self, where, source, index, num_active, wanted, outputs):
+        """dcomp_sgd_batch over checked tensors: where = _sgd_source(); wanted names the per-row inputs taken from source (source_rows
+        rows each), outputs maps a per-row output to (tensor or None, elements per row) (one row per minibatch position)."""
+        a = self.actor
+        obs, fmt, n_src, rows = where
+        f32, h, n3 = torch.float32, a.heads, a.num_logits
+        per_row = {'actions': (torch.uint8, h), 'old_logp': (f32, h), 'old_logits': (f32, n3), 'advantages': (f32, 1), 'value_targets': (f32, 1),
+                   'old_vf': (f32, 1), 'dlogits': (f32, n3), 'dvalue': (f32, 1)}
+        ptr = {}
+        for name in wanted:
+            t = source.get(name)
+            if t is not None:
+                a._check(t, per_row[name][0], n_src * per_row[name][1], name)
+                ptr[name] = t.data_ptr()
+        for name, (t, per) in outputs.items():
+            if t is not None:
+                a._check(t, f32, rows * per, name)
+                ptr[name] = t.data_ptr()
+        order = ('actions', 'old_logp', 'old_logits', 'advantages', 'value_targets', 'old_vf', 'dlogits', 'dvalue', 'logp', 'entropy', 'kl', 'vf', 'ratio')
+        return _lib.DcompSgdBatch(ctypes.sizeof(_lib.DcompSgdBatch), fmt, rows, n_src, index.data_ptr() if index is not None else None,
+                                  a.U if num_active is None else int(num_active), 0, obs.data_ptr(), *[ptr.get(n) for n in order])
+
+    def grads_indexed(self, source, index=None, *, num_active=None, logp=None, entropy=None, kl=None, vf=None, ratio=None, stats=None):
+        """grads() on the rows `index` picks out of a whole sample batch, without gathering them: source is a dict of the flattened
+        sample-batch tensors -- 'obs' float32 [source_rows, inputs] or 'obs_compact' int32 [envs, words] (multi: the record
+        collect(compact=True) returns; source row s is slot s % U of env s // U), and actions, old_logp, old_logits, advantages,
+        value_targets, old_vf (or dlogits with dvalue) with source_rows rows each.  index: a contiguous int32 device tensor of
+        minibatch positions -> source rows (None: every source row in order).  logp ... ratio: optional per-row outputs, one per
+        index entry.  The results are those of grads() on the gathered rows, bit for bit.  An index entry outside the sample batch is
+        not read: its position contributes zeros and still counts in the mean.  multi: num_active must stay the env's slots -- leave
+        the rows of unlisted slots out of the index.  Nothing synchronises."""
+        a = self.actor
+        f32 = torch.float32
+        b = self._sgd_batch(self._sgd_source(source, index), source, index, num_active,
+                            ('actions', 'old_logp', 'old_logits', 'advantages', 'value_targets', 'old_vf', 'dlogits', 'dvalue'),
+                            {'logp': (logp, a.heads), 'entropy': (entropy, 1), 'kl': (kl, 1), 'vf': (vf, 1), 'ratio': (ratio, 1)})
+        if stats is None:
+            stats = torch.zeros(_lib.PPO_NUM_STATS, dtype=f32, device=self.device)
+        a._check(stats, f32, _lib.PPO_NUM_STATS, 'stats')
+        with torch.cuda.device(self.device):
+            _lib.check(self._L.dcomp_sgd_grads(self._h, ctypes.byref(b), ctypes.byref(self._hyper_struct()), ctypes.c_void_p(stats.data_ptr()), a._stream()))
+        return stats
+
+    def evaluate_indexed(self, source, index=None, *, num_active=None):
+        """evaluate() on the rows `index` picks out of source ('obs' or 'obs_compact', and 'actions'): logp [rows, heads], the entropy
+        [rows] and the value predictions [rows], one row per index entry."""
+        a = self.actor
+        f32 = torch.float32
+        where = self._sgd_source(source, index)
+        rows = where[3]
+        logp = torch.empty((rows, a.heads), dtype=f32, device=self.device)
+        entropy, vf = torch.empty(rows, dtype=f32, device=self.device), torch.empty(rows, dtype=f32, device=self.device)
+        b = self._sgd_batch(where, source, index, num_active, ('actions',), {'logp': (logp, a.heads), 'entropy': (entropy, 1), 'vf': (vf, 1)})
+        with torch.cuda.device(self.device):
+            _lib.check(self._L.dcomp_sgd_evaluate(self._h, ctypes.byref(b), a._stream()))
         return logp, entropy, vf
 
     def apply(self, lr=None):
@@ -388,54 +477,70 @@ class PPOLearner:
 
     # ------------------------------------------------------------------ the training step
     def update(self, batch, num_sgd_iter=30, minibatch_rows=None, seed=0, num_active=None):
-        """PPO's SGD phase on one collect(..., dist_inputs=True) batch: the batch is flattened to rows, the advantages are
-        standardised over the batch (RLlib: (a - mean) / max(1e-4, std)), and per iteration a seeded device permutation splits the
-        rows into minibatches of minibatch_rows (default: the whole batch) gathered into buffers allocated once; each gets grads +
-        apply.  Afterwards the mean KL of the last iteration is read (the one synchronisation) and kl_coeff adapted by RLlib's rule.
-        num_active: listed UEs where fewer than the env's slots (multi: the other rows are dropped before the split).
-        Returns the last iteration's mean statistics and the new kl_coeff."""
+        """PPO's SGD phase on one collect(..., dist_inputs=True) batch, observation rows or the compact record (compact=True): the
+        batch is flattened to source rows, the advantages are standardised over the batch (RLlib: (a - mean) / max(1e-4, std)), and
+        per iteration a seeded device permutation splits the rows into minibatches of minibatch_rows (default: the whole batch);
+        each gets grads + apply.  A compact batch is trained where it lies: a minibatch is its slice of the permutation, handed to
+        grads_indexed as the row index -- no observation row is ever written.  A rows batch is gathered into buffers allocated once
+        and goes through grads: measured, the gather and contiguous reads beat scattered reads of whole rows at large batches
+        (profiles/r11_learner_indexed.txt); both ways give the same bits.  Afterwards the mean KL of the last iteration is read (the
+        one synchronisation) and kl_coeff adapted by RLlib's rule.  num_active: listed UEs where fewer than the env's slots (multi:
+        the other rows are dropped before the split).  Returns the last iteration's mean statistics and the new kl_coeff."""
         a = self.actor
         if 'action_dist_inputs' not in batch:
             raise ValueError("the batch has no action_dist_inputs: collect(..., dist_inputs=True)")
-        if 'obs' not in batch:
-            raise NotImplementedError("the compact record is not supported as learner input: collect(..., compact=False)")
         multi = a.kind == _lib.MULTI
-        src = {'obs': batch['obs'].reshape(-1, a.num_in), 'actions': batch['actions'].reshape(-1, a.heads),
-               'old_logp': batch['action_logp'].reshape(-1, a.heads), 'old_logits': batch['action_dist_inputs'].reshape(-1, a.num_logits),
-               'advantages': batch['advantages'].reshape(-1), 'value_targets': batch['value_targets'].reshape(-1), 'old_vf': batch['vf_preds'].reshape(-1)}
-        N = src['obs'].shape[0]
+        compact = 'obs' not in batch
+        if compact and not multi:
+            raise NotImplementedError("compact observation records exist for multi-agent observations only")
+        src = {'actions': batch['actions'].reshape(-1, a.heads), 'old_logp': batch['action_logp'].reshape(-1, a.heads),
+               'old_logits': batch['action_dist_inputs'].reshape(-1, a.num_logits), 'advantages': batch['advantages'].reshape(-1),
+               'value_targets': batch['value_targets'].reshape(-1), 'old_vf': batch['vf_preds'].reshape(-1)}
+        if not compact:
+            src['obs'] = batch['obs'].reshape(-1, a.num_in)
+        N = src['actions'].shape[0]
         if any(t.shape[0] != N for t in src.values()):
             raise ValueError("the batch's tensors disagree about the number of rows")
-        kernel_active = None
+        if compact:
+            src['obs_compact'] = batch['obs_compact'].reshape(-1, batch['obs_compact'].shape[-1])      # [T, E, words], contiguous: env t E + e
+            if src['obs_compact'].shape[0] * a.U != N:
+                raise ValueError("the batch's tensors disagree about the number of rows")
+        kernel_active, keep = None, None
         if num_active is not None and int(num_active) < a.U:
             if multi:
                 keep = torch.nonzero(torch.arange(N, device=self.device) % a.U < int(num_active)).reshape(-1)
-                src = {k: t.index_select(0, keep) for k, t in src.items()}
                 N = int(keep.numel())
+                if not compact:
+                    src = {k: t.index_select(0, keep) for k, t in src.items()}
             else:
                 kernel_active = int(num_active)
-        adv = src['advantages']
-        src['advantages'] = (adv - adv.mean()) / adv.std(unbiased=False).clamp_min(1e-4)
+        adv = src['advantages'] if keep is None or not compact else src['advantages'].index_select(0, keep)
+        adv = (adv - adv.mean()) / adv.std(unbiased=False).clamp_min(1e-4)
+        # (compact: the standardised advantages back in source order, where the index finds them)
+        src['advantages'] = adv if keep is None or not compact else torch.zeros_like(src['advantages']).index_copy_(0, keep, adv)
         mb = N if minibatch_rows is None else min(int(minibatch_rows), N)
         if mb > self.max_rows:
             raise ValueError(f"minibatches of {mb} rows > max_rows {self.max_rows} of the learner")
-        if mb not in self._mb:
+        if not compact and mb not in self._mb:
             self._mb = {mb: {k: torch.empty((mb,) + tuple(t.shape[1:]), dtype=t.dtype, device=self.device) for k, t in src.items()}}
-        buf = self._mb[mb]
         starts = list(range(0, N, mb))
         stats = torch.zeros((len(starts), _lib.PPO_NUM_STATS), dtype=torch.float32, device=self.device)
         gen = torch.Generator(device=self.device)
         gen.manual_seed(int(seed))
         for _ in range(int(num_sgd_iter)):
             perm = torch.randperm(N, generator=gen, device=self.device)
+            if compact:
+                index = (perm if keep is None else keep.index_select(0, perm)).to(torch.int32)
             for i, s in enumerate(starts):
-                idx = perm[s:s + mb]
-                n = int(idx.numel())
-                view = {k: t[:n] for k, t in buf.items()}
-                for k in src:
-                    torch.index_select(src[k], 0, idx, out=view[k])
-                self.grads(view['obs'], view['actions'], view['old_logp'], view['old_logits'], view['advantages'], view['value_targets'], view['old_vf'],
-                           num_active=kernel_active, stats=stats[i])
+                if compact:
+                    self.grads_indexed(src, index[s:s + mb], stats=stats[i])
+                else:
+                    idx = perm[s:s + mb]
+                    view = {k: t[:int(idx.numel())] for k, t in self._mb[mb].items()}
+                    for k in src:
+                        torch.index_select(src[k], 0, idx, out=view[k])
+                    self.grads(view['obs'], view['actions'], view['old_logp'], view['old_logits'], view['advantages'], view['value_targets'], view['old_vf'],
+                               num_active=kernel_active, stats=stats[i])
                 self.apply()
         mean = stats.mean(0).cpu().numpy()
         out = {n: float(mean[i]) for i, n in enumerate(STATS)}

@@ -16,7 +16,8 @@
  *
  * Supported: DCOMP_MULTI and DCOMP_CENTRAL, tanh and relu, any hidden width the actor takes, a value trunk of its own
  * (vf_share_layers=False, PPO's default).  The shared value (dcomp_actor_value_cfg.shared = 1) and the compact record as learner
- * input are refused with DCOMP_EUNSUPPORTED.
+ * input are refused with DCOMP_EUNSUPPORTED by the calls here, which take a contiguous minibatch of rows; dcomp_learner_indexed.h has
+ * the calls that pick a minibatch through a row index out of a whole sample batch, rows or compact record.
  *
  * Every struct carries its own size as its first field (anything else -> DCOMP_EABI); DCOMP_ABI_VERSION is unaffected.  Errors are
  * reported through dcomp_last_error().  Everything is validated on the host before the first HIP call. */

@@ -1,0 +1,140 @@
+"""CPU-side checks of the learner's indexed minibatches (include/dcomp_learner_indexed.h, deepcomp_amd/learner.py): the two entry points
+exist and are declared, the ctypes mirror matches the header, the header compiles as C alone and next to the other two, and every
+argument the library can judge without its handle is refused on the host before the first HIP call -- with a fake handle that is
+never dereferenced.  The refusals that read the handle (rows > max_rows, the compact record with a central handle, source rows that
+are not whole envs, num_active of a multi-agent handle) are in tests/test_learner_indexed_gpu.py.  No GPU compute is called here."""
+import ctypes
+import os
+import re
+import subprocess
+
+import pytest
+
+REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+OK, EINVAL, EUNSUPPORTED, EABI = 0, -1, -6, -7
+HEADER = os.path.join(REPO, 'include', 'dcomp_learner_indexed.h')
+
+
+@pytest.fixture(scope='module')
+def lib():
+    from deepcomp_amd import build, _lib
+    build.build()                      # hipcc cross-compiles gfx950 on a GPU-less host
+    return _lib.load()
+
+
+def test_symbols_are_exported_and_declared(lib):
+    from deepcomp_amd import _lib
+    hdr = open(HEADER).read()
+    assert _lib.SGD_EXPORTS == ['dcomp_sgd_grads', 'dcomp_sgd_evaluate']
+    for name in _lib.SGD_EXPORTS:
+        assert re.search(r'\bint %s\s*\(' % name, hdr), name
+        getattr(lib, name)
+        assert name not in _lib.EXPORTS and name not in _lib.LEARNER_EXPORTS
+    assert sorted(re.findall(r'\bint (dcomp_\w+)\s*\(', hdr)) == sorted(_lib.SGD_EXPORTS)
+    # the surfaces the existing tests pin are as they were
+    assert len(_lib.LEARNER_EXPORTS) == 7 and len(_lib.EXPORTS) == 42
+    assert not re.search(r'dcomp_sgd_', open(os.path.join(REPO, 'include', 'dcomp_learner.h')).read())
+
+
+def test_ctypes_mirror_matches_the_header(tmp_path):
+    """Member names from the header text, sizes from a C program compiled against it (C99, pedantic); dcomp_ppo_batch keeps its size."""
+    from deepcomp_amd import _lib
+    txt = re.sub(r'/\*.*?\*/', '', open(HEADER).read(), flags=re.S)
+    body = re.search(r'typedef struct dcomp_sgd_batch \{(.*?)\} dcomp_sgd_batch;', txt, flags=re.S).group(1)
+    members = [re.split(r'[\s*]+', m.strip())[-1] for decl in body.split(';') if decl.strip() for m in decl.split(',')]
+    assert members == [f[0] for f in _lib.DcompSgdBatch._fields_], members
+    inc = os.path.join(REPO, 'include')
+    gcc = ['gcc', '-std=c99', '-Wall', '-Wextra', '-Werror', '-pedantic', '-I', inc]
+    src = tmp_path / 'sizes.c'
+    src.write_text('#include <stdio.h>\n#include <stddef.h>\n#include "dcomp_learner_indexed.h"\n'
+                   'int main(void) {\n'
+                   '    printf("%zu %zu %zu %zu %zu\\n", sizeof(dcomp_sgd_batch), sizeof(dcomp_ppo_batch), offsetof(dcomp_sgd_batch, index),\n'
+                   '           offsetof(dcomp_sgd_batch, obs), offsetof(dcomp_sgd_batch, ratio));\n'
+                   '    return 0;\n'
+                   '}\n')
+    subprocess.run(gcc + ['-fsyntax-only', str(src)], check=True)                      # alone
+    for n, text in enumerate(('#include "dcomp.h"\n#include "dcomp_learner.h"\n#include "dcomp_learner_indexed.h"\n',
+                              '#include "dcomp_learner_indexed.h"\n#include "dcomp_learner.h"\n#include "dcomp.h"\n')):
+        both = tmp_path / f'both{n}.c'                                                 # with the other two public headers, either order
+        both.write_text(text + 'int main(void) { return DCOMP_EABI == -7 && DCOMP_ACTOR_COMPACT == 1 ? 0 : 1; }\n')
+        subprocess.run(gcc + ['-fsyntax-only', str(both)], check=True)
+    exe = tmp_path / 'sizes'
+    subprocess.run(['gcc', '-std=c99', '-I', inc, '-o', str(exe), str(src)], check=True)
+    sizes = [int(x) for x in subprocess.run([str(exe)], check=True, stdout=subprocess.PIPE, text=True).stdout.split()]
+    S = _lib.DcompSgdBatch
+    assert sizes == [ctypes.sizeof(S), ctypes.sizeof(_lib.DcompPpoBatch), S.index.offset, S.obs.offset, S.ratio.offset]
+    assert ctypes.sizeof(_lib.DcompPpoBatch) == 24 + 14 * 8                           # (as before this header existed)
+
+
+_FIELDS = ('obs', 'actions', 'old_logp', 'old_logits', 'advantages', 'value_targets', 'old_vf', 'dlogits', 'dvalue', 'logp', 'entropy', 'kl', 'vf', 'ratio')
+_LOSS_INPUTS = _FIELDS[:7]
+
+
+def _batch(given=_LOSS_INPUTS, size=None, fmt=0, rows=8, source_rows=64, index=4096, num_active=1):
+    from deepcomp_amd import _lib
+    return _lib.DcompSgdBatch(ctypes.sizeof(_lib.DcompSgdBatch) if size is None else size, fmt, rows, source_rows, index, num_active, 0,
+                              *[4096 if n in given else None for n in _FIELDS])          # (never dereferenced)
+
+
+def _hyper(size=None, clip=0.3, vf_clip=10.0):
+    from deepcomp_amd import _lib
+    return _lib.DcompPpoHyper(ctypes.sizeof(_lib.DcompPpoHyper) if size is None else size, clip, vf_clip, 1.0, 0.0, 0.2)
+
+
+def test_grads_refuses_bad_arguments_on_the_host(lib):
+    from deepcomp_amd import _lib
+    fake = ctypes.c_void_p(4096)
+    err = lib.dcomp_last_error
+    g = lambda l, b, h, s: lib.dcomp_sgd_grads(l, ctypes.byref(b) if b is not None else None, ctypes.byref(h) if h is not None else None, s, None)      # noqa: E731
+    assert g(None, _batch(), _hyper(), fake) == EINVAL and b'handle' in err()
+    assert g(fake, None, _hyper(), fake) == EINVAL
+    assert g(fake, _batch(), None, fake) == EINVAL and b'hyper' in err()
+    assert g(fake, _batch(), _hyper(), None) == EINVAL and b'stats_dev' in err()
+    for size in (0, ctypes.sizeof(_lib.DcompPpoBatch), ctypes.sizeof(_lib.DcompSgdBatch) + 8):
+        assert g(fake, _batch(size=size), _hyper(), fake) == EABI and b'dcomp_sgd_batch' in err()
+    assert g(fake, _batch(), _hyper(size=8), fake) == EABI and b'dcomp_ppo_hyper' in err()
+    assert g(fake, _batch(), _hyper(clip=-0.1), fake) == EINVAL and b'clip_param' in err()
+    assert g(fake, _batch(), _hyper(vf_clip=float('nan')), fake) == EINVAL
+    assert g(fake, _batch(fmt=2), _hyper(), fake) == EINVAL and b'obs_format' in err()
+    assert g(fake, _batch(fmt=-1), _hyper(), fake) == EINVAL
+    for fmt in (0, 1):                                                    # rows and the compact record: the same checks up to the handle
+        assert g(fake, _batch(given=_LOSS_INPUTS[1:], fmt=fmt), _hyper(), fake) == EINVAL and b'obs' in err()
+        for missing in _LOSS_INPUTS[1:]:
+            rc = g(fake, _batch(given=[n for n in _LOSS_INPUTS if n != missing], fmt=fmt), _hyper(), fake)
+            assert rc == EINVAL and b'NULL' in err(), missing
+        assert g(fake, _batch(given=('obs', 'dlogits'), fmt=fmt), _hyper(), fake) == EINVAL and b'together' in err()
+        assert g(fake, _batch(given=('obs', 'dvalue'), fmt=fmt), _hyper(), fake) == EINVAL
+        assert g(fake, _batch(rows=0, fmt=fmt), _hyper(), fake) == EINVAL and b'rows' in err()
+        assert g(fake, _batch(given=('obs', 'dlogits', 'dvalue'), rows=-1, fmt=fmt), _hyper(), fake) == EINVAL
+        assert g(fake, _batch(source_rows=0, fmt=fmt), _hyper(), fake) == EINVAL and b'source_rows' in err()
+        assert g(fake, _batch(source_rows=-5, fmt=fmt), _hyper(), fake) == EINVAL
+        assert g(fake, _batch(source_rows=2 ** 31, fmt=fmt), _hyper(), fake) == EINVAL and b'2^31' in err()
+        assert g(fake, _batch(rows=65, source_rows=64, index=None, fmt=fmt), _hyper(), fake) == EINVAL and b'index' in err()
+
+
+def test_evaluate_refuses_bad_arguments_on_the_host(lib):
+    fake = ctypes.c_void_p(4096)
+    err = lib.dcomp_last_error
+    ev = lambda l, b: lib.dcomp_sgd_evaluate(l, ctypes.byref(b) if b is not None else None, None)      # noqa: E731
+    ok = ('obs', 'actions', 'logp')
+    assert ev(None, _batch(given=ok)) == EINVAL
+    assert ev(fake, None) == EINVAL
+    assert ev(fake, _batch(given=ok, size=16)) == EABI and b'dcomp_sgd_batch' in err()
+    assert ev(fake, _batch(given=ok, fmt=3)) == EINVAL and b'obs_format' in err()
+    assert ev(fake, _batch(given=('actions', 'logp'))) == EINVAL and b'obs' in err()
+    assert ev(fake, _batch(given=('obs', 'logp'))) == EINVAL and b'actions' in err()
+    assert ev(fake, _batch(given=('obs', 'actions'))) == EINVAL and b'nothing to write' in err()
+    assert ev(fake, _batch(given=('obs', 'actions', 'vf', 'dlogits', 'dvalue'))) == EINVAL and b'upstream' in err()
+    assert ev(fake, _batch(given=('obs', 'actions', 'vf'), rows=0)) == EINVAL
+    assert ev(fake, _batch(given=('obs', 'actions', 'vf'), source_rows=0, fmt=1)) == EINVAL and b'source_rows' in err()
+    assert ev(fake, _batch(given=('obs', 'actions', 'vf'), rows=9, source_rows=8, index=None)) == EINVAL
+
+
+def test_the_pinned_surface_still_refuses_the_compact_record(lib):
+    """dcomp_learner_grads / _evaluate take a contiguous minibatch of rows: the compact record stays DCOMP_EUNSUPPORTED there."""
+    from deepcomp_amd import _lib
+    fake = ctypes.c_void_p(4096)
+    b = _lib.DcompPpoBatch(ctypes.sizeof(_lib.DcompPpoBatch), 1, 8, 1, 0, *([4096] * 7 + [None] * 7))
+    assert lib.dcomp_learner_grads(fake, ctypes.byref(b), ctypes.byref(_hyper()), fake, None) == EUNSUPPORTED and b'compact' in lib.dcomp_last_error()
+    b = _lib.DcompPpoBatch(ctypes.sizeof(_lib.DcompPpoBatch), 1, 8, 1, 0, *([4096] * 2 + [None] * 5 + [4096] + [None] * 6))
+    assert lib.dcomp_learner_evaluate(fake, ctypes.byref(b), None) == EUNSUPPORTED

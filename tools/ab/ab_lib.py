@@ -12,7 +12,8 @@
 
 Workloads: BASELINE config 3 (65 536 x 32 x 10 multi, one launch per step), config 2 through the fused rollout (4 096 x 10 x 5
 central, 100 steps per launch, every step's outputs), one GPU's share of config 5 (4 096 x 128 x 32) and of config 4
-(32 768 x 32 x 10), 65 536 x 10 x 5 central, 65 536 x 32 x 10 central, the closed policy loop at config 2."""
+(32 768 x 32 x 10), 65 536 x 10 x 5 central, 65 536 x 32 x 10 central, the closed policy loop at config 2; learner_c3 / learner_c2:
+PPOLearner grads + apply on one minibatch of 65 536 x 32 multi rows / 4 096 central rows (libraries from round 9 on)."""
 import argparse
 import json
 import os
@@ -45,7 +46,8 @@ def build(a):
         o = os.path.join(objdir, f'b{b}.o')
         procs.append((o, subprocess.Popen(['hipcc'] + flags + [f'-DDCOMP_B={b}', '-c', os.path.join(csrc, 'dcomp_inst.hip'), '-o', o],
                                           stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)))
-    for name in ('api', 'big'):                  # the ABI + dispatch, and the generic kernel dcomp_api.hip links against (round 5 on)
+    # the ABI + dispatch, the generic kernel dcomp_api.hip links against (round 5 on), the fcnet actor and the PPO learner (rounds 7, 9 on)
+    for name in ('api', 'big', 'actor', 'learner'):
         if not os.path.exists(os.path.join(csrc, f'dcomp_{name}.hip')):
             continue
         o = os.path.join(objdir, f'{name}.o')
@@ -63,7 +65,41 @@ def build(a):
     print(so, os.path.getsize(so) >> 20, 'MiB')
 
 
-WORKLOADS = ['big64', 'big40c', 'c3', 'c2roll', 'c5', 'c5mid', 'c5big', 'c4share', 'c4big', 'central10x5', 'central10x5roll', 'central10x5f', 'central32x10', 'c2policy', 'c3rf', 'c3roll']
+WORKLOADS = ['big64', 'big40c', 'c3', 'c2roll', 'c5', 'c5mid', 'c5big', 'c4share', 'c4big', 'central10x5', 'central10x5roll', 'central10x5f', 'central32x10', 'c2policy', 'c3rf', 'c3roll',
+             'learner_c3', 'learner_c2']
+
+
+def measure_learner(torch, dev, kind, E, U, B, n):
+    """PPOLearner grads + apply on one minibatch of E envs' rows (2 x 256 tanh, a value trunk of its own; synthetic inputs: the time
+    does not depend on the values), ms per step over n back-to-back steps, through dcomp_learner_grads -- the entry point every
+    library since round 9 has."""
+    from deepcomp_amd.actor import FcnetActor
+    from deepcomp_amd.learner import PPOLearner
+    actor = FcnetActor(kind, U, B, FcnetActor.random_weights(kind, U, B, 256, seed=0), device=dev,
+                       value_weights=FcnetActor.random_value_weights(kind, U, B, 256, seed=0))
+    rows = E * U if kind == 'multi' else E
+    learner = PPOLearner(actor, lr=5e-5, max_rows=rows)
+    g = torch.Generator(device=dev).manual_seed(3)
+    r = lambda *shape: torch.rand(shape, generator=g, device=dev)                 # noqa: E731
+    obs, logits = r(rows, actor.num_in), r(rows, actor.num_logits)
+    act = torch.randint(0, B + 1, (rows, actor.heads), generator=g, device=dev, dtype=torch.uint8)
+    olp = torch.log_softmax(logits.view(rows, actor.heads, B + 1), -1).gather(-1, act.long().unsqueeze(-1)).squeeze(-1).contiguous()
+    adv, vt, ovf = r(rows) - 0.5, r(rows), r(rows)
+    stats = torch.zeros(5, device=dev)
+
+    def step():
+        learner.grads(obs, act, olp, logits, adv, vt, ovf, stats=stats)
+        learner.apply()
+    for _ in range(3):
+        step()
+    torch.cuda.synchronize()
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    for _ in range(n):
+        step()
+    e1.record()
+    torch.cuda.synchronize()
+    return e0.elapsed_time(e1) / n
 
 
 def measure(a):
@@ -100,6 +136,10 @@ def measure(a):
             out[w] = bench.measure_steps(*mk, 65536, 10, 5, 'central')['kernel_ms']
         elif w == 'central32x10':
             out[w] = bench.measure_steps(*mk, 65536, 32, 10, 'central')['kernel_ms']
+        elif w == 'learner_c3':                    # profiles/r09_learner.txt: one minibatch of 65 536 x 32 rows, multi
+            out[w] = measure_learner(torch, dev, 'multi', 65536, 32, 10, 10)
+        elif w == 'learner_c2':                    # ... and of 4 096 central rows
+            out[w] = measure_learner(torch, dev, 'central', 4096, 10, 5, 200)
         elif w in ('central10x5f', 'c3roll'):      # the fused rollout kernel forced onto a big batch, ONE step per launch
             os.environ['DCOMP_FUSE_MAX_WAVES'] = '100000000'
             E, U, B, kind = (65536, 10, 5, 'central') if w == 'central10x5f' else (65536, 32, 10, 'multi')

@@ -6,7 +6,7 @@ this only shows where the time goes once the env runs at ~10^8-10^9 env-steps/s.
 
     python tools/closed_loop.py [--envs 65536] [--steps 200] [--dtype bf16] [--kind multi] [--actor hip [--compact]]
     python tools/closed_loop.py --collect 50 [--envs 65536] [--kind multi] [--compact] [--shared-value]
-    python tools/closed_loop.py --train 3 [--train-steps 5] [--sgd-iters 2] [--minibatch ROWS] [--envs 65536] [--kind multi]
+    python tools/closed_loop.py --train 3 [--train-steps 5] [--sgd-iters 2] [--minibatch ROWS] [--envs 65536] [--kind multi] [--compact]
 
 --actor torch (default): the actor as torch ops (bf16 matmuls, Gumbel-max through torch.rand).  --actor hip: the same weights in
 deepcomp_amd.actor.FcnetActor -- one HIP kernel from observation tensor to action tensor -- and BOTH loops are timed in this
@@ -20,7 +20,11 @@ interleaved, --steps / T batches each.
 
 --train ITERS: the whole PPO loop in this process -- sampler.collect(dist_inputs=True) then deepcomp_amd.learner.PPOLearner.update --
 printing the mean reward and the five loss statistics per iteration; then the time of grads + apply per minibatch (HIP events over
-back-to-back launches) next to the same network and loss under torch autograd with bf16 autocast and torch.optim.Adam, interleaved.
+back-to-back launches) next to the same network and loss under torch autograd with bf16 autocast and torch.optim.Adam, interleaved;
+and the time of one SGD iteration of update on the rows batch (minibatches gathered with index_select, then grads) next to the same
+iteration with the minibatches picked through a row index instead (grads_indexed: nothing is copied, rows are read scattered).
+--compact (multi-agent): collect returns the compact record and update trains on it through the row index -- no observation row is
+written anywhere in the loop; the unpack a rows-only learner would need first is timed on its own.
 """
 import argparse
 import sys
@@ -161,14 +165,21 @@ def train_mode(iters):
     learner = PPOLearner(hip, lr=5e-5, max_rows=mb)
     env.reset()
     buf = None
-    print(f'{E} envs x {U} UE x {B} BS ({a.kind}), 2x256 tanh + value trunk, batches of T = {T} ({T * rows} rows), {a.sgd_iters} SGD iterations, minibatches of {mb}')
+    print(f'{E} envs x {U} UE x {B} BS ({a.kind}), 2x256 tanh + value trunk, batches of T = {T} ({T * rows} rows), {a.sgd_iters} SGD iterations, minibatches of {mb}'
+          + (', compact record' if a.compact else ''))
     for it in range(iters):
-        buf = collect(env, hip, T, 0.99, 0.95, out=buf, dist_inputs=True)
+        buf = collect(env, hip, T, 0.99, 0.95, out=buf, dist_inputs=True, compact=a.compact)
         st = learner.update(buf, num_sgd_iter=a.sgd_iters, minibatch_rows=mb, seed=it)
         print(f'iter {it}: mean reward {float(buf["rewards"].mean()):+.4f}  ' + '  '.join(f'{n} {st[n]:+.5f}' for n in STATS) + f'  kl_coeff {st["kl_coeff"]:.3f}')
 
     # ---- grads + apply on one minibatch against torch autograd (bf16 autocast) + torch.optim.Adam on the same network and loss
-    f = lambda k, w: buf[k].reshape(-1, w)[:mb].contiguous()             # noqa: E731
+    rows_buf = buf
+    if a.compact:                                                        # the contiguous-minibatch calls below take rows
+        from deepcomp_amd.fragment import FragmentCodec
+        codec = FragmentCodec(U, B, dev)
+        rows_buf = {k: t for k, t in buf.items() if k != 'obs_compact'}
+        rows_buf['obs'] = codec.unpack(buf['obs_compact'])
+    f = lambda k, w: rows_buf[k].reshape(-1, w)[:mb].contiguous()        # noqa: E731
     obs, act = f('obs', D), f('actions', heads)
     olp, ologits = f('action_logp', heads), f('action_dist_inputs', heads * (B + 1))
     adv, vt, ovf = (buf[k].reshape(-1)[:mb].contiguous() for k in ('advantages', 'value_targets', 'vf_preds'))
@@ -225,6 +236,51 @@ def train_mode(iters):
     print('PPOLearner grads + apply                      : ' + ' / '.join(f'{t:.0f}' for t in res['hip']) + ' us')
     print('torch autograd (bf16 autocast) + Adam         : ' + ' / '.join(f'{t:.0f}' for t in res['torch']) + ' us')
     print(f'torch / PPOLearner: {min(res["torch"]) / min(res["hip"]):.2f} x')
+
+    # ---- one SGD iteration of update: gathered minibatches (rows), a row index into the rows where they lie, a row index into the record
+    N = T * rows
+    flat = {'obs': rows_buf['obs'].reshape(-1, D), 'actions': rows_buf['actions'].reshape(-1, heads), 'old_logp': rows_buf['action_logp'].reshape(-1, heads),
+            'old_logits': rows_buf['action_dist_inputs'].reshape(-1, heads * (B + 1)), 'advantages': rows_buf['advantages'].reshape(-1),
+            'value_targets': rows_buf['value_targets'].reshape(-1), 'old_vf': rows_buf['vf_preds'].reshape(-1)}
+    gen = torch.Generator(device=dev)
+
+    def indexed_iteration():
+        """update's iteration on the rows batch with grads_indexed in place of the gather"""
+        src = dict(flat)
+        adv_ = src['advantages']
+        src['advantages'] = (adv_ - adv_.mean()) / adv_.std(unbiased=False).clamp_min(1e-4)
+        starts = list(range(0, N, mb))
+        st = torch.zeros((len(starts), 5), device=dev)
+        gen.manual_seed(0)
+        index = torch.randperm(N, generator=gen, device=dev).to(torch.int32)
+        for i, s0 in enumerate(starts):
+            learner.grads_indexed(src, index[s0:s0 + mb], stats=st[i])
+            learner.apply()
+        return st.mean(0).cpu()
+
+    def wall(fn, k):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        for _ in range(k):
+            fn()
+        torch.cuda.synchronize()
+        return (time.perf_counter() - t0) * 1e6 / k
+
+    k = max(2, min(20, a.steps))
+    variants = [('update, rows batch (gathered minibatches)', lambda: learner.update(rows_buf, num_sgd_iter=1, minibatch_rows=mb, seed=0)),
+                ('the same through a row index (grads_indexed)', indexed_iteration)]
+    if a.compact:
+        variants.append(('update, compact batch (row index)', lambda: learner.update(buf, num_sgd_iter=1, minibatch_rows=mb, seed=0)))
+        variants.append(('unpack of the compact batch to rows', lambda: codec.unpack(buf['obs_compact'], out=rows_buf['obs'])))
+    for _, fn in variants:
+        wall(fn, 1)
+    times = {name: [] for name, _ in variants}
+    for _ in range(3):
+        for name, fn in variants:
+            times[name].append(wall(fn, k))
+    print(f'one SGD iteration over {N} rows in minibatches of {mb}, {k} iterations per timing, wall clock with the final read of the statistics')
+    for name, _ in variants:
+        print(f'{name:<46}: ' + ' / '.join(f'{t:.0f}' for t in times[name]) + ' us')
     env.check()
 
 
