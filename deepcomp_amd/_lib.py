@@ -142,6 +142,15 @@ class DcompSgdBatch(ctypes.Structure):
                                                'dlogits', 'dvalue', 'logp', 'entropy', 'kl', 'vf', 'ratio')]
 
 
+# include/dcomp_policy_set.h: one policy per UE slot over existing actor handles (D3-CoMP), one actor launch
+SET_EXPORTS = ['dcomp_policy_set_create', 'dcomp_policy_set_destroy', 'dcomp_policy_set_actions', 'dcomp_policy_set_actions_v']
+
+
+class DcompPolicySetCfg(ctypes.Structure):
+    _fields_ = [('struct_size', ctypes.c_int32), ('num_policies', ctypes.c_int32), ('members', ctypes.POINTER(ctypes.c_void_p)),
+                ('slot_policy', _ip)]
+
+
 class DcompPpoHyper(ctypes.Structure):
     _fields_ = [('struct_size', ctypes.c_int32), ('clip_param', ctypes.c_float), ('vf_clip_param', ctypes.c_float),
                 ('vf_loss_coeff', ctypes.c_float), ('entropy_coeff', ctypes.c_float), ('kl_coeff', ctypes.c_float)]
@@ -242,6 +251,13 @@ def load():
         L.dcomp_sgd_grads.argtypes = [vp, ctypes.POINTER(DcompSgdBatch), ctypes.POINTER(DcompPpoHyper), vp, vp]
         L.dcomp_sgd_evaluate.argtypes = [vp, ctypes.POINTER(DcompSgdBatch), vp]
         for name in SGD_EXPORTS:
+            getattr(L, name)
+    if hasattr(L, 'dcomp_policy_set_create') or not os.environ.get('DCOMP_LIB'):
+        L.dcomp_policy_set_create.argtypes = [ctypes.POINTER(DcompPolicySetCfg), ctypes.POINTER(vp)]
+        L.dcomp_policy_set_destroy.argtypes = [vp]
+        L.dcomp_policy_set_actions.argtypes = [vp, ctypes.POINTER(DcompActorRun), vp, vp, vp]
+        L.dcomp_policy_set_actions_v.argtypes = [vp, ctypes.POINTER(DcompActorRun), vp, vp, vp, vp]
+        for name in SET_EXPORTS:
             getattr(L, name)
     for name in EXPORTS:
         getattr(L, name)

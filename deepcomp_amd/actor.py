@@ -9,8 +9,8 @@ the activations kept on chip, and out comes the uint8 action tensor ``env.step``
     act = actor.act(env)                               # uint8 [E, U], feed straight into env.step(act)
 
 ``multi``: one decision row per (env, UE slot), the weights shared across UEs (DD-CoMP), one categorical head of B + 1 actions.
-``central``: one row per env, U heads (MultiDiscrete, central.py:28).  D3-CoMP's per-UE networks are not covered; training is
-deepcomp_amd.learner.PPOLearner, on this actor's handle.
+``central``: one row per env, U heads (MultiDiscrete, central.py:28).  D3-CoMP's per-UE networks are a set over such actors, run in
+one launch: deepcomp_amd.policy_set.PerUEActor.  Training is deepcomp_amd.learner.PPOLearner, on this actor's handle.
 
 The value function of a PPO policy rides in the same launch once attached (``value_weights=`` / ``set_value``): RLlib's fcnet has it
 as a trunk of its own (``fc_value_1``, ``fc_value_2``, ``value_out``: PPO's default, vf_share_layers=False) or as ``value_out`` on
@@ -62,7 +62,93 @@ def gumbel_noise(philox, seed, step, rows, heads, num_actions):
     return -np.log(-np.log(u.astype(np.float64)))
 
 
-class FcnetActor:
+class _ActorLaunch:
+    """The launch side of an actor handle: the pointer, dtype and size checks and the one launch.  FcnetActor has it, and so has the
+    per-UE set of such actors (deepcomp_amd.policy_set.PerUEActor), whose entry points take the same arguments.  A subclass provides
+    kind, U, B, heads, num_logits, num_in, device, value_weights, _L and _h."""
+    _ACTIONS, _ACTIONS_V = 'dcomp_actor_actions', 'dcomp_actor_actions_v'
+
+    def _stream(self):
+        return ctypes.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+
+    def _check(self, t, dtype, numel, what):
+        """The kernel gets raw pointers: a wrong dtype / device / size would read or write out of bounds on the device."""
+        if not isinstance(t, torch.Tensor) or t.dtype != dtype or t.device != self.device or not t.is_contiguous() or t.numel() != numel:
+            raise ValueError(f"{what} must be a contiguous {dtype} tensor with {numel} elements on {self.device}")
+
+    def actions(self, obs, *, compact=False, sample=True, seed=0, step=0, row_base=0, num_active=None, out=None, logits=None, logp=None,
+                vf=None):
+        """Actions for a batch of observations.  obs: float32 [E, U, 4B+1] (multi) / [E, U(2B+1)] (central), or with compact=True
+        the int32 record [E, U(B+2)+2B] of env.step_compact.  Returns uint8 [E, U].  logits [rows, heads*(B+1)] / logp [rows, heads]
+        (float32, optional) receive what the action was chosen from / the log-probability of the chosen action; vf [rows] (float32,
+        optional, needs a value function) the value predictions, from the same launch."""
+        return self._launch(obs, compact, sample, seed, step, row_base, num_active, out, logits, logp, vf, True)
+
+    def value(self, obs, *, compact=False, out=None):
+        """The value predictions alone (float32 [rows]): the bootstrap value of a sample batch's last observation.  The policy's
+        head and the draws are skipped."""
+        E, rows = self._batch(obs, compact)
+        if out is None:
+            out = torch.empty(rows, dtype=torch.float32, device=self.device)
+        self._launch(obs, compact, False, 0, 0, 0, None, None, None, None, out, False)
+        return out
+
+    def _batch(self, obs, compact):
+        """(envs, decision rows) of an observation tensor, after its pointer, dtype and size checks."""
+        if compact:
+            if self.kind != _lib.MULTI:
+                raise NotImplementedError("compact observation records exist for multi-agent observations only")
+            from .fragment import fragment_words
+            per_env, dtype = fragment_words(self.U, self.B), torch.int32
+        else:
+            per_env, dtype = (self.U * self.num_in if self.kind == _lib.MULTI else self.num_in), torch.float32
+        if not isinstance(obs, torch.Tensor) or obs.numel() == 0 or obs.numel() % per_env:
+            raise ValueError(f"obs must hold a whole number of envs of {per_env} elements")
+        E = obs.numel() // per_env
+        self._check(obs, dtype, E * per_env, 'obs')
+        return E, (E * self.U if self.kind == _lib.MULTI else E)
+
+    def _launch(self, obs, compact, sample, seed, step, row_base, num_active, out, logits, logp, vf, policy):
+        E, rows = self._batch(obs, compact)
+        if policy:
+            if out is None:
+                out = torch.empty((E, self.U), dtype=torch.uint8, device=self.device)
+            self._check(out, torch.uint8, E * self.U, 'out')
+        if vf is not None:
+            if self.value_weights is None:
+                raise ValueError("the actor has no value function (set_value)")
+            self._check(vf, torch.float32, rows, 'vf')
+        if logits is not None:
+            self._check(logits, torch.float32, rows * self.num_logits, 'logits')
+        if logp is not None:
+            self._check(logp, torch.float32, rows * self.heads, 'logp')
+        run = _lib.DcompActorRun(ctypes.sizeof(_lib.DcompActorRun), _lib.ACTOR_COMPACT if compact else _lib.ACTOR_ROWS, E,
+                                 self.U if num_active is None else int(num_active), 1 if sample else 0, int(step) & 0xFFFFFFFF,
+                                 int(seed) & 0xFFFFFFFFFFFFFFFF, int(row_base),
+                                 logits.data_ptr() if logits is not None else None, logp.data_ptr() if logp is not None else None)
+        with torch.cuda.device(self.device):
+            if vf is None:
+                _lib.check(getattr(self._L, self._ACTIONS)(self._h, ctypes.byref(run), ctypes.c_void_p(obs.data_ptr()),
+                                                       ctypes.c_void_p(out.data_ptr()), self._stream()))
+            else:
+                _lib.check(getattr(self._L, self._ACTIONS_V)(self._h, ctypes.byref(run), ctypes.c_void_p(obs.data_ptr()),
+                                                         ctypes.c_void_p(out.data_ptr()) if policy else None,
+                                                         ctypes.c_void_p(vf.data_ptr()), self._stream()))
+        return out
+
+    def act(self, env, sample=True, obs=None, compact=False, out=None, logp=None, vf=None, logits=None):
+        """The actor's actions on env.obs (or on `obs`, e.g. the record env.step_compact wrote: compact=True) as the tensor
+        env.step takes.  Draws are keyed by the env's seed, step = env.time + episode * episode_length and the GLOBAL decision row
+        (env_id_base * U on a sharded env): reproducible, and independent of how the env axis is split over GPUs."""
+        if env.kind != self.kind or env.U != self.U or env.B != self.B:
+            raise ValueError("the env's kind / UE slots / stations differ from the actor's")
+        rows_per_env = self.U if self.kind == _lib.MULTI else 1
+        return self.actions(env.obs if obs is None else obs, compact=compact, sample=sample, seed=env.seed_value,
+                            step=env.time + max(env.episode, 0) * env.episode_length, row_base=env.env_id_base * rows_per_env,
+                            num_active=env.num_ue, out=out, logp=logp, vf=vf, logits=logits)
+
+
+class FcnetActor(_ActorLaunch):
     """RLlib's default fcnet actor (two hidden layers, categorical heads) running as one HIP kernel."""
 
     def __init__(self, kind, num_ue, num_bs, weights, activation='tanh', device='cuda', value_weights=None):
@@ -262,83 +348,3 @@ class FcnetActor:
         if torch.is_tensor(obs_rows):
             obs_rows = obs_rows.detach().cpu().numpy()
         return self.reference_logits_of(self.weights, obs_rows, self.activation, form)
-
-    # ------------------------------------------------------------------ the kernel
-    def _stream(self):
-        return ctypes.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
-
-    def _check(self, t, dtype, numel, what):
-        """The kernel gets raw pointers: a wrong dtype / device / size would read or write out of bounds on the device."""
-        if not isinstance(t, torch.Tensor) or t.dtype != dtype or t.device != self.device or not t.is_contiguous() or t.numel() != numel:
-            raise ValueError(f"{what} must be a contiguous {dtype} tensor with {numel} elements on {self.device}")
-
-    def actions(self, obs, *, compact=False, sample=True, seed=0, step=0, row_base=0, num_active=None, out=None, logits=None, logp=None,
-                vf=None):
-        """Actions for a batch of observations.  obs: float32 [E, U, 4B+1] (multi) / [E, U(2B+1)] (central), or with compact=True
-        the int32 record [E, U(B+2)+2B] of env.step_compact.  Returns uint8 [E, U].  logits [rows, heads*(B+1)] / logp [rows, heads]
-        (float32, optional) receive what the action was chosen from / the log-probability of the chosen action; vf [rows] (float32,
-        optional, needs a value function) the value predictions, from the same launch."""
-        return self._launch(obs, compact, sample, seed, step, row_base, num_active, out, logits, logp, vf, True)
-
-    def value(self, obs, *, compact=False, out=None):
-        """The value predictions alone (float32 [rows]): the bootstrap value of a sample batch's last observation.  The policy's
-        head and the draws are skipped."""
-        E, rows = self._batch(obs, compact)
-        if out is None:
-            out = torch.empty(rows, dtype=torch.float32, device=self.device)
-        self._launch(obs, compact, False, 0, 0, 0, None, None, None, None, out, False)
-        return out
-
-    def _batch(self, obs, compact):
-        """(envs, decision rows) of an observation tensor, after its pointer, dtype and size checks."""
-        if compact:
-            if self.kind != _lib.MULTI:
-                raise NotImplementedError("compact observation records exist for multi-agent observations only")
-            from .fragment import fragment_words
-            per_env, dtype = fragment_words(self.U, self.B), torch.int32
-        else:
-            per_env, dtype = (self.U * self.num_in if self.kind == _lib.MULTI else self.num_in), torch.float32
-        if not isinstance(obs, torch.Tensor) or obs.numel() == 0 or obs.numel() % per_env:
-            raise ValueError(f"obs must hold a whole number of envs of {per_env} elements")
-        E = obs.numel() // per_env
-        self._check(obs, dtype, E * per_env, 'obs')
-        return E, (E * self.U if self.kind == _lib.MULTI else E)
-
-    def _launch(self, obs, compact, sample, seed, step, row_base, num_active, out, logits, logp, vf, policy):
-        E, rows = self._batch(obs, compact)
-        if policy:
-            if out is None:
-                out = torch.empty((E, self.U), dtype=torch.uint8, device=self.device)
-            self._check(out, torch.uint8, E * self.U, 'out')
-        if vf is not None:
-            if self.value_weights is None:
-                raise ValueError("the actor has no value function (set_value)")
-            self._check(vf, torch.float32, rows, 'vf')
-        if logits is not None:
-            self._check(logits, torch.float32, rows * self.num_logits, 'logits')
-        if logp is not None:
-            self._check(logp, torch.float32, rows * self.heads, 'logp')
-        run = _lib.DcompActorRun(ctypes.sizeof(_lib.DcompActorRun), _lib.ACTOR_COMPACT if compact else _lib.ACTOR_ROWS, E,
-                                 self.U if num_active is None else int(num_active), 1 if sample else 0, int(step) & 0xFFFFFFFF,
-                                 int(seed) & 0xFFFFFFFFFFFFFFFF, int(row_base),
-                                 logits.data_ptr() if logits is not None else None, logp.data_ptr() if logp is not None else None)
-        with torch.cuda.device(self.device):
-            if vf is None:
-                _lib.check(self._L.dcomp_actor_actions(self._h, ctypes.byref(run), ctypes.c_void_p(obs.data_ptr()),
-                                                       ctypes.c_void_p(out.data_ptr()), self._stream()))
-            else:
-                _lib.check(self._L.dcomp_actor_actions_v(self._h, ctypes.byref(run), ctypes.c_void_p(obs.data_ptr()),
-                                                         ctypes.c_void_p(out.data_ptr()) if policy else None,
-                                                         ctypes.c_void_p(vf.data_ptr()), self._stream()))
-        return out
-
-    def act(self, env, sample=True, obs=None, compact=False, out=None, logp=None, vf=None, logits=None):
-        """The actor's actions on env.obs (or on `obs`, e.g. the record env.step_compact wrote: compact=True) as the tensor
-        env.step takes.  Draws are keyed by the env's seed, step = env.time + episode * episode_length and the GLOBAL decision row
-        (env_id_base * U on a sharded env): reproducible, and independent of how the env axis is split over GPUs."""
-        if env.kind != self.kind or env.U != self.U or env.B != self.B:
-            raise ValueError("the env's kind / UE slots / stations differ from the actor's")
-        rows_per_env = self.U if self.kind == _lib.MULTI else 1
-        return self.actions(env.obs if obs is None else obs, compact=compact, sample=sample, seed=env.seed_value,
-                            step=env.time + max(env.episode, 0) * env.episode_length, row_base=env.env_id_base * rows_per_env,
-                            num_active=env.num_ue, out=out, logp=logp, vf=vf, logits=logits)

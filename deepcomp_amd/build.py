@@ -3,7 +3,7 @@
     python -m deepcomp_amd.build [--force] [--jobs N]
 
 One object per base-station count listed in csrc/dcomp_blist.h (all UE-group widths inside), compiled
-in parallel, plus the API object, the generic kernel's, the actor's (csrc/dcomp_actor.hip: actor, value function, GAE) and the learner's
+in parallel, plus the API object, the generic kernel's, the actor's (csrc/dcomp_actor.hip: actor, value function, GAE, per-UE policy sets) and the learner's
 (csrc/dcomp_learner.hip: PPO loss, backward pass, Adam); linked into deepcomp_amd/csrc/libdcomp_hip.so.  hipcc cross-compiles
 for gfx950 without a GPU present.
 """
@@ -37,7 +37,7 @@ def b_list():
 def _sources():
     return [os.path.join(CSRC, f) for f in ('dcomp_device.h', 'dcomp_wide.h', 'dcomp_dyn.h', 'dcomp_blist.h', 'dcomp_inst.hip', 'dcomp_api.hip', 'dcomp_fragment.h',
                                             'dcomp_big.h', 'dcomp_big.hip', 'dcomp_actor.hip', 'dcomp_actor_impl.h', 'dcomp_learner.hip')] + \
-        [os.path.join(os.path.dirname(HERE), 'include', f) for f in ('dcomp.h', 'dcomp_types.h', 'dcomp_learner.h', 'dcomp_learner_indexed.h')]
+        [os.path.join(os.path.dirname(HERE), 'include', f) for f in ('dcomp.h', 'dcomp_types.h', 'dcomp_learner.h', 'dcomp_learner_indexed.h', 'dcomp_policy_set.h')]
 
 
 def _dev_flags():
@@ -139,7 +139,7 @@ def build(force=False, jobs=None, extra_flags=()):
                 continue
             if f.endswith(os.sep + 'dcomp.h') and not t[0].endswith(('dcomp_api.o', 'dcomp_actor.o', 'dcomp_learner.o')):
                 continue
-            if f.endswith('dcomp_actor.hip') and not t[0].endswith('dcomp_actor.o'):
+            if f.endswith(('dcomp_actor.hip', 'dcomp_policy_set.h')) and not t[0].endswith('dcomp_actor.o'):
                 continue
             if f.endswith('dcomp_actor_impl.h') and not t[0].endswith(('dcomp_actor.o', 'dcomp_learner.o')):
                 continue

@@ -32,6 +32,10 @@
 //   - the value-only call (action == NULL) runs the value sweep alone (VF = 1) / the one output tile that holds the column (VF = 2)
 // VF = 0 is what dcomp_actor_actions launches, with or without a value function attached.
 //
+// One policy per UE slot (include/dcomp_policy_set.h: D3-CoMP) is the same kernel with another tile map, instantiations of their own
+// (PER, see actor_kernel): a tile is 32 envs of one slot, its trunks come from the set's device table of pointers into the members'
+// images.  The set's entry points follow dcomp_actor_actions_v and share actor_launch.
+//
 // This file has the actor's own: the staging of observation rows and compact records (the fetch it hands to layer1), the ring that
 // streams the weights of layers 2 and 3, the row walk with its draws, and the entry points.  The pieces the learner's kernel runs
 // too -- layer 1, the hidden fragments, the logit tile, the log-sum-exp step -- the fragment layout, the net description (Net) and
@@ -45,6 +49,7 @@
 
 #define DCOMP_BUILDING_LIBRARY 1
 #include "../../include/dcomp.h"
+#include "../../include/dcomp_policy_set.h"
 #include "dcomp_actor_impl.h"       // the forward-pass helpers, the fragment layout, Net and struct dcomp_actor, fail / HIP_TRY: shared with dcomp_learner.hip
 
 namespace dactor {
@@ -60,7 +65,23 @@ struct Params {
     int32_t num_active, compact, sample;
     uint32_t step, seed_lo, seed_hi;
     int32_t vcol, policy;             // VF = 2: the value's column of the packed W3; policy = 0: the value-only call
+    // PER (a policy set, include/dcomp_policy_set.h) only, behind everything the other instantiations read:
+    const Trunk *table;               // [U][2]: slot u's policy trunk, value trunk -- pointers into its member's images
+    int32_t envs;                     // E; tiles = ceil(E / 32) * U
 };
+
+// entry i (wave-uniform) of a policy set's table.  The table is written once, before any launch: read through the constant address
+// space the twelve pointers are scalar loads into SGPRs, like the kernel arguments select_trunk picks from.
+__device__ __forceinline__ Trunk slot_trunk(const Trunk *table, int i)
+{
+    typedef const uint64_t __attribute__((address_space(4))) *cptr;
+    cptr q = (cptr)(uintptr_t)(table + i);
+    Trunk t;
+    t.w1 = reinterpret_cast<const uint4 *>(q[0]); t.w2 = reinterpret_cast<const uint4 *>(q[1]); t.w3 = reinterpret_cast<const uint4 *>(q[2]);
+    t.b1 = reinterpret_cast<const float *>(q[3]); t.b2 = reinterpret_cast<const float *>(q[4]); t.b3 = reinterpret_cast<const float *>(q[5]);
+    return t;
+}
+static_assert(sizeof(Trunk) == 6 * sizeof(uint64_t), "slot_trunk reads a Trunk as six 64-bit words");
 
 __device__ __forceinline__ void philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0, uint32_t k1, uint32_t (&out)[4])
 {
@@ -76,7 +97,13 @@ __device__ __forceinline__ void philox4x32_10(uint32_t c0, uint32_t c1, uint32_t
 
 
 // MT = hidden width / 32 (padded: 1, 2, 4 or 8); VF: 0 = no value, 1 = a value trunk of its own, 2 = value_out on the actor's h2
-template <int MT, bool RELU, int VF>
+// PER: one policy per UE slot.  A tile is 32 ENVS of one slot, tile id = env group * U + slot; lane r's decision row is
+// (32 g + r) U + slot, the address the shared launch has it at, and both sweeps' trunks come from the slot's table entry.
+// (Env-major: the U tiles of an env group run together, so their strided row reads and 1- and 4-byte stores meet in the same cache
+// lines while those are in L2.  Slot-major keeps one or two members' weights in flight instead of U and measured 1-14 % SLOWER,
+// profiles/r12_policy_set.txt: the weights are at most 340 KB per member and stay cache-resident either way.)  A row is one column of the B operand and depends on
+// no tile-mate, so its results are those of the shared launch with the same weights, bit for bit.
+template <int MT, bool RELU, int VF, bool PER = false>
 __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(2, 2))) void actor_kernel(const Params p)
 {
     extern __shared__ uint4 lds4[];
@@ -96,17 +123,27 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(2, 2))) v
     const float *rowsf = reinterpret_cast<const float *>(p.obs);
 
     for (int64_t tile = (int64_t)blockIdx.x * WAVES + wave; tile < p.tiles; tile += (int64_t)gridDim.x * WAVES) {
+        int pslot = 0, env0 = 0;                                                     // PER: the tile's UE slot and first env, wave-uniform
+        if constexpr (PER) {
+            const uint32_t id = __builtin_amdgcn_readfirstlane((uint32_t)tile);      // (tiles <= rows / 32 + U < 2^32)
+            pslot = (int)(id % (uint32_t)U);
+            env0 = TILE * (int)(id / (uint32_t)U);
+        }
         const int64_t row0 = tile * TILE;
-        const int nrow = (int)(p.rows - row0 < TILE ? p.rows - row0 : TILE);
-        const int64_t myrow = row0 + r;                                              // the decision row on this lane
+        auto row_of = [&](int rr) -> int64_t {                                       // the decision row of the tile's row rr
+            if constexpr (PER) return (int64_t)(env0 + rr) * U + pslot;
+            else return row0 + rr;
+        };
+        const int nrow = PER ? (p.envs - env0 < TILE ? p.envs - env0 : TILE) : (int)(p.rows - row0 < TILE ? p.rows - row0 : TILE);
+        const int64_t myrow = row_of(r);                                             // the decision row on this lane
         const bool have = r < nrow;
-        int slot = 0;                                                                // multi-agent: the row's UE slot
-        if (n.multi && have) slot = (int)(myrow % U);
+        int slot = PER ? pslot : 0;                                                  // multi-agent: the row's UE slot
+        if (!PER && n.multi && have) slot = (int)(myrow % U);
         if (p.compact) {
             if (lane < TILE) {
                 uint32_t lo = 0, hi = 0, listed = 0;
                 if (have) {
-                    const int64_t env = myrow / U;
+                    const int64_t env = PER ? (int64_t)(env0 + r) : myrow / U;
                     const uint64_t off = (uint64_t)env * (uint64_t)env_words(U, B) + (uint64_t)slot * CW;
                     lo = (uint32_t)off; hi = (uint32_t)(off >> 32); listed = compact_listed(cwords, off, B);
                 }
@@ -119,7 +156,7 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(2, 2))) v
 #pragma nounroll
         for (int sweep = (VF == 1 && !p.policy) ? 1 : 0; sweep < (VF == 1 ? 2 : 1); sweep++) {
         const bool val = VF == 1 && sweep != 0;
-        const Trunk t = select_trunk(n, val);
+        const Trunk t = PER ? slot_trunk(p.table, 2 * pslot + (val ? 1 : 0)) : select_trunk(n, val);
         const int NT3 = val ? 1 : n.NT3, N3 = val ? 0 : n.N3;                        // (the value trunk has no logits to walk or store)
         const int vcol = VF == 0 ? -1 : VF == 1 ? (val ? 0 : -1) : p.vcol;
         const bool staged = val && p.policy && n.K1p <= KC;                          // the policy sweep left the bf16 rows in LDS
@@ -131,7 +168,7 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(2, 2))) v
                        float v = 0.f;
                        if (rr < nrow && k < K1) {
                            if (!p.compact) {
-                               v = rowsf[(size_t)(row0 + rr) * K1 + k];
+                               v = rowsf[(size_t)row_of(rr) * K1 + k];
                            } else {
                                const uint64_t off = (uint64_t)ri[rr * 4] | ((uint64_t)ri[rr * 4 + 1] << 32);
                                v = compact_input(cwords, off, ri + rr * 4 + 2, k, B, U, CW);
@@ -230,7 +267,7 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(2, 2))) v
             if (p.logits) {
                 for (int i = lane; i < TILE * 32; i += 64) {
                     const int rr = i >> 5, c = i & 31;
-                    if (rr < nrow && c < ncol) p.logits[(size_t)(row0 + rr) * N3 + 32 * nt + c] = lt[rr * LT + c];
+                    if (rr < nrow && c < ncol) p.logits[(size_t)row_of(rr) * N3 + 32 * nt + c] = lt[rr * LT + c];
                 }
             }
             if (VF != 0) {
@@ -244,13 +281,17 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(2, 2))) v
 }
 
 typedef void (*kernel_fn)(const Params);
-template <int VF> static kernel_fn pick_width(int mt, bool relu)
+template <int VF, bool PER = false> static kernel_fn pick_width(int mt, bool relu)
 {
-    return pick_shape(mt, relu, [](auto s) -> kernel_fn { return actor_kernel<decltype(s)::MT, decltype(s)::RELU, VF>; });
+    return pick_shape(mt, relu, [](auto s) -> kernel_fn { return actor_kernel<decltype(s)::MT, decltype(s)::RELU, VF, PER>; });
 }
 static kernel_fn pick(int mt, bool relu, int vf)
 {
     return vf == 0 ? pick_width<0>(mt, relu) : vf == 1 ? pick_width<1>(mt, relu) : pick_width<2>(mt, relu);
+}
+static kernel_fn pick_set(int mt, bool relu, int vf)             // a policy set: no value, or trunks of their own
+{
+    return vf == 0 ? pick_width<0, true>(mt, relu) : pick_width<1, true>(mt, relu);
 }
 
 // RLlib's compute_advantages(use_gae=True) as pinned f32 operations (include/dcomp.h: dcomp_gae): one lane per column walks t
@@ -358,8 +399,17 @@ extern "C" int dcomp_actor_destroy(dcomp_actor *a)
     return e == hipSuccess ? DCOMP_OK : fail(DCOMP_EHIP, "dcomp_actor_destroy: hipFree failed: %s", hipGetErrorString(e));
 }
 
-// dcomp_actor_actions (vf_call = false) and dcomp_actor_actions_v: every check on the host first, then ONE launch
-static int actor_launch(const char *fn, bool vf_call, dcomp_actor *a, const dcomp_actor_run *r, const void *obs, uint8_t *action, float *vf, void *stream)
+// a policy set (include/dcomp_policy_set.h): the members and the device table of every slot's two trunks
+struct dcomp_policy_set {
+    std::vector<dcomp_actor *> members;
+    dactor::Trunk *table;             // device [U][2]
+    int32_t value;                    // the members' value form when the table was written: 0 none, 1 a trunk of its own
+};
+
+// dcomp_actor_actions (vf_call = false) and dcomp_actor_actions_v: every check on the host first, then ONE launch.
+// set: the same for a policy set, a = its first member (the shapes are equal across members)
+static int actor_launch(const char *fn, bool vf_call, dcomp_actor *a, const dcomp_actor_run *r, const void *obs, uint8_t *action, float *vf, void *stream,
+                        const dcomp_policy_set *set = nullptr)
 {
     using namespace dactor;
     if (!a || !r) return fail(DCOMP_EINVAL, "%s: handle and run must not be NULL", fn);
@@ -374,7 +424,7 @@ static int actor_launch(const char *fn, bool vf_call, dcomp_actor *a, const dcom
         if (!obs) return fail(DCOMP_EINVAL, "%s: obs must not be NULL", fn);
         if (!vf) return fail(DCOMP_EINVAL, "%s: vf must not be NULL (dcomp_actor_actions is the call without a value)", fn);
         if (!action && (r->logits || r->logp)) return fail(DCOMP_EINVAL, "%s: action == NULL is the value-only call: run.logits and run.logp must be NULL", fn);
-        if (!a->value) return fail(DCOMP_EINVAL, "%s: the handle has no value function (dcomp_actor_set_value)", fn);
+        if (!(set ? set->value : a->value)) return fail(DCOMP_EINVAL, "%s: the handle has no value function (dcomp_actor_set_value)", fn);
     }
     if (r->num_envs < 1) return fail(DCOMP_EINVAL, "%s: num_envs %d < 1", fn, r->num_envs);
     if (r->num_active < 0 || r->num_active > a->net.U) return fail(DCOMP_EINVAL, "%s: num_active %d outside [0, %d]", fn, r->num_active, a->net.U);
@@ -382,7 +432,7 @@ static int actor_launch(const char *fn, bool vf_call, dcomp_actor *a, const dcom
     if (r->row_base < 0 || r->row_base + rows > 0x100000000ll)
         return fail(DCOMP_EINVAL, "%s: decision rows %lld ... %lld do not fit the 32-bit draw counter word", fn, (long long)r->row_base,
                      (long long)(r->row_base + rows - 1));
-    const int mode = vf_call ? a->value : 0;
+    const int mode = vf_call ? (set ? set->value : a->value) : 0;      // (a set: the form its table was written for, 0 or 1)
     Params p;
     memset(&p, 0, sizeof(p));
     p.obs = obs; p.action = action; p.logits = r->logits; p.logp = r->logp; p.vf = vf;
@@ -397,9 +447,13 @@ static int actor_launch(const char *fn, bool vf_call, dcomp_actor *a, const dcom
         p.net.NT3 = a->NT3v - first; p.vcol = a->net.N3 - 32 * first;
         if (!p.policy) p.net.N3 = 0;
     }
+    if (set) {                                               // tiles of 32 envs per UE slot (members are multi, value form 0 or 1)
+        p.table = set->table; p.envs = r->num_envs;
+        p.tiles = (int64_t)a->net.U * ((r->num_envs + TILE - 1) / TILE);
+    }
     const int64_t want = (p.tiles + WAVES - 1) / WAVES;
     const int grid = (int)(want < a->max_blocks ? want : a->max_blocks);
-    hipLaunchKernelGGL(pick(a->mt, a->relu != 0, mode), dim3(grid), dim3(BLOCK), (size_t)a->net.lds_per_wave * WAVES, static_cast<hipStream_t>(stream), p);
+    hipLaunchKernelGGL(set ? pick_set(a->mt, a->relu != 0, mode) : pick(a->mt, a->relu != 0, mode), dim3(grid), dim3(BLOCK), (size_t)a->net.lds_per_wave * WAVES, static_cast<hipStream_t>(stream), p);
     HIP_TRY(hipGetLastError());
     return DCOMP_OK;
 }
@@ -412,6 +466,106 @@ extern "C" int dcomp_actor_actions(dcomp_actor *a, const dcomp_actor_run *r, con
 extern "C" int dcomp_actor_actions_v(dcomp_actor *a, const dcomp_actor_run *r, const void *obs, uint8_t *action, float *vf, void *stream)
 {
     return actor_launch("dcomp_actor_actions_v", true, a, r, obs, action, vf, stream);
+}
+
+extern "C" int dcomp_policy_set_create(const dcomp_policy_set_cfg *cfg, dcomp_policy_set **out)
+{
+    using namespace dactor;
+    if (out) *out = nullptr;
+    // what needs no dereference of a member
+    if (!cfg || !out) return fail(DCOMP_EINVAL, "dcomp_policy_set_create: cfg and out must not be NULL");
+    if (cfg->struct_size != (int32_t)sizeof(dcomp_policy_set_cfg))
+        return fail(DCOMP_EABI, "dcomp_policy_set_create: caller's dcomp_policy_set_cfg has %d bytes, the library's %d", cfg->struct_size, (int)sizeof(dcomp_policy_set_cfg));
+    if (!cfg->members) return fail(DCOMP_EINVAL, "dcomp_policy_set_create: members must not be NULL");
+    const int P = cfg->num_policies;
+    if (P < 1 || P > DCOMP_MAX_UE) return fail(DCOMP_EINVAL, "dcomp_policy_set_create: num_policies %d outside [1, %d]", P, DCOMP_MAX_UE);
+    for (int i = 0; i < P; i++)
+        if (!cfg->members[i]) return fail(DCOMP_EINVAL, "dcomp_policy_set_create: member %d is NULL", i);
+    // the members agree
+    const dcomp_actor *f = cfg->members[0];
+    for (int i = 1; i < P; i++) {
+        const dcomp_actor *m = cfg->members[i];
+        const struct { const char *what; int a, b; } same[] = {
+            {"obs_kind", f->net.multi, m->net.multi}, {"num_ue", f->net.U, m->net.U}, {"num_bs", f->net.B, m->net.B}, {"hidden", f->hidden, m->hidden},
+            {"activation", f->relu, m->relu}, {"device", f->device, m->device}, {"value function", f->value, m->value}};
+        for (const auto &c : same)
+            if (c.a != c.b) return fail(DCOMP_EINVAL, "dcomp_policy_set_create: member %d differs from member 0 in %s (%d, %d)", i, c.what, c.b, c.a);
+    }
+    // agreed, but not supported
+    if (!f->net.multi) return fail(DCOMP_EUNSUPPORTED, "dcomp_policy_set_create: DCOMP_CENTRAL members: a central policy is one network by construction");
+    if (f->value == 2)
+        return fail(DCOMP_EUNSUPPORTED, "dcomp_policy_set_create: members with a shared value function (dcomp_actor_value_cfg.shared = 1) are not supported");
+    const int U = f->net.U;
+    if (cfg->slot_policy)
+        for (int u = 0; u < U; u++)
+            if (cfg->slot_policy[u] < 0 || cfg->slot_policy[u] >= P)
+                return fail(DCOMP_EINVAL, "dcomp_policy_set_create: slot_policy[%d] = %d outside [0, %d)", u, cfg->slot_policy[u], P);
+
+    int dev = -1;
+    hipError_t e = hipGetDevice(&dev);
+    if (e == hipSuccess && dev != f->device)
+        return fail(DCOMP_EINVAL, "dcomp_policy_set_create: the members live on device %d, the calling thread's current device is %d", f->device, dev);
+    if (e != hipSuccess) return fail(DCOMP_EHIP, "dcomp_policy_set_create: %s", hipGetErrorString(e));
+    // (without a value function the second entries are NULL; no launch reads them: set->value keeps the value sweep off, and a member
+    // that gets a value function later makes every call on the set fail on the host, set_first)
+    std::vector<Trunk> host((size_t)2 * U);
+    for (int u = 0; u < U; u++) {
+        const dcomp_actor *m = cfg->members[cfg->slot_policy ? cfg->slot_policy[u] : u % P];
+        host[2 * u] = m->net.pi; host[2 * u + 1] = m->net.vf;
+    }
+    dcomp_policy_set *s = new dcomp_policy_set();
+    s->members.assign(cfg->members, cfg->members + P);
+    s->table = nullptr;
+    s->value = f->value;
+    e = hipMalloc(reinterpret_cast<void **>(&s->table), host.size() * sizeof(Trunk));
+    if (e == hipSuccess) {
+        e = hipMemcpy(s->table, host.data(), host.size() * sizeof(Trunk), hipMemcpyHostToDevice);
+        if (e != hipSuccess) (void)hipFree(s->table);
+    }
+    if (e != hipSuccess) {
+        delete s;
+        return fail(DCOMP_EHIP, "dcomp_policy_set_create: %s", hipGetErrorString(e));
+    }
+    *out = s;
+    return DCOMP_OK;
+}
+
+extern "C" int dcomp_policy_set_destroy(dcomp_policy_set *s)
+{
+    if (!s) return DCOMP_OK;
+    const hipError_t e = hipFree(s->table);
+    delete s;
+    return e == hipSuccess ? DCOMP_OK : fail(DCOMP_EHIP, "dcomp_policy_set_destroy: hipFree failed: %s", hipGetErrorString(e));
+}
+
+// the checks that come before the set is dereferenced (actor_launch repeats them on the first member: the same order as for an actor),
+// then the one the set adds: the table holds the trunks the members had at create, so a value function attached to a member since
+// (dcomp_actor_set_value works once per handle) is not in it -- refused here, on the host, for every call on the set
+static int set_first(const char *fn, dcomp_policy_set *s, const dcomp_actor_run *r, dcomp_actor **first)
+{
+    if (!s || !r) return fail(DCOMP_EINVAL, "%s: handle and run must not be NULL", fn);
+    if (r->struct_size != (int32_t)sizeof(dcomp_actor_run))
+        return fail(DCOMP_EABI, "%s: caller's dcomp_actor_run has %d bytes, the library's %d", fn, r->struct_size, (int)sizeof(dcomp_actor_run));
+    for (size_t i = 0; i < s->members.size(); i++)
+        if (s->members[i]->value != s->value)
+            return fail(DCOMP_EINVAL, "%s: member %d got a value function after the set was created (value form %d, the set's %d): attach value "
+                        "functions first, then create the set", fn, (int)i, s->members[i]->value, s->value);
+    *first = s->members[0];
+    return DCOMP_OK;
+}
+
+extern "C" int dcomp_policy_set_actions(dcomp_policy_set *s, const dcomp_actor_run *r, const void *obs, uint8_t *action, void *stream)
+{
+    dcomp_actor *a = nullptr;
+    const int rc = set_first("dcomp_policy_set_actions", s, r, &a);
+    return rc != DCOMP_OK ? rc : actor_launch("dcomp_policy_set_actions", false, a, r, obs, action, nullptr, stream, s);
+}
+
+extern "C" int dcomp_policy_set_actions_v(dcomp_policy_set *s, const dcomp_actor_run *r, const void *obs, uint8_t *action, float *vf, void *stream)
+{
+    dcomp_actor *a = nullptr;
+    const int rc = set_first("dcomp_policy_set_actions_v", s, r, &a);
+    return rc != DCOMP_OK ? rc : actor_launch("dcomp_policy_set_actions_v", true, a, r, obs, action, vf, stream, s);
 }
 
 extern "C" int dcomp_actor_set_value(dcomp_actor *a, const dcomp_actor_value_cfg *cfg)

@@ -476,7 +476,7 @@ class PPOLearner:
         self.actor.weights, self.actor.value_weights = split_weights(host['weights'])
 
     # ------------------------------------------------------------------ the training step
-    def update(self, batch, num_sgd_iter=30, minibatch_rows=None, seed=0, num_active=None):
+    def update(self, batch, num_sgd_iter=30, minibatch_rows=None, seed=0, num_active=None, rows=None, check_rows=True):
         """PPO's SGD phase on one collect(..., dist_inputs=True) batch, observation rows or the compact record (compact=True): the
         batch is flattened to source rows, the advantages are standardised over the batch (RLlib: (a - mean) / max(1e-4, std)), and
         per iteration a seeded device permutation splits the rows into minibatches of minibatch_rows (default: the whole batch);
@@ -485,7 +485,12 @@ class PPOLearner:
         and goes through grads: measured, the gather and contiguous reads beat scattered reads of whole rows at large batches
         (profiles/r11_learner_indexed.txt); both ways give the same bits.  Afterwards the mean KL of the last iteration is read (the
         one synchronisation) and kl_coeff adapted by RLlib's rule.  num_active: listed UEs where fewer than the env's slots (multi:
-        the other rows are dropped before the split).  Returns the last iteration's mean statistics and the new kl_coeff."""
+        the other rows are dropped before the split).  rows: an integer device tensor of distinct source rows of the flattened batch
+        -- the learner then trains on exactly those rows: the advantages are standardised over them alone, the permutation runs over
+        them only, and the result is that of update() on the batch gathered at rows, bit for bit (deepcomp_amd.policy_set hands each
+        per-UE policy the rows of its slots this way); not together with num_active.  rows are checked to be inside the batch and
+        distinct (one sort and one synchronisation; check_rows=False skips it for rows the caller built itself).  Returns the last iteration's mean statistics
+        and the new kl_coeff."""
         a = self.actor
         if 'action_dist_inputs' not in batch:
             raise ValueError("the batch has no action_dist_inputs: collect(..., dist_inputs=True)")
@@ -506,7 +511,24 @@ class PPOLearner:
             if src['obs_compact'].shape[0] * a.U != N:
                 raise ValueError("the batch's tensors disagree about the number of rows")
         kernel_active, keep = None, None
-        if num_active is not None and int(num_active) < a.U:
+        if rows is not None:
+            if num_active is not None:
+                raise ValueError("rows and num_active exclude each other: leave the rows of unlisted slots out of rows")
+            if not isinstance(rows, torch.Tensor) or rows.dim() != 1 or rows.numel() == 0 or rows.device != self.device or \
+                    rows.dtype not in (torch.int32, torch.int64):
+                raise ValueError(f"rows must be a non-empty 1-d int32 / int64 tensor on {self.device}")
+            keep = rows.to(torch.int64)
+            if check_rows:
+                srt = keep.sort().values
+                lo, hi, dup = torch.stack((srt[0], srt[-1], (srt[1:] == srt[:-1]).any().to(torch.int64))).tolist()      # one synchronisation
+                if lo < 0 or hi >= N:
+                    raise ValueError(f"rows has entries outside the batch's {N} source rows")
+                if dup:
+                    raise ValueError("rows has repeated entries: they must be distinct source rows")
+            N = int(keep.numel())
+            if not compact:
+                src = {k: t.index_select(0, keep) for k, t in src.items()}
+        elif num_active is not None and int(num_active) < a.U:
             if multi:
                 keep = torch.nonzero(torch.arange(N, device=self.device) % a.U < int(num_active)).reshape(-1)
                 N = int(keep.numel())

@@ -13,7 +13,9 @@
 Workloads: BASELINE config 3 (65 536 x 32 x 10 multi, one launch per step), config 2 through the fused rollout (4 096 x 10 x 5
 central, 100 steps per launch, every step's outputs), one GPU's share of config 5 (4 096 x 128 x 32) and of config 4
 (32 768 x 32 x 10), 65 536 x 10 x 5 central, 65 536 x 32 x 10 central, the closed policy loop at config 2; learner_c3 / learner_c2:
-PPOLearner grads + apply on one minibatch of 65 536 x 32 multi rows / 4 096 central rows (libraries from round 9 on)."""
+PPOLearner grads + apply on one minibatch of 65 536 x 32 multi rows / 4 096 central rows (libraries from round 9 on); actor_c3 / actor_c2:
+dcomp_actor_actions_v (actions, logp and the value of a trunk of its own, sampled) at 65 536 x 32 x 10 multi / 4 096 x 10 x 5 central
+(libraries from round 8 on)."""
 import argparse
 import json
 import os
@@ -66,7 +68,33 @@ def build(a):
 
 
 WORKLOADS = ['big64', 'big40c', 'c3', 'c2roll', 'c5', 'c5mid', 'c5big', 'c4share', 'c4big', 'central10x5', 'central10x5roll', 'central10x5f', 'central32x10', 'c2policy', 'c3rf', 'c3roll',
-             'learner_c3', 'learner_c2']
+             'learner_c3', 'learner_c2', 'actor_c3', 'actor_c2']
+
+
+def measure_actor(torch, dev, kind, E, U, B, n):
+    """FcnetActor.actions with logp and vf (2 x 256 tanh, a value trunk of its own, sampled; synthetic observations: the time does not
+    depend on the values), ms per launch over n back-to-back launches."""
+    from deepcomp_amd.actor import FcnetActor
+    actor = FcnetActor(kind, U, B, FcnetActor.random_weights(kind, U, B, 256, seed=0), device=dev,
+                       value_weights=FcnetActor.random_value_weights(kind, U, B, 256, seed=0))
+    rows = E * U if kind == 'multi' else E
+    g = torch.Generator(device=dev).manual_seed(3)
+    obs = torch.rand((E, U, actor.num_in) if kind == 'multi' else (E, actor.num_in), generator=g, device=dev)
+    out = torch.zeros((E, U), dtype=torch.uint8, device=dev)
+    logp, vf = torch.zeros((rows, actor.heads), device=dev), torch.zeros(rows, device=dev)
+
+    def step(i):
+        actor.actions(obs, sample=True, seed=1, step=i, out=out, logp=logp, vf=vf)
+    for i in range(3):
+        step(i)
+    torch.cuda.synchronize()
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    for i in range(n):
+        step(i)
+    e1.record()
+    torch.cuda.synchronize()
+    return e0.elapsed_time(e1) / n
 
 
 def measure_learner(torch, dev, kind, E, U, B, n):
@@ -140,6 +168,10 @@ def measure(a):
             out[w] = measure_learner(torch, dev, 'multi', 65536, 32, 10, 10)
         elif w == 'learner_c2':                    # ... and of 4 096 central rows
             out[w] = measure_learner(torch, dev, 'central', 4096, 10, 5, 200)
+        elif w == 'actor_c3':
+            out[w] = measure_actor(torch, dev, 'multi', 65536, 32, 10, 50)
+        elif w == 'actor_c2':
+            out[w] = measure_actor(torch, dev, 'central', 4096, 10, 5, 500)
         elif w in ('central10x5f', 'c3roll'):      # the fused rollout kernel forced onto a big batch, ONE step per launch
             os.environ['DCOMP_FUSE_MAX_WAVES'] = '100000000'
             E, U, B, kind = (65536, 10, 5, 'central') if w == 'central10x5f' else (65536, 32, 10, 'multi')

@@ -7,6 +7,7 @@ this only shows where the time goes once the env runs at ~10^8-10^9 env-steps/s.
     python tools/closed_loop.py [--envs 65536] [--steps 200] [--dtype bf16] [--kind multi] [--actor hip [--compact]]
     python tools/closed_loop.py --collect 50 [--envs 65536] [--kind multi] [--compact] [--shared-value]
     python tools/closed_loop.py --train 3 [--train-steps 5] [--sgd-iters 2] [--minibatch ROWS] [--envs 65536] [--kind multi] [--compact]
+    python tools/closed_loop.py --per-ue [--actor hip | --collect 50 | --train 3] [--hidden 64] [--compact] [--envs 4096 --ues 128 --bs 32]
 
 --actor torch (default): the actor as torch ops (bf16 matmuls, Gumbel-max through torch.rand).  --actor hip: the same weights in
 deepcomp_amd.actor.FcnetActor -- one HIP kernel from observation tensor to action tensor -- and BOTH loops are timed in this
@@ -25,6 +26,11 @@ and the time of one SGD iteration of update on the rows batch (minibatches gathe
 iteration with the minibatches picked through a row index instead (grads_indexed: nothing is copied, rows are read scattered).
 --compact (multi-agent): collect returns the compact record and update trains on it through the row index -- no observation row is
 written anywhere in the loop; the unpack a rows-only learner would need first is timed on its own.
+
+--per-ue (multi-agent): one policy network per UE (D3-CoMP) -- deepcomp_amd.policy_set.PerUEActor over U random-init members and, with
+--train, PerUELearner -- timed next to the shared-policy actor / learner on the same env, interleaved: the loop env step + actor
+(--actor hip), sampler.collect (--collect T), or collect + update with the time of one SGD iteration (--train ITERS; --minibatch is
+per policy there).
 """
 import argparse
 import sys
@@ -53,8 +59,12 @@ ap.add_argument('--train', type=int, default=0, metavar='ITERS', help='collect -
 ap.add_argument('--train-steps', type=int, default=5, help='--train: steps per collected batch')
 ap.add_argument('--sgd-iters', type=int, default=2, help='--train: SGD iterations per batch')
 ap.add_argument('--minibatch', type=int, default=0, help='--train: rows per minibatch (default: one step\'s rows)')
+ap.add_argument('--hidden', type=int, default=256, help='hidden width of the fcnet (two layers)')
+ap.add_argument('--per-ue', action='store_true', help='one policy per UE (PerUEActor / PerUELearner) next to the shared policy; multi-agent')
 a = ap.parse_args()
-if a.collect or a.train:
+if a.per_ue and a.kind != 'multi':
+    ap.error('--per-ue needs --kind multi')
+if a.collect or a.train or a.per_ue:
     a.actor = 'hip'
 if a.compact and (a.actor != 'hip' or a.kind != 'multi'):
     ap.error('--compact needs --actor hip and --kind multi')
@@ -68,7 +78,7 @@ env = BatchedMobileEnv(m, bs, ues, a.kind, num_envs=E, seed=42, episode_length=1
 dt = torch.bfloat16 if a.dtype == 'bf16' else torch.float32
 D = 4 * B + 1 if multi else U * (2 * B + 1)
 heads = 1 if multi else U
-host_w = FcnetActor.random_weights(a.kind, U, B, 256, seed=0)           # N(0, 1 / fan_in) kernels, zero biases
+host_w = FcnetActor.random_weights(a.kind, U, B, a.hidden, seed=0)           # N(0, 1 / fan_in) kernels, zero biases
 W1, W2, W3 = (torch.from_numpy(host_w[n]).to(dev).to(dt) for n in ('w1', 'w2', 'w3'))
 
 
@@ -86,7 +96,7 @@ hip = FcnetActor(a.kind, U, B, host_w, device=dev) if a.actor == 'hip' else None
 def collect_mode(T):
     from deepcomp_amd.sampler import collect
     gamma, lam = 0.99, 0.95
-    host_v = FcnetActor.random_value_weights(a.kind, U, B, 256, seed=0, shared=a.shared_value)
+    host_v = FcnetActor.random_value_weights(a.kind, U, B, a.hidden, seed=0, shared=a.shared_value)
     hip.set_value(host_v, shared=a.shared_value)
     trunk = host_v if not a.shared_value else host_w
     V1, V2 = (torch.from_numpy(trunk[n]).to(dev).to(dt) for n in ('w1', 'w2'))
@@ -146,7 +156,7 @@ def collect_mode(T):
         env.reset()
         res['hip'].append(timed(hip_batch, n))
     form = 'shared value_out' if a.shared_value else 'value trunk of its own'
-    print(f'{E} envs x {U} UE x {B} BS ({a.kind}), actor 2x256 tanh + {form}, batches of T = {T}, {n} batches per timing')
+    print(f'{E} envs x {U} UE x {B} BS ({a.kind}), actor 2x{a.hidden} tanh + {form}, batches of T = {T}, {n} batches per timing')
     for k, name in (('torch', f'hip actor + torch value ({a.dtype}) + torch GAE'), ('hip', 'sampler.collect' + (' (compact record)' if a.compact else ''))):
         ts = res[k]
         print(f'{name:<46}: ' + ' / '.join(f'{t * 1e3:.3f}' for t in ts) + f' ms/step  (best {E / min(ts):.3e} env-steps/s)')
@@ -158,14 +168,14 @@ def train_mode(iters):
     from deepcomp_amd.learner import PPOLearner, STATS
     from deepcomp_amd.sampler import collect
     T = a.train_steps
-    host_v = FcnetActor.random_value_weights(a.kind, U, B, 256, seed=0)
+    host_v = FcnetActor.random_value_weights(a.kind, U, B, a.hidden, seed=0)
     hip.set_value(host_v)
     rows = E * U if multi else E
     mb = a.minibatch or rows
     learner = PPOLearner(hip, lr=5e-5, max_rows=mb)
     env.reset()
     buf = None
-    print(f'{E} envs x {U} UE x {B} BS ({a.kind}), 2x256 tanh + value trunk, batches of T = {T} ({T * rows} rows), {a.sgd_iters} SGD iterations, minibatches of {mb}'
+    print(f'{E} envs x {U} UE x {B} BS ({a.kind}), 2x{a.hidden} tanh + value trunk, batches of T = {T} ({T * rows} rows), {a.sgd_iters} SGD iterations, minibatches of {mb}'
           + (', compact record' if a.compact else ''))
     for it in range(iters):
         buf = collect(env, hip, T, 0.99, 0.95, out=buf, dist_inputs=True, compact=a.compact)
@@ -284,6 +294,82 @@ def train_mode(iters):
     env.check()
 
 
+def per_ue_mode():
+    """The shared policy and a set of U distinct members on the same env, interleaved."""
+    from deepcomp_amd.learner import PPOLearner
+    from deepcomp_amd.policy_set import PerUEActor, PerUELearner
+    from deepcomp_amd.sampler import collect
+    hip.set_value(FcnetActor.random_value_weights(a.kind, U, B, a.hidden, seed=0))
+    pset = PerUEActor.random(U, B, hidden=a.hidden, seed=0, device=dev)                # member p from seed p: member 0 is the shared policy's twin
+    actors = {'shared policy': hip, f'per-UE set, {U} policies': pset}
+    rows = E * U
+    form = ', compact record' if a.compact else ''
+    print(f'{E} envs x {U} UE x {B} BS (multi), 2x{a.hidden} tanh + value trunk{form}')
+
+    def wall(fn, n):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        for _ in range(n):
+            fn()
+        torch.cuda.synchronize()
+        return (time.perf_counter() - t0) * 1e3 / n
+
+    def report(what, fns, n, per=1):
+        for fn in fns.values():
+            fn()
+        res = {k: [] for k in fns}
+        for _ in range(3):
+            for k, fn in fns.items():
+                res[k].append(wall(fn, n) / per)
+        for k, ts in res.items():
+            print(f'{what}, {k:<28}: ' + ' / '.join(f'{t:.3f}' for t in ts) + ' ms')
+        best = [min(ts) for ts in res.values()]
+        print(f'{what}: set / shared = {best[1] / best[0]:.2f} x')
+
+    env.reset()
+    if a.train:
+        T = a.train_steps
+        mb = a.minibatch or rows // U
+        learners = {k: (PPOLearner(x, lr=5e-5, max_rows=mb * (U if x is hip else 1)) if x is hip else PerUELearner(x, lr=5e-5, max_rows=mb))
+                    for k, x in actors.items()}
+        bufs = {k: None for k in actors}
+        print(f'batches of T = {T} ({T * rows} rows), minibatches of {mb} rows per policy ({mb * U} for the shared policy)')
+        for it in range(a.train):
+            for k, x in actors.items():
+                bufs[k] = collect(env, x, T, 0.99, 0.95, out=bufs[k], dist_inputs=True, compact=a.compact)
+                st = learners[k].update(bufs[k], num_sgd_iter=a.sgd_iters, minibatch_rows=mb * (U if x is hip else 1), seed=it)
+                st = st if isinstance(st, dict) else {n: sum(s[n] for s in st) / len(st) for n in st[0]}
+                print(f'iter {it}, {k}: mean reward {float(bufs[k]["rewards"].mean()):+.4f}  total_loss {st["total_loss"]:+.5f}  kl {st["kl"]:+.5f} (mean over policies)')
+        report('one SGD iteration of update', {k: (lambda k=k, x=x: learners[k].update(bufs[k], num_sgd_iter=1, minibatch_rows=mb * (U if x is hip else 1), seed=0))
+                                               for k, x in actors.items()}, max(2, min(10, a.steps)))
+    elif a.collect:
+        T = a.collect
+        bufs = {k: None for k in actors}
+
+        def batch(k):
+            bufs[k] = collect(env, actors[k], T, 0.99, 0.95, compact=a.compact, out=bufs[k])
+        report(f'collect, T = {T}, per step', {k: (lambda k=k: batch(k)) for k in actors}, max(1, a.steps // T), per=T)
+    else:
+        pk = torch.zeros((E, env.compact_words), dtype=torch.int32, device=dev) if a.compact else None
+        out = torch.zeros((E, U), dtype=torch.uint8, device=dev)
+
+        def loop(x):
+            if env.time >= env.episode_length:
+                env.reset_compact(pk) if a.compact else env.reset()
+            x.act(env, obs=pk if a.compact else None, compact=a.compact, out=out)
+            if a.compact:
+                env.step_compact(out, pk, env.reward)
+            else:
+                env.step(out)
+        if a.compact:
+            env.reset_compact(pk)
+        report('env step + actor, per step', {k: (lambda x=x: loop(x)) for k, x in actors.items()}, a.steps)
+    env.check()
+
+
+if a.per_ue:
+    per_ue_mode()
+    sys.exit(0)
 if a.collect:
     collect_mode(a.collect)
     sys.exit(0)
@@ -324,7 +410,7 @@ run(20, 'torch')
 if hip is not None:
     run(20, 'hip')
 t_env = run(a.steps, None)
-print(f'{E} envs x {U} UE x {B} BS ({a.kind}), actor 2x256 tanh, sampled actions')
+print(f'{E} envs x {U} UE x {B} BS ({a.kind}), actor 2x{a.hidden} tanh, sampled actions')
 print(f'{"env only":<34}: {t_env * 1e3:8.3f} ms/step  {E / t_env:.3e} env-steps/s')
 t_torch = run(a.steps, 'torch')
 report(f'env + torch actor ({a.dtype})', t_torch)
