@@ -55,7 +55,7 @@ struct LParams {
     const uint4 *w2b, *w3b, *vw2b, *vw3b;             // the backward orientation
     __bf16 *X, *H1, *H2, *D1, *D2, *D3, *VH1, *VH2, *VD1, *VD2, *VD3;    // [width][ld]
     float4 *headws;                                   // [rows][heads]: lse, old lse, entropy of the head
-    float4 *part;                                     // [tiles]: sums of surrogate, kl, entropy, vf loss over the tile's counted rows
+    double *part;                                     // [tiles][4]: sums of surrogate, kl, entropy, vf loss over the tile's counted rows
     int64_t rows, tiles, ld;
     int32_t num_active, fwd_only, upstream;
     float clip, vf_clip, vf_coeff, ent_coeff, kl_coeff;
@@ -128,7 +128,10 @@ template <bool IDX> __device__ __forceinline__ size_t source_row(const uint32_t 
     return IDX ? (size_t)ri[r * 4] : (size_t)myrow;
 }
 
-__device__ __forceinline__ float wave_sum(float v)       // a fixed tree over the 64 lanes
+// a fixed tree over the 64 lanes.  In double: the statistics are means of f32 row terms summed in double (reduce_kernel), and an f32
+// tree here would put its own rounding (a few 2^-24 of the tile's sum) into a mean that is otherwise exact up to its last rounding --
+// with few rows that is the statistic's last bit
+__device__ __forceinline__ double wave_sum(double v)
 {
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
@@ -414,9 +417,12 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(1, 1))) v
         }
 
         if (!p.fwd_only) {
-            const float a0 = wave_sum(lane < TILE ? s_surr : 0.f), a1 = wave_sum(lane < TILE ? s_kl : 0.f);
-            const float a2 = wave_sum(lane < TILE ? s_ent : 0.f), a3 = wave_sum(lane < TILE ? s_vfl : 0.f);
-            if (lane == 0) p.part[tile] = make_float4(a0, a1, a2, a3);
+            const double a0 = wave_sum(lane < TILE ? (double)s_surr : 0.), a1 = wave_sum(lane < TILE ? (double)s_kl : 0.);
+            const double a2 = wave_sum(lane < TILE ? (double)s_ent : 0.), a3 = wave_sum(lane < TILE ? (double)s_vfl : 0.);
+            if (lane == 0) {
+                double *q = p.part + 4 * tile;
+                q[0] = a0; q[1] = a1; q[2] = a2; q[3] = a3;
+            }
         }
         wave_fence();
     }
@@ -551,7 +557,7 @@ struct AParams {
     int32_t total, nchunks;
     float scale;
     float *w, *g, *m, *v;
-    const float4 *tile_part;
+    const double *tile_part;                                 // [tiles][4]
     int64_t tiles;
     float *stats;
     double count;
@@ -587,8 +593,8 @@ __global__ __launch_bounds__(256) void reduce_kernel(const AParams p)
         const int64_t per = (p.tiles + 255) / 256, lo = threadIdx.x * per, hi = lo + per < p.tiles ? lo + per : p.tiles;
         double s0 = 0., s1 = 0., s2 = 0., s3 = 0.;
         for (int64_t t = lo; t < hi; t++) {
-            const float4 v = p.tile_part[t];
-            s0 += v.x; s1 += v.y; s2 += v.z; s3 += v.w;
+            const double *v = p.tile_part + 4 * t;
+            s0 += v[0]; s1 += v[1]; s2 += v[2]; s3 += v[3];
         }
         sh[threadIdx.x][0] = s0; sh[threadIdx.x][1] = s1; sh[threadIdx.x][2] = s2; sh[threadIdx.x][3] = s3;
         __syncthreads();
@@ -728,7 +734,7 @@ extern "C" int dcomp_learner_create(dcomp_actor *a, const dcomp_learner_cfg *cfg
     size_t o_H[8];
     for (int i = 0; i < 8; i++) o_H[i] = take((size_t)Hp * ld * 2);
     const size_t o_D3 = take((size_t)N3p * ld * 2), o_VD3 = take((size_t)32 * ld * 2);
-    const size_t o_head = take((size_t)cfg->max_rows * n.heads * 16), o_tpart = take((ld / 32) * 16);      // (ld / 32 >= the tiles of max_rows)
+    const size_t o_head = take((size_t)cfg->max_rows * n.heads * 16), o_tpart = take((ld / 32) * 32);      // (ld / 32 >= the tiles of max_rows)
     const int in_p[6] = {K1pp, Hp, Hp, K1pp, Hp, Hp}, out_p[6] = {Hp, Hp, N3p, Hp, Hp, 32};
     size_t o_part[6], o_bpart[6];
     for (int i = 0; i < 6; i++) { o_part[i] = take((size_t)MAX_CHUNKS * in_p[i] * out_p[i] * 4); o_bpart[i] = take((size_t)MAX_CHUNKS * out_p[i] * 4); }
@@ -761,7 +767,7 @@ extern "C" int dcomp_learner_create(dcomp_actor *a, const dcomp_learner_cfg *cfg
     auto bf = [&](size_t o) { return reinterpret_cast<__bf16 *>(d + o); };
     p.X = bf(o_X); p.H1 = bf(o_H[0]); p.H2 = bf(o_H[1]); p.D1 = bf(o_H[2]); p.D2 = bf(o_H[3]);
     p.VH1 = bf(o_H[4]); p.VH2 = bf(o_H[5]); p.VD1 = bf(o_H[6]); p.VD2 = bf(o_H[7]); p.D3 = bf(o_D3); p.VD3 = bf(o_VD3);
-    p.headws = reinterpret_cast<float4 *>(d + o_head); p.part = reinterpret_cast<float4 *>(d + o_tpart);
+    p.headws = reinterpret_cast<float4 *>(d + o_head); p.part = reinterpret_cast<double *>(d + o_tpart);
     p.ld = l->ld;
 
     WParams &w = l->wp;
