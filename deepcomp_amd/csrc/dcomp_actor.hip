@@ -333,46 +333,69 @@ __global__ __launch_bounds__(256) void gae_kernel(const GaeParams g)
 }  // namespace dactor
 
 
+// The shapes a net can have: what dcomp_actor_create refuses before it plans, and dcomp_fcnet_describe with it (the same codes and
+// texts).  Host only: no HIP call.
+static int fcnet_shape_check(const char *fn, int obs_kind, int U, int B, int H)
+{
+    if (obs_kind != DCOMP_MULTI && obs_kind != DCOMP_CENTRAL) return fail(DCOMP_EINVAL, "%s: obs_kind %d is neither DCOMP_CENTRAL nor DCOMP_MULTI", fn, obs_kind);
+    if (U < 1 || B < 1) return fail(DCOMP_EINVAL, "%s: num_ue %d / num_bs %d must be >= 1", fn, U, B);
+    if (H < 32 || H % 32) return fail(DCOMP_EINVAL, "%s: hidden %d is not a multiple of 32 >= 32", fn, H);
+    if (B > DCOMP_MAX_BS) return fail(DCOMP_EUNSUPPORTED, "%s: num_bs %d > %d", fn, B, DCOMP_MAX_BS);
+    if (U > DCOMP_MAX_UE) return fail(DCOMP_EUNSUPPORTED, "%s: num_ue %d > %d", fn, U, DCOMP_MAX_UE);
+    if (H > DCOMP_ACTOR_MAX_HIDDEN) return fail(DCOMP_EUNSUPPORTED, "%s: hidden %d > %d", fn, H, DCOMP_ACTOR_MAX_HIDDEN);
+    const dactor::ActorPlan pl = dactor::actor_plan(obs_kind, U, B, H);
+    if (pl.K1 > DCOMP_ACTOR_MAX_IN) return fail(DCOMP_EUNSUPPORTED, "%s: a central row of %d x %d has %d inputs > %d", fn, U, B, pl.K1, DCOMP_ACTOR_MAX_IN);
+    if (pl.N3 > DCOMP_ACTOR_MAX_LOGITS) return fail(DCOMP_EUNSUPPORTED, "%s: a central row of %d x %d has %d logits > %d", fn, U, B, pl.N3, DCOMP_ACTOR_MAX_LOGITS);
+    return DCOMP_OK;
+}
+
+extern "C" int dcomp_fcnet_describe(const dcomp_fcnet_shape *s, dcomp_fcnet_desc *d)
+{
+    const char *fn = "dcomp_fcnet_describe";
+    if (!s || !d) return fail(DCOMP_EINVAL, "%s: shape and desc must not be NULL", fn);
+    if (int rc = check_struct(fn, "dcomp_fcnet_shape", s->struct_size, sizeof(dcomp_fcnet_shape))) return rc;
+    if (int rc = check_struct(fn, "dcomp_fcnet_desc", d->struct_size, sizeof(dcomp_fcnet_desc))) return rc;
+    if (s->rows < 0 || s->rows > (1ll << 28)) return fail(DCOMP_EINVAL, "%s: rows %lld outside [0, 2^28]", fn, (long long)s->rows);      // (dcomp_learner_create's max_rows)
+    if (s->compute_units < 0) return fail(DCOMP_EINVAL, "%s: compute_units %d < 0", fn, s->compute_units);
+    if (int rc = fcnet_shape_check(fn, s->obs_kind, s->num_ue, s->num_bs, s->hidden)) return rc;
+    memset(d, 0, sizeof(*d));
+    d->struct_size = (int32_t)sizeof(*d);
+    d->TILE = dplan::TILE; d->WAVES = dplan::WAVES; d->BLOCK = dplan::BLOCK; d->KC = dplan::KC; d->LT = dplan::LT;
+    d->CHUNK_UNIT = dplan::CHUNK_UNIT; d->MAX_CHUNKS = dplan::MAX_CHUNKS;
+    d->max_blocks = dactor::max_blocks_of(s->compute_units); d->grid_tiles = d->max_blocks * dplan::WAVES;
+    d->actor = dactor::actor_plan(s->obs_kind, s->num_ue, s->num_bs, s->hidden);
+    d->learner = dlearn::learner_plan(d->actor);
+    if (s->rows > 0) d->split = dlearn::row_split(s->rows);
+    return DCOMP_OK;
+}
+
 extern "C" int dcomp_actor_create(const dcomp_actor_cfg *cfg, dcomp_actor **out)
 {
     using namespace dactor;
+    const char *fn = "dcomp_actor_create";
     if (out) *out = nullptr;
-    if (!cfg || !out) return fail(DCOMP_EINVAL, "dcomp_actor_create: cfg and out must not be NULL");
-    if (cfg->struct_size != (int32_t)sizeof(dcomp_actor_cfg))
-        return fail(DCOMP_EABI, "dcomp_actor_create: caller's dcomp_actor_cfg has %d bytes, the library's %d", cfg->struct_size, (int)sizeof(dcomp_actor_cfg));
+    if (!cfg || !out) return fail(DCOMP_EINVAL, "%s: cfg and out must not be NULL", fn);
+    if (int rc = check_struct(fn, "dcomp_actor_cfg", cfg->struct_size, sizeof(dcomp_actor_cfg))) return rc;
     // host-only validation first: nothing below touches HIP before the arguments are known to be good
-    if (cfg->obs_kind != DCOMP_MULTI && cfg->obs_kind != DCOMP_CENTRAL) return fail(DCOMP_EINVAL, "dcomp_actor_create: obs_kind %d is neither DCOMP_CENTRAL nor DCOMP_MULTI", cfg->obs_kind);
-    if (cfg->num_ue < 1 || cfg->num_bs < 1) return fail(DCOMP_EINVAL, "dcomp_actor_create: num_ue %d / num_bs %d must be >= 1", cfg->num_ue, cfg->num_bs);
-    if (cfg->hidden < 32 || cfg->hidden % 32) return fail(DCOMP_EINVAL, "dcomp_actor_create: hidden %d is not a multiple of 32 >= 32", cfg->hidden);
-    if (cfg->activation != DCOMP_ACT_TANH && cfg->activation != DCOMP_ACT_RELU) return fail(DCOMP_EINVAL, "dcomp_actor_create: unknown activation %d", cfg->activation);
-    if (!cfg->w1 || !cfg->b1 || !cfg->w2 || !cfg->b2 || !cfg->w3 || !cfg->b3) return fail(DCOMP_EINVAL, "dcomp_actor_create: a weight or bias pointer is NULL");
-    if (cfg->num_bs > DCOMP_MAX_BS) return fail(DCOMP_EUNSUPPORTED, "dcomp_actor_create: num_bs %d > %d", cfg->num_bs, DCOMP_MAX_BS);
-    if (cfg->num_ue > DCOMP_MAX_UE) return fail(DCOMP_EUNSUPPORTED, "dcomp_actor_create: num_ue %d > %d", cfg->num_ue, DCOMP_MAX_UE);
-    if (cfg->hidden > DCOMP_ACTOR_MAX_HIDDEN) return fail(DCOMP_EUNSUPPORTED, "dcomp_actor_create: hidden %d > %d", cfg->hidden, DCOMP_ACTOR_MAX_HIDDEN);
-    const bool multi = cfg->obs_kind == DCOMP_MULTI;
-    const int U = cfg->num_ue, B = cfg->num_bs, H = cfg->hidden;
-    const int K1 = multi ? 4 * B + 1 : U * (2 * B + 1), heads = multi ? 1 : U, N3 = heads * (B + 1);
-    if (K1 > DCOMP_ACTOR_MAX_IN) return fail(DCOMP_EUNSUPPORTED, "dcomp_actor_create: a central row of %d x %d has %d inputs > %d", U, B, K1, DCOMP_ACTOR_MAX_IN);
-    if (N3 > DCOMP_ACTOR_MAX_LOGITS) return fail(DCOMP_EUNSUPPORTED, "dcomp_actor_create: a central row of %d x %d has %d logits > %d", U, B, N3, DCOMP_ACTOR_MAX_LOGITS);
+    if (int rc = fcnet_shape_check(fn, cfg->obs_kind, cfg->num_ue, cfg->num_bs, cfg->hidden)) return rc;
+    if (cfg->activation != DCOMP_ACT_TANH && cfg->activation != DCOMP_ACT_RELU) return fail(DCOMP_EINVAL, "%s: unknown activation %d", fn, cfg->activation);
+    if (!cfg->w1 || !cfg->b1 || !cfg->w2 || !cfg->b2 || !cfg->w3 || !cfg->b3) return fail(DCOMP_EINVAL, "%s: a weight or bias pointer is NULL", fn);
 
     dcomp_actor *a = new dcomp_actor();
-    Net &n = a->net;
-    n.multi = multi; n.U = U; n.B = B; a->hidden = H;
-    a->mt = H <= 32 ? 1 : H <= 64 ? 2 : H <= 128 ? 4 : 8;
+    const ActorPlan &pl = a->plan = actor_plan(cfg->obs_kind, cfg->num_ue, cfg->num_bs, cfg->hidden);
+    Net &n = a->net;                                         // the kernels' description of the net: the plan's numbers (the trunks: upload_image)
+    n.multi = pl.multi; n.U = cfg->num_ue; n.B = cfg->num_bs;
+    n.K1 = pl.K1; n.K1p = pl.K1p; n.XS = pl.XS; n.N3 = pl.N3; n.NT3 = pl.NT3; n.heads = pl.heads; n.lds_per_wave = pl.lds_per_wave;
     a->relu = cfg->activation == DCOMP_ACT_RELU;
-    n.K1 = K1; n.K1p = (K1 + 15) & ~15; n.N3 = N3; n.NT3 = (N3 + 31) / 32; n.heads = heads;
-    const int kcp = n.K1p < KC ? n.K1p : KC;
-    n.XS = kcp + 8;                                          // row stride = an odd number of 16-byte slots: 16 rows, 16 slots
-    n.lds_per_wave = TILE * n.XS * 2 + TILE * LT * 4 + TILE * 16;
-    const int Hp = 32 * a->mt, KS2 = 2 * a->mt;
+    const int H = pl.hidden, Hp = pl.Hp;
     std::vector<uint16_t> p1, p2, p3;
-    pack(p1, cfg->w1, K1, H, n.K1p / 16, a->mt, false);
-    pack(p2, cfg->w2, H, H, KS2, a->mt, true);
-    pack(p3, cfg->w3, H, N3, KS2, n.NT3, true);
-    std::vector<float> bias((size_t)2 * Hp + 32 * n.NT3, 0.f);
+    pack(p1, cfg->w1, pl.K1, H, pl.K1p / 16, pl.mt, false);
+    pack(p2, cfg->w2, H, H, pl.KS2, pl.mt, true);
+    pack(p3, cfg->w3, H, pl.N3, pl.KS2, pl.NT3, true);
+    std::vector<float> bias((size_t)2 * Hp + 32 * pl.NT3, 0.f);
     memcpy(bias.data(), cfg->b1, sizeof(float) * H);
     memcpy(bias.data() + Hp, cfg->b2, sizeof(float) * H);
-    memcpy(bias.data() + 2 * Hp, cfg->b3, sizeof(float) * N3);
+    memcpy(bias.data() + 2 * Hp, cfg->b3, sizeof(float) * pl.N3);
 
     hipError_t e = hipGetDevice(&a->device);
     int cus = 0;
@@ -380,9 +403,9 @@ extern "C" int dcomp_actor_create(const dcomp_actor_cfg *cfg, dcomp_actor **out)
     if (e == hipSuccess) e = upload_image(p1, p2, p3, bias, Hp, &a->dev_mem, &n.pi);
     if (e != hipSuccess) {
         delete a;
-        return fail(DCOMP_EHIP, "dcomp_actor_create: %s", hipGetErrorString(e));
+        return fail(DCOMP_EHIP, "%s: %s", fn, hipGetErrorString(e));
     }
-    a->max_blocks = (cus > 0 ? cus : 256) * 2;               // two workgroups of four waves per CU: two waves per SIMD
+    a->max_blocks = max_blocks_of(cus);
     *out = a;
     return DCOMP_OK;
 }
@@ -413,8 +436,7 @@ static int actor_launch(const char *fn, bool vf_call, dcomp_actor *a, const dcom
 {
     using namespace dactor;
     if (!a || !r) return fail(DCOMP_EINVAL, "%s: handle and run must not be NULL", fn);
-    if (r->struct_size != (int32_t)sizeof(dcomp_actor_run))
-        return fail(DCOMP_EABI, "%s: caller's dcomp_actor_run has %d bytes, the library's %d", fn, r->struct_size, (int)sizeof(dcomp_actor_run));
+    if (int rc = check_struct(fn, "dcomp_actor_run", r->struct_size, sizeof(dcomp_actor_run))) return rc;
     if (r->obs_format != DCOMP_ACTOR_ROWS && r->obs_format != DCOMP_ACTOR_COMPACT) return fail(DCOMP_EINVAL, "%s: unknown obs_format %d", fn, r->obs_format);
     if (r->obs_format == DCOMP_ACTOR_COMPACT && !a->net.multi)
         return fail(DCOMP_EUNSUPPORTED, "%s: the compact record exists for multi-agent observations only", fn);
@@ -437,23 +459,23 @@ static int actor_launch(const char *fn, bool vf_call, dcomp_actor *a, const dcom
     memset(&p, 0, sizeof(p));
     p.obs = obs; p.action = action; p.logits = r->logits; p.logp = r->logp; p.vf = vf;
     p.net = a->net;
-    p.rows = rows; p.tiles = (rows + TILE - 1) / TILE; p.row_base = r->row_base;
+    const ActorPlan &pl = a->plan;
+    p.rows = rows; p.tiles = tiles_of(rows); p.row_base = r->row_base;
     p.num_active = r->num_active; p.compact = r->obs_format == DCOMP_ACTOR_COMPACT; p.sample = r->sample != 0;
     p.step = r->step; p.seed_lo = (uint32_t)r->seed; p.seed_hi = (uint32_t)(r->seed >> 32);
     p.policy = action != nullptr; p.vcol = -1;
     if (mode == 2) {
-        const int first = p.policy ? 0 : a->NT3v - 1;        // value only: the one output tile that holds the value's column, no logits
-        p.net.pi.w3 = a->net.vf.w3 + (size_t)first * 2 * a->mt * 64; p.net.pi.b3 = a->net.vf.b3 + 32 * first;
-        p.net.NT3 = a->NT3v - first; p.vcol = a->net.N3 - 32 * first;
+        const int first = p.policy ? 0 : pl.NT3v - 1;        // value only: the one output tile that holds the value's column, no logits
+        p.net.pi.w3 = a->net.vf.w3 + (size_t)first * pl.KS2 * 64; p.net.pi.b3 = a->net.vf.b3 + 32 * first;
+        p.net.NT3 = pl.NT3v - first; p.vcol = pl.N3 - 32 * first;
         if (!p.policy) p.net.N3 = 0;
     }
     if (set) {                                               // tiles of 32 envs per UE slot (members are multi, value form 0 or 1)
         p.table = set->table; p.envs = r->num_envs;
-        p.tiles = (int64_t)a->net.U * ((r->num_envs + TILE - 1) / TILE);
+        p.tiles = (int64_t)a->net.U * tiles_of(r->num_envs);
     }
-    const int64_t want = (p.tiles + WAVES - 1) / WAVES;
-    const int grid = (int)(want < a->max_blocks ? want : a->max_blocks);
-    hipLaunchKernelGGL(set ? pick_set(a->mt, a->relu != 0, mode) : pick(a->mt, a->relu != 0, mode), dim3(grid), dim3(BLOCK), (size_t)a->net.lds_per_wave * WAVES, static_cast<hipStream_t>(stream), p);
+    const int grid = launch_blocks(p.tiles, a->max_blocks);
+    hipLaunchKernelGGL(set ? pick_set(pl.mt, a->relu != 0, mode) : pick(pl.mt, a->relu != 0, mode), dim3(grid), dim3(BLOCK), (size_t)pl.lds_per_wave * WAVES, static_cast<hipStream_t>(stream), p);
     HIP_TRY(hipGetLastError());
     return DCOMP_OK;
 }
@@ -474,8 +496,7 @@ extern "C" int dcomp_policy_set_create(const dcomp_policy_set_cfg *cfg, dcomp_po
     if (out) *out = nullptr;
     // what needs no dereference of a member
     if (!cfg || !out) return fail(DCOMP_EINVAL, "dcomp_policy_set_create: cfg and out must not be NULL");
-    if (cfg->struct_size != (int32_t)sizeof(dcomp_policy_set_cfg))
-        return fail(DCOMP_EABI, "dcomp_policy_set_create: caller's dcomp_policy_set_cfg has %d bytes, the library's %d", cfg->struct_size, (int)sizeof(dcomp_policy_set_cfg));
+    if (int rc = check_struct("dcomp_policy_set_create", "dcomp_policy_set_cfg", cfg->struct_size, sizeof(dcomp_policy_set_cfg))) return rc;
     if (!cfg->members) return fail(DCOMP_EINVAL, "dcomp_policy_set_create: members must not be NULL");
     const int P = cfg->num_policies;
     if (P < 1 || P > DCOMP_MAX_UE) return fail(DCOMP_EINVAL, "dcomp_policy_set_create: num_policies %d outside [1, %d]", P, DCOMP_MAX_UE);
@@ -486,7 +507,7 @@ extern "C" int dcomp_policy_set_create(const dcomp_policy_set_cfg *cfg, dcomp_po
     for (int i = 1; i < P; i++) {
         const dcomp_actor *m = cfg->members[i];
         const struct { const char *what; int a, b; } same[] = {
-            {"obs_kind", f->net.multi, m->net.multi}, {"num_ue", f->net.U, m->net.U}, {"num_bs", f->net.B, m->net.B}, {"hidden", f->hidden, m->hidden},
+            {"obs_kind", f->net.multi, m->net.multi}, {"num_ue", f->net.U, m->net.U}, {"num_bs", f->net.B, m->net.B}, {"hidden", f->plan.hidden, m->plan.hidden},
             {"activation", f->relu, m->relu}, {"device", f->device, m->device}, {"value function", f->value, m->value}};
         for (const auto &c : same)
             if (c.a != c.b) return fail(DCOMP_EINVAL, "dcomp_policy_set_create: member %d differs from member 0 in %s (%d, %d)", i, c.what, c.b, c.a);
@@ -501,11 +522,7 @@ extern "C" int dcomp_policy_set_create(const dcomp_policy_set_cfg *cfg, dcomp_po
             if (cfg->slot_policy[u] < 0 || cfg->slot_policy[u] >= P)
                 return fail(DCOMP_EINVAL, "dcomp_policy_set_create: slot_policy[%d] = %d outside [0, %d)", u, cfg->slot_policy[u], P);
 
-    int dev = -1;
-    hipError_t e = hipGetDevice(&dev);
-    if (e == hipSuccess && dev != f->device)
-        return fail(DCOMP_EINVAL, "dcomp_policy_set_create: the members live on device %d, the calling thread's current device is %d", f->device, dev);
-    if (e != hipSuccess) return fail(DCOMP_EHIP, "dcomp_policy_set_create: %s", hipGetErrorString(e));
+    if (int rc = check_device("dcomp_policy_set_create", "the members live", f->device)) return rc;
     // (without a value function the second entries are NULL; no launch reads them: set->value keeps the value sweep off, and a member
     // that gets a value function later makes every call on the set fail on the host, set_first)
     std::vector<Trunk> host((size_t)2 * U);
@@ -517,7 +534,7 @@ extern "C" int dcomp_policy_set_create(const dcomp_policy_set_cfg *cfg, dcomp_po
     s->members.assign(cfg->members, cfg->members + P);
     s->table = nullptr;
     s->value = f->value;
-    e = hipMalloc(reinterpret_cast<void **>(&s->table), host.size() * sizeof(Trunk));
+    hipError_t e = hipMalloc(reinterpret_cast<void **>(&s->table), host.size() * sizeof(Trunk));
     if (e == hipSuccess) {
         e = hipMemcpy(s->table, host.data(), host.size() * sizeof(Trunk), hipMemcpyHostToDevice);
         if (e != hipSuccess) (void)hipFree(s->table);
@@ -544,8 +561,7 @@ extern "C" int dcomp_policy_set_destroy(dcomp_policy_set *s)
 static int set_first(const char *fn, dcomp_policy_set *s, const dcomp_actor_run *r, dcomp_actor **first)
 {
     if (!s || !r) return fail(DCOMP_EINVAL, "%s: handle and run must not be NULL", fn);
-    if (r->struct_size != (int32_t)sizeof(dcomp_actor_run))
-        return fail(DCOMP_EABI, "%s: caller's dcomp_actor_run has %d bytes, the library's %d", fn, r->struct_size, (int)sizeof(dcomp_actor_run));
+    if (int rc = check_struct(fn, "dcomp_actor_run", r->struct_size, sizeof(dcomp_actor_run))) return rc;
     for (size_t i = 0; i < s->members.size(); i++)
         if (s->members[i]->value != s->value)
             return fail(DCOMP_EINVAL, "%s: member %d got a value function after the set was created (value form %d, the set's %d): attach value "
@@ -572,8 +588,7 @@ extern "C" int dcomp_actor_set_value(dcomp_actor *a, const dcomp_actor_value_cfg
 {
     using namespace dactor;
     if (!a || !cfg) return fail(DCOMP_EINVAL, "dcomp_actor_set_value: handle and cfg must not be NULL");
-    if (cfg->struct_size != (int32_t)sizeof(dcomp_actor_value_cfg))
-        return fail(DCOMP_EABI, "dcomp_actor_set_value: caller's dcomp_actor_value_cfg has %d bytes, the library's %d", cfg->struct_size, (int)sizeof(dcomp_actor_value_cfg));
+    if (int rc = check_struct("dcomp_actor_set_value", "dcomp_actor_value_cfg", cfg->struct_size, sizeof(dcomp_actor_value_cfg))) return rc;
     if (cfg->shared != 0 && cfg->shared != 1) return fail(DCOMP_EINVAL, "dcomp_actor_set_value: shared %d is neither 0 nor 1", cfg->shared);
     if (!cfg->wv || !cfg->bv) return fail(DCOMP_EINVAL, "dcomp_actor_set_value: wv or bv is NULL");
     const bool any = cfg->w1 || cfg->b1 || cfg->w2 || cfg->b2, all = cfg->w1 && cfg->b1 && cfg->w2 && cfg->b2;
@@ -581,31 +596,25 @@ extern "C" int dcomp_actor_set_value(dcomp_actor *a, const dcomp_actor_value_cfg
     if (!cfg->shared && !all) return fail(DCOMP_EINVAL, "dcomp_actor_set_value: shared = 0 needs the value trunk: a pointer of w1 ... b2 is NULL");
     if (a->value) return fail(DCOMP_EINVAL, "dcomp_actor_set_value: the handle has a value function already (once per handle)");
 
-    int dev = -1;
-    hipError_t e = hipGetDevice(&dev);
-    if (e == hipSuccess && dev != a->device) return fail(DCOMP_EINVAL, "dcomp_actor_set_value: the handle lives on device %d, the calling thread's current device is %d", a->device, dev);
-    if (e != hipSuccess) return fail(DCOMP_EHIP, "dcomp_actor_set_value: %s", hipGetErrorString(e));
+    if (int rc = check_device("dcomp_actor_set_value", "the handle lives", a->device)) return rc;
 
     const Net &n = a->net;
-    const int H = a->hidden, Hp = 32 * a->mt, KS2 = 2 * a->mt;
+    const ActorPlan &pl = a->plan;
+    const int H = pl.hidden, Hp = pl.Hp, KS2 = pl.KS2;
     const size_t frag = (size_t)KS2 * 64 * 8;                // bf16 elements of one output tile of a hidden -> out layer
     std::vector<uint16_t> p1, p2, p3;
     std::vector<float> bias;
-    int nt3v;
     if (cfg->shared) {
-        // the actor's packed W3 (read back from the handle's device memory) with one more column: output N3 = lane r = N3 % 32 of
-        // tile N3 / 32 (a new tile when N3 % 32 == 0)
-        nt3v = n.N3 / 32 + 1;
-        p3.assign((size_t)nt3v * frag, 0);
-        bias.assign((size_t)32 * nt3v, 0.f);
-        HIP_TRY(hipMemcpy(p3.data(), n.pi.w3, (size_t)n.NT3 * frag * 2, hipMemcpyDeviceToHost));
-        HIP_TRY(hipMemcpy(bias.data(), n.pi.b3, sizeof(float) * 32 * n.NT3, hipMemcpyDeviceToHost));
-        for (int k = 0; k < H; k++) p3[pack_index(k, n.N3, KS2, true)] = bf16_rne(cfg->wv[k]);
-        bias[n.N3] = cfg->bv[0];
+        // the actor's packed W3 (read back from the handle's device memory) with one more column, NT3v tiles (ActorPlan)
+        p3.assign((size_t)pl.NT3v * frag, 0);
+        bias.assign((size_t)32 * pl.NT3v, 0.f);
+        HIP_TRY(hipMemcpy(p3.data(), n.pi.w3, (size_t)pl.NT3 * frag * 2, hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(bias.data(), n.pi.b3, sizeof(float) * 32 * pl.NT3, hipMemcpyDeviceToHost));
+        for (int k = 0; k < H; k++) p3[pack_index(k, pl.N3, KS2, true)] = bf16_rne(cfg->wv[k]);
+        bias[pl.N3] = cfg->bv[0];
     } else {
-        nt3v = 1;
-        pack(p1, cfg->w1, n.K1, H, n.K1p / 16, a->mt, false);
-        pack(p2, cfg->w2, H, H, KS2, a->mt, true);
+        pack(p1, cfg->w1, pl.K1, H, pl.K1p / 16, pl.mt, false);
+        pack(p2, cfg->w2, H, H, KS2, pl.mt, true);
         pack(p3, cfg->wv, H, 1, KS2, 1, true);
         bias.assign((size_t)2 * Hp + 32, 0.f);
         memcpy(bias.data(), cfg->b1, sizeof(float) * H);
@@ -614,11 +623,10 @@ extern "C" int dcomp_actor_set_value(dcomp_actor *a, const dcomp_actor_value_cfg
     }
     // shared: no hidden biases in the image, b3 at its start
     void *mem = nullptr;
-    e = upload_image(p1, p2, p3, bias, cfg->shared ? 0 : Hp, &mem, &a->net.vf);
+    const hipError_t e = upload_image(p1, p2, p3, bias, cfg->shared ? 0 : Hp, &mem, &a->net.vf);
     if (e != hipSuccess) return fail(DCOMP_EHIP, "dcomp_actor_set_value: %s", hipGetErrorString(e));
     a->value_mem = mem;
     if (cfg->shared) a->net.vf.b1 = a->net.vf.b2 = nullptr;
-    a->NT3v = nt3v;
     a->value = cfg->shared ? 2 : 1;
     return DCOMP_OK;
 }
@@ -627,8 +635,7 @@ extern "C" int dcomp_gae(const dcomp_gae_args *g, void *stream)
 {
     using namespace dactor;
     if (!g) return fail(DCOMP_EINVAL, "dcomp_gae: args must not be NULL");
-    if (g->struct_size != (int32_t)sizeof(dcomp_gae_args))
-        return fail(DCOMP_EABI, "dcomp_gae: caller's dcomp_gae_args has %d bytes, the library's %d", g->struct_size, (int)sizeof(dcomp_gae_args));
+    if (int rc = check_struct("dcomp_gae", "dcomp_gae_args", g->struct_size, sizeof(dcomp_gae_args))) return rc;
     if (!g->reward || !g->vf || !g->advantages || !g->value_targets) return fail(DCOMP_EINVAL, "dcomp_gae: reward, vf, advantages and value_targets must not be NULL");
     if (g->num_steps < 1) return fail(DCOMP_EINVAL, "dcomp_gae: num_steps %d < 1", g->num_steps);
     if (g->num_rows < 1) return fail(DCOMP_EINVAL, "dcomp_gae: num_rows %lld < 1", (long long)g->num_rows);

@@ -10,7 +10,10 @@
 //   - the packed-fragment layout: pack_index() is the permutation and bf16_rne() the rounding, on the host (pack) and on the device
 //     (the learner's Adam kernel)
 //   - the description of the net (Trunk, Net) that the handle holds and both kernels' arguments embed
-//   - host helpers: the failure text (fail, HIP_TRY), the device image of a trunk (upload_image), the width x activation dispatch
+//   - host helpers: the failure text (fail, HIP_TRY), the two checks every entry point's prologue makes (check_struct,
+//     check_device), the device image of a trunk (upload_image), the width x activation dispatch
+// Every shape number of a handle comes from dcomp_fcnet_plan.h (the one statement of the host dispatch); its constants are asserted
+// equal to the kernels' below.
 // Internal: not installed, not part of the ABI.
 #ifndef DCOMP_ACTOR_IMPL_H
 #define DCOMP_ACTOR_IMPL_H
@@ -24,6 +27,7 @@
 #include <vector>
 
 #include "../../include/dcomp.h"
+#include "dcomp_fcnet_plan.h"
 
 namespace dcomp { int report(int code, const char *msg); }       // dcomp_api.hip: the thread's dcomp_last_error() text
 
@@ -32,9 +36,11 @@ namespace dactor {
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 
+// the kernels' names for the plan's constants (dcomp_fcnet_plan.h, which a host without HIP reads): equal, or this does not compile
 constexpr int WAVES = 4, BLOCK = WAVES * 64, TILE = 32;
 constexpr int KC = 144;               // inputs staged at a time (a multiple of 16; KC + 8 elements = an odd number of 16-byte slots per row)
 constexpr int LT = 33;                // row stride of the logit tile (floats): lanes walk their rows conflict-free
+static_assert(WAVES == dplan::WAVES && BLOCK == dplan::BLOCK && TILE == dplan::TILE && KC == dplan::KC && LT == dplan::LT, "dcomp_fcnet_plan.h plans for other constants");
 
 // one trunk: packed bf16 fragments [m tile][k step][lane] x 8 elements, and the biases padded with zeros to the padded widths
 struct Trunk {
@@ -270,11 +276,12 @@ static hipError_t upload_image(const std::vector<uint16_t> &p1, const std::vecto
 }  // namespace dactor
 
 struct dcomp_actor {
-    int32_t hidden, mt, relu, device, max_blocks;
+    dactor::ActorPlan plan;                                  // every shape number of the handle
+    int32_t relu, device, max_blocks;
     dactor::Net net;                                         // (net.multi: the handle's obs_kind is DCOMP_MULTI)
     void *dev_mem;
     // the value function (dcomp_actor_set_value): value = 0 none, 1 a trunk of its own, 2 value_out on the actor's h2
-    int32_t value, NT3v;
+    int32_t value;
     void *value_mem;
 };
 
@@ -294,5 +301,20 @@ static int fail(int code, const char *fmt, ...)
         hipError_t e_ = (expr);                                                                     \
         if (e_ != hipSuccess) return fail(DCOMP_EHIP, "%s failed: %s", #expr, hipGetErrorString(e_)); \
     } while (0)
+
+
+// the two checks of an entry point's prologue.  A struct of the ABI carries its size as its first field:
+static int check_struct(const char *fn, const char *name, int32_t got, size_t size)
+{
+    return got == (int32_t)size ? DCOMP_OK : fail(DCOMP_EABI, "%s: caller's %s has %d bytes, the library's %d", fn, name, got, (int)size);
+}
+// and a handle is used on the device it was created on (what: "the handle lives")
+static int check_device(const char *fn, const char *what, int device)
+{
+    int dev = -1;
+    const hipError_t e = hipGetDevice(&dev);
+    if (e != hipSuccess) return fail(DCOMP_EHIP, "%s: %s", fn, hipGetErrorString(e));
+    return dev == device ? DCOMP_OK : fail(DCOMP_EINVAL, "%s: %s on device %d, the calling thread's current device is %d", fn, what, device, dev);
+}
 
 #endif

@@ -41,9 +41,10 @@ namespace dlearn {
 
 using namespace dactor;
 
-constexpr int NARR = 12;                  // w1 b1 w2 b2 w3 b3 | vw1 vb1 vw2 vb2 wv bv
+// the kernels' names for the plan's constants (dcomp_fcnet_plan.h): equal, or this does not compile
 constexpr int CHUNK_UNIT = 2048;          // rows of a weight-gradient chunk: CHUNK_UNIT x the smallest factor that keeps ...
 constexpr int MAX_CHUNKS = 128;           // ... the chunk count at or below this
+static_assert(CHUNK_UNIT == dplan::CHUNK_UNIT && MAX_CHUNKS == dplan::MAX_CHUNKS, "dcomp_fcnet_plan.h plans for other constants");
 
 struct LParams {
     const float *obs;
@@ -451,11 +452,7 @@ struct WParams {
     int32_t ntask;
 };
 
-// a wave's block of dW: MB x NB tiles of 32 x 32 -- 2 x 4 (six operand loads feed eight MFMAs per 16 rows) where the tile counts
-// divide, 1 where they do not (the out = 1 tile of a small head, an odd number of input tiles)
-__host__ __device__ inline int wgrad_mb(int mi_tiles) { return mi_tiles % 2 == 0 ? 2 : 1; }
-__host__ __device__ inline int wgrad_nb(int ni_tiles) { return ni_tiles % 4 == 0 ? 4 : 1; }
-
+// a wave's block of dW: MB x NB tiles of 32 x 32, wgrad_mb x wgrad_nb of the product's tile counts (dcomp_fcnet_plan.h)
 template <int MB, int NB>
 __device__ __forceinline__ void wgrad_block(const WParams &p, const WDesc &g, int local, int lane)
 {
@@ -641,14 +638,14 @@ __global__ __launch_bounds__(256) void adam_kernel(const AParams p)
 struct dcomp_learner {
     dcomp_actor *a;
     int64_t max_rows, ld, step;
-    int32_t device, total;
+    int32_t device;
     float beta1, beta2, eps;
     void *mem;
     float *w, *g, *m, *v;
+    dlearn::LearnerPlan plan;             // every shape number of the handle behind the actor's own (a->plan)
     dlearn::LParams lp;                   // the handle's part of the kernel arguments
     dlearn::WParams wp;
     dlearn::AParams ap;
-    int32_t off[dlearn::NARR], len[dlearn::NARR];
 };
 
 static const char *const ARRAY_NAMES[dlearn::NARR] = {"w1", "b1", "w2", "b2", "w3", "b3", "vw1", "vb1", "vw2", "vb2", "wv", "bv"};
@@ -663,8 +660,7 @@ static void members(const dcomp_learner_arrays *s, float *(&out)[dlearn::NARR])
 static int check_arrays(const char *fn, const char *what, const dcomp_learner_arrays *s, bool all)
 {
     if (!s) return fail(DCOMP_EINVAL, "%s: %s must not be NULL", fn, what);
-    if (s->struct_size != (int32_t)sizeof(dcomp_learner_arrays))
-        return fail(DCOMP_EABI, "%s: caller's dcomp_learner_arrays has %d bytes, the library's %d", fn, s->struct_size, (int)sizeof(dcomp_learner_arrays));
+    if (int rc = check_struct(fn, "dcomp_learner_arrays", s->struct_size, sizeof(dcomp_learner_arrays))) return rc;
     if (all) {
         float *m[dlearn::NARR];
         members(s, m);
@@ -685,7 +681,7 @@ static void launch_adam(dcomp_learner *l, bool adam, float lr, hipStream_t strea
         ap.step_size = (float)((double)lr / (1.0 - std::pow((double)l->beta1, t)));
         ap.bc2_sqrt = (float)std::sqrt(1.0 - std::pow((double)l->beta2, t));
     }
-    hipLaunchKernelGGL(dlearn::adam_kernel, dim3((l->total + 255) / 256), dim3(256), 0, stream, ap);
+    hipLaunchKernelGGL(dlearn::adam_kernel, dim3((l->plan.total + 255) / 256), dim3(256), 0, stream, ap);
 }
 
 extern "C" int dcomp_learner_create(dcomp_actor *a, const dcomp_learner_cfg *cfg, dcomp_learner **out)
@@ -694,8 +690,7 @@ extern "C" int dcomp_learner_create(dcomp_actor *a, const dcomp_learner_cfg *cfg
     const char *fn = "dcomp_learner_create";
     if (out) *out = nullptr;
     if (!a || !cfg || !out) return fail(DCOMP_EINVAL, "%s: actor, cfg and out must not be NULL", fn);
-    if (cfg->struct_size != (int32_t)sizeof(dcomp_learner_cfg))
-        return fail(DCOMP_EABI, "%s: caller's dcomp_learner_cfg has %d bytes, the library's %d", fn, cfg->struct_size, (int)sizeof(dcomp_learner_cfg));
+    if (int rc = check_struct(fn, "dcomp_learner_cfg", cfg->struct_size, sizeof(dcomp_learner_cfg))) return rc;
     if (cfg->value_shared == 1) return fail(DCOMP_EUNSUPPORTED, "%s: the shared value function (vf_share_layers=True) is not supported: the learner needs a value trunk of its own", fn);
     if (cfg->value_shared != 0) return fail(DCOMP_EINVAL, "%s: value_shared %d is neither 0 nor 1", fn, cfg->value_shared);
     if (cfg->max_rows < 1 || cfg->max_rows > (1ll << 28)) return fail(DCOMP_EINVAL, "%s: max_rows %lld outside [1, 2^28]", fn, (long long)cfg->max_rows);
@@ -706,54 +701,45 @@ extern "C" int dcomp_learner_create(dcomp_actor *a, const dcomp_learner_cfg *cfg
     if (a->value == 2) return fail(DCOMP_EUNSUPPORTED, "%s: the actor's value function is shared (vf_share_layers=True): the learner needs a value trunk of its own", fn);
     if (a->value != 1) return fail(DCOMP_EINVAL, "%s: the actor has no value trunk (dcomp_actor_set_value with shared = 0)", fn);
 
+    if (int rc = check_device(fn, "the actor lives", a->device)) return rc;
+
     const Net &n = a->net;
-    const int H = a->hidden, Hp = 32 * a->mt, KS2 = 2 * a->mt, K1 = n.K1, N3 = n.N3, NT3 = n.NT3;
-    const int K1pp = (K1 + 31) & ~31, N3p = 32 * NT3;
+    const ActorPlan &apl = a->plan;
+    const int Hp = apl.Hp, KS2 = apl.KS2, NT3 = apl.NT3;
     dcomp_learner *l = new dcomp_learner();
     memset(l, 0, sizeof(*l));
-    l->a = a; l->max_rows = cfg->max_rows;
-    // the row stride of the [width][rows] workspaces: whole tiles, + 128 bytes so that a power-of-two batch does not put the 32 rows a
-    // wgrad operand load touches into one memory channel
-    l->ld = ((cfg->max_rows + 31) & ~(int64_t)31) + 64;
+    l->a = a; l->max_rows = cfg->max_rows; l->device = a->device;
+    const LearnerPlan &pl = l->plan = learner_plan(apl);
+    l->ld = pl.ld_of(cfg->max_rows);
     l->beta1 = cfg->beta1; l->beta2 = cfg->beta2; l->eps = cfg->eps;
-    const int nin[NARR] = {K1, 1, H, 1, H, 1, K1, 1, H, 1, H, 1}, nout[NARR] = {H, H, H, H, N3, N3, H, H, H, H, 1, 1};
-    int total = 0;
-    for (int i = 0; i < NARR; i++) { l->off[i] = total; l->len[i] = nin[i] * nout[i]; total += l->len[i]; }
-    l->total = total;
+    const int total = pl.total;
 
     // one allocation: flat f32 arrays | backward fragments | activation / delta workspaces | walk and statistics workspaces | partials
     auto up = [](size_t v) { return (v + 255) & ~(size_t)255; };
     size_t at = 0;
     auto take = [&](size_t bytes) { const size_t o = at; at = up(at + bytes); return o; };
     const size_t o_flat = take((size_t)4 * total * 4);
-    const size_t n_w2b = (size_t)a->mt * KS2 * 512, n_w3b = (size_t)a->mt * 2 * NT3 * 512, n_vw3b = (size_t)a->mt * 2 * 512;
+    const size_t n_w2b = (size_t)apl.mt * KS2 * 512, n_w3b = (size_t)apl.mt * 2 * NT3 * 512, n_vw3b = (size_t)apl.mt * 2 * 512;
     const size_t o_w2b = take(n_w2b * 2), o_w3b = take(n_w3b * 2), o_vw2b = take(n_w2b * 2), o_vw3b = take(n_vw3b * 2);
     const size_t zero_end = at;                                                      // (zeroed up to here and over X: padding must read as zero)
     const size_t ld = (size_t)l->ld;
-    const size_t o_X = take((size_t)K1pp * ld * 2);
+    const size_t o_X = take((size_t)pl.K1pp * ld * 2);
     size_t o_H[8];
     for (int i = 0; i < 8; i++) o_H[i] = take((size_t)Hp * ld * 2);
-    const size_t o_D3 = take((size_t)N3p * ld * 2), o_VD3 = take((size_t)32 * ld * 2);
-    const size_t o_head = take((size_t)cfg->max_rows * n.heads * 16), o_tpart = take((ld / 32) * 32);      // (ld / 32 >= the tiles of max_rows)
-    const int in_p[6] = {K1pp, Hp, Hp, K1pp, Hp, Hp}, out_p[6] = {Hp, Hp, N3p, Hp, Hp, 32};
+    const size_t o_D3 = take((size_t)pl.N3p * ld * 2), o_VD3 = take((size_t)32 * ld * 2);
+    const size_t o_head = take((size_t)cfg->max_rows * apl.heads * 16), o_tpart = take((ld / 32) * 32);      // (ld / 32 >= the tiles of max_rows)
     size_t o_part[6], o_bpart[6];
-    for (int i = 0; i < 6; i++) { o_part[i] = take((size_t)MAX_CHUNKS * in_p[i] * out_p[i] * 4); o_bpart[i] = take((size_t)MAX_CHUNKS * out_p[i] * 4); }
+    for (int i = 0; i < 6; i++) { o_part[i] = take((size_t)MAX_CHUNKS * pl.in_p[i] * pl.out_p[i] * 4); o_bpart[i] = take((size_t)MAX_CHUNKS * pl.out_p[i] * 4); }
     const size_t bytes = at;
 
-    hipError_t e = hipGetDevice(&l->device);
-    if (e == hipSuccess && l->device != a->device) {
-        const int dev = l->device;
-        delete l;
-        return fail(DCOMP_EINVAL, "%s: the actor lives on device %d, the calling thread's current device is %d", fn, a->device, dev);
-    }
-    if (e == hipSuccess) e = hipMalloc(&l->mem, bytes);
+    hipError_t e = hipMalloc(&l->mem, bytes);
     unsigned char *d = static_cast<unsigned char *>(l->mem);
     if (e == hipSuccess) e = hipMemset(d, 0, zero_end);
-    if (e == hipSuccess) e = hipMemset(d + o_X, 0, (size_t)K1pp * ld * 2);
+    if (e == hipSuccess) e = hipMemset(d + o_X, 0, (size_t)pl.K1pp * ld * 2);
     float *src[NARR];
     members(cfg->weights, src);
     l->w = reinterpret_cast<float *>(d + o_flat); l->g = l->w + total; l->m = l->g + total; l->v = l->m + total;
-    for (int i = 0; i < NARR && e == hipSuccess; i++) e = hipMemcpy(l->w + l->off[i], src[i], (size_t)l->len[i] * 4, hipMemcpyHostToDevice);
+    for (int i = 0; i < NARR && e == hipSuccess; i++) e = hipMemcpy(l->w + pl.off[i], src[i], (size_t)pl.len[i] * 4, hipMemcpyHostToDevice);
     if (e != hipSuccess) {
         if (l->mem) (void)hipFree(l->mem);
         delete l;
@@ -772,15 +758,12 @@ extern "C" int dcomp_learner_create(dcomp_actor *a, const dcomp_learner_cfg *cfg
 
     WParams &w = l->wp;
     const __bf16 *wa[6] = {p.X, p.H1, p.H2, p.X, p.VH1, p.VH2}, *wd[6] = {p.D1, p.D2, p.D3, p.VD1, p.VD2, p.VD3};
-    int ntask = 0;
     for (int i = 0; i < 6; i++) {
         w.g[i].a = wa[i]; w.g[i].d = wd[i];
         w.g[i].part = reinterpret_cast<float *>(d + o_part[i]); w.g[i].bpart = reinterpret_cast<float *>(d + o_bpart[i]);
-        w.g[i].mi_tiles = in_p[i] / 32; w.g[i].ni_tiles = out_p[i] / 32; w.g[i].first_task = ntask;
-        w.g[i].nmain = (w.g[i].mi_tiles / wgrad_mb(w.g[i].mi_tiles)) * (w.g[i].ni_tiles / wgrad_nb(w.g[i].ni_tiles));
-        ntask += w.g[i].nmain + w.g[i].ni_tiles / wgrad_nb(w.g[i].ni_tiles);
+        w.g[i].mi_tiles = pl.in_p[i] / 32; w.g[i].ni_tiles = pl.out_p[i] / 32; w.g[i].first_task = pl.first_task[i]; w.g[i].nmain = pl.nmain[i];
     }
-    w.ld = l->ld; w.ntask = ntask;
+    w.ld = l->ld; w.ntask = pl.ntask;
 
     AParams &ap = l->ap;
     ap.total = total; ap.w = l->w; ap.g = l->g; ap.m = l->m; ap.v = l->v; ap.tile_part = p.part;
@@ -789,14 +772,14 @@ extern "C" int dcomp_learner_create(dcomp_actor *a, const dcomp_learner_cfg *cfg
     for (int i = 0; i < NARR; i++) {
         ADesc &x = ap.a[i];
         const int layer = i / 2;                                                     // 0 ... 5: the weight-gradient products
-        x.off = l->off[i]; x.nin = nin[i]; x.nout = nout[i]; x.in_p = in_p[layer]; x.out_p = out_p[layer]; x.is_bias = i & 1;
+        x.off = pl.off[i]; x.nin = pl.nin[i]; x.nout = pl.nout[i]; x.in_p = pl.in_p[layer]; x.out_p = pl.out_p[layer]; x.is_bias = i & 1;
         x.part = (i & 1) ? w.g[layer].bpart : w.g[layer].part;
     }
     const Trunk *trunk[2] = {&n.pi, &n.vf};
     const uint4 *w2b[2] = {p.w2b, p.vw2b}, *w3b[2] = {p.w3b, p.vw3b};
     for (int t = 0; t < 2; t++) {
         ADesc *x = ap.a + 6 * t;                                                     // w1 b1 w2 b2 w3 b3 of the trunk
-        x[0].fwd = u16(trunk[t]->w1); x[0].fwd_ks = n.K1p / 16; x[0].fwd_perm = 0;
+        x[0].fwd = u16(trunk[t]->w1); x[0].fwd_ks = apl.K1p / 16; x[0].fwd_perm = 0;
         x[2].fwd = u16(trunk[t]->w2); x[2].fwd_ks = KS2; x[2].fwd_perm = 1; x[2].bwd = u16(w2b[t]); x[2].bwd_ks = KS2; x[2].bwd_perm = 1;
         x[4].fwd = u16(trunk[t]->w3); x[4].fwd_ks = KS2; x[4].fwd_perm = 1; x[4].bwd = u16(w3b[t]); x[4].bwd_ks = t ? 2 : 2 * NT3; x[4].bwd_perm = 0;
         x[1].bias = f32(trunk[t]->b1); x[3].bias = f32(trunk[t]->b2); x[5].bias = f32(trunk[t]->b3);
@@ -842,8 +825,7 @@ static int learner_launch(const char *fn, bool evaluate, dcomp_learner *l, const
     using namespace dlearn;
     if (!evaluate) {
         if (!hy) return fail(DCOMP_EINVAL, "%s: hyper must not be NULL", fn);
-        if (hy->struct_size != (int32_t)sizeof(dcomp_ppo_hyper))
-            return fail(DCOMP_EABI, "%s: caller's dcomp_ppo_hyper has %d bytes, the library's %d", fn, hy->struct_size, (int)sizeof(dcomp_ppo_hyper));
+        if (int rc = check_struct(fn, "dcomp_ppo_hyper", hy->struct_size, sizeof(dcomp_ppo_hyper))) return rc;
         if (!stats) return fail(DCOMP_EINVAL, "%s: stats_dev must not be NULL", fn);
         if (!(hy->clip_param >= 0.f) || !(hy->vf_clip_param >= 0.f)) return fail(DCOMP_EINVAL, "%s: clip_param %g / vf_clip_param %g must be >= 0", fn, hy->clip_param, hy->vf_clip_param);
     }
@@ -886,39 +868,36 @@ static int learner_launch(const char *fn, bool evaluate, dcomp_learner *l, const
     p.vtarg = b->value_targets; p.old_vf = b->old_vf;
     p.o_logp = b->logp; p.o_ent = b->entropy; p.o_kl = b->kl; p.o_vf = b->vf; p.o_ratio = b->ratio;
     p.up_dlogits = b->dlogits; p.up_dvalue = b->dvalue;
-    p.rows = b->rows; p.tiles = (b->rows + TILE - 1) / TILE; p.num_active = b->num_active;
+    const RowSplit rs = row_split(b->rows);
+    p.rows = b->rows; p.tiles = rs.tiles; p.num_active = b->num_active;
     p.fwd_only = evaluate; p.upstream = upstream;
     if (hy) { p.clip = hy->clip_param; p.vf_clip = hy->vf_clip_param; p.vf_coeff = hy->vf_loss_coeff; p.ent_coeff = hy->entropy_coeff; p.kl_coeff = hy->kl_coeff; }
-    const int64_t want = (p.tiles + WAVES - 1) / WAVES;
-    const int grid = (int)(want < a->max_blocks ? want : a->max_blocks);
+    const int grid = launch_blocks(p.tiles, a->max_blocks);
+    const size_t lds = (size_t)a->plan.lds_per_wave * WAVES;
     if (b->indexed) {
         IParams ip;
         static_cast<LParams &>(ip) = p;
         ip.index = b->index; ip.source_rows = b->source_rows; ip.compact = compact;
-        hipLaunchKernelGGL(pick_indexed(a->mt, a->relu != 0), dim3(grid), dim3(BLOCK), (size_t)a->net.lds_per_wave * WAVES, s, ip);
+        hipLaunchKernelGGL(pick_indexed(a->plan.mt, a->relu != 0), dim3(grid), dim3(BLOCK), lds, s, ip);
     } else {
-        hipLaunchKernelGGL(pick(a->mt, a->relu != 0), dim3(grid), dim3(BLOCK), (size_t)a->net.lds_per_wave * WAVES, s, p);
+        hipLaunchKernelGGL(pick(a->plan.mt, a->relu != 0), dim3(grid), dim3(BLOCK), lds, s, p);
     }
     HIP_TRY(hipGetLastError());
     if (evaluate) return DCOMP_OK;
 
-    // the row split of the weight gradients: a function of the row count alone
     WParams w = l->wp;
-    w.rows_pad = p.tiles * TILE;
-    const int64_t mult = (w.rows_pad + (int64_t)CHUNK_UNIT * MAX_CHUNKS - 1) / ((int64_t)CHUNK_UNIT * MAX_CHUNKS);
-    w.chunk_rows = CHUNK_UNIT * mult;
-    const int nchunks = (int)((w.rows_pad + w.chunk_rows - 1) / w.chunk_rows);
-    hipLaunchKernelGGL(wgrad_kernel, dim3((w.ntask + WAVES - 1) / WAVES, nchunks), dim3(BLOCK), 0, s, w);
+    w.rows_pad = rs.rows_pad; w.chunk_rows = rs.chunk_rows;
+    hipLaunchKernelGGL(wgrad_kernel, dim3((w.ntask + WAVES - 1) / WAVES, rs.nchunks), dim3(BLOCK), 0, s, w);
     HIP_TRY(hipGetLastError());
 
     AParams ap = l->ap;
-    ap.nchunks = nchunks; ap.tiles = p.tiles; ap.stats = stats; ap.want_stats = 1;
+    ap.nchunks = rs.nchunks; ap.tiles = p.tiles; ap.stats = stats; ap.want_stats = 1;
     // the count behind 1 / N, on the host: indexed, every position (the index's contents cannot change it)
     const int64_t counted = b->indexed || !a->net.multi ? b->rows : (b->rows / U) * b->num_active + (b->rows % U < b->num_active ? b->rows % U : b->num_active);
     ap.count = upstream ? 0. : (double)counted;
     ap.scale = upstream ? 1.f : (counted > 0 ? (float)(1.0 / (double)counted) : 0.f);
     ap.vf_coeff = p.vf_coeff; ap.ent_coeff = p.ent_coeff; ap.kl_coeff = p.kl_coeff;
-    hipLaunchKernelGGL(reduce_kernel, dim3((l->total + 255) / 256), dim3(256), 0, s, ap);
+    hipLaunchKernelGGL(reduce_kernel, dim3((l->plan.total + 255) / 256), dim3(256), 0, s, ap);
     HIP_TRY(hipGetLastError());
     return DCOMP_OK;
 }
@@ -927,8 +906,7 @@ static int learner_launch(const char *fn, bool evaluate, dcomp_learner *l, const
 static int ppo_launch(const char *fn, bool evaluate, dcomp_learner *l, const dcomp_ppo_batch *b, const dcomp_ppo_hyper *hy, float *stats, void *stream)
 {
     if (!l || !b) return fail(DCOMP_EINVAL, "%s: handle and batch must not be NULL", fn);
-    if (b->struct_size != (int32_t)sizeof(dcomp_ppo_batch))
-        return fail(DCOMP_EABI, "%s: caller's dcomp_ppo_batch has %d bytes, the library's %d", fn, b->struct_size, (int)sizeof(dcomp_ppo_batch));
+    if (int rc = check_struct(fn, "dcomp_ppo_batch", b->struct_size, sizeof(dcomp_ppo_batch))) return rc;
     const BatchView v = {false, b->obs_format, b->num_active, b->rows, b->rows, nullptr, b->obs, b->actions, b->old_logp, b->old_logits, b->advantages,
                          b->value_targets, b->old_vf, b->logp, b->entropy, b->kl, b->vf, b->ratio, b->dlogits, b->dvalue};
     return learner_launch(fn, evaluate, l, &v, hy, stats, stream);
@@ -937,8 +915,7 @@ static int ppo_launch(const char *fn, bool evaluate, dcomp_learner *l, const dco
 static int sgd_launch(const char *fn, bool evaluate, dcomp_learner *l, const dcomp_sgd_batch *b, const dcomp_ppo_hyper *hy, float *stats, void *stream)
 {
     if (!l || !b) return fail(DCOMP_EINVAL, "%s: handle and batch must not be NULL", fn);
-    if (b->struct_size != (int32_t)sizeof(dcomp_sgd_batch))
-        return fail(DCOMP_EABI, "%s: caller's dcomp_sgd_batch has %d bytes, the library's %d", fn, b->struct_size, (int)sizeof(dcomp_sgd_batch));
+    if (int rc = check_struct(fn, "dcomp_sgd_batch", b->struct_size, sizeof(dcomp_sgd_batch))) return rc;
     const BatchView v = {true, b->obs_format, b->num_active, b->rows, b->source_rows, b->index, b->obs, b->actions, b->old_logp, b->old_logits, b->advantages,
                          b->value_targets, b->old_vf, b->logp, b->entropy, b->kl, b->vf, b->ratio, b->dlogits, b->dvalue};
     return learner_launch(fn, evaluate, l, &v, hy, stats, stream);
@@ -985,7 +962,7 @@ extern "C" int dcomp_learner_read(dcomp_learner *l, int32_t which, const dcomp_l
     float *m[dlearn::NARR];
     members(dst, m);
     for (int i = 0; i < dlearn::NARR; i++)
-        if (m[i]) HIP_TRY(hipMemcpy(m[i], src + l->off[i], (size_t)l->len[i] * 4, hipMemcpyDeviceToHost));
+        if (m[i]) HIP_TRY(hipMemcpy(m[i], src + l->plan.off[i], (size_t)l->plan.len[i] * 4, hipMemcpyDeviceToHost));
     if (step) *step = l->step;
     return DCOMP_OK;
 }
@@ -1006,7 +983,7 @@ extern "C" int dcomp_learner_load_state(dcomp_learner *l, const dcomp_learner_ar
     for (int k = 0; k < 3; k++) {
         float *m[dlearn::NARR];
         members(from[k], m);
-        for (int i = 0; i < dlearn::NARR; i++) HIP_TRY(hipMemcpy(to[k] + l->off[i], m[i], (size_t)l->len[i] * 4, hipMemcpyHostToDevice));
+        for (int i = 0; i < dlearn::NARR; i++) HIP_TRY(hipMemcpy(to[k] + l->plan.off[i], m[i], (size_t)l->plan.len[i] * 4, hipMemcpyHostToDevice));
     }
     l->step = step;
     launch_adam(l, false, 0.f, s);

@@ -3,83 +3,112 @@ tests/test_fcnet_matrix_gpu.py runs it).
 
 The kernels are template families -- actor_kernel<MT, RELU, VF, PER> (24 shared + 16 policy-set instantiations), learner_kernel<MT,
 RELU, IDX> (16), wgrad_block<MB, NB> (4), wgrad_bias<NB> (2) -- and the host picks among them, and among loop counts inside them, from
-the shape alone.  This module mirrors that dispatch in plain Python (each formula next to the source line it mirrors; the constants
-are READ from the sources, so a changed constant fails the CPU test instead of silently moving a case off its cell), lists the cases
-with the cells each one reaches, and builds the references that need no device: the integer nets' float64 outputs with their
-exactness conditions, and float32 emulations of the log-sum-exp walk and of the loss epilogue, which show that the stated bounds are
-reachable by a correct implementation.
+the shape alone.  Which cell a shape reaches is the LIBRARY's answer: dcomp_fcnet_describe (deepcomp_amd/csrc/dcomp_fcnet_plan.h, the
+one statement of that dispatch, which the create and launch functions read too) is asked here, so a changed formula moves the cases
+and the CPU test says which cell lost its case.  The module lists the cases with the cells each one reaches, and builds the
+references that need no device: the integer nets' float64 outputs with their exactness conditions, and float32 emulations of the
+log-sum-exp walk and of the loss epilogue, which show that the stated bounds are reachable by a correct implementation.
 
-To extend: a new template parameter or dispatch branch gets its formula in the mirror, a cell in cells(), a line in REQUIRED, and
-the smallest case that reaches it.  Pure numpy / torch on the CPU; nothing here touches the device."""
+To extend: a new template parameter or dispatch branch gets its number in the plan header, a cell in cells(), a line in REQUIRED, and
+the smallest case that reaches it.  Pure numpy / torch on the CPU; nothing here touches the device (dcomp_fcnet_describe makes no
+HIP call)."""
+import ctypes
+import functools
 import os
-import re
 
 import numpy as np
 
 from tests import test_actor_gpu as tag
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(REPO, 'deepcomp_amd', 'csrc')
-
-
-def _constant(source, name):
-    """`constexpr int ... NAME = <digits>` of a source file."""
-    txt = open(os.path.join(CSRC, source)).read()
-    m = re.search(r'constexpr\s+int\s[^;]*?\b%s\s*=\s*(\d+)\s*[,;]' % name, txt)
-    assert m, f'{source}: no constexpr int {name}'
-    return int(m.group(1))
-
-
-KC = _constant('dcomp_actor_impl.h', 'KC')                    # inputs staged at a time
-TILE = _constant('dcomp_actor_impl.h', 'TILE')                # decision rows of a wavefront
-WAVES = _constant('dcomp_actor_impl.h', 'WAVES')              # wavefronts of a workgroup
-CHUNK_UNIT = _constant('dcomp_learner.hip', 'CHUNK_UNIT')     # rows of a weight-gradient chunk, times mult
-MAX_CHUNKS = _constant('dcomp_learner.hip', 'MAX_CHUNKS')
-CUS = 256                                                     # an MI355X; dcomp_actor_create: a->max_blocks = cus * 2
-GRID_TILES = 2 * CUS * WAVES                                  # tiles of one round of the persistent grid
 
 
 # ------------------------------------------------------------------------------------------------------------ the host dispatch
+def _i32(*names):
+    return [(n, ctypes.c_int32) for n in names]
+
+
+class _ActorPlan(ctypes.Structure):
+    _fields_ = _i32('multi', 'hidden', 'K1', 'heads', 'N3', 'mt', 'Hp', 'KS2', 'K1p', 'NT3', 'NT3v', 'chunks', 'XS', 'lds_per_wave')
+
+
+class _LearnerPlan(ctypes.Structure):
+    _fields_ = _i32('K1pp', 'N3p') + [(n, ctypes.c_int32 * 6) for n in ('in_p', 'out_p', 'mb', 'nb', 'nmain', 'first_task')] + _i32('ntask') + \
+        [(n, ctypes.c_int32 * 12) for n in ('nin', 'nout', 'off', 'len')] + _i32('total')
+
+
+class _RowSplit(ctypes.Structure):
+    _fields_ = [(n, ctypes.c_int64) for n in ('tiles', 'rows_pad', 'mult', 'chunk_rows')] + _i32('nchunks')
+
+
+class _Shape(ctypes.Structure):
+    _fields_ = _i32('struct_size', 'obs_kind', 'num_ue', 'num_bs', 'hidden') + [('rows', ctypes.c_int64)] + _i32('compute_units')
+
+
+class _Desc(ctypes.Structure):
+    _fields_ = _i32('struct_size', 'TILE', 'WAVES', 'BLOCK', 'KC', 'LT', 'CHUNK_UNIT', 'MAX_CHUNKS', 'max_blocks', 'grid_tiles') + \
+        [('actor', _ActorPlan), ('learner', _LearnerPlan), ('split', _RowSplit)]
+
+
+@functools.lru_cache(maxsize=None)
+def describe(kind, U, B, H, rows=0, cus=0):
+    """dcomp_fcnet_describe of a shape (bound on first use; the struct sizes guard these mirrors): the library's own plan.
+    rows: the row split of that many rows; cus: the device's compute units, 0 = the library's fallback."""
+    from deepcomp_amd import _lib
+    L = _lib.load()
+    L.dcomp_fcnet_describe.argtypes = [ctypes.POINTER(_Shape), ctypes.POINTER(_Desc)]
+    s = _Shape(ctypes.sizeof(_Shape), _lib.MULTI if kind == 'multi' else _lib.CENTRAL, U, B, H, rows, cus)
+    d = _Desc(ctypes.sizeof(_Desc))
+    _lib.check(L.dcomp_fcnet_describe(ctypes.byref(s), ctypes.byref(d)))
+    return d
+
+
+_ANY = ('multi', 1, 1, 32)                                    # the constants and the row split are the same for every shape
+_CONSTANTS = ('KC', 'TILE', 'WAVES', 'CHUNK_UNIT', 'MAX_CHUNKS')
+
+
+def grid_tiles(cus=256):
+    """Tiles of one round of the persistent grid on a device of `cus` compute units (256: an MI355X)."""
+    return describe(*_ANY, cus=cus).grid_tiles
+
+
+def __getattr__(name):
+    """fc.KC, fc.TILE, fc.WAVES, fc.CHUNK_UNIT, fc.MAX_CHUNKS: the library's; fc.GRID_TILES: of an MI355X."""
+    if name in _CONSTANTS:
+        return getattr(describe(*_ANY), name)
+    if name == 'GRID_TILES':
+        return grid_tiles()
+    raise AttributeError(name)
+
+
 def actor_dispatch(kind, U, B, H):
-    """dcomp_actor.hip, dcomp_actor_create / dcomp_actor_set_value."""
-    multi = kind == 'multi'
-    K1 = 4 * B + 1 if multi else U * (2 * B + 1)              # const int K1 = multi ? 4 * B + 1 : U * (2 * B + 1), heads = multi ? 1 : U, N3 = heads * (B + 1);
-    heads = 1 if multi else U
-    N3 = heads * (B + 1)
-    mt = 1 if H <= 32 else 2 if H <= 64 else 4 if H <= 128 else 8      # a->mt = H <= 32 ? 1 : H <= 64 ? 2 : H <= 128 ? 4 : 8;
-    K1p = (K1 + 15) & ~15                                     # n.K1p = (K1 + 15) & ~15; n.N3 = N3; n.NT3 = (N3 + 31) / 32;
-    NT3 = (N3 + 31) // 32
-    chunks = (K1p + KC - 1) // KC                             # layer1: for (int k0 = 0; k0 < K1p; k0 += KC)
-    NT3v = N3 // 32 + 1                                       # nt3v = n.N3 / 32 + 1;  (shared: a new tile when N3 % 32 == 0)
-    return dict(multi=multi, K1=K1, heads=heads, N3=N3, mt=mt, K1p=K1p, NT3=NT3, chunks=chunks, NT3v=NT3v, Hp=32 * mt)
-
-
-def wgrad_mb(mi_tiles):
-    return 2 if mi_tiles % 2 == 0 else 1                      # wgrad_mb: return mi_tiles % 2 == 0 ? 2 : 1;
-
-
-def wgrad_nb(ni_tiles):
-    return 4 if ni_tiles % 4 == 0 else 1                      # wgrad_nb: return ni_tiles % 4 == 0 ? 4 : 1;
+    a = describe(kind, U, B, H).actor
+    return dict(multi=bool(a.multi), K1=a.K1, heads=a.heads, N3=a.N3, mt=a.mt, K1p=a.K1p, NT3=a.NT3, chunks=a.chunks, NT3v=a.NT3v, Hp=a.Hp)
 
 
 def learner_dispatch(kind, U, B, H):
-    """dcomp_learner.hip, dcomp_learner_create: the six weight-gradient products dW1 dW2 dW3 | dvW1 dvW2 dwv."""
-    a = actor_dispatch(kind, U, B, H)
-    K1pp = (a['K1'] + 31) & ~31                               # const int K1pp = (K1 + 31) & ~31, N3p = 32 * NT3;
-    N3p, Hp = 32 * a['NT3'], a['Hp']
-    in_p = [K1pp, Hp, Hp, K1pp, Hp, Hp]                       # const int in_p[6] = {K1pp, Hp, Hp, K1pp, Hp, Hp}, out_p[6] = {Hp, Hp, N3p, Hp, Hp, 32};
-    out_p = [Hp, Hp, N3p, Hp, Hp, 32]
-    blocks = [(wgrad_mb(i // 32), wgrad_nb(o // 32)) for i, o in zip(in_p, out_p)]
-    return dict(a, K1pp=K1pp, pairs=list(zip(in_p, out_p)), blocks=blocks, bias=[nb for _, nb in blocks])
+    """The six weight-gradient products dW1 dW2 dW3 | dvW1 dvW2 dwv."""
+    p = describe(kind, U, B, H).learner
+    return dict(actor_dispatch(kind, U, B, H), K1pp=p.K1pp, pairs=list(zip(p.in_p, p.out_p)), blocks=list(zip(p.mb, p.nb)), bias=list(p.nb))
+
+
+def wgrad_mb(mi_tiles):
+    """Of a product of mi_tiles (<= 8) input tiles: dW1 of a multi-agent net of 8 mi_tiles - 1 stations."""
+    p = describe('multi', 1, 8 * mi_tiles - 1, 32).learner
+    assert p.in_p[0] == 32 * mi_tiles
+    return p.mb[0]
+
+
+def wgrad_nb(ni_tiles):
+    """Of a product of ni_tiles (<= 16) output tiles: dW3 of a central net of 16 ni_tiles UEs and one station."""
+    p = describe('central', 16 * ni_tiles, 1, 32).learner
+    assert p.out_p[2] == 32 * ni_tiles
+    return p.nb[2]
 
 
 def row_split(rows):
-    """dcomp_learner.hip, learner_launch, where chunk_rows is set."""
-    rows_pad = (rows + TILE - 1) // TILE * TILE               # w.rows_pad = p.tiles * TILE;
-    mult = (rows_pad + CHUNK_UNIT * MAX_CHUNKS - 1) // (CHUNK_UNIT * MAX_CHUNKS)      # mult = (rows_pad + CHUNK_UNIT * MAX_CHUNKS - 1) / (CHUNK_UNIT * MAX_CHUNKS);
-    chunk_rows = CHUNK_UNIT * mult                            # w.chunk_rows = CHUNK_UNIT * mult;
-    nchunks = (rows_pad + chunk_rows - 1) // chunk_rows       # nchunks = (rows_pad + chunk_rows - 1) / chunk_rows;
-    return dict(mult=mult, chunk_rows=chunk_rows, nchunks=nchunks)
+    s = describe(*_ANY, rows=rows).split
+    return dict(mult=s.mult, chunk_rows=s.chunk_rows, nchunks=s.nchunks)
 
 
 def rows_of(kind, E, U):
@@ -87,7 +116,7 @@ def rows_of(kind, E, U):
 
 
 def tiles_of(kind, E, U):
-    return (rows_of(kind, E, U) + TILE - 1) // TILE
+    return describe(*_ANY, rows=rows_of(kind, E, U)).split.tiles
 
 
 # ------------------------------------------------------------------------------------------------------------ the cases
@@ -145,10 +174,10 @@ def cells():
         reach(('staging chunks', d['chunks']), sid(shape))
         reach(('logit tiles', d['NT3']), sid(shape))
         reach(('hidden', H), sid(shape))
-        if d['K1p'] == KC:
+        if d['K1p'] == describe(*_ANY).KC:
             reach(('K1p == KC',), sid(shape))
         if d['N3'] % 32 == 0:
-            assert d['NT3v'] == d['NT3'] + 1
+            assert d['NT3v'] == d['NT3'] + 1, f"{sid(shape)}: ('N3 % 32 == 0 with the shared value',) needs a tile of its own for the value, NT3v {d['NT3v']}"
             reach(('N3 % 32 == 0 with the shared value',), sid(shape))
         reach(('num_ue', U), sid(shape))
         reach(('num_bs', B), sid(shape))
@@ -156,7 +185,7 @@ def cells():
         kind, E, U, B, H = shape
         d = actor_dispatch(kind, U, B, H)
         reach(('actor', d['mt'], 'relu', 1), sid(shape))
-        if tiles_of(kind, E, U) > GRID_TILES:
+        if tiles_of(kind, E, U) > grid_tiles():
             reach(('actor: more tiles than one round of the grid', d['mt']), sid(shape))
     ps = POLICY_SET
     for H in POLICY_SET_HIDDEN:
@@ -181,7 +210,7 @@ def cells():
         reach(('learner: staging chunks', d['chunks']), sid(shape))
         reach(('learner: logit tiles', d['NT3']), sid(shape))
         reach(('learner: num_bs', B), sid(shape))
-        if tiles_of(kind, E, U) > GRID_TILES:
+        if tiles_of(kind, E, U) > grid_tiles():
             reach(('learner: more tiles than one round of the grid', d['mt']), sid(shape))
     ix = INDEXED
     for H in INDEXED_HIDDEN:

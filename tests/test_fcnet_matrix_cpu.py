@@ -1,4 +1,5 @@
-"""The self-check of tests/fcnet_cases.py, without a GPU: (1) the constants it reads are the sources'; (2) the table reaches every
+"""The self-check of tests/fcnet_cases.py, without a GPU: (1) the library's own constants and plans (dcomp_fcnet_describe) on known
+shapes, and what the kernels rely on over every accepted shape (tests/fcnet_plan_check.cpp); (2) the table reaches every
 instantiation of actor_kernel / learner_kernel / wgrad_block / wgrad_bias and every host-side branch listed in REQUIRED -- a case
 taken out of the table fails here, by the name of the cell it alone reached; (3) every integer case's float64 reference meets its
 exactness conditions, so a case that does not is found here and not on the device; (4) float32 emulations of the log-sum-exp walk
@@ -10,14 +11,15 @@ from tests import fcnet_cases as fc
 from tests import test_learner_gpu as tlg
 
 
-def test_constants_are_the_sources():
+def test_constants_are_the_librarys():
     assert (fc.KC, fc.TILE, fc.WAVES) == (144, 32, 4)
     assert (fc.CHUNK_UNIT, fc.MAX_CHUNKS) == (2048, 128)
     assert fc.CHUNK_UNIT == tlg.CHUNK
     assert fc.GRID_TILES == 2048                                  # tests/test_actor_gpu.py: "2 048 tiles a round on 256 CUs"
+    assert fc.grid_tiles(256) == 2048 and fc.grid_tiles(0) == 2048 and fc.grid_tiles(64) == 512      # (0: the library's fallback)
 
 
-def test_the_mirror_on_known_shapes():
+def test_the_librarys_plan_on_known_shapes():
     """Shapes whose dispatch the existing tests' comments state."""
     d = fc.actor_dispatch('multi', 32, 64, 256)                   # test_actor_gpu: K = 257 (two input chunks), N = 65
     assert (d['K1'], d['chunks'], d['N3'], d['NT3'], d['mt']) == (257, 2, 65, 3, 8)
@@ -34,6 +36,25 @@ def test_the_mirror_on_known_shapes():
     assert fc.row_split(6400) == dict(mult=1, chunk_rows=2048, nchunks=4)          # test_learner_gpu: three chunks and a partial one
     assert fc.row_split(128 * 2048)['mult'] == 1 and fc.row_split(128 * 2048 + 1)['mult'] == 2
     assert fc.row_split(fc.rows_of(*fc.MULT2_SHAPE[:3])) == dict(mult=2, chunk_rows=4096, nchunks=65)
+    assert [fc.wgrad_mb(t) for t in (1, 2, 3, 8)] == [1, 2, 1, 2] and [fc.wgrad_nb(t) for t in (1, 3, 4, 16)] == [1, 1, 4, 4]
+    # a shape dcomp_actor_create refuses (tests/test_actor_cpu.py) is refused with the same code
+    with pytest.raises(NotImplementedError, match='inputs'):
+        fc.describe('central', 94, 5, 64)
+    with pytest.raises(ValueError, match='hidden'):
+        fc.describe('multi', 4, 5, 48)
+
+
+def test_what_the_kernels_rely_on_holds_for_every_accepted_shape(tmp_path):
+    """tests/fcnet_plan_check.cpp, a stand-alone host program over the plan header alone, under the host sanitizers: K1p a multiple
+    of 16, XS an odd number of 16-byte slots, four waves' LDS under 64 KB, nchunks <= MAX_CHUNKS, ntask the sum of its parts, ..."""
+    import os
+    import subprocess
+    exe = str(tmp_path / 'fcnet_plan_check')
+    # (the runtimes linked statically: the program does not depend on where the loader puts them among its libraries)
+    subprocess.run(['g++', '-std=c++17', '-fsanitize=address,undefined', '-fno-sanitize-recover=all', '-static-libasan', '-static-libubsan', '-o', exe,
+                    os.path.join(fc.REPO, 'tests', 'fcnet_plan_check.cpp')], check=True)
+    r = subprocess.run([exe], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
+    assert r.returncode == 0, r.stdout
 
 
 def test_every_cell_is_reached():

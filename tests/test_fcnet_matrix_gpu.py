@@ -97,7 +97,7 @@ def test_actor_relu_integer_data_exact(torch_cuda, shape):
 @pytest.mark.parametrize('shape', fc.LOOP_SHAPES, ids=[fc.sid(s) for s in fc.LOOP_SHAPES])
 def test_actor_grid_stride_loop_exact(torch_cuda, shape):
     """2 200 tiles on a grid of at most 2 048 wavefronts: relu with a value trunk of its own, the exact bar."""
-    assert fc.tiles_of(*shape[:3]) > fc.GRID_TILES
+    assert fc.tiles_of(*shape[:3]) > fc.grid_tiles(torch_cuda.cuda.get_device_properties(torch_cuda.cuda.current_device()).multi_processor_count)
     for variant in fc.LOOP_VARIANTS:
         _relu_exact(torch_cuda, shape, variant, ('own',))
 
