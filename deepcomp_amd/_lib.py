@@ -151,6 +151,20 @@ class DcompPolicySetCfg(ctypes.Structure):
                 ('slot_policy', _ip)]
 
 
+# include/dcomp_learner_group.h: the learners of a policy set trained in one launch round per minibatch round
+GROUP_EXPORTS = ['dcomp_learner_group_create', 'dcomp_learner_group_destroy', 'dcomp_learner_group_grads', 'dcomp_learner_group_apply']
+
+
+class DcompLearnerGroupCfg(ctypes.Structure):
+    _fields_ = [('struct_size', ctypes.c_int32), ('num_learners', ctypes.c_int32), ('learners', ctypes.POINTER(ctypes.c_void_p))]
+
+
+class DcompGroupBatch(ctypes.Structure):
+    _fields_ = [('struct_size', ctypes.c_int32), ('obs_format', ctypes.c_int32), ('source_rows', ctypes.c_int64)] + \
+               [(n, ctypes.c_void_p) for n in ('obs', 'actions', 'old_logp', 'old_logits', 'advantages', 'value_targets', 'old_vf', 'index')] + \
+               [('index_stride', ctypes.c_int64), ('rows', ctypes.POINTER(ctypes.c_int64))]
+
+
 class DcompPpoHyper(ctypes.Structure):
     _fields_ = [('struct_size', ctypes.c_int32), ('clip_param', ctypes.c_float), ('vf_clip_param', ctypes.c_float),
                 ('vf_loss_coeff', ctypes.c_float), ('entropy_coeff', ctypes.c_float), ('kl_coeff', ctypes.c_float)]
@@ -258,6 +272,13 @@ def load():
         L.dcomp_policy_set_actions.argtypes = [vp, ctypes.POINTER(DcompActorRun), vp, vp, vp]
         L.dcomp_policy_set_actions_v.argtypes = [vp, ctypes.POINTER(DcompActorRun), vp, vp, vp, vp]
         for name in SET_EXPORTS:
+            getattr(L, name)
+    if hasattr(L, 'dcomp_learner_group_create') or not os.environ.get('DCOMP_LIB'):
+        L.dcomp_learner_group_create.argtypes = [ctypes.POINTER(DcompLearnerGroupCfg), ctypes.POINTER(vp)]
+        L.dcomp_learner_group_destroy.argtypes = [vp]
+        L.dcomp_learner_group_grads.argtypes = [vp, ctypes.POINTER(DcompGroupBatch), ctypes.POINTER(DcompPpoHyper), vp, vp]
+        L.dcomp_learner_group_apply.argtypes = [vp, _fp, _ip, vp]
+        for name in GROUP_EXPORTS:
             getattr(L, name)
     for name in EXPORTS:
         getattr(L, name)

@@ -1,6 +1,6 @@
 // dcomp_fcnet_plan.h -- which instantiation, how many tiles, chunks and blocks for a shape: the fcnet kernels' host dispatch, stated
-// ONCE.  dcomp_actor_create / dcomp_actor_set_value / actor_launch (dcomp_actor.hip), dcomp_learner_create / learner_launch
-// (dcomp_learner.hip) and the tests' table of cases (tests/fcnet_cases.py, through dcomp_fcnet_describe) all read it; the kernels
+// ONCE.  dcomp_actor_create / dcomp_actor_set_value / actor_launch (dcomp_actor.hip), dcomp_learner_create / learner_launch /
+// dcomp_learner_group_grads (dcomp_learner.hip) and the tests' table of cases (tests/fcnet_cases.py, through dcomp_fcnet_describe) all read it; the kernels
 // read the constants and wgrad_mb / wgrad_nb.  tests/fcnet_plan_check.cpp walks every accepted shape and checks what the kernels
 // rely on without saying so (K1p a multiple of 16, XS an odd number of 16-byte slots, four waves' LDS under 64 KB, ...).
 //
@@ -61,7 +61,7 @@ inline ActorPlan actor_plan(int obs_kind, int U, int B, int H)
     return p;
 }
 
-inline int64_t tiles_of(int64_t rows) { return (rows + dplan::TILE - 1) / dplan::TILE; }
+DCOMP_PLAN_HD inline int64_t tiles_of(int64_t rows) { return (rows + dplan::TILE - 1) / dplan::TILE; }
 
 // the persistent grid: two workgroups of four waves per CU (two waves per SIMD), a wave per tile up to that
 inline int max_blocks_of(int cus) { return (cus > 0 ? cus : 256) * 2; }
@@ -114,13 +114,14 @@ inline LearnerPlan learner_plan(const ActorPlan &a)
     return p;
 }
 
-// the row split of the weight gradients: a function of the row count alone
+// the row split of the weight gradients: a function of the row count alone (on the device too: the grouped kernels split each
+// policy's own row count)
 struct RowSplit {
     int64_t tiles, rows_pad, mult, chunk_rows;
     int32_t nchunks;
 };
 
-inline RowSplit row_split(int64_t rows)
+DCOMP_PLAN_HD inline RowSplit row_split(int64_t rows)
 {
     RowSplit s;
     using dplan::CHUNK_UNIT;
@@ -130,6 +131,27 @@ inline RowSplit row_split(int64_t rows)
     s.chunk_rows = CHUNK_UNIT * s.mult;
     s.nchunks = (int)((s.rows_pad + s.chunk_rows - 1) / s.chunk_rows);
     return s;
+}
+
+// The grouped launches (include/dcomp_learner_group.h): the policy is a grid axis of up to DCOMP_GROUP_SLICE policies per launch, and a
+// workgroup beyond its own policy's tiles or chunks returns at once.  The tile axis is sized by the slice's largest policy: tiles_of is
+// monotonic.  The chunk axis is NOT: row_split(rows).nchunks falls where mult steps up (262 144 rows: 128 chunks, 262 176: 65; 300 000:
+// 74, 200 000: 98), so it is sized by the largest chunk count among the slice's policies.
+inline int group_chunks(const int64_t *rows, int policies)
+{
+    int most = 0;
+    for (int i = 0; i < policies; i++) {
+        if (rows[i] <= 0) continue;                          // sits this call out
+        const int c = row_split(rows[i]).nchunks;
+        most = c > most ? c : most;
+    }
+    return most;
+}
+// x blocks per policy of the grouped learner kernel: the persistent grid shared among the slice's active policies
+inline int group_blocks(int64_t max_tiles, int max_blocks, int active)
+{
+    const int share = max_blocks / (active > 0 ? active : 1);
+    return launch_blocks(max_tiles, share > 0 ? share : 1);
 }
 
 }  // namespace dlearn

@@ -1,5 +1,8 @@
 // dcomp_learner.hip -- the PPO learner of the fcnet a dcomp_actor runs (include/dcomp_learner.h): loss, backward pass and Adam; and
-// its minibatches picked through a row index out of a whole sample batch, rows or compact record (include/dcomp_learner_indexed.h).
+// its minibatches picked through a row index out of a whole sample batch, rows or compact record (include/dcomp_learner_indexed.h);
+// and the learners of a per-UE policy set trained in one launch round (include/dcomp_learner_group.h): the same four kernels with the
+// policy as a grid dimension, behind the per-learner ones below.  The bodies both forms share are text (dcomp_learner_tiles.inc,
+// dcomp_learner_reduce.inc, dcomp_learner_adam.inc), included in each kernel.
 //
 // Four kernels per minibatch, all deterministic (no floating-point atomics; every sum has an order fixed by the row count):
 //   learner_kernel   forward + loss + backward-data.  The shape of actor_kernel: a wavefront owns 32 decision rows on its lanes and
@@ -35,6 +38,7 @@
 #include "../../include/dcomp.h"
 #include "../../include/dcomp_learner.h"
 #include "../../include/dcomp_learner_indexed.h"
+#include "../../include/dcomp_learner_group.h"
 #include "dcomp_actor_impl.h"       // the forward-pass helpers, the fragment layout, Net and struct dcomp_actor, fail / HIP_TRY: shared with dcomp_actor.hip
 
 namespace dlearn {
@@ -145,288 +149,7 @@ __device__ __forceinline__ double wave_sum(double v)
 template <int MT, bool RELU, bool IDX>
 __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(1, 1))) void learner_kernel(const std::conditional_t<IDX, IParams, LParams> p)
 {
-    extern __shared__ uint4 lds4[];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, r = lane & 31, h = lane >> 5;
-    const uint32_t lane16 = (uint32_t)lane * 16u;
-    const Net &n = p.net;
-    unsigned char *base = reinterpret_cast<unsigned char *>(lds4) + (size_t)wave * n.lds_per_wave;
-    __bf16 *xs = reinterpret_cast<__bf16 *>(base);                                   // [32][XS] bf16: the chunk of the tile's rows
-    float *lt = reinterpret_cast<float *>(base + (size_t)TILE * n.XS * 2);           // [32][LT] f32: 32 logits / dlogits of every row
-    // [32]: the row is read and counted.  IDX: [32][4], position r's source row (NO_ROW: nothing is read) | its env | listed | UE slot
-    uint32_t *ri = reinterpret_cast<uint32_t *>(lt + TILE * LT);
-    const int XS = n.XS, K1 = n.K1, U = n.U, NA = n.B + 1;
-    const int B = n.B, CW = ue_words(B);
-    const uint32_t *cwords = reinterpret_cast<const uint32_t *>(p.obs);
-    constexpr int KS2 = 2 * MT;
-    const int64_t ld = p.ld;
-
-    for (int64_t tile = (int64_t)blockIdx.x * WAVES + wave; tile < p.tiles; tile += (int64_t)gridDim.x * WAVES) {
-        const int64_t row0 = tile * TILE;
-        const int nrow = (int)(p.rows - row0 < TILE ? p.rows - row0 : TILE);
-        const int64_t myrow = row0 + r;                                              // the decision row on this lane
-        const bool have = r < nrow;
-        if constexpr (IDX) {
-            // the source row of every position, resolved once per tile; an entry outside the sample batch is never dereferenced
-            if (lane < TILE) {
-                uint32_t src = NO_ROW, env = 0, listed = 0, slot = 0;
-                if (have) {
-                    const int64_t s = p.index ? (int64_t)p.index[myrow] : myrow;
-                    if (s >= 0 && s < p.source_rows) {
-                        src = (uint32_t)s;
-                        if (p.compact) {
-                            env = src / (uint32_t)U; slot = src - env * (uint32_t)U;
-                            listed = compact_listed(cwords, (uint64_t)env * (uint64_t)env_words(U, B) + (uint64_t)slot * CW, B);
-                        }
-                    }
-                }
-                ri[lane * 4 + 0] = src; ri[lane * 4 + 1] = env; ri[lane * 4 + 2] = listed; ri[lane * 4 + 3] = slot;
-            }
-            wave_fence();
-        }
-        // a row beyond the batch, a multi-agent row of an unlisted slot, or (IDX) a position whose index entry is outside the sample
-        // batch: computed on zeros, every delta zero, nothing of it read
-        const bool live = IDX ? have && ri[r * 4] != NO_ROW : have && !(n.multi && (int)(myrow % U) >= p.num_active);
-        const bool walker = lane < TILE && live;
-        const uint32_t voff = (uint32_t)(2 * ((uint64_t)myrow + (uint64_t)(4 * h) * (uint64_t)ld));      // store_frags: this lane's column
-        if constexpr (!IDX) {
-            if (lane < TILE) ri[lane] = live ? 1u : 0u;
-            wave_fence();
-        }
-
-        float s_surr = 0.f, s_kl = 0.f, s_ent = 0.f, s_vfl = 0.f;                     // this row's terms (lanes < 32)
-        float c_lp = 0.f;                                                            // d(-surrogate) / d(logp)
-
-#pragma nounroll
-        for (int sweep = 0; sweep < 2; sweep++) {
-        const bool val = sweep != 0;
-        const Trunk t = select_trunk(n, val);
-        const uint4 *w2b = val ? p.vw2b : p.w2b, *w3b = val ? p.vw3b : p.w3b;
-        __bf16 *H1 = val ? p.VH1 : p.H1, *H2 = val ? p.VH2 : p.H2, *D1 = val ? p.VD1 : p.D1, *D2 = val ? p.VD2 : p.D2, *D3 = val ? p.VD3 : p.D3;
-        const int NT3 = val ? 1 : n.NT3, N3 = val ? 1 : n.N3;
-        const bool staged = val && n.K1p <= KC;                                      // the policy sweep left the bf16 rows in LDS
-
-        // ---- layer 1, with x as bf16 [input][rows] on the way for dW1 of both trunks
-        f32x16 acc[MT];
-        layer1<MT>(acc, t.w1, n.K1p, xs, XS, lane, lane16, staged,
-                   [&](int rr, int k) {
-                       if constexpr (IDX) {                                          // at the source row: a float row or a compact record
-                           const uint32_t s = ri[rr * 4];
-                           float v = 0.f;
-                           if (s != NO_ROW && k < K1) {
-                               if (!p.compact) v = p.obs[(size_t)s * K1 + k];
-                               else v = compact_input(cwords, (uint64_t)ri[rr * 4 + 1] * (uint64_t)env_words(U, B) + (uint64_t)ri[rr * 4 + 3] * CW,
-                                                      ri + rr * 4 + 2, k, B, U, CW);
-                           }
-                           return v;
-                       } else {
-                           return ri[rr] && k < K1 ? p.obs[(size_t)(row0 + rr) * K1 + k] : 0.f;
-                       }
-                   },
-                   [&](int k0, int kc) {
-                       if (!val && !p.fwd_only) {
-                           for (int i = lane; i < kc * TILE; i += 64) {
-                               const int c = i >> 5, rr = i & 31;
-                               p.X[(size_t)(k0 + c) * (size_t)ld + (size_t)(row0 + rr)] = xs[rr * XS + c];
-                           }
-                       }
-                   });
-
-        bf16x8 h1[MT][2];
-        hidden_fragments<MT, RELU>(acc, t.b1, h, h1);
-        if (!p.fwd_only) store_frags<MT>(H1, ld, voff, h1);
-
-        // ---- layer 2
-        bf16x8 h2[MT][2];
-#pragma unroll
-        for (int m = 0; m < MT; m++) {
-            const f32x16 a2 = tile_dot<MT>(t.w2, (size_t)m * KS2, h1, lane16);
-            h2[m][0] = next_fragment<RELU>(a2, 0, t.b2 + 32 * m + 4 * h);
-            h2[m][1] = next_fragment<RELU>(a2, 1, t.b2 + 32 * m + 4 * h);
-            asm volatile("" : "+v"(h2[m][0]), "+v"(h2[m][1]));
-            __builtin_amdgcn_sched_barrier(0);
-        }
-        if (!p.fwd_only) store_frags<MT>(H2, ld, voff, h2);
-
-        // ---- layer 3, first walk: the log-sum-exp of every head (new and old logits), logp of the given action, the entropy
-        float logp_sum = 0.f, oldlp_sum = 0.f, ent_sum = 0.f;
-        {
-            int hd = 0, a = 0, act = 0;
-            float xa = 0.f, mx = -INFINITY, sm = 0.f, tn = 0.f, mo = -INFINITY, so = 0.f;
-            for (int nt = 0; nt < NT3; nt++) {
-                put_logit_tile(tile_dot<MT>(t.w3, (size_t)nt * KS2, h2, lane16), t.b3, nt, lt, r, h);
-                wave_fence();
-                if (!val && walker && p.actions) {
-                    const int ncol = N3 - 32 * nt < 32 ? N3 - 32 * nt : 32;
-                    for (int c = 0; c < ncol; c++) {
-                        const float x = lt[r * LT + c];
-                        if (a == 0) act = p.actions[source_row<IDX>(ri, r, myrow) * n.heads + hd];
-                        if (a == act) xa = x;
-                        float e1, e2;
-                        lse_push(x, mx, sm, e1, e2);
-                        tn = tn * e1 + x * e2;
-                        if (p.old_logits) lse_push(p.old_logits[source_row<IDX>(ri, r, myrow) * n.N3 + 32 * nt + c], mo, so, e1, e2);
-                        if (++a == NA) {
-                            const size_t at = (size_t)myrow * n.heads + hd;
-                            const float lse = mx + logf(sm), lp = xa - lse, eh = lse - tn / sm;
-                            if (p.o_logp) p.o_logp[at] = lp;
-                            if (n.multi || hd < p.num_active) {
-                                logp_sum += lp; ent_sum += eh;
-                                if (p.old_logp) oldlp_sum += p.old_logp[IDX ? source_row<IDX>(ri, r, myrow) * n.heads + hd : at];
-                            }
-                            if (!p.fwd_only) p.headws[at] = make_float4(lse, mo + logf(so), eh, 0.f);
-                            a = 0; hd++; xa = 0.f;
-                            mx = -INFINITY; sm = 0.f; tn = 0.f; mo = -INFINITY; so = 0.f;
-                        }
-                    }
-                }
-                wave_fence();
-            }
-        }
-        if (!val) {
-            if (walker && p.o_ent) p.o_ent[myrow] = ent_sum;
-            s_ent = walker ? ent_sum : 0.f;
-            if (!p.fwd_only && !p.upstream && walker) {
-                const float adv = p.adv[source_row<IDX>(ri, r, myrow)], ratio = expf(logp_sum - oldlp_sum);
-                const float s1 = adv * ratio, s2 = adv * fminf(fmaxf(ratio, 1.f - p.clip), 1.f + p.clip);
-                s_surr = fminf(s1, s2);
-                c_lp = s1 <= s2 ? -s1 : 0.f;                                          // d(-min) / d(logp): d(adv ratio) / d(logp) = adv ratio
-                if (p.o_ratio) p.o_ratio[myrow] = ratio;
-            }
-            if constexpr (IDX) {
-                if (lane < TILE && have && !live) {                                  // nothing was read: its outputs are zeros
-                    if (p.actions && p.o_logp)
-                        for (int hd = 0; hd < n.heads; hd++) p.o_logp[(size_t)myrow * n.heads + hd] = 0.f;
-                    if (p.o_ent) p.o_ent[myrow] = 0.f;
-                    if (!p.fwd_only && !p.upstream) {
-                        if (p.o_ratio) p.o_ratio[myrow] = 0.f;
-                        if (p.o_kl) p.o_kl[myrow] = 0.f;
-                    }
-                }
-            }
-        } else if (lane < TILE && have && p.o_vf) {
-            p.o_vf[myrow] = !IDX || live ? lt[r * LT] : 0.f;                         // (the tile of the value sweep is still in LDS)
-        }
-        if (p.fwd_only) continue;
-
-        // ---- dlogits tile by tile into the LDS tile, and dH2^T = W3 dlogits^T
-        f32x16 dh[MT];
-#pragma unroll
-        for (int m = 0; m < MT; m++)
-#pragma unroll
-            for (int i = 0; i < 16; i++) dh[m][i] = 0.f;
-        {
-            int hd = 0, a = 0, act = 0;
-            float4 hw = make_float4(0.f, 0.f, 0.f, 0.f);
-            float kl_sum = 0.f;
-            for (int nt = 0; nt < NT3; nt++) {
-                const int ncol = N3 - 32 * nt < 32 ? N3 - 32 * nt : 32;
-                if (val) {
-                    // the value's one column: d(vf_loss_coeff max((v - vt)^2, (old_v + clip(v - old_v) - vt)^2)) / dv
-                    if (lane < TILE) {
-                        float dv = 0.f;
-                        if (walker) {
-                            if (p.upstream) dv = p.up_dvalue[source_row<IDX>(ri, r, myrow)];
-                            else {
-                                const float v = lt[r * LT], vt = p.vtarg[source_row<IDX>(ri, r, myrow)], ov = p.old_vf[source_row<IDX>(ri, r, myrow)];
-                                const float d1 = v - vt, dc = fminf(fmaxf(v - ov, -p.vf_clip), p.vf_clip), d2 = (ov + dc) - vt;
-                                const float l1 = d1 * d1, l2 = d2 * d2;
-                                s_vfl = fmaxf(l1, l2);
-                                dv = p.vf_coeff * (l1 >= l2 ? 2.f * d1 : (fabsf(v - ov) < p.vf_clip ? 2.f * d2 : 0.f));
-                            }
-                        }
-                        for (int c = 1; c < 32; c++) lt[r * LT + c] = 0.f;
-                        lt[r * LT] = dv;
-                    }
-                } else if (p.upstream) {
-                    for (int i = lane; i < TILE * 32; i += 64) {
-                        const int rr = i >> 5, c = i & 31;
-                        if constexpr (IDX) lt[rr * LT + c] = ri[rr * 4] != NO_ROW && c < ncol ? p.up_dlogits[(size_t)ri[rr * 4] * n.N3 + 32 * nt + c] : 0.f;
-                        else lt[rr * LT + c] = ri[rr] && c < ncol ? p.up_dlogits[(size_t)(row0 + rr) * n.N3 + 32 * nt + c] : 0.f;
-                    }
-                } else {
-                    put_logit_tile(tile_dot<MT>(t.w3, (size_t)nt * KS2, h2, lane16), t.b3, nt, lt, r, h);
-                    wave_fence();
-                    if (lane < TILE) {
-                        if (!walker) {
-                            for (int c = 0; c < 32; c++) lt[r * LT + c] = 0.f;
-                        } else {
-                            for (int c = 0; c < ncol; c++) {
-                                const float x = lt[r * LT + c];
-                                if (a == 0) {
-                                    hw = p.headws[(size_t)myrow * n.heads + hd];
-                                    act = p.actions[source_row<IDX>(ri, r, myrow) * n.heads + hd];
-                                }
-                                float dl = 0.f;
-                                if (n.multi || hd < p.num_active) {
-                                    const float lpn = x - hw.x, pn = expf(lpn);
-                                    const float lpo = p.old_logits[source_row<IDX>(ri, r, myrow) * n.N3 + 32 * nt + c] - hw.y, po = expf(lpo);
-                                    kl_sum += po * (lpo - lpn);
-                                    dl = c_lp * ((a == act ? 1.f : 0.f) - pn) + p.kl_coeff * (pn - po) + p.ent_coeff * (pn * (lpn + hw.z));
-                                }
-                                lt[r * LT + c] = dl;
-                                if (++a == NA) { a = 0; hd++; }
-                            }
-                            for (int c = ncol; c < 32; c++) lt[r * LT + c] = 0.f;
-                        }
-                    }
-                }
-                wave_fence();
-                // dlogits as bf16 [logit][rows] for dW3 (columns beyond N3 are zeros)
-                for (int i = lane; i < TILE * 32; i += 64) {
-                    const int c = i >> 5, rr = i & 31;
-                    D3[(size_t)(32 * nt + c) * (size_t)ld + (size_t)(row0 + rr)] = (__bf16)lt[rr * LT + c];
-                }
-#pragma unroll
-                for (int s = 0; s < 2; s++) {
-                    bf16x8 b;
-#pragma unroll
-                    for (int j = 0; j < 8; j++) b[j] = (__bf16)lt[r * LT + 16 * s + 8 * h + j];
-                    uint4 q[MT];
-#pragma unroll
-                    for (int m = 0; m < MT; m++) q[m] = load_frag(w3b, ((size_t)m * NT3 + nt) * 2 + s, lane16);
-#pragma unroll
-                    for (int m = 0; m < MT; m++) dh[m] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(as_frag(q[m]), b, dh[m], 0, 0, 0);
-                    __builtin_amdgcn_sched_barrier(0);
-                }
-                wave_fence();
-            }
-            if (!val) {
-                s_kl = walker && !p.upstream ? kl_sum : 0.f;
-                if (walker && p.o_kl && !p.upstream) p.o_kl[myrow] = kl_sum;
-            }
-        }
-
-        // ---- dA2 = bf16(dH2 (.) act'(h2)), dH1^T = W2 dA2^T, dA1
-        bf16x8 d2[MT][2];
-        delta_frags<MT, RELU>(dh, h2, d2);
-        store_frags<MT>(D2, ld, voff, d2);
-        bf16x8 d1[MT][2];
-#pragma unroll
-        for (int m = 0; m < MT; m++) {
-            const f32x16 g = tile_dot<MT>(w2b, (size_t)m * KS2, d2, lane16);
-#pragma unroll
-            for (int s = 0; s < 2; s++)
-#pragma unroll
-                for (int j = 0; j < 8; j++) {
-                    const float hv = (float)h1[m][s][j], gv = g[8 * s + j];
-                    d1[m][s][j] = (__bf16)(RELU ? (hv > 0.f ? gv : 0.f) : gv * (1.f - hv * hv));
-                }
-            asm volatile("" : "+v"(d1[m][0]), "+v"(d1[m][1]));
-            __builtin_amdgcn_sched_barrier(0);
-        }
-        store_frags<MT>(D1, ld, voff, d1);
-        }
-
-        if (!p.fwd_only) {
-            const double a0 = wave_sum(lane < TILE ? (double)s_surr : 0.), a1 = wave_sum(lane < TILE ? (double)s_kl : 0.);
-            const double a2 = wave_sum(lane < TILE ? (double)s_ent : 0.), a3 = wave_sum(lane < TILE ? (double)s_vfl : 0.);
-            if (lane == 0) {
-                double *q = p.part + 4 * tile;
-                q[0] = a0; q[1] = a1; q[2] = a2; q[3] = a3;
-            }
-        }
-        wave_fence();
-    }
+#include "dcomp_learner_tiles.inc"
 }
 
 typedef void (*learner_fn)(const LParams);
@@ -563,7 +286,7 @@ struct AParams {
     float beta1, omb1, beta2, omb2, step_size, bc2_sqrt, eps;
 };
 
-__device__ __forceinline__ int find_array(const AParams &p, int e)
+template <class P> __device__ __forceinline__ int find_array(const P &p, int e)      // (P: AParams, or the grouped kernels' view of it)
 {
     int ai = 0;
 #pragma unroll
@@ -573,65 +296,194 @@ __device__ __forceinline__ int find_array(const AParams &p, int e)
 
 __global__ __launch_bounds__(256) void reduce_kernel(const AParams p)
 {
-    const int e = blockIdx.x * 256 + threadIdx.x;
-    if (e < p.total) {
-        const int ai = find_array(p, e);
-        const ADesc d = p.a[ai];
-        const int idx = e - d.off, k = idx / d.nout, o = idx - k * d.nout;
-        const size_t stride = d.is_bias ? (size_t)d.out_p : (size_t)d.in_p * d.out_p, at = (size_t)k * d.out_p + o;
-        float s = 0.f;
-        for (int c = 0; c < p.nchunks; c++) s += d.part[c * stride + at];             // chunk order
-        p.g[e] = s * p.scale;
-    }
-    if (p.want_stats && blockIdx.x == 0) {
-        // the five statistics: 256 fixed ranges of tiles, then the 256 sums in order.  Summed in double: a mean over millions of rows
-        // averages the bf16 roundings away, and what is left of the error would be the f32 rounding of this one sum
-        __shared__ double sh[256][4];
-        const int64_t per = (p.tiles + 255) / 256, lo = threadIdx.x * per, hi = lo + per < p.tiles ? lo + per : p.tiles;
-        double s0 = 0., s1 = 0., s2 = 0., s3 = 0.;
-        for (int64_t t = lo; t < hi; t++) {
-            const double *v = p.tile_part + 4 * t;
-            s0 += v[0]; s1 += v[1]; s2 += v[2]; s3 += v[3];
-        }
-        sh[threadIdx.x][0] = s0; sh[threadIdx.x][1] = s1; sh[threadIdx.x][2] = s2; sh[threadIdx.x][3] = s3;
-        __syncthreads();
-        if (threadIdx.x == 0) {
-            double t0 = 0., t1 = 0., t2 = 0., t3 = 0.;
-            for (int i = 0; i < 256; i++) { t0 += sh[i][0]; t1 += sh[i][1]; t2 += sh[i][2]; t3 += sh[i][3]; }
-            const double inv = p.count > 0. ? 1.0 / p.count : 0.0;
-            const float pol = (float)(-t0 * inv), kl = (float)(t1 * inv), ent = (float)(t2 * inv), vfl = (float)(t3 * inv);
-            p.stats[0] = pol + p.kl_coeff * kl + p.vf_coeff * vfl - p.ent_coeff * ent;
-            p.stats[1] = pol; p.stats[2] = vfl; p.stats[3] = kl; p.stats[4] = ent;
-        }
-    }
+#include "dcomp_learner_reduce.inc"
 }
 
 __global__ __launch_bounds__(256) void adam_kernel(const AParams p)
 {
-#pragma clang fp contract(off)
-    const int e = blockIdx.x * 256 + threadIdx.x;
-    if (e >= p.total) return;
-    float w = p.w[e];
-    if (p.adam) {                                                                    // adam_reference: every operation rounded on its own
-        const float g = p.g[e];
-        const float m = p.m[e] * p.beta1 + g * p.omb1;
-        const float v = p.v[e] * p.beta2 + (g * g) * p.omb2;
-        const float denom = sqrtf(v) / p.bc2_sqrt + p.eps;
-        w = w - p.step_size * (m / denom);
-        p.m[e] = m; p.v[e] = v; p.w[e] = w;
-    }
-    const int ai = find_array(p, e);
-    const ADesc d = p.a[ai];
-    const int idx = e - d.off;
-    if (d.is_bias) {
-        d.bias[idx] = w;
-        return;
-    }
-    const int k = idx / d.nout, o = idx - k * d.nout;
-    const uint16_t q = bf16_rne(w);
-    d.fwd[pack_index(k, o, d.fwd_ks, d.fwd_perm)] = q;
-    if (d.bwd) d.bwd[pack_index(o, k, d.bwd_ks, d.bwd_perm)] = q;                     // the other orientation: W^T
+#include "dcomp_learner_adam.inc"
 }
+
+// ---------------------------------------------------------------- all learners of a group in one launch (include/dcomp_learner_group.h)
+// The four kernels above with the policy as a grid dimension.  What dcomp_learner keeps in lp / wp / ap is one entry per policy of a
+// device table written at dcomp_learner_group_create; what changes per call (rows, hyper-parameters, Adam's scalars) are arrays in
+// the kernel arguments, indexed like the table by the policy's number within the launch's slice.  The policy is wave-uniform
+// (blockIdx), so read through the constant address space an entry arrives in SGPRs like the kernel arguments it stands for
+// (actor_kernel<..., PER = true> reads its trunk table the same way), and every statement of a policy's arithmetic is the
+// per-learner kernel's own (the .inc bodies).
+constexpr int GROUP_SLICE = DCOMP_GROUP_SLICE;
+
+struct GEntry {
+    LParams lp;                           // first: the member's net, backward fragments, workspaces and ld (the per-call members unused)
+    WDesc wg[6];
+    ADesc a[NARR];
+    float *w, *g, *m, *v;
+    int32_t total, ntask;
+    float beta1, omb1, beta2, omb2, eps;
+    int32_t reserved;
+};
+typedef const GEntry __attribute__((address_space(4))) *gentry_ptr;
+__device__ __forceinline__ gentry_ptr group_entry(const GEntry *table, int i) { return (gentry_ptr)(uintptr_t)(table + i); }
+// a whole member of an entry through the constant address space, as 64-bit words (slot_trunk's way, dcomp_actor.hip)
+template <class T> __device__ __forceinline__ T const_copy(const T __attribute__((address_space(4))) *src)
+{
+    static_assert(sizeof(T) % 8 == 0 && std::is_trivially_copyable<T>::value, "read as 64-bit words");
+    const uint64_t __attribute__((address_space(4))) *q = (const uint64_t __attribute__((address_space(4))) *)src;
+    union { T v; uint64_t w[sizeof(T) / 8]; } u;
+#pragma unroll
+    for (size_t i = 0; i < sizeof(T) / 8; i++) u.w[i] = q[i];
+    return u.v;
+}
+
+// learner_kernel<MT, RELU, true> per policy.  The members a grouped call never uses (per-row outputs, upstream gradients, fwd_only)
+// are arguments all the same, NULL / 0 from the host: known at compile time they would prune the body, and which f32 operations
+// the compiler contracts must not depend on who launches it.
+struct GLParams {
+    const float *obs;
+    const uint8_t *actions;
+    const float *old_logp, *old_logits, *adv, *vtarg, *old_vf;
+    float *o_logp, *o_ent, *o_kl, *o_vf, *o_ratio;
+    const float *up_dlogits, *up_dvalue;
+    const GEntry *table;                  // of the slice's first policy, as index is
+    const int32_t *index;
+    int64_t index_stride, source_rows;
+    int32_t compact, num_active, fwd_only, upstream;
+    int32_t rows[GROUP_SLICE];            // 0: the policy sits this call out
+    float clip[GROUP_SLICE], vf_clip[GROUP_SLICE], vf_coeff[GROUP_SLICE], ent_coeff[GROUP_SLICE], kl_coeff[GROUP_SLICE];
+};
+
+template <int MT, bool RELU>
+__global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(1, 1))) void learner_group_kernel(const GLParams gp)
+{
+    constexpr bool IDX = true;
+    const int pol = blockIdx.y;
+    const int32_t nrows = gp.rows[pol];
+    if (nrows == 0 || (int64_t)blockIdx.x * WAVES >= tiles_of(nrows)) return;        // not in this call; beyond the policy's tiles
+    IParams p;
+    static_cast<LParams &>(p) = const_copy(&group_entry(gp.table, pol)->lp);
+    p.obs = gp.obs; p.actions = gp.actions; p.old_logp = gp.old_logp; p.old_logits = gp.old_logits; p.adv = gp.adv; p.vtarg = gp.vtarg; p.old_vf = gp.old_vf;
+    p.o_logp = gp.o_logp; p.o_ent = gp.o_ent; p.o_kl = gp.o_kl; p.o_vf = gp.o_vf; p.o_ratio = gp.o_ratio;
+    p.up_dlogits = gp.up_dlogits; p.up_dvalue = gp.up_dvalue;
+    p.rows = nrows; p.tiles = tiles_of(nrows);
+    p.num_active = gp.num_active; p.fwd_only = gp.fwd_only; p.upstream = gp.upstream;
+    p.clip = gp.clip[pol]; p.vf_clip = gp.vf_clip[pol]; p.vf_coeff = gp.vf_coeff[pol]; p.ent_coeff = gp.ent_coeff[pol]; p.kl_coeff = gp.kl_coeff[pol];
+    p.index = gp.index + (int64_t)pol * gp.index_stride; p.source_rows = gp.source_rows; p.compact = gp.compact;
+    {
+#include "dcomp_learner_tiles.inc"
+    }
+}
+
+typedef void (*group_fn)(const GLParams);
+static group_fn pick_group(int mt, bool relu)
+{
+    return pick_shape(mt, relu, [](auto s) -> group_fn { return learner_group_kernel<decltype(s)::MT, decltype(s)::RELU>; });
+}
+
+// wgrad_kernel per policy (blockIdx.z), the row split from the policy's own row count
+struct GWParams {
+    const GEntry *table;
+    int32_t rows[GROUP_SLICE];
+};
+
+__global__ __launch_bounds__(BLOCK) void wgrad_group_kernel(const GWParams gp)
+{
+    const int pol = blockIdx.z;
+    const int32_t nrows = gp.rows[pol];
+    if (nrows == 0) return;
+    const RowSplit rs = row_split(nrows);
+    if ((int)blockIdx.y >= rs.nchunks) return;                                        // beyond the policy's chunks
+    const gentry_ptr en = group_entry(gp.table, pol);
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int task = blockIdx.x * WAVES + wave;
+    if (task >= en->ntask) return;
+    int gi = 0;
+#pragma unroll
+    for (int i = 1; i < 6; i++) gi = task >= en->wg[i].first_task ? i : gi;
+    const WDesc g = const_copy(&en->wg[gi]);
+    WParams p;                                                                        // (what wgrad_block / wgrad_bias read of it)
+    p.ld = en->lp.ld; p.rows_pad = rs.rows_pad; p.chunk_rows = rs.chunk_rows;
+    const int local = task - g.first_task, mb = wgrad_mb(g.mi_tiles), nb = wgrad_nb(g.ni_tiles);      // (wave-uniform)
+    if (local >= g.nmain) {
+        if (nb == 4) wgrad_bias<4>(p, g, local - g.nmain, lane);
+        else wgrad_bias<1>(p, g, local - g.nmain, lane);
+    } else if (mb == 2 && nb == 4) wgrad_block<2, 4>(p, g, local, lane);
+    else if (nb == 4) wgrad_block<1, 4>(p, g, local, lane);
+    else if (mb == 2) wgrad_block<2, 1>(p, g, local, lane);
+    else wgrad_block<1, 1>(p, g, local, lane);
+}
+
+// a policy's AParams as reduce_kernel / adam_kernel name them: the array descriptions stay in the table (a thread's own is a
+// divergent index; the offsets find_array compares are at uniform addresses and compile to scalar loads as they are:
+// adam_group_kernel has adam_kernel's 16 vector-memory instructions), everything else is scalar
+struct GAView {
+    const ADesc *a;
+    int32_t total, nchunks;
+    float scale;
+    float *w, *g, *m, *v;
+    const double *tile_part;
+    int64_t tiles;
+    float *stats;
+    double count;
+    float vf_coeff, ent_coeff, kl_coeff;
+    int32_t adam, want_stats;
+    float beta1, omb1, beta2, omb2, step_size, bc2_sqrt, eps;
+};
+__device__ __forceinline__ GAView group_view(const GEntry *table, int pol)
+{
+    const gentry_ptr en = group_entry(table, pol);
+    GAView p = {};
+    p.a = table[pol].a;
+    p.total = en->total; p.w = en->w; p.g = en->g; p.m = en->m; p.v = en->v; p.tile_part = en->lp.part;
+    return p;
+}
+
+// reduce_kernel per policy (blockIdx.y): 1 / N from the host as launch computes it, the count and the split from the row count
+struct GRParams {
+    const GEntry *table;
+    float *stats;                         // [policy of the slice][DCOMP_PPO_NUM_STATS]
+    int32_t rows[GROUP_SLICE];
+    float scale[GROUP_SLICE], vf_coeff[GROUP_SLICE], ent_coeff[GROUP_SLICE], kl_coeff[GROUP_SLICE];
+};
+
+__global__ __launch_bounds__(256) void reduce_group_kernel(const GRParams gp)
+{
+    const int pol = blockIdx.y;
+    const int32_t nrows = gp.rows[pol];
+    if (nrows == 0) return;
+    GAView p = group_view(gp.table, pol);
+    const RowSplit rs = row_split(nrows);
+    p.nchunks = rs.nchunks; p.tiles = rs.tiles; p.scale = gp.scale[pol]; p.count = (double)nrows;
+    p.stats = gp.stats + DCOMP_PPO_NUM_STATS * pol; p.want_stats = 1;
+    p.vf_coeff = gp.vf_coeff[pol]; p.ent_coeff = gp.ent_coeff[pol]; p.kl_coeff = gp.kl_coeff[pol];
+    {
+#include "dcomp_learner_reduce.inc"
+    }
+}
+
+// adam_kernel per policy (blockIdx.y): the bias corrections per policy from the host, in double as launch_adam has them -- the
+// members have taken different numbers of steps
+struct GAParams {
+    const GEntry *table;
+    int32_t active[GROUP_SLICE];
+    float step_size[GROUP_SLICE], bc2_sqrt[GROUP_SLICE];
+};
+
+__global__ __launch_bounds__(256) void adam_group_kernel(const GAParams gp)
+{
+    const int pol = blockIdx.y;
+    if (!gp.active[pol]) return;
+    GAView p = group_view(gp.table, pol);
+    const gentry_ptr en = group_entry(gp.table, pol);
+    p.adam = 1; p.beta1 = en->beta1; p.omb1 = en->omb1; p.beta2 = en->beta2; p.omb2 = en->omb2; p.eps = en->eps;
+    p.step_size = gp.step_size[pol]; p.bc2_sqrt = gp.bc2_sqrt[pol];
+    {
+#include "dcomp_learner_adam.inc"
+    }
+}
+
+static_assert(sizeof(GLParams) <= 4096 && sizeof(GWParams) <= 4096 && sizeof(GRParams) <= 4096 && sizeof(GAParams) <= 4096,
+              "the kernel arguments of a grouped launch: lower DCOMP_GROUP_SLICE");
+static_assert(DCOMP_GROUP_SLICE >= 64 && DCOMP_GROUP_SLICE <= 65535, "a slice is a grid's y / z extent");
 
 }  // namespace dlearn
 
@@ -819,10 +671,9 @@ struct BatchView {
     const float *dlogits, *dvalue;
 };
 
-// the grads (evaluate = false) and evaluate calls of both surfaces: every check on the host first
-static int learner_launch(const char *fn, bool evaluate, dcomp_learner *l, const BatchView *b, const dcomp_ppo_hyper *hy, float *stats, void *stream)
+// every host check of a grads (evaluate = false) or evaluate call on one learner; the grouped call makes them per policy
+static int learner_check(const char *fn, bool evaluate, const dcomp_learner *l, const BatchView *b, const dcomp_ppo_hyper *hy, const float *stats)
 {
-    using namespace dlearn;
     if (!evaluate) {
         if (!hy) return fail(DCOMP_EINVAL, "%s: hyper must not be NULL", fn);
         if (int rc = check_struct(fn, "dcomp_ppo_hyper", hy->struct_size, sizeof(dcomp_ppo_hyper))) return rc;
@@ -861,6 +712,17 @@ static int learner_launch(const char *fn, bool evaluate, dcomp_learner *l, const
     if (b->num_active < 0 || b->num_active > U) return fail(DCOMP_EINVAL, "%s: num_active %d outside [0, %d]", fn, b->num_active, U);
     if (b->indexed && a->net.multi && b->num_active != U)
         return fail(DCOMP_EINVAL, "%s: num_active %d != num_ue %d: with multi-agent rows select the listed rows through the index (every position counts in 1 / N)", fn, b->num_active, U);
+    return DCOMP_OK;
+}
+
+// the grads and evaluate calls of both surfaces: every check on the host first
+static int learner_launch(const char *fn, bool evaluate, dcomp_learner *l, const BatchView *b, const dcomp_ppo_hyper *hy, float *stats, void *stream)
+{
+    using namespace dlearn;
+    if (int rc = learner_check(fn, evaluate, l, b, hy, stats)) return rc;
+    const dcomp_actor *a = l->a;
+    const int U = a->net.U;
+    const bool compact = b->indexed && b->obs_format == DCOMP_ACTOR_COMPACT, upstream = b->dlogits || b->dvalue;
 
     hipStream_t s = static_cast<hipStream_t>(stream);
     LParams p = l->lp;
@@ -988,5 +850,188 @@ extern "C" int dcomp_learner_load_state(dcomp_learner *l, const dcomp_learner_ar
     l->step = step;
     launch_adam(l, false, 0.f, s);
     HIP_TRY(hipGetLastError());
+    return DCOMP_OK;
+}
+
+// ---------------------------------------------------------------- a group of learners (include/dcomp_learner_group.h)
+struct dcomp_learner_group {
+    std::vector<dcomp_learner *> members;
+    int32_t device;
+    dlearn::GEntry *table;                // [members]: device
+};
+
+extern "C" int dcomp_learner_group_create(const dcomp_learner_group_cfg *cfg, dcomp_learner_group **out)
+{
+    using namespace dlearn;
+    const char *fn = "dcomp_learner_group_create";
+    if (out) *out = nullptr;
+    if (!cfg || !out) return fail(DCOMP_EINVAL, "%s: cfg and out must not be NULL", fn);
+    if (int rc = check_struct(fn, "dcomp_learner_group_cfg", cfg->struct_size, sizeof(dcomp_learner_group_cfg))) return rc;
+    if (!cfg->learners) return fail(DCOMP_EINVAL, "%s: learners must not be NULL", fn);
+    const int P = cfg->num_learners;
+    if (P < 1 || P > DCOMP_MAX_UE) return fail(DCOMP_EINVAL, "%s: num_learners %d outside [1, %d]", fn, P, DCOMP_MAX_UE);
+    for (int i = 0; i < P; i++) {
+        if (!cfg->learners[i]) return fail(DCOMP_EINVAL, "%s: learner %d is NULL", fn, i);
+        for (int j = 0; j < i; j++)
+            if (cfg->learners[j] == cfg->learners[i]) return fail(DCOMP_EINVAL, "%s: learner %d is learner %d again: a member is listed once", fn, i, j);
+    }
+    // the members, from here on
+    for (int i = 0; i < P; i++)
+        for (int j = 0; j < i; j++)
+            if (cfg->learners[j]->a == cfg->learners[i]->a) return fail(DCOMP_EINVAL, "%s: learners %d and %d train the same actor", fn, j, i);
+    const dcomp_learner *f = cfg->learners[0];
+    for (int i = 1; i < P; i++) {
+        const dcomp_learner *m = cfg->learners[i];
+        const struct { const char *what; int a, b; } same[] = {
+            {"obs_kind", f->a->net.multi, m->a->net.multi}, {"num_ue", f->a->net.U, m->a->net.U}, {"num_bs", f->a->net.B, m->a->net.B},
+            {"hidden", f->a->plan.hidden, m->a->plan.hidden}, {"activation", f->a->relu, m->a->relu}, {"device", f->device, m->device}};
+        for (const auto &c : same)
+            if (c.a != c.b) return fail(DCOMP_EINVAL, "%s: learner %d differs from learner 0 in %s (%d, %d)", fn, i, c.what, c.b, c.a);
+    }
+    if (!f->a->net.multi) return fail(DCOMP_EUNSUPPORTED, "%s: DCOMP_CENTRAL learners: a central policy is one network by construction", fn);
+    if (int rc = check_device(fn, "the learners live", f->device)) return rc;
+
+    std::vector<GEntry> host((size_t)P);
+    for (int i = 0; i < P; i++) {
+        const dcomp_learner *m = cfg->learners[i];
+        GEntry &e = host[(size_t)i];
+        memset(&e, 0, sizeof(e));
+        e.lp = m->lp;
+        for (int k = 0; k < 6; k++) e.wg[k] = m->wp.g[k];
+        for (int k = 0; k < NARR; k++) e.a[k] = m->ap.a[k];
+        e.w = m->w; e.g = m->g; e.m = m->m; e.v = m->v;
+        e.total = m->plan.total; e.ntask = m->plan.ntask;
+        e.beta1 = m->beta1; e.beta2 = m->beta2; e.eps = m->eps;
+        e.omb1 = (float)(1.0 - (double)m->beta1); e.omb2 = (float)(1.0 - (double)m->beta2);      // (as launch_adam)
+    }
+    dcomp_learner_group *g = new dcomp_learner_group();
+    g->members.assign(cfg->learners, cfg->learners + P);
+    g->device = f->device; g->table = nullptr;
+    hipError_t e = hipMalloc(reinterpret_cast<void **>(&g->table), host.size() * sizeof(GEntry));
+    if (e == hipSuccess) {
+        e = hipMemcpy(g->table, host.data(), host.size() * sizeof(GEntry), hipMemcpyHostToDevice);
+        if (e != hipSuccess) (void)hipFree(g->table);
+    }
+    if (e != hipSuccess) {
+        delete g;
+        return fail(DCOMP_EHIP, "%s: %s", fn, hipGetErrorString(e));
+    }
+    *out = g;
+    return DCOMP_OK;
+}
+
+extern "C" int dcomp_learner_group_destroy(dcomp_learner_group *g)
+{
+    if (!g) return DCOMP_OK;
+    const hipError_t e = hipFree(g->table);
+    delete g;
+    return e == hipSuccess ? DCOMP_OK : fail(DCOMP_EHIP, "dcomp_learner_group_destroy: hipFree failed: %s", hipGetErrorString(e));
+}
+
+extern "C" int dcomp_learner_group_grads(dcomp_learner_group *g, const dcomp_group_batch *b, const dcomp_ppo_hyper *hyper, float *stats_dev, void *stream)
+{
+    using namespace dlearn;
+    const char *fn = "dcomp_learner_group_grads";
+    if (!g || !b || !hyper || !stats_dev) return fail(DCOMP_EINVAL, "%s: group, batch, hyper and stats_dev must not be NULL", fn);
+    if (int rc = check_struct(fn, "dcomp_group_batch", b->struct_size, sizeof(dcomp_group_batch))) return rc;
+    if (!b->rows || !b->index) return fail(DCOMP_EINVAL, "%s: batch.rows and batch.index must not be NULL", fn);
+    const int P = (int)g->members.size();
+    int active = 0;
+    for (int i = 0; i < P; i++) {
+        const dcomp_learner *m = g->members[(size_t)i];
+        const int64_t r = b->rows[i];
+        if (r < 0 || r > m->max_rows) return fail(DCOMP_EINVAL, "%s: rows[%d] %lld outside [0, max_rows %lld of the learner]", fn, i, (long long)r, (long long)m->max_rows);
+        if (r > b->index_stride) return fail(DCOMP_EINVAL, "%s: rows[%d] %lld > index_stride %lld", fn, i, (long long)r, (long long)b->index_stride);
+        if (r == 0) continue;
+        active++;
+        // one policy's call as dcomp_sgd_grads would see it: its checks are learner_launch's
+        const BatchView v = {true, b->obs_format, m->a->net.U, r, b->source_rows, b->index + (int64_t)i * b->index_stride, b->obs, b->actions, b->old_logp,
+                             b->old_logits, b->advantages, b->value_targets, b->old_vf, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+        if (int rc = learner_check(fn, false, m, &v, hyper + i, stats_dev)) return rc;
+    }
+    if (!active) return fail(DCOMP_EINVAL, "%s: every rows[p] is 0: at least one policy must take part", fn);
+    if (int rc = check_device(fn, "the group lives", g->device)) return rc;
+
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const dcomp_learner *f = g->members[0];
+    const dcomp_actor *a = f->a;
+    const size_t lds = (size_t)a->plan.lds_per_wave * WAVES;
+    const group_fn kernel = pick_group(a->plan.mt, a->relu != 0);
+    for (int first = 0; first < P; first += GROUP_SLICE) {
+        const int n = P - first < GROUP_SLICE ? P - first : GROUP_SLICE;
+        GLParams lp;
+        GWParams wp;
+        GRParams rp;
+        memset(&lp, 0, sizeof(lp)); memset(&wp, 0, sizeof(wp)); memset(&rp, 0, sizeof(rp));
+        int64_t max_rows = 0;
+        int nactive = 0;
+        for (int i = 0; i < n; i++) {
+            const int64_t r = b->rows[first + i];
+            const dcomp_ppo_hyper &hy = hyper[first + i];
+            lp.rows[i] = wp.rows[i] = rp.rows[i] = (int32_t)r;                       // (<= max_rows <= 2^28)
+            lp.clip[i] = hy.clip_param; lp.vf_clip[i] = hy.vf_clip_param;
+            lp.vf_coeff[i] = rp.vf_coeff[i] = hy.vf_loss_coeff; lp.ent_coeff[i] = rp.ent_coeff[i] = hy.entropy_coeff; lp.kl_coeff[i] = rp.kl_coeff[i] = hy.kl_coeff;
+            rp.scale[i] = r > 0 ? (float)(1.0 / (double)r) : 0.f;                   // learner_launch's 1 / N: indexed, every position counts
+            if (r > 0) nactive++;
+            if (r > max_rows) max_rows = r;
+        }
+        if (!nactive) continue;
+        // the tile axis is sized by the slice's largest policy (tiles grow with rows); the chunk axis by the largest CHUNK COUNT, which
+        // is not the largest policy's: past CHUNK_UNIT x MAX_CHUNKS rows the chunks get longer and fewer (group_chunks)
+        const int64_t max_tiles = tiles_of(max_rows);
+        const int max_chunks = group_chunks(b->rows + first, n);
+        lp.obs = static_cast<const float *>(b->obs); lp.actions = b->actions; lp.old_logp = b->old_logp; lp.old_logits = b->old_logits;
+        lp.adv = b->advantages; lp.vtarg = b->value_targets; lp.old_vf = b->old_vf;
+        lp.table = wp.table = rp.table = g->table + first;
+        lp.index = b->index + (int64_t)first * b->index_stride; lp.index_stride = b->index_stride; lp.source_rows = b->source_rows;
+        lp.compact = b->obs_format == DCOMP_ACTOR_COMPACT; lp.num_active = a->net.U;
+        rp.stats = stats_dev + (size_t)first * DCOMP_PPO_NUM_STATS;
+        hipLaunchKernelGGL(kernel, dim3(group_blocks(max_tiles, a->max_blocks, nactive), n), dim3(BLOCK), lds, s, lp);
+        HIP_TRY(hipGetLastError());
+        hipLaunchKernelGGL(wgrad_group_kernel, dim3((f->plan.ntask + WAVES - 1) / WAVES, max_chunks, n), dim3(BLOCK), 0, s, wp);
+        HIP_TRY(hipGetLastError());
+        hipLaunchKernelGGL(reduce_group_kernel, dim3((f->plan.total + 255) / 256, n), dim3(256), 0, s, rp);
+        HIP_TRY(hipGetLastError());
+    }
+    return DCOMP_OK;
+}
+
+extern "C" int dcomp_learner_group_apply(dcomp_learner_group *g, const float *lr, const int32_t *active, void *stream)
+{
+    using namespace dlearn;
+    const char *fn = "dcomp_learner_group_apply";
+    if (!g || !lr) return fail(DCOMP_EINVAL, "%s: group and lr must not be NULL", fn);
+    const int P = (int)g->members.size();
+    int nactive = 0;
+    for (int i = 0; i < P; i++) {
+        if (active && !active[i]) continue;
+        nactive++;
+        if (!(lr[i] >= 0.f) || !std::isfinite(lr[i])) return fail(DCOMP_EINVAL, "%s: lr[%d] %g is not a finite number >= 0", fn, i, lr[i]);
+    }
+    if (!nactive) return fail(DCOMP_EINVAL, "%s: no member is active", fn);
+    if (int rc = check_device(fn, "the group lives", g->device)) return rc;
+
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const int total = g->members[0]->plan.total;
+    for (int first = 0; first < P; first += GROUP_SLICE) {
+        const int n = P - first < GROUP_SLICE ? P - first : GROUP_SLICE;
+        GAParams ap;
+        memset(&ap, 0, sizeof(ap));
+        ap.table = g->table + first;
+        bool any = false;
+        for (int i = 0; i < n; i++) {
+            const dcomp_learner *m = g->members[(size_t)(first + i)];
+            if (active && !active[first + i]) continue;
+            const double t = (double)(m->step + 1);                                  // launch_adam's scalars, per member
+            ap.active[i] = 1; any = true;
+            ap.step_size[i] = (float)((double)lr[first + i] / (1.0 - std::pow((double)m->beta1, t)));
+            ap.bc2_sqrt[i] = (float)std::sqrt(1.0 - std::pow((double)m->beta2, t));
+        }
+        if (!any) continue;
+        hipLaunchKernelGGL(adam_group_kernel, dim3((total + 255) / 256, n), dim3(256), 0, s, ap);
+        HIP_TRY(hipGetLastError());
+        for (int i = 0; i < n; i++)
+            if (ap.active[i]) g->members[(size_t)(first + i)]->step++;
+    }
     return DCOMP_OK;
 }

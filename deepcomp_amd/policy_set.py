@@ -24,7 +24,7 @@ import torch
 
 from . import _lib
 from .actor import FcnetActor, _ActorLaunch
-from .learner import PPOLearner
+from .learner import PPOLearner, STATS, adapt_kl_coeff
 
 
 def default_slot_policy(num_ue, num_policies):
@@ -127,8 +127,10 @@ class PerUELearner:
     which the set's next launch reads.
 
     ppo_kwargs are PPOLearner's.  minibatch_rows and max_rows are PER POLICY, and the workspaces are P times one learner's: max_rows
-    should be a policy's minibatch, not the batch.  The P updates run one after the other (a grouped launch over all policies is a
-    follow-up), so small per-policy batches are bound by launches."""
+    should be a policy's minibatch, not the batch.  ``update`` runs the P updates one after the other, P x minibatches x (gathers +
+    four launches), so small per-policy batches are bound by launches; ``update(grouped=True)`` trains all policies in one launch
+    round per minibatch round (include/dcomp_learner_group.h) and leaves every learner in the same state, bit for bit.  The two can
+    be mixed with each other and with calls on a member learner."""
 
     def __init__(self, actor, **ppo_kwargs):
         if not isinstance(actor, PerUEActor):
@@ -139,6 +141,16 @@ class PerUELearner:
                              "map its slots to it with slot_policy")
         self.learners = [PPOLearner(m, **ppo_kwargs) for m in actor.members]
         self._split = {}
+        self._group = None                                       # dcomp_learner_group over the learners: built by the first grouped update
+
+    def __del__(self):
+        g = getattr(self, '_group', None)
+        if g is not None and g.value:                            # (before the learners its table points into)
+            self._group = None
+            try:
+                self.actor._L.dcomp_learner_group_destroy(g)
+            except Exception:                                    # interpreter shutdown: the actor or the library is gone already
+                pass
 
     def rows_of(self, num_rows):
         """policy_rows() for this set on the device, kept per batch size."""
@@ -147,14 +159,111 @@ class PerUELearner:
             self._split = {num_rows: policy_rows(num_rows, a.U, a.slot_policy, a.num_policies, self.device)}
         return self._split[num_rows]
 
-    def update(self, batch, num_sgd_iter=30, minibatch_rows=None, seed=0):
+    def update(self, batch, num_sgd_iter=30, minibatch_rows=None, seed=0, grouped=False):
         """PPO's SGD phase on one collect(env, per_ue_actor, ..., dist_inputs=True) batch, rows or compact record: policy p's
         PPOLearner.update on the source rows whose UE slot maps to p (rows=), with seed + p.  Returns one statistics dict per policy
-        (None for a policy no slot maps to)."""
+        (None for a policy no slot maps to, whose state stays untouched).
+
+        grouped=True: the same update with all policies in one launch round per minibatch round.  Every policy keeps its own
+        advantage standardisation, its own permutations (a generator seeded seed + p), its own minibatch boundaries, Adam state and
+        kl_coeff; round k hands every policy its k-th minibatch through one [P, rows] index into the batch where it lies (both batch
+        formats), and a policy with fewer minibatches sits the later rounds out.  One synchronisation at the end.  The learners'
+        states and the returned statistics are those of grouped=False, bit for bit."""
         rows = self.rows_of(int(batch['actions'].numel()))
+        if grouped:
+            return self._update_grouped(batch, rows, int(num_sgd_iter), minibatch_rows, int(seed))
         return [ln.update(batch, num_sgd_iter=num_sgd_iter, minibatch_rows=minibatch_rows, seed=int(seed) + p, rows=rows[p], check_rows=False)
                 if rows[p].numel() else None                     # (check_rows: policy_rows() built them, distinct and in range)
                 for p, ln in enumerate(self.learners)]
+
+    def _group_handle(self):
+        if self._group is None:
+            P = len(self.learners)
+            handles = (ctypes.c_void_p * P)(*[ln._h.value for ln in self.learners])
+            cfg = _lib.DcompLearnerGroupCfg(ctypes.sizeof(_lib.DcompLearnerGroupCfg), P, handles)
+            h = ctypes.c_void_p()
+            with torch.cuda.device(self.device):
+                _lib.check(self.actor._L.dcomp_learner_group_create(ctypes.byref(cfg), ctypes.byref(h)))
+            self._group = h
+        return self._group
+
+    def _update_grouped(self, batch, rows, num_sgd_iter, minibatch_rows, seed):
+        a, L, dev = self.actor, self.actor._L, self.device
+        first, P = a.members[0], len(self.learners)
+        if 'action_dist_inputs' not in batch:
+            raise ValueError("the batch has no action_dist_inputs: collect(..., dist_inputs=True)")
+        compact = 'obs' not in batch
+        f32 = torch.float32
+        src = {'actions': (batch['actions'].reshape(-1), torch.uint8, 1), 'old_logp': (batch['action_logp'].reshape(-1), f32, 1),
+               'old_logits': (batch['action_dist_inputs'].reshape(-1, a.num_logits), f32, a.num_logits),
+               'value_targets': (batch['value_targets'].reshape(-1), f32, 1), 'old_vf': (batch['vf_preds'].reshape(-1), f32, 1)}
+        N = src['actions'][0].shape[0]
+        adv_in = batch['advantages'].reshape(-1)
+        if compact:
+            obs = batch['obs_compact'].reshape(-1, batch['obs_compact'].shape[-1])       # [T, E, words], contiguous: env t E + e
+            if first._batch(obs, True)[1] != N:
+                raise ValueError("the batch's tensors disagree about the number of rows")
+        else:
+            obs = batch['obs'].reshape(-1, a.num_in)
+            first._check(obs, f32, N * a.num_in, 'obs')
+        for name, (t, dtype, per) in src.items():
+            first._check(t, dtype, N * per, name)
+        first._check(adv_in, f32, N, 'advantages')
+        if N > 2 ** 31 - 1:
+            raise ValueError(f"{N} source rows > 2^31 - 1")
+
+        live = [p for p in range(P) if rows[p].numel()]
+        n_of = [int(rows[p].numel()) for p in range(P)]
+        mb_of = [0 if not n_of[p] else n_of[p] if minibatch_rows is None else min(int(minibatch_rows), n_of[p]) for p in range(P)]
+        for p in live:
+            if mb_of[p] > self.learners[p].max_rows:
+                raise ValueError(f"minibatches of {mb_of[p]} rows > max_rows {self.learners[p].max_rows} of the learner")
+        # every policy's advantages standardised over its own rows (PPOLearner.update's operations on the gathered tensor), back in
+        # source order in ONE tensor: the row sets are disjoint
+        adv = torch.zeros_like(adv_in)
+        for p in live:
+            ap = adv_in.index_select(0, rows[p])
+            adv.index_copy_(0, rows[p], (ap - ap.mean()) / ap.std(unbiased=False).clamp_min(1e-4))
+        # round k: positions [k step, k step + mb_p) of every policy that has that many.  A policy's minibatch is `step` rows unless
+        # it has fewer rows than that -- then it is its one minibatch, in round 0
+        step = max(mb_of)
+        rounds = max((n_of[p] + mb_of[p] - 1) // mb_of[p] for p in live)
+        stride = max(n_of)
+        index = torch.zeros((P, stride), dtype=torch.int32, device=dev)
+        stats = torch.zeros((rounds, P, _lib.PPO_NUM_STATS), dtype=f32, device=dev)
+        gens = {}
+        for p in live:
+            gens[p] = torch.Generator(device=dev)
+            gens[p].manual_seed(seed + p)
+        hyper = (_lib.DcompPpoHyper * P)(*[ln._hyper_struct() for ln in self.learners])
+        lr = (ctypes.c_float * P)(*[ln.lr for ln in self.learners])
+        round_rows = [(ctypes.c_int64 * P)(*[max(0, min(mb_of[p], n_of[p] - k * step)) if mb_of[p] else 0 for p in range(P)]) for k in range(rounds)]
+        round_active = [(ctypes.c_int32 * P)(*[1 if r else 0 for r in rr]) for rr in round_rows]
+        g = self._group_handle()
+        b = _lib.DcompGroupBatch(ctypes.sizeof(_lib.DcompGroupBatch), _lib.ACTOR_COMPACT if compact else _lib.ACTOR_ROWS, N, obs.data_ptr(),
+                                 src['actions'][0].data_ptr(), src['old_logp'][0].data_ptr(), src['old_logits'][0].data_ptr(), adv.data_ptr(),
+                                 src['value_targets'][0].data_ptr(), src['old_vf'][0].data_ptr(), 0, stride, None)
+        with torch.cuda.device(dev):
+            stream = first._stream()
+            for _ in range(num_sgd_iter):
+                for p in live:
+                    perm = torch.randperm(n_of[p], generator=gens[p], device=dev)
+                    index[p, :n_of[p]] = rows[p].index_select(0, perm)
+                for k in range(rounds):
+                    b.index, b.rows = index.data_ptr() + 4 * k * step, round_rows[k]
+                    _lib.check(L.dcomp_learner_group_grads(g, ctypes.byref(b), hyper, ctypes.c_void_p(stats[k].data_ptr()), stream))
+                    _lib.check(L.dcomp_learner_group_apply(g, lr, round_active[k], stream))
+        # a policy's mean over the rounds it took part in: PPOLearner.update's own reduction of its own [minibatches, 5] tensor
+        taken = {p: (n_of[p] + mb_of[p] - 1) // mb_of[p] for p in live}
+        means = torch.stack([stats[:taken[p], p].contiguous().mean(0) for p in live]).cpu().numpy()      # the one synchronisation
+        out = [None] * P
+        for i, p in enumerate(live):
+            ln = self.learners[p]
+            st = {n: float(means[i][j]) for j, n in enumerate(STATS)}
+            ln.hyper['kl_coeff'] = adapt_kl_coeff(ln.hyper['kl_coeff'], st['kl'], ln.kl_target)
+            st['kl_coeff'] = ln.hyper['kl_coeff']
+            out[p] = st
+        return out
 
     def get_weights(self):
         """[(weights, value_weights)] per policy; refreshes the members' host copies (PPOLearner.get_weights)."""

@@ -7,7 +7,7 @@ this only shows where the time goes once the env runs at ~10^8-10^9 env-steps/s.
     python tools/closed_loop.py [--envs 65536] [--steps 200] [--dtype bf16] [--kind multi] [--actor hip [--compact]]
     python tools/closed_loop.py --collect 50 [--envs 65536] [--kind multi] [--compact] [--shared-value]
     python tools/closed_loop.py --train 3 [--train-steps 5] [--sgd-iters 2] [--minibatch ROWS] [--envs 65536] [--kind multi] [--compact]
-    python tools/closed_loop.py --per-ue [--actor hip | --collect 50 | --train 3] [--hidden 64] [--compact] [--envs 4096 --ues 128 --bs 32]
+    python tools/closed_loop.py --per-ue [--actor hip | --collect 50 | --train 3 [--grouped]] [--hidden 64] [--compact] [--envs 4096 --ues 128 --bs 32]
 
 --actor torch (default): the actor as torch ops (bf16 matmuls, Gumbel-max through torch.rand).  --actor hip: the same weights in
 deepcomp_amd.actor.FcnetActor -- one HIP kernel from observation tensor to action tensor -- and BOTH loops are timed in this
@@ -30,7 +30,8 @@ written anywhere in the loop; the unpack a rows-only learner would need first is
 --per-ue (multi-agent): one policy network per UE (D3-CoMP) -- deepcomp_amd.policy_set.PerUEActor over U random-init members and, with
 --train, PerUELearner -- timed next to the shared-policy actor / learner on the same env, interleaved: the loop env step + actor
 (--actor hip), sampler.collect (--collect T), or collect + update with the time of one SGD iteration (--train ITERS; --minibatch is
-per policy there).
+per policy there; --grouped adds PerUELearner.update(grouped=True), all policies in one launch round per minibatch round, as a third
+interleaved variant and prints medians and ranges).
 """
 import argparse
 import sys
@@ -60,6 +61,7 @@ ap.add_argument('--train-steps', type=int, default=5, help='--train: steps per c
 ap.add_argument('--sgd-iters', type=int, default=2, help='--train: SGD iterations per batch')
 ap.add_argument('--minibatch', type=int, default=0, help='--train: rows per minibatch (default: one step\'s rows)')
 ap.add_argument('--hidden', type=int, default=256, help='hidden width of the fcnet (two layers)')
+ap.add_argument('--grouped', action='store_true', help='--per-ue --train: also time PerUELearner.update(grouped=True), interleaved with the sequential update and the shared learner')
 ap.add_argument('--per-ue', action='store_true', help='one policy per UE (PerUEActor / PerUELearner) next to the shared policy; multi-agent')
 a = ap.parse_args()
 if a.per_ue and a.kind != 'multi':
@@ -325,6 +327,7 @@ def per_ue_mode():
             print(f'{what}, {k:<28}: ' + ' / '.join(f'{t:.3f}' for t in ts) + ' ms')
         best = [min(ts) for ts in res.values()]
         print(f'{what}: set / shared = {best[1] / best[0]:.2f} x')
+        return res
 
     env.reset()
     if a.train:
@@ -340,8 +343,16 @@ def per_ue_mode():
                 st = learners[k].update(bufs[k], num_sgd_iter=a.sgd_iters, minibatch_rows=mb * (U if x is hip else 1), seed=it)
                 st = st if isinstance(st, dict) else {n: sum(s[n] for s in st) / len(st) for n in st[0]}
                 print(f'iter {it}, {k}: mean reward {float(bufs[k]["rewards"].mean()):+.4f}  total_loss {st["total_loss"]:+.5f}  kl {st["kl"]:+.5f} (mean over policies)')
-        report('one SGD iteration of update', {k: (lambda k=k, x=x: learners[k].update(bufs[k], num_sgd_iter=1, minibatch_rows=mb * (U if x is hip else 1), seed=0))
-                                               for k, x in actors.items()}, max(2, min(10, a.steps)))
+        fns = {k: (lambda k=k, x=x: learners[k].update(bufs[k], num_sgd_iter=1, minibatch_rows=mb * (U if x is hip else 1), seed=0))
+               for k, x in actors.items()}
+        if a.grouped:
+            ks = list(actors)[1]
+            fns['per-UE set, grouped launches'] = lambda: learners[ks].update(bufs[ks], num_sgd_iter=1, minibatch_rows=mb, seed=0, grouped=True)
+        res = report('one SGD iteration of update', fns, max(2, min(10, a.steps)))
+        if a.grouped:
+            seq, grp = sorted(res[list(actors)[1]]), sorted(res['per-UE set, grouped launches'])
+            print(f'grouped / sequential (medians) = {grp[1] / seq[1]:.3f} x; sequential {seq[0]:.3f} ... {seq[2]:.3f} ms, grouped {grp[0]:.3f} ... {grp[2]:.3f} ms, '
+                  f'shared learner (the floor) median {sorted(res[list(actors)[0]])[1]:.3f} ms')
     elif a.collect:
         T = a.collect
         bufs = {k: None for k in actors}
