@@ -19,4 +19,8 @@ def __getattr__(name):
         import importlib
         mod = importlib.import_module('.policy_set', __name__)
         return mod if name == 'policy_set' else getattr(mod, name)
+    if name in ('DataParallelLearner', 'dp_learner'):             # one rank's learner on one rank's shard of the sample batch
+        import importlib
+        mod = importlib.import_module('.dp_learner', __name__)
+        return mod if name == 'dp_learner' else getattr(mod, name)
     raise AttributeError(name)

@@ -165,6 +165,11 @@ class DcompGroupBatch(ctypes.Structure):
                [('index_stride', ctypes.c_int64), ('rows', ctypes.POINTER(ctypes.c_int64))]
 
 
+# include/dcomp_learner_accum.h: the gradients as a running sum the caller owns (micro-batches, data-parallel ranks), then finish
+ACCUM_EXPORTS = ['dcomp_learner_flat_size', 'dcomp_learner_accumulate', 'dcomp_sgd_accumulate', 'dcomp_learner_accum_finish']
+ACCUM_SUMS = 8
+
+
 class DcompPpoHyper(ctypes.Structure):
     _fields_ = [('struct_size', ctypes.c_int32), ('clip_param', ctypes.c_float), ('vf_clip_param', ctypes.c_float),
                 ('vf_loss_coeff', ctypes.c_float), ('entropy_coeff', ctypes.c_float), ('kl_coeff', ctypes.c_float)]
@@ -279,6 +284,13 @@ def load():
         L.dcomp_learner_group_grads.argtypes = [vp, ctypes.POINTER(DcompGroupBatch), ctypes.POINTER(DcompPpoHyper), vp, vp]
         L.dcomp_learner_group_apply.argtypes = [vp, _fp, _ip, vp]
         for name in GROUP_EXPORTS:
+            getattr(L, name)
+    if hasattr(L, 'dcomp_learner_accumulate') or not os.environ.get('DCOMP_LIB'):
+        L.dcomp_learner_flat_size.argtypes = [vp, ctypes.POINTER(i64)]
+        L.dcomp_learner_accumulate.argtypes = [vp, ctypes.POINTER(DcompPpoBatch), ctypes.POINTER(DcompPpoHyper), vp, vp, vp]
+        L.dcomp_sgd_accumulate.argtypes = [vp, ctypes.POINTER(DcompSgdBatch), ctypes.POINTER(DcompPpoHyper), vp, vp, vp]
+        L.dcomp_learner_accum_finish.argtypes = [vp, vp, vp, ctypes.POINTER(DcompPpoHyper), ctypes.c_float, vp, vp, vp]
+        for name in ACCUM_EXPORTS:
             getattr(L, name)
     for name in EXPORTS:
         getattr(L, name)

@@ -39,7 +39,7 @@ def _sources():
                                             'dcomp_big.h', 'dcomp_big.hip', 'dcomp_actor.hip', 'dcomp_actor_impl.h', 'dcomp_fcnet_plan.h', 'dcomp_learner.hip', 'dcomp_learner_tiles.inc',
                                             'dcomp_learner_reduce.inc', 'dcomp_learner_adam.inc')] + \
         [os.path.join(os.path.dirname(HERE), 'include', f) for f in ('dcomp.h', 'dcomp_types.h', 'dcomp_learner.h', 'dcomp_learner_indexed.h', 'dcomp_policy_set.h',
-                                                                            'dcomp_learner_group.h')]
+                                                                            'dcomp_learner_group.h', 'dcomp_learner_accum.h')]
 
 
 def _dev_flags():
@@ -146,7 +146,7 @@ def build(force=False, jobs=None, extra_flags=()):
             if f.endswith(('dcomp_actor_impl.h', 'dcomp_fcnet_plan.h')) and not t[0].endswith(('dcomp_actor.o', 'dcomp_learner.o')):
                 continue
             if f.endswith(('dcomp_learner.hip', 'dcomp_learner_tiles.inc', 'dcomp_learner_reduce.inc', 'dcomp_learner_adam.inc', 'dcomp_learner.h',
-                           'dcomp_learner_indexed.h', 'dcomp_learner_group.h')) and not t[0].endswith('dcomp_learner.o'):
+                           'dcomp_learner_indexed.h', 'dcomp_learner_group.h', 'dcomp_learner_accum.h')) and not t[0].endswith('dcomp_learner.o'):
                 continue
             if f.endswith(('dcomp_big.h', 'dcomp_big.hip')) and not t[0].endswith(('dcomp_api.o', 'dcomp_big.o')):
                 continue

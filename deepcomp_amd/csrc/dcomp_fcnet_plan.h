@@ -156,7 +156,8 @@ inline int group_blocks(int64_t max_tiles, int max_blocks, int active)
 
 }  // namespace dlearn
 
-// Introspection for the tests (tests/fcnet_cases.py): the plans of a shape, from the functions above and nothing else.  NOT part of
+// Introspection for the tests (tests/fcnet_cases.py) and for the binding's own checks (deepcomp_amd.learner.chunk_unit: the unit a
+// micro-batch must be a multiple of): the plans of a shape, from the functions above and nothing else.  NOT part of
 // the ABI: in no public header, not installed, free to change without an ABI bump.  Makes no HIP call; a shape dcomp_actor_create
 // refuses is refused here with the same code.
 struct dcomp_fcnet_shape {

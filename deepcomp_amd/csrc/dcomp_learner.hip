@@ -1,8 +1,10 @@
 // dcomp_learner.hip -- the PPO learner of the fcnet a dcomp_actor runs (include/dcomp_learner.h): loss, backward pass and Adam; and
 // its minibatches picked through a row index out of a whole sample batch, rows or compact record (include/dcomp_learner_indexed.h);
 // and the learners of a per-UE policy set trained in one launch round (include/dcomp_learner_group.h): the same four kernels with the
-// policy as a grid dimension, behind the per-learner ones below.  The bodies both forms share are text (dcomp_learner_tiles.inc,
-// dcomp_learner_reduce.inc, dcomp_learner_adam.inc), included in each kernel.
+// policy as a grid dimension, behind the per-learner ones below; and the gradients as a running sum the caller owns, for micro-batches
+// and data-parallel ranks (include/dcomp_learner_accum.h): accumulate_kernel in reduce_kernel's place, then norm_kernel / finish_kernel.
+// The bodies the per-learner and grouped forms share are text (dcomp_learner_tiles.inc, dcomp_learner_reduce.inc,
+// dcomp_learner_adam.inc), included in each kernel.
 //
 // Four kernels per minibatch, all deterministic (no floating-point atomics; every sum has an order fixed by the row count):
 //   learner_kernel   forward + loss + backward-data.  The shape of actor_kernel: a wavefront owns 32 decision rows on its lanes and
@@ -39,6 +41,7 @@
 #include "../../include/dcomp_learner.h"
 #include "../../include/dcomp_learner_indexed.h"
 #include "../../include/dcomp_learner_group.h"
+#include "../../include/dcomp_learner_accum.h"
 #include "dcomp_actor_impl.h"       // the forward-pass helpers, the fragment layout, Net and struct dcomp_actor, fail / HIP_TRY: shared with dcomp_actor.hip
 
 namespace dlearn {
@@ -304,6 +307,108 @@ __global__ __launch_bounds__(256) void adam_kernel(const AParams p)
 #include "dcomp_learner_adam.inc"
 }
 
+// ---------------------------------------------------------------- accumulated gradients (include/dcomp_learner_accum.h)
+// reduce_kernel's loop with the running sum carried in: acc += the chunk partials in chunk order, unscaled; the four loss sums of the
+// per-tile workspace (reduce_kernel's 256 ranges, then the 256 sums in order) and the counted rows are added to sums.  One launch per
+// (micro-)batch on one stream: a thread owns its entry of acc, thread 0 of block 0 owns sums -- no atomics.
+__global__ __launch_bounds__(256) void accumulate_kernel(const AParams p, float *acc, double *sums)
+{
+    const int e = blockIdx.x * 256 + threadIdx.x;
+    if (e < p.total) {
+        const int ai = find_array(p, e);
+        const ADesc d = p.a[ai];
+        const int idx = e - d.off, k = idx / d.nout, o = idx - k * d.nout;
+        const size_t stride = d.is_bias ? (size_t)d.out_p : (size_t)d.in_p * d.out_p, at = (size_t)k * d.out_p + o;
+        float s = acc[e];
+        for (int c = 0; c < p.nchunks; c++) s += d.part[c * stride + at];             // chunk order
+        acc[e] = s;
+    }
+    if (blockIdx.x == 0) {
+        __shared__ double sh[256][4];
+        const int64_t per = (p.tiles + 255) / 256, lo = threadIdx.x * per, hi = lo + per < p.tiles ? lo + per : p.tiles;
+        double s0 = 0., s1 = 0., s2 = 0., s3 = 0.;
+        for (int64_t t = lo; t < hi; t++) {
+            const double *v = p.tile_part + 4 * t;
+            s0 += v[0]; s1 += v[1]; s2 += v[2]; s3 += v[3];
+        }
+        sh[threadIdx.x][0] = s0; sh[threadIdx.x][1] = s1; sh[threadIdx.x][2] = s2; sh[threadIdx.x][3] = s3;
+        __syncthreads();
+        if (threadIdx.x == 0) {
+            double t0 = 0., t1 = 0., t2 = 0., t3 = 0.;
+            for (int i = 0; i < 256; i++) { t0 += sh[i][0]; t1 += sh[i][1]; t2 += sh[i][2]; t3 += sh[i][3]; }
+            sums[0] += t0; sums[1] += t1; sums[2] += t2; sums[3] += t3; sums[4] += p.count;
+        }
+    }
+}
+
+struct FParams {
+    const float *acc;                                        // [total]
+    const double *sums;                                      // [DCOMP_ACCUM_SUMS]
+    float *g, *stats, *grad_norm;                            // the handle's gradients; stats and grad_norm may be NULL
+    double *norm_part;                                       // [nparts]: the handle's workspace
+    int32_t total, nparts, want_norm;
+    float clip, vf_coeff, ent_coeff, kl_coeff;
+};
+constexpr int NORM_SPAN = 4096;                              // entries of a norm_kernel block: 16 per thread
+
+// 1 / N from the accumulated count, as learner_launch forms reduce_kernel's scale on the host
+__device__ __forceinline__ float accum_scale(const double *sums) { return sums[4] > 0. ? (float)(1.0 / sums[4]) : 0.f; }
+
+// the squares of the scaled gradients, in double: a thread its 16 entries in order, a fixed tree over the block, one partial per block
+__global__ __launch_bounds__(256) void norm_kernel(const FParams p)
+{
+    __shared__ double sh[256];
+    const float scale = accum_scale(p.sums);
+    double s = 0.;
+    for (int i = 0; i < NORM_SPAN / 256; i++) {
+        const int e = blockIdx.x * NORM_SPAN + i * 256 + threadIdx.x;
+        if (e < p.total) {
+            const float g = p.acc[e] * scale;
+            s += (double)g * (double)g;
+        }
+    }
+    sh[threadIdx.x] = s;
+    __syncthreads();
+    for (int o = 128; o > 0; o >>= 1) {
+        if ((int)threadIdx.x < o) sh[threadIdx.x] += sh[threadIdx.x + o];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) p.norm_part[blockIdx.x] = sh[0];
+}
+
+// g = acc / N (x the clip coefficient), and the statistics from sums as reduce_kernel forms them from its totals.  Every block adds
+// the norm partials itself, in block order: the same number in every block.
+__global__ __launch_bounds__(256) void finish_kernel(const FParams p)
+{
+    __shared__ float coef_sh;
+    const float scale = accum_scale(p.sums);
+    float coef = 1.f;
+    if (p.want_norm) {
+        if (threadIdx.x == 0) {
+            double s = 0.;
+            for (int i = 0; i < p.nparts; i++) s += p.norm_part[i];
+            const double norm = sqrt(s), c = (double)p.clip / (norm + 1e-6);
+            coef_sh = p.clip > 0.f ? (float)(c < 1.0 ? c : 1.0) : 1.f;
+            if (blockIdx.x == 0 && p.grad_norm) *p.grad_norm = (float)norm;
+        }
+        __syncthreads();
+        coef = coef_sh;
+    }
+    const int e = blockIdx.x * 256 + threadIdx.x;
+    if (e < p.total) {
+        float g = p.acc[e] * scale;
+        if (p.clip > 0.f) g = g * coef;
+        p.g[e] = g;
+    }
+    if (p.stats && blockIdx.x == 0 && threadIdx.x == 0) {
+        const double t0 = p.sums[0], t1 = p.sums[1], t2 = p.sums[2], t3 = p.sums[3], count = p.sums[4];
+        const double inv = count > 0. ? 1.0 / count : 0.0;
+        const float pol = (float)(-t0 * inv), kl = (float)(t1 * inv), ent = (float)(t2 * inv), vfl = (float)(t3 * inv);
+        p.stats[0] = pol + p.kl_coeff * kl + p.vf_coeff * vfl - p.ent_coeff * ent;
+        p.stats[1] = pol; p.stats[2] = vfl; p.stats[3] = kl; p.stats[4] = ent;
+    }
+}
+
 // ---------------------------------------------------------------- all learners of a group in one launch (include/dcomp_learner_group.h)
 // The four kernels above with the policy as a grid dimension.  What dcomp_learner keeps in lp / wp / ap is one entry per policy of a
 // device table written at dcomp_learner_group_create; what changes per call (rows, hyper-parameters, Adam's scalars) are arrays in
@@ -494,6 +599,8 @@ struct dcomp_learner {
     float beta1, beta2, eps;
     void *mem;
     float *w, *g, *m, *v;
+    double *norm_part;                    // [norm_parts]: norm_kernel's partials (dcomp_learner_accum_finish)
+    int32_t norm_parts;
     dlearn::LearnerPlan plan;             // every shape number of the handle behind the actor's own (a->plan)
     dlearn::LParams lp;                   // the handle's part of the kernel arguments
     dlearn::WParams wp;
@@ -582,6 +689,8 @@ extern "C" int dcomp_learner_create(dcomp_actor *a, const dcomp_learner_cfg *cfg
     const size_t o_head = take((size_t)cfg->max_rows * apl.heads * 16), o_tpart = take((ld / 32) * 32);      // (ld / 32 >= the tiles of max_rows)
     size_t o_part[6], o_bpart[6];
     for (int i = 0; i < 6; i++) { o_part[i] = take((size_t)MAX_CHUNKS * pl.in_p[i] * pl.out_p[i] * 4); o_bpart[i] = take((size_t)MAX_CHUNKS * pl.out_p[i] * 4); }
+    l->norm_parts = (total + NORM_SPAN - 1) / NORM_SPAN;
+    const size_t o_norm = take((size_t)l->norm_parts * 8);
     const size_t bytes = at;
 
     hipError_t e = hipMalloc(&l->mem, bytes);
@@ -591,6 +700,7 @@ extern "C" int dcomp_learner_create(dcomp_actor *a, const dcomp_learner_cfg *cfg
     float *src[NARR];
     members(cfg->weights, src);
     l->w = reinterpret_cast<float *>(d + o_flat); l->g = l->w + total; l->m = l->g + total; l->v = l->m + total;
+    l->norm_part = reinterpret_cast<double *>(d + o_norm);
     for (int i = 0; i < NARR && e == hipSuccess; i++) e = hipMemcpy(l->w + pl.off[i], src[i], (size_t)pl.len[i] * 4, hipMemcpyHostToDevice);
     if (e != hipSuccess) {
         if (l->mem) (void)hipFree(l->mem);
@@ -715,8 +825,10 @@ static int learner_check(const char *fn, bool evaluate, const dcomp_learner *l, 
     return DCOMP_OK;
 }
 
-// the grads and evaluate calls of both surfaces: every check on the host first
-static int learner_launch(const char *fn, bool evaluate, dcomp_learner *l, const BatchView *b, const dcomp_ppo_hyper *hy, float *stats, void *stream)
+// the grads and evaluate calls of both surfaces: every check on the host first.  acc / sums (dcomp_learner_accum.h, both or
+// neither; grads only): the chunk partials go into the caller's running sum instead of the handle's gradients
+static int learner_launch(const char *fn, bool evaluate, dcomp_learner *l, const BatchView *b, const dcomp_ppo_hyper *hy, float *stats, void *stream,
+                          float *acc = nullptr, double *sums = nullptr)
 {
     using namespace dlearn;
     if (int rc = learner_check(fn, evaluate, l, b, hy, stats)) return rc;
@@ -759,28 +871,31 @@ static int learner_launch(const char *fn, bool evaluate, dcomp_learner *l, const
     ap.count = upstream ? 0. : (double)counted;
     ap.scale = upstream ? 1.f : (counted > 0 ? (float)(1.0 / (double)counted) : 0.f);
     ap.vf_coeff = p.vf_coeff; ap.ent_coeff = p.ent_coeff; ap.kl_coeff = p.kl_coeff;
-    hipLaunchKernelGGL(reduce_kernel, dim3((l->plan.total + 255) / 256), dim3(256), 0, s, ap);
+    if (acc) hipLaunchKernelGGL(accumulate_kernel, dim3((l->plan.total + 255) / 256), dim3(256), 0, s, ap, acc, sums);
+    else hipLaunchKernelGGL(reduce_kernel, dim3((l->plan.total + 255) / 256), dim3(256), 0, s, ap);
     HIP_TRY(hipGetLastError());
     return DCOMP_OK;
 }
 
 // the NULL and struct-size checks of a surface's batch, then its view
-static int ppo_launch(const char *fn, bool evaluate, dcomp_learner *l, const dcomp_ppo_batch *b, const dcomp_ppo_hyper *hy, float *stats, void *stream)
+static int ppo_launch(const char *fn, bool evaluate, dcomp_learner *l, const dcomp_ppo_batch *b, const dcomp_ppo_hyper *hy, float *stats, void *stream,
+                      float *acc = nullptr, double *sums = nullptr)
 {
     if (!l || !b) return fail(DCOMP_EINVAL, "%s: handle and batch must not be NULL", fn);
     if (int rc = check_struct(fn, "dcomp_ppo_batch", b->struct_size, sizeof(dcomp_ppo_batch))) return rc;
     const BatchView v = {false, b->obs_format, b->num_active, b->rows, b->rows, nullptr, b->obs, b->actions, b->old_logp, b->old_logits, b->advantages,
                          b->value_targets, b->old_vf, b->logp, b->entropy, b->kl, b->vf, b->ratio, b->dlogits, b->dvalue};
-    return learner_launch(fn, evaluate, l, &v, hy, stats, stream);
+    return learner_launch(fn, evaluate, l, &v, hy, stats, stream, acc, sums);
 }
 
-static int sgd_launch(const char *fn, bool evaluate, dcomp_learner *l, const dcomp_sgd_batch *b, const dcomp_ppo_hyper *hy, float *stats, void *stream)
+static int sgd_launch(const char *fn, bool evaluate, dcomp_learner *l, const dcomp_sgd_batch *b, const dcomp_ppo_hyper *hy, float *stats, void *stream,
+                      float *acc = nullptr, double *sums = nullptr)
 {
     if (!l || !b) return fail(DCOMP_EINVAL, "%s: handle and batch must not be NULL", fn);
     if (int rc = check_struct(fn, "dcomp_sgd_batch", b->struct_size, sizeof(dcomp_sgd_batch))) return rc;
     const BatchView v = {true, b->obs_format, b->num_active, b->rows, b->source_rows, b->index, b->obs, b->actions, b->old_logp, b->old_logits, b->advantages,
                          b->value_targets, b->old_vf, b->logp, b->entropy, b->kl, b->vf, b->ratio, b->dlogits, b->dvalue};
-    return learner_launch(fn, evaluate, l, &v, hy, stats, stream);
+    return learner_launch(fn, evaluate, l, &v, hy, stats, stream, acc, sums);
 }
 
 extern "C" int dcomp_learner_grads(dcomp_learner *l, const dcomp_ppo_batch *b, const dcomp_ppo_hyper *hy, float *stats_dev, void *stream)
@@ -801,6 +916,63 @@ extern "C" int dcomp_sgd_grads(dcomp_learner *l, const dcomp_sgd_batch *b, const
 extern "C" int dcomp_sgd_evaluate(dcomp_learner *l, const dcomp_sgd_batch *b, void *stream)
 {
     return sgd_launch("dcomp_sgd_evaluate", true, l, b, nullptr, nullptr, stream);
+}
+
+// ---------------------------------------------------------------- include/dcomp_learner_accum.h
+extern "C" int dcomp_learner_flat_size(const dcomp_learner *l, int64_t *floats)
+{
+    if (!l || !floats) return fail(DCOMP_EINVAL, "dcomp_learner_flat_size: handle and floats must not be NULL");
+    *floats = l->plan.total;
+    return DCOMP_OK;
+}
+
+// what the accumulate calls check beyond learner_check (which sees sums_dev where the grads calls have stats_dev: non-NULL by then)
+template <class B> static int accumulate_check(const char *fn, const dcomp_learner *l, const B *b, const float *acc, const double *sums)
+{
+    if (!l || !b) return fail(DCOMP_EINVAL, "%s: handle and batch must not be NULL", fn);
+    if (!acc || !sums) return fail(DCOMP_EINVAL, "%s: acc_dev and sums_dev must not be NULL", fn);
+    if (b->struct_size == (int32_t)sizeof(B) && (b->dlogits || b->dvalue))
+        return fail(DCOMP_EINVAL, "%s: upstream gradients (batch.dlogits / dvalue) are plain sums already: they belong to the grads call", fn);
+    return DCOMP_OK;
+}
+
+extern "C" int dcomp_learner_accumulate(dcomp_learner *l, const dcomp_ppo_batch *b, const dcomp_ppo_hyper *hy, float *acc_dev, double *sums_dev, void *stream)
+{
+    const char *fn = "dcomp_learner_accumulate";
+    if (int rc = accumulate_check(fn, l, b, acc_dev, sums_dev)) return rc;
+    return ppo_launch(fn, false, l, b, hy, reinterpret_cast<float *>(sums_dev), stream, acc_dev, sums_dev);
+}
+
+extern "C" int dcomp_sgd_accumulate(dcomp_learner *l, const dcomp_sgd_batch *b, const dcomp_ppo_hyper *hy, float *acc_dev, double *sums_dev, void *stream)
+{
+    const char *fn = "dcomp_sgd_accumulate";
+    if (int rc = accumulate_check(fn, l, b, acc_dev, sums_dev)) return rc;
+    return sgd_launch(fn, false, l, b, hy, reinterpret_cast<float *>(sums_dev), stream, acc_dev, sums_dev);
+}
+
+extern "C" int dcomp_learner_accum_finish(dcomp_learner *l, const float *acc_dev, const double *sums_dev, const dcomp_ppo_hyper *hy, float grad_clip,
+                                          float *stats_dev, float *grad_norm_dev, void *stream)
+{
+    using namespace dlearn;
+    const char *fn = "dcomp_learner_accum_finish";
+    if (!l) return fail(DCOMP_EINVAL, "%s: handle must not be NULL", fn);
+    if (!acc_dev || !sums_dev) return fail(DCOMP_EINVAL, "%s: acc_dev and sums_dev must not be NULL", fn);
+    if (!hy) return fail(DCOMP_EINVAL, "%s: hyper must not be NULL", fn);
+    if (int rc = check_struct(fn, "dcomp_ppo_hyper", hy->struct_size, sizeof(dcomp_ppo_hyper))) return rc;
+    if (!(grad_clip >= 0.f)) return fail(DCOMP_EINVAL, "%s: grad_clip %g must be >= 0 (0: no clipping)", fn, grad_clip);
+    // the handle, from here on
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    FParams p;
+    p.acc = acc_dev; p.sums = sums_dev; p.g = l->g; p.stats = stats_dev; p.grad_norm = grad_norm_dev; p.norm_part = l->norm_part;
+    p.total = l->plan.total; p.nparts = l->norm_parts; p.want_norm = grad_clip > 0.f || grad_norm_dev;
+    p.clip = grad_clip; p.vf_coeff = hy->vf_loss_coeff; p.ent_coeff = hy->entropy_coeff; p.kl_coeff = hy->kl_coeff;
+    if (p.want_norm) {
+        hipLaunchKernelGGL(norm_kernel, dim3(p.nparts), dim3(256), 0, s, p);
+        HIP_TRY(hipGetLastError());
+    }
+    hipLaunchKernelGGL(finish_kernel, dim3((p.total + 255) / 256), dim3(256), 0, s, p);
+    HIP_TRY(hipGetLastError());
+    return DCOMP_OK;
 }
 
 extern "C" int dcomp_learner_apply(dcomp_learner *l, float lr, void *stream)

@@ -13,7 +13,9 @@ Supported: ``multi`` and ``central``, tanh and relu, every hidden width the acto
 (``collect(compact=True)``, multi), whose minibatches it picks through a row index (``grads_indexed``): from a compact batch no
 observation row is ever written.  The shared value function is refused (NotImplementedError), and so is the
 compact record by ``grads`` / ``evaluate``, which take a contiguous minibatch of rows; envs with UE arrival are refused by ``collect``
-already.
+already.  ``accumulate`` / ``accumulate_indexed`` / ``finish`` (include/dcomp_learner_accum.h) keep the unnormalised gradient as a running
+sum in a buffer of the caller's: ``update(micro_rows=, grad_clip=)`` trains minibatches larger than the handle micro-batch by micro-batch and
+clips by the global norm, and deepcomp_amd.dp_learner sums the buffer across the ranks of a data-parallel learner.
 
 The arithmetic is the specification, spelled out here in torch / numpy on the CPU: ``ppo_loss_reference`` (RLlib's
 ppo_surrogate_loss and its gradients, as the float64 model and as the bf16 chain the kernels implement) and ``adam_reference``
@@ -228,6 +230,49 @@ def adam_reference(w, g, m, v, t, lr, beta1=0.9, beta2=0.999, eps=1e-8):
     return w, m, v
 
 
+def clip_reference(g_flat, grad_clip):
+    """torch.nn.utils.clip_grad_norm_ on the flat float32 gradient, as finish() computes it: the global L2 norm in float64, the
+    coefficient min(1, grad_clip / (norm + 1e-6)) rounded to float32, one float32 product per entry.  grad_clip None or 0: the
+    gradient as it is.  Returns (clipped gradient float32, norm as float32)."""
+    g = np.asarray(g_flat, dtype=np.float32).reshape(-1)
+    norm = math.sqrt(float((g.astype(np.float64) ** 2).sum()))
+    if not grad_clip:
+        return g.copy(), np.float32(norm)
+    coef = np.float32(min(1.0, float(grad_clip) / (norm + 1e-6)))
+    return g * coef, np.float32(norm)
+
+
+class _FcnetDesc(ctypes.Structure):
+    """The head of dcomp_fcnet_desc (csrc/dcomp_fcnet_plan.h): the constants; the plans behind them are not read here."""
+    _fields_ = [(n, ctypes.c_int32) for n in ('struct_size', 'TILE', 'WAVES', 'BLOCK', 'KC', 'LT', 'CHUNK_UNIT', 'MAX_CHUNKS', 'max_blocks', 'grid_tiles')] + \
+        [('actor', ctypes.c_int32 * 14), ('learner', ctypes.c_int32 * 88), ('split', ctypes.c_int64 * 5)]
+
+
+class _FcnetShape(ctypes.Structure):
+    _fields_ = [(n, ctypes.c_int32) for n in ('struct_size', 'obs_kind', 'num_ue', 'num_bs', 'hidden')] + [('rows', ctypes.c_int64), ('compute_units', ctypes.c_int32)]
+
+
+def chunk_unit():
+    """Rows of a weight-gradient chunk (CHUNK_UNIT), from the library: what a micro-batch must be a multiple of."""
+    L = _lib.load()
+    s = _FcnetShape(ctypes.sizeof(_FcnetShape), _lib.MULTI, 1, 1, 32, 0, 0)
+    d = _FcnetDesc(ctypes.sizeof(_FcnetDesc))
+    L.dcomp_fcnet_describe.argtypes = [ctypes.POINTER(_FcnetShape), ctypes.POINTER(_FcnetDesc)]
+    _lib.check(L.dcomp_fcnet_describe(ctypes.byref(s), ctypes.byref(d)))
+    return int(d.CHUNK_UNIT)
+
+
+def check_micro_rows(micro_rows, max_rows):
+    """update(micro_rows=...): a multiple of the chunk unit (every micro-batch but the last then ends on a chunk boundary, and the
+    accumulated sum has the whole minibatch's order) and at most the handle's max_rows."""
+    unit = chunk_unit()
+    if isinstance(micro_rows, bool) or int(micro_rows) != micro_rows or int(micro_rows) < unit or int(micro_rows) % unit:
+        raise ValueError(f"micro_rows {micro_rows!r} must be a positive multiple of {unit} rows (a weight-gradient chunk)")
+    if int(micro_rows) > max_rows:
+        raise ValueError(f"micro_rows {int(micro_rows)} > max_rows {max_rows} of the learner")
+    return int(micro_rows)
+
+
 def adapt_kl_coeff(kl_coeff, kl, kl_target):
     """RLlib's update_kl: x 1.5 above twice the target, x 0.5 below half of it."""
     if kl > 2.0 * kl_target:
@@ -281,6 +326,7 @@ class PPOLearner:
             _lib.check(self._L.dcomp_learner_create(actor._h, ctypes.byref(cfg), ctypes.byref(h)))
         self._h = h
         self._mb = {}
+        self._flat = None
         self.step = 0
 
     def __del__(self):
@@ -433,8 +479,81 @@ class PPOLearner:
             _lib.check(self._L.dcomp_sgd_evaluate(self._h, ctypes.byref(b), a._stream()))
         return logp, entropy, vf
 
+    # ------------------------------------------------------------------ accumulated gradients (include/dcomp_learner_accum.h)
+    @property
+    def flat_size(self):
+        """Elements of the flat gradient array: the twelve arrays one behind the other, in ARRAYS' order."""
+        if self._flat is None:
+            n = ctypes.c_int64()
+            _lib.check(self._L.dcomp_learner_flat_size(self._h, ctypes.byref(n)))
+            self._flat = int(n.value)
+        return self._flat
+
+    def new_accumulators(self):
+        """(acc float32 [flat_size], sums float64 [8]) on the learner's device, zeroed: the running sums of one minibatch.  sums: the
+        sums of the surrogate, kl, entropy and value loss over the counted rows, the counted rows, three reserved."""
+        return (torch.zeros(self.flat_size, dtype=torch.float32, device=self.device),
+                torch.zeros(_lib.ACCUM_SUMS, dtype=torch.float64, device=self.device))
+
+    def _accumulators(self, acc, sums):
+        self.actor._check(acc, torch.float32, self.flat_size, 'acc')
+        self.actor._check(sums, torch.float64, _lib.ACCUM_SUMS, 'sums')
+        return ctypes.c_void_p(acc.data_ptr()), ctypes.c_void_p(sums.data_ptr())
+
+    def accumulate(self, obs, actions, old_logp, old_logits, advantages, value_targets, old_vf, acc, sums, *, num_active=None,
+                   logp=None, entropy=None, kl=None, vf=None, ratio=None):
+        """grads() up to the sums over the rows, which are ADDED to acc / sums (new_accumulators(); the caller zeroes them before a
+        minibatch's first call) instead of being scaled into the handle: acc += the unnormalised gradient of these rows, sums += their
+        loss sums and their count.  The handle's gradients are not written.  finish() turns the accumulated sums into the gradients
+        apply() consumes.  While every call but the last has a multiple of the chunk unit (chunk_unit(): 2 048 rows) and the calls
+        together have at most 262 144 rows, finish() gives the gradients of grads() on all rows at once, bit for bit.  Upstream
+        gradients are not taken here: they are plain sums already."""
+        a = self.actor
+        rows = self._rows(obs)
+        f32, h, n3 = torch.float32, a.heads, a.num_logits
+        b = self._batch(obs, rows, num_active, {
+            'actions': (actions, torch.uint8, h), 'old_logp': (old_logp, f32, h), 'old_logits': (old_logits, f32, n3), 'advantages': (advantages, f32, 1),
+            'value_targets': (value_targets, f32, 1), 'old_vf': (old_vf, f32, 1), 'logp': (logp, f32, h), 'entropy': (entropy, f32, 1), 'kl': (kl, f32, 1),
+            'vf': (vf, f32, 1), 'ratio': (ratio, f32, 1)})
+        pa, ps = self._accumulators(acc, sums)
+        with torch.cuda.device(self.device):
+            _lib.check(self._L.dcomp_learner_accumulate(self._h, ctypes.byref(b), ctypes.byref(self._hyper_struct()), pa, ps, a._stream()))
+
+    def accumulate_indexed(self, source, index, acc, sums, *, num_active=None, logp=None, entropy=None, kl=None, vf=None, ratio=None):
+        """accumulate() on the rows `index` picks out of a whole sample batch (grads_indexed's source and index)."""
+        a = self.actor
+        b = self._sgd_batch(self._sgd_source(source, index), source, index, num_active,
+                            ('actions', 'old_logp', 'old_logits', 'advantages', 'value_targets', 'old_vf'),
+                            {'logp': (logp, a.heads), 'entropy': (entropy, 1), 'kl': (kl, 1), 'vf': (vf, 1), 'ratio': (ratio, 1)})
+        pa, ps = self._accumulators(acc, sums)
+        with torch.cuda.device(self.device):
+            _lib.check(self._L.dcomp_sgd_accumulate(self._h, ctypes.byref(b), ctypes.byref(self._hyper_struct()), pa, ps, a._stream()))
+
+    def finish(self, acc, sums, grad_clip=None, stats=None, grad_norm=None):
+        """The handle's gradients from accumulated sums: g = acc * float32(1 / sums[4]); with grad_clip (> 0) g is scaled by
+        min(1, grad_clip / (norm + 1e-6)), norm the global L2 norm over all twelve arrays (torch.nn.utils.clip_grad_norm_,
+        clip_reference()).  grad_norm: a float32 [1] device tensor that receives the norm of the unclipped g (also without grad_clip).
+        acc and sums are read only.  Returns the five statistics (a float32 [5] device tensor, `stats` if given) formed from sums as
+        grads() forms them.  Nothing synchronises."""
+        a = self.actor
+        clip = 0.0 if grad_clip is None else float(grad_clip)
+        if not clip >= 0.0:
+            raise ValueError(f"grad_clip {grad_clip!r} must be >= 0 (None or 0: no clipping)")
+        pa, ps = self._accumulators(acc, sums)
+        if stats is None:
+            stats = torch.zeros(_lib.PPO_NUM_STATS, dtype=torch.float32, device=self.device)
+        a._check(stats, torch.float32, _lib.PPO_NUM_STATS, 'stats')
+        if grad_norm is not None:
+            a._check(grad_norm, torch.float32, 1, 'grad_norm')
+        with torch.cuda.device(self.device):
+            _lib.check(self._L.dcomp_learner_accum_finish(self._h, pa, ps, ctypes.byref(self._hyper_struct()), clip, ctypes.c_void_p(stats.data_ptr()),
+                                                          ctypes.c_void_p(grad_norm.data_ptr()) if grad_norm is not None else None, a._stream()))
+        return stats
+
+    clip_reference = staticmethod(clip_reference)
+
     def apply(self, lr=None):
-        """One Adam step on the gradients of the last grads(); the actor's next launch runs the new weights."""
+        """One Adam step on the gradients of the last grads() or finish(); the actor's next launch runs the new weights."""
         with torch.cuda.device(self.device):
             _lib.check(self._L.dcomp_learner_apply(self._h, float(self.lr if lr is None else lr), self.actor._stream()))
 
@@ -476,27 +595,14 @@ class PPOLearner:
         self.actor.weights, self.actor.value_weights = split_weights(host['weights'])
 
     # ------------------------------------------------------------------ the training step
-    def update(self, batch, num_sgd_iter=30, minibatch_rows=None, seed=0, num_active=None, rows=None, check_rows=True):
-        """PPO's SGD phase on one collect(..., dist_inputs=True) batch, observation rows or the compact record (compact=True): the
-        batch is flattened to source rows, the advantages are standardised over the batch (RLlib: (a - mean) / max(1e-4, std)), and
-        per iteration a seeded device permutation splits the rows into minibatches of minibatch_rows (default: the whole batch);
-        each gets grads + apply.  A compact batch is trained where it lies: a minibatch is its slice of the permutation, handed to
-        grads_indexed as the row index -- no observation row is ever written.  A rows batch is gathered into buffers allocated once
-        and goes through grads: measured, the gather and contiguous reads beat scattered reads of whole rows at large batches
-        (profiles/r11_learner_indexed.txt); both ways give the same bits.  Afterwards the mean KL of the last iteration is read (the
-        one synchronisation) and kl_coeff adapted by RLlib's rule.  num_active: listed UEs where fewer than the env's slots (multi:
-        the other rows are dropped before the split).  rows: an integer device tensor of distinct source rows of the flattened batch
-        -- the learner then trains on exactly those rows: the advantages are standardised over them alone, the permutation runs over
-        them only, and the result is that of update() on the batch gathered at rows, bit for bit (deepcomp_amd.policy_set hands each
-        per-UE policy the rows of its slots this way); not together with num_active.  rows are checked to be inside the batch and
-        distinct (one sort and one synchronisation; check_rows=False skips it for rows the caller built itself).  Returns the last iteration's mean statistics
-        and the new kl_coeff."""
+    def _flatten(self, batch):
+        """(src, N, compact) of a collect(..., dist_inputs=True) batch: the per-row tensors flattened to N source rows, under the names
+        grads_indexed takes, with 'obs' (rows) or 'obs_compact' (the compact record)."""
         a = self.actor
         if 'action_dist_inputs' not in batch:
             raise ValueError("the batch has no action_dist_inputs: collect(..., dist_inputs=True)")
-        multi = a.kind == _lib.MULTI
         compact = 'obs' not in batch
-        if compact and not multi:
+        if compact and a.kind != _lib.MULTI:
             raise NotImplementedError("compact observation records exist for multi-agent observations only")
         src = {'actions': batch['actions'].reshape(-1, a.heads), 'old_logp': batch['action_logp'].reshape(-1, a.heads),
                'old_logits': batch['action_dist_inputs'].reshape(-1, a.num_logits), 'advantages': batch['advantages'].reshape(-1),
@@ -510,6 +616,55 @@ class PPOLearner:
             src['obs_compact'] = batch['obs_compact'].reshape(-1, batch['obs_compact'].shape[-1])      # [T, E, words], contiguous: env t E + e
             if src['obs_compact'].shape[0] * a.U != N:
                 raise ValueError("the batch's tensors disagree about the number of rows")
+        return src, N, compact
+
+    def _gather_buffers(self, src, size):
+        """The gather buffers of a rows batch, allocated once per size: one row per position of a (micro-)batch."""
+        if size not in self._mb:
+            self._mb = {size: {k: torch.empty((size,) + tuple(t.shape[1:]), dtype=t.dtype, device=self.device) for k, t in src.items()}}
+        return self._mb[size]
+
+    def accumulate_minibatch(self, src, compact, picks, micro, acc, sums, num_active=None):
+        """One minibatch of a flattened sample batch (src as _flatten() leaves it) into acc / sums, `micro` positions at a time: picks
+        are the minibatch's source rows in order (int32 with the compact record, whose micro-batches are slices of it handed to
+        accumulate_indexed; otherwise any integer type, each micro-batch gathered into the buffers and handed to accumulate)."""
+        n = int(picks.numel())
+        for s in range(0, n, micro):
+            part = picks[s:s + micro]
+            if compact:
+                self.accumulate_indexed(src, part, acc, sums)
+            else:
+                view = {k: t[:int(part.numel())] for k, t in self._gather_buffers(src, micro).items()}
+                for k in src:
+                    torch.index_select(src[k], 0, part, out=view[k])
+                self.accumulate(view['obs'], view['actions'], view['old_logp'], view['old_logits'], view['advantages'], view['value_targets'], view['old_vf'],
+                                acc, sums, num_active=num_active)
+
+    def update(self, batch, num_sgd_iter=30, minibatch_rows=None, seed=0, num_active=None, rows=None, check_rows=True, micro_rows=None,
+               grad_clip=None):
+        """PPO's SGD phase on one collect(..., dist_inputs=True) batch, observation rows or the compact record (compact=True): the
+        batch is flattened to source rows, the advantages are standardised over the batch (RLlib: (a - mean) / max(1e-4, std)), and
+        per iteration a seeded device permutation splits the rows into minibatches of minibatch_rows (default: the whole batch);
+        each gets grads + apply.  A compact batch is trained where it lies: a minibatch is its slice of the permutation, handed to
+        grads_indexed as the row index -- no observation row is ever written.  A rows batch is gathered into buffers allocated once
+        and goes through grads: measured, the gather and contiguous reads beat scattered reads of whole rows at large batches
+        (profiles/r11_learner_indexed.txt); both ways give the same bits.  Afterwards the mean KL of the last iteration is read (the
+        one synchronisation) and kl_coeff adapted by RLlib's rule.  num_active: listed UEs where fewer than the env's slots (multi:
+        the other rows are dropped before the split).  rows: an integer device tensor of distinct source rows of the flattened batch
+        -- the learner then trains on exactly those rows: the advantages are standardised over them alone, the permutation runs over
+        them only, and the result is that of update() on the batch gathered at rows, bit for bit (deepcomp_amd.policy_set hands each
+        per-UE policy the rows of its slots this way); not together with num_active.  rows are checked to be inside the batch and
+        distinct (one sort and one synchronisation; check_rows=False skips it for rows the caller built itself).  Returns the last iteration's mean statistics
+        and the new kl_coeff.
+
+        micro_rows / grad_clip (both None: the path above, unchanged): a minibatch is then trained as zeroed accumulators, one
+        accumulate per micro-batch of micro_rows positions (default: the whole minibatch), finish (1 / N of the minibatch, and the
+        global-norm clip of RLlib's grad_clip) and apply.  micro_rows is a multiple of the chunk unit (2 048 rows) and at most
+        max_rows; the workspaces and gather buffers are then sized by the micro-batch, and a minibatch may be larger than max_rows.
+        Up to 262 144 rows per minibatch the new weights are those of the whole-minibatch path, bit for bit (without grad_clip)."""
+        a = self.actor
+        multi = a.kind == _lib.MULTI
+        src, N, compact = self._flatten(batch)
         kernel_active, keep = None, None
         if rows is not None:
             if num_active is not None:
@@ -541,9 +696,19 @@ class PPOLearner:
         # (compact: the standardised advantages back in source order, where the index finds them)
         src['advantages'] = adv if keep is None or not compact else torch.zeros_like(src['advantages']).index_copy_(0, keep, adv)
         mb = N if minibatch_rows is None else min(int(minibatch_rows), N)
-        if mb > self.max_rows:
+        accumulated = micro_rows is not None or grad_clip is not None
+        if micro_rows is not None:
+            micro = check_micro_rows(micro_rows, self.max_rows)
+        elif mb > self.max_rows:
             raise ValueError(f"minibatches of {mb} rows > max_rows {self.max_rows} of the learner")
-        if not compact and mb not in self._mb:
+        else:
+            micro = mb
+        if grad_clip is not None and not float(grad_clip) >= 0.0:
+            raise ValueError(f"grad_clip {grad_clip!r} must be >= 0")
+        if accumulated:
+            micro = min(micro, mb)                                             # (the gather buffers' size)
+            acc, sums = self.new_accumulators()
+        elif not compact and mb not in self._mb:
             self._mb = {mb: {k: torch.empty((mb,) + tuple(t.shape[1:]), dtype=t.dtype, device=self.device) for k, t in src.items()}}
         starts = list(range(0, N, mb))
         stats = torch.zeros((len(starts), _lib.PPO_NUM_STATS), dtype=torch.float32, device=self.device)
@@ -554,7 +719,12 @@ class PPOLearner:
             if compact:
                 index = (perm if keep is None else keep.index_select(0, perm)).to(torch.int32)
             for i, s in enumerate(starts):
-                if compact:
+                if accumulated:
+                    acc.zero_()
+                    sums.zero_()
+                    self.accumulate_minibatch(src, compact, index[s:s + mb] if compact else perm[s:s + mb], micro, acc, sums, kernel_active)
+                    self.finish(acc, sums, grad_clip, stats=stats[i])
+                elif compact:
                     self.grads_indexed(src, index[s:s + mb], stats=stats[i])
                 else:
                     idx = perm[s:s + mb]

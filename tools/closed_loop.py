@@ -7,6 +7,7 @@ this only shows where the time goes once the env runs at ~10^8-10^9 env-steps/s.
     python tools/closed_loop.py [--envs 65536] [--steps 200] [--dtype bf16] [--kind multi] [--actor hip [--compact]]
     python tools/closed_loop.py --collect 50 [--envs 65536] [--kind multi] [--compact] [--shared-value]
     python tools/closed_loop.py --train 3 [--train-steps 5] [--sgd-iters 2] [--minibatch ROWS] [--envs 65536] [--kind multi] [--compact]
+                                [--micro-rows ROWS] [--grad-clip NORM]
     python tools/closed_loop.py --per-ue [--actor hip | --collect 50 | --train 3 [--grouped]] [--hidden 64] [--compact] [--envs 4096 --ues 128 --bs 32]
 
 --actor torch (default): the actor as torch ops (bf16 matmuls, Gumbel-max through torch.rand).  --actor hip: the same weights in
@@ -26,6 +27,9 @@ and the time of one SGD iteration of update on the rows batch (minibatches gathe
 iteration with the minibatches picked through a row index instead (grads_indexed: nothing is copied, rows are read scattered).
 --compact (multi-agent): collect returns the compact record and update trains on it through the row index -- no observation row is
 written anywhere in the loop; the unpack a rows-only learner would need first is timed on its own.
+--grad-clip NORM: update(grad_clip=NORM), RLlib's global-norm clip.  --micro-rows ROWS (a multiple of 2 048): the learner's handle is
+sized by ROWS instead of the minibatch and update(micro_rows=ROWS) accumulates a minibatch's gradient micro-batch by micro-batch; the
+time of one SGD iteration that way is printed and the comparisons that need a whole-minibatch handle are left out.
 
 --per-ue (multi-agent): one policy network per UE (D3-CoMP) -- deepcomp_amd.policy_set.PerUEActor over U random-init members and, with
 --train, PerUELearner -- timed next to the shared-policy actor / learner on the same env, interleaved: the loop env step + actor
@@ -60,6 +64,8 @@ ap.add_argument('--train', type=int, default=0, metavar='ITERS', help='collect -
 ap.add_argument('--train-steps', type=int, default=5, help='--train: steps per collected batch')
 ap.add_argument('--sgd-iters', type=int, default=2, help='--train: SGD iterations per batch')
 ap.add_argument('--minibatch', type=int, default=0, help='--train: rows per minibatch (default: one step\'s rows)')
+ap.add_argument('--micro-rows', type=int, default=0, help='--train: rows per micro-batch (a multiple of 2048): the handle is sized by it, a minibatch is accumulated')
+ap.add_argument('--grad-clip', type=float, default=0.0, help='--train: global-norm gradient clip (RLlib grad_clip); 0: none')
 ap.add_argument('--hidden', type=int, default=256, help='hidden width of the fcnet (two layers)')
 ap.add_argument('--grouped', action='store_true', help='--per-ue --train: also time PerUELearner.update(grouped=True), interleaved with the sequential update and the shared learner')
 ap.add_argument('--per-ue', action='store_true', help='one policy per UE (PerUEActor / PerUELearner) next to the shared policy; multi-agent')
@@ -174,15 +180,28 @@ def train_mode(iters):
     hip.set_value(host_v)
     rows = E * U if multi else E
     mb = a.minibatch or rows
-    learner = PPOLearner(hip, lr=5e-5, max_rows=mb)
+    extra = dict(micro_rows=a.micro_rows or None, grad_clip=a.grad_clip or None)
+    learner = PPOLearner(hip, lr=5e-5, max_rows=a.micro_rows or mb)
     env.reset()
     buf = None
     print(f'{E} envs x {U} UE x {B} BS ({a.kind}), 2x{a.hidden} tanh + value trunk, batches of T = {T} ({T * rows} rows), {a.sgd_iters} SGD iterations, minibatches of {mb}'
           + (', compact record' if a.compact else ''))
     for it in range(iters):
         buf = collect(env, hip, T, 0.99, 0.95, out=buf, dist_inputs=True, compact=a.compact)
-        st = learner.update(buf, num_sgd_iter=a.sgd_iters, minibatch_rows=mb, seed=it)
+        st = learner.update(buf, num_sgd_iter=a.sgd_iters, minibatch_rows=mb, seed=it, **extra)
         print(f'iter {it}: mean reward {float(buf["rewards"].mean()):+.4f}  ' + '  '.join(f'{n} {st[n]:+.5f}' for n in STATS) + f'  kl_coeff {st["kl_coeff"]:.3f}')
+    if a.micro_rows:
+        ts = []
+        for _ in range(4):                                               # (the first: warm-up)
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            learner.update(buf, num_sgd_iter=1, minibatch_rows=mb, seed=0, **extra)
+            torch.cuda.synchronize()
+            ts.append((time.perf_counter() - t0) * 1e6)
+        print(f'one SGD iteration over {T * rows} rows, minibatches of {mb} accumulated in micro-batches of {a.micro_rows} (handle of {a.micro_rows} rows): '
+              + ' / '.join(f'{t:.0f}' for t in ts[1:]) + ' us')
+        env.check()
+        return
 
     # ---- grads + apply on one minibatch against torch autograd (bf16 autocast) + torch.optim.Adam on the same network and loss
     rows_buf = buf
