@@ -67,6 +67,16 @@ typedef struct dcomp_cfg {
                                             * negative / NaN = use the integer range above.  Such a UE never draws a velocity. */
 } dcomp_cfg;
 
+/* Initialisation and alignment contract of the caller's buffers (held by tests/test_guard_bands_gpu.py: guard bands around every array,
+ * state filled with garbage before the first reset, outputs at every 4-byte phase of a 16-byte line):
+ *  - `flags` is the one array the CALLER must zero before the first dcomp_reset: it is a sticky error word the kernels only OR bits into.
+ *  - dcomp_reset initialises every element of pos, mv, conn, ewma, of uid and orig_consumed where they are given, and of conn_hi on the generic
+ *    kernel -- dead slots of an env whose UE list changes included.  They may hold anything before the first reset.
+ *  - conn_since is not touched by dcomp_reset.  An entry [slot][b] is written by the step that connects the slot to a max-cap station b (and travels
+ *    with its UE when slots shift) and is read only while that connection exists; every other entry is never read, so the array may hold anything.
+ *  - No call writes outside [0, size) of any array, and every call writes EVERY element of every dcomp_out buffer it is given (dead slots: zeros).
+ *    dcomp_out buffers therefore need no initialisation, and they need 4-byte alignment only (a slice of a larger tensor is fine).  State arrays
+ *    and uint8 action buffers are expected where hipMalloc / a tensor allocator puts them (16-byte aligned). */
 typedef struct dcomp_state {     /* device, caller-allocated; sizes via dcomp_state_sizes() */
     double *pos;
     uint64_t *mv;
