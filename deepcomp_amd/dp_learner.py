@@ -22,10 +22,9 @@ import time
 import numpy as np
 import torch
 
-from . import _lib
-from .learner import ARRAYS, STATS, adapt_kl_coeff, check_micro_rows
+from .learner import ARRAYS, SUM, close_out, flatten_batch, minibatch_plan, minibatch_stats, sgd_epochs
 
-SUM, MIN, MAX = 'sum', 'min', 'max'
+MIN, MAX = 'min', 'max'
 
 
 # ---------------------------------------------------------------------------------------------- the phases that need no learner
@@ -128,58 +127,34 @@ class DataParallelLearner:
         self._reduce = group_reduce(group)
         self.profile = False                                 # True: synchronise around every phase and add its seconds to self.seconds
         self.seconds = {'accumulate': 0.0, 'reduce': 0.0, 'finish': 0.0, 'apply': 0.0}
+        self._lap_start = 0.0
 
-    def _clock(self):
-        if not self.profile:
-            return 0.0
-        torch.cuda.synchronize(self.learner.device)
-        return time.perf_counter()
+    def _lap(self, name=None):
+        """profile: synchronise and add the seconds since the last lap to self.seconds[name]."""
+        if self.profile:
+            torch.cuda.synchronize(self.learner.device)
+            now = time.perf_counter()
+            if name is not None:
+                self.seconds[name] += now - self._lap_start
+            self._lap_start = now
 
     def update_phases(self, batch, num_sgd_iter=30, minibatch_rows=None, micro_rows=None, seed=0, grad_clip=None):
         """update() as a generator of local phases: yields (tensor, op) at every all-reduce point and expects the reduction in the
         tensor when it is resumed.  Returns update()'s result."""
         L = self.learner
-        src, N, compact = L._flatten(batch)
+        src, N, compact = flatten_batch(L.actor, batch)
         mb = yield from shard_agreement_phases(N, minibatch_rows, self.world, L.device)
-        if micro_rows is not None:
-            micro = min(check_micro_rows(micro_rows, L.max_rows), mb)
-        elif mb > L.max_rows:
-            raise ValueError(f"a rank's share of a minibatch is {mb} rows > max_rows {L.max_rows} of the learner: give micro_rows")
-        else:
-            micro = mb
-        if grad_clip is not None and not float(grad_clip) >= 0.0:
-            raise ValueError(f"grad_clip {grad_clip!r} must be >= 0")
+        mb, micro, _ = minibatch_plan(N, mb, L.max_rows, micro_rows, grad_clip, "a rank's share of a minibatch is {} rows", ": give micro_rows")
         src['advantages'] = yield from standardize_phases(src['advantages'])
         acc, sums = L.new_accumulators()
-        starts = list(range(0, N, mb))
-        stats = torch.zeros((len(starts), _lib.PPO_NUM_STATS), dtype=torch.float32, device=L.device)
-        gen = torch.Generator(device=L.device)
-        gen.manual_seed(int(seed) + self.rank)               # each rank shuffles its own rows
-        sec = self.seconds
-        for _ in range(int(num_sgd_iter)):
-            perm = torch.randperm(N, generator=gen, device=L.device)
+        starts, stats = minibatch_stats(N, mb, L.device)
+        for perm in sgd_epochs(N, num_sgd_iter, int(seed) + self.rank, L.device):      # each rank shuffles its own rows
             picks = perm.to(torch.int32) if compact else perm
             for i, s in enumerate(starts):
-                t0 = self._clock()
-                acc.zero_()
-                sums.zero_()
-                L.accumulate_minibatch(src, compact, picks[s:s + mb], micro, acc, sums)
-                t1 = self._clock()
-                yield acc, SUM
-                yield sums, SUM
-                t2 = self._clock()
-                L.finish(acc, sums, grad_clip, stats=stats[i])
-                t3 = self._clock()
-                L.apply()
-                t4 = self._clock()
-                for name, dt in (('accumulate', t1 - t0), ('reduce', t2 - t1), ('finish', t3 - t2), ('apply', t4 - t3)):
-                    sec[name] += dt
+                self._lap()
+                yield from L.accumulated_step(src, compact, picks[s:s + mb], micro, acc, sums, grad_clip, stats[i], lap=self._lap)
         # the statistics come from the reduced sums: the same numbers, and so the same kl_coeff, on every rank
-        mean = stats.mean(0).cpu().numpy()
-        out = {n: float(mean[i]) for i, n in enumerate(STATS)}
-        L.hyper['kl_coeff'] = adapt_kl_coeff(L.hyper['kl_coeff'], out['kl'], L.kl_target)
-        out['kl_coeff'] = L.hyper['kl_coeff']
-        return out
+        return close_out([L], stats.mean(0)[None])[0]
 
     def update(self, batch, num_sgd_iter=30, minibatch_rows=None, micro_rows=None, seed=0, grad_clip=None):
         """PPO's SGD phase on this rank's shard of a collect(..., dist_inputs=True) batch (rows or the compact record), in step with

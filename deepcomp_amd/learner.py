@@ -299,6 +299,159 @@ def _arrays_struct(arrays):
     return _lib.DcompLearnerArrays(ctypes.sizeof(_lib.DcompLearnerArrays), 0, *[arrays[n].ctypes.data_as(fp) for n in ARRAYS])
 
 
+# ---------------------------------------------------------------------------------------------- the SGD phase, stated once
+# PPOLearner.update, DataParallelLearner.update_phases and PerUELearner's grouped update are loops over these pieces; the entry
+# methods (grads ... evaluate_indexed) and the three batch structs take their checks and pointers from FIELDS.
+INPUT, UPSTREAM, OUTPUT = 'input', 'upstream', 'output'
+SUM = 'sum'                                                    # the reduction a data-parallel learner applies where accumulated_step yields
+_f32, _heads, _logits, _one = torch.float32, 'heads', 'num_logits', 1
+# per-row field of a batch struct -> (dtype, elements per row: a number or the actor's attribute that holds it, role)
+FIELDS = {'actions': (torch.uint8, _heads, INPUT), 'old_logp': (_f32, _heads, INPUT), 'old_logits': (_f32, _logits, INPUT),
+          'advantages': (_f32, _one, INPUT), 'value_targets': (_f32, _one, INPUT), 'old_vf': (_f32, _one, INPUT),
+          'dlogits': (_f32, _logits, UPSTREAM), 'dvalue': (_f32, _one, UPSTREAM),
+          'logp': (_f32, _heads, OUTPUT), 'entropy': (_f32, _one, OUTPUT), 'kl': (_f32, _one, OUTPUT), 'vf': (_f32, _one, OUTPUT),
+          'ratio': (_f32, _one, OUTPUT)}
+INPUTS = tuple(n for n, f in FIELDS.items() if f[2] == INPUT)
+# ... and the name a collect() batch has the input under
+BATCH_KEYS = dict(zip(INPUTS, ('actions', 'action_logp', 'action_dist_inputs', 'advantages', 'value_targets', 'vf_preds')))
+
+
+def per_row(actor, name):
+    """Elements per row of a field for this actor."""
+    n = FIELDS[name][1]
+    return getattr(actor, n) if isinstance(n, str) else n
+
+
+def fill(struct, **members):
+    """A batch struct filled by member name, struct_size included.  (ctypes would take a misspelt member as a new attribute.)"""
+    unknown = set(members) - {n for n, _ in struct._fields_}
+    if unknown:
+        raise TypeError(f"{struct.__name__} has no member {sorted(unknown)}")
+    return struct(struct_size=ctypes.sizeof(struct), **members)
+
+
+def field_pointers(actor, given, rows_of):
+    """name -> device pointer of the per-row tensors given (None entries are left out), each checked against FIELDS; rows_of: the
+    rows a tensor of each role must hold.  The result fills a batch struct by keyword: the member order is the struct's own."""
+    ptr = {}
+    for name, t in given.items():
+        if t is not None:
+            dtype, _, role = FIELDS[name]
+            actor._check(t, dtype, rows_of[role] * per_row(actor, name), name)
+            ptr[name] = t.data_ptr()
+    return ptr
+
+
+def flatten_batch(actor, batch):
+    """(src, N, compact) of a collect(..., dist_inputs=True) batch: the per-row tensors flattened to N source rows, under the names
+    grads_indexed takes, with 'obs' (rows) or 'obs_compact' (the compact record)."""
+    a = actor
+    if 'action_dist_inputs' not in batch:
+        raise ValueError("the batch has no action_dist_inputs: collect(..., dist_inputs=True)")
+    compact = 'obs' not in batch
+    if compact and a.kind != _lib.MULTI:
+        raise NotImplementedError("compact observation records exist for multi-agent observations only")
+    src = {}
+    for name, key in BATCH_KEYS.items():                       # [N, heads] / [N, logits] for the fields an actor sizes, [N] for the others
+        src[name] = batch[key].reshape(-1, per_row(a, name)) if isinstance(FIELDS[name][1], str) else batch[key].reshape(-1)
+    if not compact:
+        src['obs'] = batch['obs'].reshape(-1, a.num_in)
+    N = src['actions'].shape[0]
+    if any(t.shape[0] != N for t in src.values()):
+        raise ValueError("the batch's tensors disagree about the number of rows")
+    if compact:
+        src['obs_compact'] = batch['obs_compact'].reshape(-1, batch['obs_compact'].shape[-1])      # [T, E, words], contiguous: env t E + e
+        if src['obs_compact'].shape[0] * a.U != N:
+            raise ValueError("the batch's tensors disagree about the number of rows")
+    return src, N, compact
+
+
+def standardize(adv):
+    """RLlib's standardisation of one learner's advantages: (a - mean) / max(1e-4, std), in the tensor's own precision."""
+    return (adv - adv.mean()) / adv.std(unbiased=False).clamp_min(1e-4)
+
+
+def select_rows(actor, src, N, compact, rows=None, num_active=None, check_rows=True):
+    """The single-learner rule for which rows of a flattened batch a learner trains on, with their advantages standardised over the
+    selected rows alone.  rows: distinct source rows (update()'s rows=); num_active: listed UEs (multi: the rows of the other slots
+    are dropped; central: the kernel leaves the other heads out).  Returns (src, N, keep, kernel_active).  A rows batch is gathered
+    at the selected rows (keep None).  The compact record is trained where it lies: src keeps every source row, keep holds the
+    selected ones (None: all) and the standardised advantages stand in source order, where the index finds them."""
+    a = actor
+    kernel_active, keep = None, None
+    if rows is not None:
+        if num_active is not None:
+            raise ValueError("rows and num_active exclude each other: leave the rows of unlisted slots out of rows")
+        if not isinstance(rows, torch.Tensor) or rows.dim() != 1 or rows.numel() == 0 or rows.device != a.device or \
+                rows.dtype not in (torch.int32, torch.int64):
+            raise ValueError(f"rows must be a non-empty 1-d int32 / int64 tensor on {a.device}")
+        keep = rows.to(torch.int64)
+        if check_rows:
+            srt = keep.sort().values
+            lo, hi, dup = torch.stack((srt[0], srt[-1], (srt[1:] == srt[:-1]).any().to(torch.int64))).tolist()      # one synchronisation
+            if lo < 0 or hi >= N:
+                raise ValueError(f"rows has entries outside the batch's {N} source rows")
+            if dup:
+                raise ValueError("rows has repeated entries: they must be distinct source rows")
+    elif num_active is not None and int(num_active) < a.U:
+        if a.kind == _lib.MULTI:
+            keep = torch.nonzero(torch.arange(N, device=a.device) % a.U < int(num_active)).reshape(-1)
+        else:
+            kernel_active = int(num_active)
+    if keep is not None:
+        N = int(keep.numel())
+        if not compact:
+            src, keep = {k: t.index_select(0, keep) for k, t in src.items()}, None
+    scattered = keep is not None
+    adv = src['advantages'].index_select(0, keep) if scattered else src['advantages']
+    adv = standardize(adv)
+    if scattered:
+        adv = torch.zeros_like(src['advantages']).index_copy_(0, keep, adv)
+    return dict(src, advantages=adv), N, keep, kernel_active
+
+
+def minibatch_plan(N, minibatch_rows, max_rows, micro_rows=None, grad_clip=None, noun="minibatches of {} rows", hint=""):
+    """(mb, micro, accumulated): the rows of a minibatch (minibatch_rows, at most N; None: N), of a micro-batch -- the gather
+    buffers' size -- and whether the minibatches go through the accumulators (micro_rows or grad_clip given)."""
+    mb = N if minibatch_rows is None else min(int(minibatch_rows), N)
+    if micro_rows is not None:
+        micro = check_micro_rows(micro_rows, max_rows)
+    elif mb > max_rows:
+        raise ValueError(f"{noun.format(mb)} > max_rows {max_rows} of the learner{hint}")
+    else:
+        micro = mb
+    if grad_clip is not None and not float(grad_clip) >= 0.0:
+        raise ValueError(f"grad_clip {grad_clip!r} must be >= 0")
+    return mb, min(micro, mb), micro_rows is not None or grad_clip is not None
+
+
+def sgd_epochs(N, num_sgd_iter, seed, device):
+    """Per SGD iteration one device permutation of N rows, from a generator seeded once."""
+    gen = torch.Generator(device=device)
+    gen.manual_seed(int(seed))
+    for _ in range(int(num_sgd_iter)):
+        yield torch.randperm(N, generator=gen, device=device)
+
+
+def minibatch_stats(N, mb, device):
+    """(starts, stats): where the minibatches of an iteration begin, and their zeroed [minibatches, 5] statistics."""
+    starts = list(range(0, N, mb))
+    return starts, torch.zeros((len(starts), _lib.PPO_NUM_STATS), dtype=torch.float32, device=device)
+
+
+def close_out(learners, means):
+    """The end of an update: means is a float32 [len(learners), 5] device tensor, per learner the mean statistics of its last
+    iteration's minibatches.  One transfer to the host (the update's one synchronisation); every learner's kl_coeff is adapted by
+    RLlib's rule.  Returns one dict per learner: the statistics and the new kl_coeff."""
+    outs = []
+    for ln, mean in zip(learners, means.cpu().numpy()):
+        out = {n: float(mean[i]) for i, n in enumerate(STATS)}
+        ln.hyper['kl_coeff'] = adapt_kl_coeff(ln.hyper['kl_coeff'], out['kl'], ln.kl_target)
+        out['kl_coeff'] = ln.hyper['kl_coeff']
+        outs.append(out)
+    return outs
+
+
 class PPOLearner:
     """PPO on the device for the policy an FcnetActor runs; every update lands in the actor's own handle."""
 
@@ -336,68 +489,13 @@ class PPOLearner:
             self._h = None
 
     # ------------------------------------------------------------------ the kernels
-    def _rows(self, obs):
-        a = self.actor
-        if not isinstance(obs, torch.Tensor) or obs.numel() == 0 or obs.numel() % a.num_in:
-            raise ValueError(f"obs must hold a whole number of rows of {a.num_in} elements")
-        rows = obs.numel() // a.num_in
-        a._check(obs, torch.float32, rows * a.num_in, 'obs')
+    def _fits(self, rows):
         if rows > self.max_rows:
             raise ValueError(f"{rows} rows > max_rows {self.max_rows} of the learner")
         return rows
 
-    def _hyper_struct(self):
-        return _lib.DcompPpoHyper(ctypes.sizeof(_lib.DcompPpoHyper), *[self.hyper[n] for n in ('clip_param', 'vf_clip_param', 'vf_loss_coeff', 'entropy_coeff', 'kl_coeff')])
-
-    def _batch(self, obs, rows, num_active, tensors):
-        """dcomp_ppo_batch over checked tensors: tensors maps a field to (tensor or None, dtype, elements per row)."""
-        a = self.actor
-        ptr = {}
-        for name, (t, dtype, per_row) in tensors.items():
-            if t is not None:
-                a._check(t, dtype, rows * per_row, name)
-            ptr[name] = t.data_ptr() if t is not None else None
-        order = ('actions', 'old_logp', 'old_logits', 'advantages', 'value_targets', 'old_vf', 'logp', 'entropy', 'kl', 'vf', 'ratio', 'dlogits', 'dvalue')
-        return _lib.DcompPpoBatch(ctypes.sizeof(_lib.DcompPpoBatch), _lib.ACTOR_ROWS, rows, a.U if num_active is None else int(num_active), 0,
-                                  obs.data_ptr(), *[ptr.get(n) for n in order])
-
-    def grads(self, obs, actions=None, old_logp=None, old_logits=None, advantages=None, value_targets=None, old_vf=None, *, num_active=None,
-              logp=None, entropy=None, kl=None, vf=None, ratio=None, dlogits=None, dvalue=None, stats=None):
-        """The loss statistics (a float32 [5] device tensor: total_loss, policy_loss, vf_loss, kl, entropy) and the gradients of all
-        twelve arrays into the handle, from one (mini)batch of device tensors: obs float32 [rows, inputs], actions uint8 [rows,
-        heads], old_logp [rows, heads], old_logits [rows, logits], advantages / value_targets / old_vf [rows].  logp ... ratio:
-        optional per-row outputs.  dlogits [rows, logits] with dvalue [rows]: upstream gradients used instead of the loss's (the
-        gradients are then plain sums over the rows, the statistics zero).  Nothing synchronises."""
-        a = self.actor
-        rows = self._rows(obs)
-        f32, h, n3 = torch.float32, a.heads, a.num_logits
-        b = self._batch(obs, rows, num_active, {
-            'actions': (actions, torch.uint8, h), 'old_logp': (old_logp, f32, h), 'old_logits': (old_logits, f32, n3), 'advantages': (advantages, f32, 1),
-            'value_targets': (value_targets, f32, 1), 'old_vf': (old_vf, f32, 1), 'logp': (logp, f32, h), 'entropy': (entropy, f32, 1), 'kl': (kl, f32, 1),
-            'vf': (vf, f32, 1), 'ratio': (ratio, f32, 1), 'dlogits': (dlogits, f32, n3), 'dvalue': (dvalue, f32, 1)})
-        if stats is None:
-            stats = torch.zeros(_lib.PPO_NUM_STATS, dtype=f32, device=self.device)
-        a._check(stats, f32, _lib.PPO_NUM_STATS, 'stats')
-        with torch.cuda.device(self.device):
-            _lib.check(self._L.dcomp_learner_grads(self._h, ctypes.byref(b), ctypes.byref(self._hyper_struct()), ctypes.c_void_p(stats.data_ptr()), a._stream()))
-        return stats
-
-    def evaluate(self, obs, actions, *, num_active=None):
-        """logp [rows, heads] of the GIVEN actions, the entropy [rows] and the value predictions [rows] under the current weights."""
-        a = self.actor
-        rows = self._rows(obs)
-        f32 = torch.float32
-        logp = torch.empty((rows, a.heads), dtype=f32, device=self.device)
-        entropy, vf = torch.empty(rows, dtype=f32, device=self.device), torch.empty(rows, dtype=f32, device=self.device)
-        b = self._batch(obs, rows, num_active, {'actions': (actions, torch.uint8, a.heads), 'logp': (logp, f32, a.heads), 'entropy': (entropy, f32, 1),
-                                                'vf': (vf, f32, 1)})
-        with torch.cuda.device(self.device):
-            _lib.check(self._L.dcomp_learner_evaluate(self._h, ctypes.byref(b), a._stream()))
-        return logp, entropy, vf
-
-    # ------------------------------------------------------------------ minibatches through a row index (include/dcomp_learner_indexed.h)
-    def _sgd_source(self, source, index):
-        """(obs tensor, obs_format, source rows, minibatch rows) of a flattened sample batch and an index, after their checks."""
+    def _source_obs(self, source):
+        """(obs tensor, obs_format, source rows) of a dict that holds 'obs' or 'obs_compact', after their checks."""
         a = self.actor
         if not isinstance(source, dict) or ('obs' in source) == ('obs_compact' in source):
             raise ValueError("source must be a dict that holds either 'obs' or 'obs_compact'")
@@ -412,38 +510,89 @@ class PPOLearner:
             n_src = a._batch(obs, True)[1]                                     # (central: NotImplementedError)
         if n_src > 2 ** 31 - 1:
             raise ValueError(f"{n_src} source rows > 2^31 - 1")
+        return obs, fmt, n_src
+
+    def _hyper_struct(self):
+        return _lib.DcompPpoHyper(ctypes.sizeof(_lib.DcompPpoHyper), *[self.hyper[n] for n in ('clip_param', 'vf_clip_param', 'vf_loss_coeff', 'entropy_coeff', 'kl_coeff')])
+
+    def _rows(self, obs):
+        return self._fits(self._source_obs({'obs': obs})[2])
+
+    def _batch(self, obs, rows, num_active, fields):
+        """dcomp_ppo_batch over checked tensors: a contiguous minibatch of `rows` rows, fields maps a per-row field to its tensor or None."""
+        a = self.actor
+        return fill(_lib.DcompPpoBatch, obs_format=_lib.ACTOR_ROWS, rows=rows, obs=obs.data_ptr(), num_active=a.U if num_active is None else int(num_active),
+                    **field_pointers(a, fields, dict.fromkeys((INPUT, UPSTREAM, OUTPUT), rows)))
+
+    def _sgd_source(self, source, index):
+        """(obs tensor, obs_format, source rows, minibatch rows) of a flattened sample batch and an index, after their checks."""
+        obs, fmt, n_src = self._source_obs(source)
         rows = n_src
         if index is not None:
             if not isinstance(index, torch.Tensor) or index.numel() == 0:
                 raise ValueError("index must be a non-empty contiguous int32 device tensor")
             rows = index.numel()
-            a._check(index, torch.int32, rows, 'index')
-        if rows > self.max_rows:
-            raise ValueError(f"{rows} rows > max_rows {self.max_rows} of the learner")
-        return obs, fmt, n_src, rows
+            self.actor._check(index, torch.int32, rows, 'index')
+        return obs, fmt, n_src, self._fits(rows)
 
     def _sgd_batch(self, where, source, index, num_active, wanted, outputs):
         """dcomp_sgd_batch over checked tensors: where = _sgd_source(); wanted names the per-row inputs taken from source (source_rows
-        rows each), outputs maps a per-row output to (tensor or None, elements per row) (one row per minibatch position)."""
+        rows each), outputs maps a per-row output to its tensor or None (one row per minibatch position; the helper's earlier form, a
+        (tensor, elements per row) pair, is still taken: the count is the field table's)."""
         a = self.actor
         obs, fmt, n_src, rows = where
-        f32, h, n3 = torch.float32, a.heads, a.num_logits
-        per_row = {'actions': (torch.uint8, h), 'old_logp': (f32, h), 'old_logits': (f32, n3), 'advantages': (f32, 1), 'value_targets': (f32, 1),
-                   'old_vf': (f32, 1), 'dlogits': (f32, n3), 'dvalue': (f32, 1)}
-        ptr = {}
-        for name in wanted:
-            t = source.get(name)
-            if t is not None:
-                a._check(t, per_row[name][0], n_src * per_row[name][1], name)
-                ptr[name] = t.data_ptr()
-        for name, (t, per) in outputs.items():
-            if t is not None:
-                a._check(t, f32, rows * per, name)
-                ptr[name] = t.data_ptr()
-        order = ('actions', 'old_logp', 'old_logits', 'advantages', 'value_targets', 'old_vf', 'dlogits', 'dvalue', 'logp', 'entropy', 'kl', 'vf', 'ratio')
-        return _lib.DcompSgdBatch(ctypes.sizeof(_lib.DcompSgdBatch), fmt, rows, n_src, index.data_ptr() if index is not None else None,
-                                  a.U if num_active is None else int(num_active), 0, obs.data_ptr(), *[ptr.get(n) for n in order])
+        outputs = {n: t[0] if isinstance(t, tuple) else t for n, t in outputs.items()}
+        ptr = field_pointers(a, {**{n: source.get(n) for n in wanted}, **outputs}, {INPUT: n_src, UPSTREAM: n_src, OUTPUT: rows})
+        return fill(_lib.DcompSgdBatch, obs_format=fmt, rows=rows, source_rows=n_src, obs=obs.data_ptr(), index=index.data_ptr() if index is not None else None,
+                    num_active=a.U if num_active is None else int(num_active), **ptr)
 
+    def _stats(self, stats):
+        if stats is None:
+            stats = torch.zeros(_lib.PPO_NUM_STATS, dtype=torch.float32, device=self.device)
+        self.actor._check(stats, torch.float32, _lib.PPO_NUM_STATS, 'stats')
+        return stats
+
+    def _submit(self, b, stats=None, into=None):
+        """A checked batch struct, contiguous or indexed, to grads (into None: the statistics into `stats`, which is returned) or to
+        accumulate (into = (acc, sums))."""
+        entry = ('dcomp_sgd_' if isinstance(b, _lib.DcompSgdBatch) else 'dcomp_learner_') + ('grads' if into is None else 'accumulate')
+        if into is None:
+            stats = self._stats(stats)
+            args = (ctypes.c_void_p(stats.data_ptr()),)
+        else:
+            args = self._accumulators(*into)
+        with torch.cuda.device(self.device):
+            _lib.check(getattr(self._L, entry)(self._h, ctypes.byref(b), ctypes.byref(self._hyper_struct()), *args, self.actor._stream()))
+        return stats
+
+    def _evaluate(self, rows, batch_with):
+        """evaluate / evaluate_indexed: the outputs allocated, the struct batch_with(outputs) builds over them, the launch."""
+        a = self.actor
+        out = {'logp': torch.empty((rows, a.heads), dtype=torch.float32, device=self.device),
+               'entropy': torch.empty(rows, dtype=torch.float32, device=self.device), 'vf': torch.empty(rows, dtype=torch.float32, device=self.device)}
+        b = batch_with(out)
+        entry = 'dcomp_sgd_evaluate' if isinstance(b, _lib.DcompSgdBatch) else 'dcomp_learner_evaluate'
+        with torch.cuda.device(self.device):
+            _lib.check(getattr(self._L, entry)(self._h, ctypes.byref(b), a._stream()))
+        return out['logp'], out['entropy'], out['vf']
+
+    def grads(self, obs, actions=None, old_logp=None, old_logits=None, advantages=None, value_targets=None, old_vf=None, *, num_active=None,
+              logp=None, entropy=None, kl=None, vf=None, ratio=None, dlogits=None, dvalue=None, stats=None):
+        """The loss statistics (a float32 [5] device tensor: total_loss, policy_loss, vf_loss, kl, entropy) and the gradients of all
+        twelve arrays into the handle, from one (mini)batch of device tensors: obs float32 [rows, inputs], actions uint8 [rows,
+        heads], old_logp [rows, heads], old_logits [rows, logits], advantages / value_targets / old_vf [rows].  logp ... ratio:
+        optional per-row outputs.  dlogits [rows, logits] with dvalue [rows]: upstream gradients used instead of the loss's (the
+        gradients are then plain sums over the rows, the statistics zero).  Nothing synchronises."""
+        return self._submit(self._batch(obs, self._rows(obs), num_active, dict(
+            actions=actions, old_logp=old_logp, old_logits=old_logits, advantages=advantages, value_targets=value_targets, old_vf=old_vf,
+            logp=logp, entropy=entropy, kl=kl, vf=vf, ratio=ratio, dlogits=dlogits, dvalue=dvalue)), stats)
+
+    def evaluate(self, obs, actions, *, num_active=None):
+        """logp [rows, heads] of the GIVEN actions, the entropy [rows] and the value predictions [rows] under the current weights."""
+        rows = self._rows(obs)
+        return self._evaluate(rows, lambda out: self._batch(obs, rows, num_active, dict(out, actions=actions)))
+
+    # ------------------------------------------------------------------ minibatches through a row index (include/dcomp_learner_indexed.h)
     def grads_indexed(self, source, index=None, *, num_active=None, logp=None, entropy=None, kl=None, vf=None, ratio=None, stats=None):
         """grads() on the rows `index` picks out of a whole sample batch, without gathering them: source is a dict of the flattened
         sample-batch tensors -- 'obs' float32 [source_rows, inputs] or 'obs_compact' int32 [envs, words] (multi: the record
@@ -453,31 +602,14 @@ class PPOLearner:
         index entry.  The results are those of grads() on the gathered rows, bit for bit.  An index entry outside the sample batch is
         not read: its position contributes zeros and still counts in the mean.  multi: num_active must stay the env's slots -- leave
         the rows of unlisted slots out of the index.  Nothing synchronises."""
-        a = self.actor
-        f32 = torch.float32
-        b = self._sgd_batch(self._sgd_source(source, index), source, index, num_active,
-                            ('actions', 'old_logp', 'old_logits', 'advantages', 'value_targets', 'old_vf', 'dlogits', 'dvalue'),
-                            {'logp': (logp, a.heads), 'entropy': (entropy, 1), 'kl': (kl, 1), 'vf': (vf, 1), 'ratio': (ratio, 1)})
-        if stats is None:
-            stats = torch.zeros(_lib.PPO_NUM_STATS, dtype=f32, device=self.device)
-        a._check(stats, f32, _lib.PPO_NUM_STATS, 'stats')
-        with torch.cuda.device(self.device):
-            _lib.check(self._L.dcomp_sgd_grads(self._h, ctypes.byref(b), ctypes.byref(self._hyper_struct()), ctypes.c_void_p(stats.data_ptr()), a._stream()))
-        return stats
+        return self._submit(self._sgd_batch(self._sgd_source(source, index), source, index, num_active, INPUTS + ('dlogits', 'dvalue'),
+                                            dict(logp=logp, entropy=entropy, kl=kl, vf=vf, ratio=ratio)), stats)
 
     def evaluate_indexed(self, source, index=None, *, num_active=None):
         """evaluate() on the rows `index` picks out of source ('obs' or 'obs_compact', and 'actions'): logp [rows, heads], the entropy
         [rows] and the value predictions [rows], one row per index entry."""
-        a = self.actor
-        f32 = torch.float32
         where = self._sgd_source(source, index)
-        rows = where[3]
-        logp = torch.empty((rows, a.heads), dtype=f32, device=self.device)
-        entropy, vf = torch.empty(rows, dtype=f32, device=self.device), torch.empty(rows, dtype=f32, device=self.device)
-        b = self._sgd_batch(where, source, index, num_active, ('actions',), {'logp': (logp, a.heads), 'entropy': (entropy, 1), 'vf': (vf, 1)})
-        with torch.cuda.device(self.device):
-            _lib.check(self._L.dcomp_sgd_evaluate(self._h, ctypes.byref(b), a._stream()))
-        return logp, entropy, vf
+        return self._evaluate(where[3], lambda out: self._sgd_batch(where, source, index, num_active, ('actions',), out))
 
     # ------------------------------------------------------------------ accumulated gradients (include/dcomp_learner_accum.h)
     @property
@@ -508,26 +640,14 @@ class PPOLearner:
         apply() consumes.  While every call but the last has a multiple of the chunk unit (chunk_unit(): 2 048 rows) and the calls
         together have at most 262 144 rows, finish() gives the gradients of grads() on all rows at once, bit for bit.  Upstream
         gradients are not taken here: they are plain sums already."""
-        a = self.actor
-        rows = self._rows(obs)
-        f32, h, n3 = torch.float32, a.heads, a.num_logits
-        b = self._batch(obs, rows, num_active, {
-            'actions': (actions, torch.uint8, h), 'old_logp': (old_logp, f32, h), 'old_logits': (old_logits, f32, n3), 'advantages': (advantages, f32, 1),
-            'value_targets': (value_targets, f32, 1), 'old_vf': (old_vf, f32, 1), 'logp': (logp, f32, h), 'entropy': (entropy, f32, 1), 'kl': (kl, f32, 1),
-            'vf': (vf, f32, 1), 'ratio': (ratio, f32, 1)})
-        pa, ps = self._accumulators(acc, sums)
-        with torch.cuda.device(self.device):
-            _lib.check(self._L.dcomp_learner_accumulate(self._h, ctypes.byref(b), ctypes.byref(self._hyper_struct()), pa, ps, a._stream()))
+        self._submit(self._batch(obs, self._rows(obs), num_active, dict(
+            actions=actions, old_logp=old_logp, old_logits=old_logits, advantages=advantages, value_targets=value_targets, old_vf=old_vf,
+            logp=logp, entropy=entropy, kl=kl, vf=vf, ratio=ratio)), into=(acc, sums))
 
     def accumulate_indexed(self, source, index, acc, sums, *, num_active=None, logp=None, entropy=None, kl=None, vf=None, ratio=None):
         """accumulate() on the rows `index` picks out of a whole sample batch (grads_indexed's source and index)."""
-        a = self.actor
-        b = self._sgd_batch(self._sgd_source(source, index), source, index, num_active,
-                            ('actions', 'old_logp', 'old_logits', 'advantages', 'value_targets', 'old_vf'),
-                            {'logp': (logp, a.heads), 'entropy': (entropy, 1), 'kl': (kl, 1), 'vf': (vf, 1), 'ratio': (ratio, 1)})
-        pa, ps = self._accumulators(acc, sums)
-        with torch.cuda.device(self.device):
-            _lib.check(self._L.dcomp_sgd_accumulate(self._h, ctypes.byref(b), ctypes.byref(self._hyper_struct()), pa, ps, a._stream()))
+        self._submit(self._sgd_batch(self._sgd_source(source, index), source, index, num_active, INPUTS,
+                                     dict(logp=logp, entropy=entropy, kl=kl, vf=vf, ratio=ratio)), into=(acc, sums))
 
     def finish(self, acc, sums, grad_clip=None, stats=None, grad_norm=None):
         """The handle's gradients from accumulated sums: g = acc * float32(1 / sums[4]); with grad_clip (> 0) g is scaled by
@@ -540,9 +660,7 @@ class PPOLearner:
         if not clip >= 0.0:
             raise ValueError(f"grad_clip {grad_clip!r} must be >= 0 (None or 0: no clipping)")
         pa, ps = self._accumulators(acc, sums)
-        if stats is None:
-            stats = torch.zeros(_lib.PPO_NUM_STATS, dtype=torch.float32, device=self.device)
-        a._check(stats, torch.float32, _lib.PPO_NUM_STATS, 'stats')
+        stats = self._stats(stats)
         if grad_norm is not None:
             a._check(grad_norm, torch.float32, 1, 'grad_norm')
         with torch.cuda.device(self.device):
@@ -595,50 +713,46 @@ class PPOLearner:
         self.actor.weights, self.actor.value_weights = split_weights(host['weights'])
 
     # ------------------------------------------------------------------ the training step
-    def _flatten(self, batch):
-        """(src, N, compact) of a collect(..., dist_inputs=True) batch: the per-row tensors flattened to N source rows, under the names
-        grads_indexed takes, with 'obs' (rows) or 'obs_compact' (the compact record)."""
-        a = self.actor
-        if 'action_dist_inputs' not in batch:
-            raise ValueError("the batch has no action_dist_inputs: collect(..., dist_inputs=True)")
-        compact = 'obs' not in batch
-        if compact and a.kind != _lib.MULTI:
-            raise NotImplementedError("compact observation records exist for multi-agent observations only")
-        src = {'actions': batch['actions'].reshape(-1, a.heads), 'old_logp': batch['action_logp'].reshape(-1, a.heads),
-               'old_logits': batch['action_dist_inputs'].reshape(-1, a.num_logits), 'advantages': batch['advantages'].reshape(-1),
-               'value_targets': batch['value_targets'].reshape(-1), 'old_vf': batch['vf_preds'].reshape(-1)}
-        if not compact:
-            src['obs'] = batch['obs'].reshape(-1, a.num_in)
-        N = src['actions'].shape[0]
-        if any(t.shape[0] != N for t in src.values()):
-            raise ValueError("the batch's tensors disagree about the number of rows")
-        if compact:
-            src['obs_compact'] = batch['obs_compact'].reshape(-1, batch['obs_compact'].shape[-1])      # [T, E, words], contiguous: env t E + e
-            if src['obs_compact'].shape[0] * a.U != N:
-                raise ValueError("the batch's tensors disagree about the number of rows")
-        return src, N, compact
-
     def _gather_buffers(self, src, size):
         """The gather buffers of a rows batch, allocated once per size: one row per position of a (micro-)batch."""
         if size not in self._mb:
             self._mb = {size: {k: torch.empty((size,) + tuple(t.shape[1:]), dtype=t.dtype, device=self.device) for k, t in src.items()}}
         return self._mb[size]
 
+    def submit_picks(self, src, compact, picks, size, num_active=None, stats=None, into=None):
+        """One (micro-)batch of a flattened sample batch (src as flatten_batch() leaves it) to grads (into None) or to accumulate (into
+        = (acc, sums)): picks are its source rows in order.  The compact record is trained where it lies -- picks (int32) is the row
+        index of the indexed call; a rows batch is gathered into the buffers of `size` positions and goes through the contiguous call."""
+        if compact:
+            b = self._sgd_batch(self._sgd_source(src, picks), src, picks, None, INPUTS, {})
+        else:
+            view = {k: t[:int(picks.numel())] for k, t in self._gather_buffers(src, size).items()}
+            for k in src:
+                torch.index_select(src[k], 0, picks, out=view[k])
+            obs = view.pop('obs')
+            b = self._batch(obs, self._rows(obs), num_active, view)
+        return self._submit(b, stats, into)
+
     def accumulate_minibatch(self, src, compact, picks, micro, acc, sums, num_active=None):
-        """One minibatch of a flattened sample batch (src as _flatten() leaves it) into acc / sums, `micro` positions at a time: picks
-        are the minibatch's source rows in order (int32 with the compact record, whose micro-batches are slices of it handed to
-        accumulate_indexed; otherwise any integer type, each micro-batch gathered into the buffers and handed to accumulate)."""
-        n = int(picks.numel())
-        for s in range(0, n, micro):
-            part = picks[s:s + micro]
-            if compact:
-                self.accumulate_indexed(src, part, acc, sums)
-            else:
-                view = {k: t[:int(part.numel())] for k, t in self._gather_buffers(src, micro).items()}
-                for k in src:
-                    torch.index_select(src[k], 0, part, out=view[k])
-                self.accumulate(view['obs'], view['actions'], view['old_logp'], view['old_logits'], view['advantages'], view['value_targets'], view['old_vf'],
-                                acc, sums, num_active=num_active)
+        """One minibatch of a flattened sample batch into acc / sums, `micro` positions at a time (submit_picks)."""
+        for s in range(0, int(picks.numel()), micro):
+            self.submit_picks(src, compact, picks[s:s + micro], micro, num_active, into=(acc, sums))
+
+    def accumulated_step(self, src, compact, picks, micro, acc, sums, grad_clip, stats, num_active=None, lap=lambda name: None):
+        """One minibatch of the accumulated path as phases: zeroed accumulators, accumulate per micro-batch, then (acc, SUM) and (sums,
+        SUM) are yielded -- where the ranks of a data-parallel learner add theirs together; one learner just goes on -- then finish
+        (1 / N, grad_clip; the statistics into `stats`) and apply.  lap(name) is called at the end of each of the four phases."""
+        acc.zero_()
+        sums.zero_()
+        self.accumulate_minibatch(src, compact, picks, micro, acc, sums, num_active)
+        lap('accumulate')
+        yield acc, SUM
+        yield sums, SUM
+        lap('reduce')
+        self.finish(acc, sums, grad_clip, stats=stats)
+        lap('finish')
+        self.apply()
+        lap('apply')
 
     def update(self, batch, num_sgd_iter=30, minibatch_rows=None, seed=0, num_active=None, rows=None, check_rows=True, micro_rows=None,
                grad_clip=None):
@@ -662,80 +776,19 @@ class PPOLearner:
         global-norm clip of RLlib's grad_clip) and apply.  micro_rows is a multiple of the chunk unit (2 048 rows) and at most
         max_rows; the workspaces and gather buffers are then sized by the micro-batch, and a minibatch may be larger than max_rows.
         Up to 262 144 rows per minibatch the new weights are those of the whole-minibatch path, bit for bit (without grad_clip)."""
-        a = self.actor
-        multi = a.kind == _lib.MULTI
-        src, N, compact = self._flatten(batch)
-        kernel_active, keep = None, None
-        if rows is not None:
-            if num_active is not None:
-                raise ValueError("rows and num_active exclude each other: leave the rows of unlisted slots out of rows")
-            if not isinstance(rows, torch.Tensor) or rows.dim() != 1 or rows.numel() == 0 or rows.device != self.device or \
-                    rows.dtype not in (torch.int32, torch.int64):
-                raise ValueError(f"rows must be a non-empty 1-d int32 / int64 tensor on {self.device}")
-            keep = rows.to(torch.int64)
-            if check_rows:
-                srt = keep.sort().values
-                lo, hi, dup = torch.stack((srt[0], srt[-1], (srt[1:] == srt[:-1]).any().to(torch.int64))).tolist()      # one synchronisation
-                if lo < 0 or hi >= N:
-                    raise ValueError(f"rows has entries outside the batch's {N} source rows")
-                if dup:
-                    raise ValueError("rows has repeated entries: they must be distinct source rows")
-            N = int(keep.numel())
-            if not compact:
-                src = {k: t.index_select(0, keep) for k, t in src.items()}
-        elif num_active is not None and int(num_active) < a.U:
-            if multi:
-                keep = torch.nonzero(torch.arange(N, device=self.device) % a.U < int(num_active)).reshape(-1)
-                N = int(keep.numel())
-                if not compact:
-                    src = {k: t.index_select(0, keep) for k, t in src.items()}
-            else:
-                kernel_active = int(num_active)
-        adv = src['advantages'] if keep is None or not compact else src['advantages'].index_select(0, keep)
-        adv = (adv - adv.mean()) / adv.std(unbiased=False).clamp_min(1e-4)
-        # (compact: the standardised advantages back in source order, where the index finds them)
-        src['advantages'] = adv if keep is None or not compact else torch.zeros_like(src['advantages']).index_copy_(0, keep, adv)
-        mb = N if minibatch_rows is None else min(int(minibatch_rows), N)
-        accumulated = micro_rows is not None or grad_clip is not None
-        if micro_rows is not None:
-            micro = check_micro_rows(micro_rows, self.max_rows)
-        elif mb > self.max_rows:
-            raise ValueError(f"minibatches of {mb} rows > max_rows {self.max_rows} of the learner")
-        else:
-            micro = mb
-        if grad_clip is not None and not float(grad_clip) >= 0.0:
-            raise ValueError(f"grad_clip {grad_clip!r} must be >= 0")
+        src, N, compact = flatten_batch(self.actor, batch)
+        src, N, keep, kernel_active = select_rows(self.actor, src, N, compact, rows, num_active, check_rows)
+        mb, micro, accumulated = minibatch_plan(N, minibatch_rows, self.max_rows, micro_rows, grad_clip)
         if accumulated:
-            micro = min(micro, mb)                                             # (the gather buffers' size)
             acc, sums = self.new_accumulators()
-        elif not compact and mb not in self._mb:
-            self._mb = {mb: {k: torch.empty((mb,) + tuple(t.shape[1:]), dtype=t.dtype, device=self.device) for k, t in src.items()}}
-        starts = list(range(0, N, mb))
-        stats = torch.zeros((len(starts), _lib.PPO_NUM_STATS), dtype=torch.float32, device=self.device)
-        gen = torch.Generator(device=self.device)
-        gen.manual_seed(int(seed))
-        for _ in range(int(num_sgd_iter)):
-            perm = torch.randperm(N, generator=gen, device=self.device)
-            if compact:
-                index = (perm if keep is None else keep.index_select(0, perm)).to(torch.int32)
+        starts, stats = minibatch_stats(N, mb, self.device)
+        for perm in sgd_epochs(N, num_sgd_iter, seed, self.device):
+            picks = perm if not compact else (perm if keep is None else keep.index_select(0, perm)).to(torch.int32)
             for i, s in enumerate(starts):
                 if accumulated:
-                    acc.zero_()
-                    sums.zero_()
-                    self.accumulate_minibatch(src, compact, index[s:s + mb] if compact else perm[s:s + mb], micro, acc, sums, kernel_active)
-                    self.finish(acc, sums, grad_clip, stats=stats[i])
-                elif compact:
-                    self.grads_indexed(src, index[s:s + mb], stats=stats[i])
+                    for _ in self.accumulated_step(src, compact, picks[s:s + mb], micro, acc, sums, grad_clip, stats[i], kernel_active):
+                        pass                                               # (one learner: nothing to add together)
                 else:
-                    idx = perm[s:s + mb]
-                    view = {k: t[:int(idx.numel())] for k, t in self._mb[mb].items()}
-                    for k in src:
-                        torch.index_select(src[k], 0, idx, out=view[k])
-                    self.grads(view['obs'], view['actions'], view['old_logp'], view['old_logits'], view['advantages'], view['value_targets'], view['old_vf'],
-                               num_active=kernel_active, stats=stats[i])
-                self.apply()
-        mean = stats.mean(0).cpu().numpy()
-        out = {n: float(mean[i]) for i, n in enumerate(STATS)}
-        self.hyper['kl_coeff'] = adapt_kl_coeff(self.hyper['kl_coeff'], out['kl'], self.kl_target)
-        out['kl_coeff'] = self.hyper['kl_coeff']
-        return out
+                    self.submit_picks(src, compact, picks[s:s + mb], mb, kernel_active, stats=stats[i])
+                    self.apply()
+        return close_out([self], stats.mean(0)[None])[0]

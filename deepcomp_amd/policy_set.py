@@ -24,7 +24,7 @@ import torch
 
 from . import _lib
 from .actor import FcnetActor, _ActorLaunch
-from .learner import PPOLearner, STATS, adapt_kl_coeff
+from .learner import INPUT, INPUTS, PPOLearner, close_out, field_pointers, fill, flatten_batch, minibatch_plan, sgd_epochs, standardize
 
 
 def default_slot_policy(num_ue, num_policies):
@@ -188,80 +188,46 @@ class PerUELearner:
         return self._group
 
     def _update_grouped(self, batch, rows, num_sgd_iter, minibatch_rows, seed):
-        a, L, dev = self.actor, self.actor._L, self.device
-        first, P = a.members[0], len(self.learners)
-        if 'action_dist_inputs' not in batch:
-            raise ValueError("the batch has no action_dist_inputs: collect(..., dist_inputs=True)")
-        compact = 'obs' not in batch
-        f32 = torch.float32
-        src = {'actions': (batch['actions'].reshape(-1), torch.uint8, 1), 'old_logp': (batch['action_logp'].reshape(-1), f32, 1),
-               'old_logits': (batch['action_dist_inputs'].reshape(-1, a.num_logits), f32, a.num_logits),
-               'value_targets': (batch['value_targets'].reshape(-1), f32, 1), 'old_vf': (batch['vf_preds'].reshape(-1), f32, 1)}
-        N = src['actions'][0].shape[0]
-        adv_in = batch['advantages'].reshape(-1)
-        if compact:
-            obs = batch['obs_compact'].reshape(-1, batch['obs_compact'].shape[-1])       # [T, E, words], contiguous: env t E + e
-            if first._batch(obs, True)[1] != N:
-                raise ValueError("the batch's tensors disagree about the number of rows")
-        else:
-            obs = batch['obs'].reshape(-1, a.num_in)
-            first._check(obs, f32, N * a.num_in, 'obs')
-        for name, (t, dtype, per) in src.items():
-            first._check(t, dtype, N * per, name)
-        first._check(adv_in, f32, N, 'advantages')
-        if N > 2 ** 31 - 1:
-            raise ValueError(f"{N} source rows > 2^31 - 1")
-
+        L, dev = self.actor._L, self.device
+        first, P = self.learners[0], len(self.learners)
+        src, N, compact = flatten_batch(first.actor, batch)
+        obs, fmt, _ = first._source_obs(src)
         live = [p for p in range(P) if rows[p].numel()]
-        n_of = [int(rows[p].numel()) for p in range(P)]
-        mb_of = [0 if not n_of[p] else n_of[p] if minibatch_rows is None else min(int(minibatch_rows), n_of[p]) for p in range(P)]
+        # every policy's advantages standardised over its own rows (PPOLearner.update's rule), back in source order in ONE tensor: the
+        # row sets are disjoint
+        adv = torch.zeros_like(src['advantages'])
+        n_of, mb_of = [int(rows[p].numel()) for p in range(P)], [0] * P
         for p in live:
-            if mb_of[p] > self.learners[p].max_rows:
-                raise ValueError(f"minibatches of {mb_of[p]} rows > max_rows {self.learners[p].max_rows} of the learner")
-        # every policy's advantages standardised over its own rows (PPOLearner.update's operations on the gathered tensor), back in
-        # source order in ONE tensor: the row sets are disjoint
-        adv = torch.zeros_like(adv_in)
-        for p in live:
-            ap = adv_in.index_select(0, rows[p])
-            adv.index_copy_(0, rows[p], (ap - ap.mean()) / ap.std(unbiased=False).clamp_min(1e-4))
+            mb_of[p] = minibatch_plan(n_of[p], minibatch_rows, self.learners[p].max_rows)[0]
+            adv.index_copy_(0, rows[p], standardize(src['advantages'].index_select(0, rows[p])))
+        ptr = field_pointers(first.actor, dict({n: src[n] for n in INPUTS}, advantages=adv), {INPUT: N})
         # round k: positions [k step, k step + mb_p) of every policy that has that many.  A policy's minibatch is `step` rows unless
         # it has fewer rows than that -- then it is its one minibatch, in round 0
         step = max(mb_of)
-        rounds = max((n_of[p] + mb_of[p] - 1) // mb_of[p] for p in live)
+        taken = {p: (n_of[p] + mb_of[p] - 1) // mb_of[p] for p in live}
+        rounds = max(taken.values())
         stride = max(n_of)
         index = torch.zeros((P, stride), dtype=torch.int32, device=dev)
-        stats = torch.zeros((rounds, P, _lib.PPO_NUM_STATS), dtype=f32, device=dev)
-        gens = {}
-        for p in live:
-            gens[p] = torch.Generator(device=dev)
-            gens[p].manual_seed(seed + p)
+        stats = torch.zeros((rounds, P, _lib.PPO_NUM_STATS), dtype=torch.float32, device=dev)
+        epochs = {p: sgd_epochs(n_of[p], num_sgd_iter, seed + p, dev) for p in live}
         hyper = (_lib.DcompPpoHyper * P)(*[ln._hyper_struct() for ln in self.learners])
         lr = (ctypes.c_float * P)(*[ln.lr for ln in self.learners])
         round_rows = [(ctypes.c_int64 * P)(*[max(0, min(mb_of[p], n_of[p] - k * step)) if mb_of[p] else 0 for p in range(P)]) for k in range(rounds)]
         round_active = [(ctypes.c_int32 * P)(*[1 if r else 0 for r in rr]) for rr in round_rows]
         g = self._group_handle()
-        b = _lib.DcompGroupBatch(ctypes.sizeof(_lib.DcompGroupBatch), _lib.ACTOR_COMPACT if compact else _lib.ACTOR_ROWS, N, obs.data_ptr(),
-                                 src['actions'][0].data_ptr(), src['old_logp'][0].data_ptr(), src['old_logits'][0].data_ptr(), adv.data_ptr(),
-                                 src['value_targets'][0].data_ptr(), src['old_vf'][0].data_ptr(), 0, stride, None)
+        b = fill(_lib.DcompGroupBatch, obs_format=fmt, source_rows=N, obs=obs.data_ptr(), index_stride=stride, **ptr)
         with torch.cuda.device(dev):
-            stream = first._stream()
+            stream = first.actor._stream()
             for _ in range(num_sgd_iter):
                 for p in live:
-                    perm = torch.randperm(n_of[p], generator=gens[p], device=dev)
-                    index[p, :n_of[p]] = rows[p].index_select(0, perm)
+                    index[p, :n_of[p]] = rows[p].index_select(0, next(epochs[p]))
                 for k in range(rounds):
                     b.index, b.rows = index.data_ptr() + 4 * k * step, round_rows[k]
                     _lib.check(L.dcomp_learner_group_grads(g, ctypes.byref(b), hyper, ctypes.c_void_p(stats[k].data_ptr()), stream))
                     _lib.check(L.dcomp_learner_group_apply(g, lr, round_active[k], stream))
         # a policy's mean over the rounds it took part in: PPOLearner.update's own reduction of its own [minibatches, 5] tensor
-        taken = {p: (n_of[p] + mb_of[p] - 1) // mb_of[p] for p in live}
-        means = torch.stack([stats[:taken[p], p].contiguous().mean(0) for p in live]).cpu().numpy()      # the one synchronisation
         out = [None] * P
-        for i, p in enumerate(live):
-            ln = self.learners[p]
-            st = {n: float(means[i][j]) for j, n in enumerate(STATS)}
-            ln.hyper['kl_coeff'] = adapt_kl_coeff(ln.hyper['kl_coeff'], st['kl'], ln.kl_target)
-            st['kl_coeff'] = ln.hyper['kl_coeff']
+        for p, st in zip(live, close_out([self.learners[p] for p in live], torch.stack([stats[:taken[p], p].contiguous().mean(0) for p in live]))):
             out[p] = st
         return out
 

@@ -138,3 +138,27 @@ def test_the_pinned_surface_still_refuses_the_compact_record(lib):
     assert lib.dcomp_learner_grads(fake, ctypes.byref(b), ctypes.byref(_hyper()), fake, None) == EUNSUPPORTED and b'compact' in lib.dcomp_last_error()
     b = _lib.DcompPpoBatch(ctypes.sizeof(_lib.DcompPpoBatch), 1, 8, 1, 0, *([4096] * 2 + [None] * 5 + [4096] + [None] * 6))
     assert lib.dcomp_learner_evaluate(fake, ctypes.byref(b), None) == EUNSUPPORTED
+
+
+def test_batch_structs_are_filled_by_member_name_from_one_field_table():
+    """learner.FIELDS names members the structs have (ctypes would take a misspelt keyword as a new attribute, so fill() refuses
+    one), and the per-row members follow `obs` in every struct, as the headers declare them."""
+    import ctypes
+    import pytest
+    from deepcomp_amd import _lib
+    from deepcomp_amd import learner as lm
+    members = lambda s: [n for n, _ in s._fields_]                              # noqa: E731
+    assert set(lm.FIELDS) <= set(members(_lib.DcompPpoBatch)) and set(lm.FIELDS) <= set(members(_lib.DcompSgdBatch))
+    assert set(lm.INPUTS) <= set(members(_lib.DcompGroupBatch))
+    assert not (set(lm.FIELDS) - set(lm.INPUTS)) & set(members(_lib.DcompGroupBatch))      # the grouped call has no outputs, no upstream
+    for struct in (_lib.DcompPpoBatch, _lib.DcompSgdBatch):                     # every pointer member but obs / index is in the table
+        assert {n for n, t in struct._fields_ if t is ctypes.c_void_p} - {'obs', 'index'} == set(lm.FIELDS)
+    assert lm.INPUTS == ('actions', 'old_logp', 'old_logits', 'advantages', 'value_targets', 'old_vf') and set(lm.BATCH_KEYS) == set(lm.INPUTS)
+    b = lm.fill(_lib.DcompSgdBatch, obs_format=_lib.ACTOR_COMPACT, rows=3, source_rows=7, index=None, num_active=2, obs=64, ratio=128)
+    assert (b.struct_size, b.obs_format, b.rows, b.source_rows, b.index, b.num_active, b.reserved, b.obs, b.ratio, b.logp) == \
+        (ctypes.sizeof(_lib.DcompSgdBatch), _lib.ACTOR_COMPACT, 3, 7, None, 2, 0, 64, 128, None)
+    g = lm.fill(_lib.DcompGroupBatch, obs_format=_lib.ACTOR_ROWS, source_rows=9, obs=64, index_stride=5, old_vf=128)
+    assert (g.struct_size, g.source_rows, g.index_stride, g.old_vf, g.index) == (ctypes.sizeof(_lib.DcompGroupBatch), 9, 5, 128, None)
+    for struct, bad in ((_lib.DcompPpoBatch, 'source_rows'), (_lib.DcompSgdBatch, 'old_logit'), (_lib.DcompGroupBatch, 'logp')):
+        with pytest.raises(TypeError, match=bad):
+            lm.fill(struct, **{bad: 1})

@@ -15,7 +15,9 @@ central, 100 steps per launch, every step's outputs), one GPU's share of config 
 (32 768 x 32 x 10), 65 536 x 10 x 5 central, 65 536 x 32 x 10 central, the closed policy loop at config 2; learner_c3 / learner_c2:
 PPOLearner grads + apply on one minibatch of 65 536 x 32 multi rows / 4 096 central rows (libraries from round 9 on); actor_c3 / actor_c2:
 dcomp_actor_actions_v (actions, logp and the value of a trunk of its own, sampled) at 65 536 x 32 x 10 multi / 4 096 x 10 x 5 central
-(libraries from round 8 on)."""
+(libraries from round 8 on); update_c2 / update_c3s / update_per_ue: the host side of the learners' update() at launch-bound shapes
+(profiles/r18_sgd_phase.txt) -- wall-clock ms per call, not kernel time.  A tag `py:TREE` times the working tree's library under the
+Python package of another checkout (TREE/deepcomp_amd, e.g. `git archive <ref> deepcomp_amd | tar -x -C TREE`): a host-side A/B."""
 import argparse
 import json
 import os
@@ -69,6 +71,7 @@ def build(a):
 
 WORKLOADS = ['big64', 'big40c', 'c3', 'c2roll', 'c5', 'c5mid', 'c5big', 'c4share', 'c4big', 'central10x5', 'central10x5roll', 'central10x5f', 'central32x10', 'c2policy', 'c3rf', 'c3roll',
              'learner_c3', 'learner_c2', 'actor_c3', 'actor_c2']
+UPDATES = ['update_c2', 'update_c3s', 'update_per_ue']        # run on request only (--only): wall clock, and a collect() batch each
 
 
 def measure_actor(torch, dev, kind, E, U, B, n):
@@ -130,8 +133,48 @@ def measure_learner(torch, dev, kind, E, U, B, n):
     return e0.elapsed_time(e1) / n
 
 
+def measure_update(torch, dev, w, calls=12):
+    """One learner update() per call, wall clock with a device synchronise on both sides: the median of `calls` calls after two
+    warm-up calls, in ms.  num_sgd_iter 4, four minibatches; a collect() batch of the shape.  update_c2: PPOLearner, 4 096 x 10 x 5
+    central, T = 2, hidden 256, rows; update_c3s: PPOLearner, 1 024 x 32 x 10 multi, T = 2, hidden 256, the compact record;
+    update_per_ue: PerUELearner(grouped=True), 256 x 10 x 5, T = 4, hidden 64, ten policies."""
+    import statistics
+    import time
+    from deepcomp_amd import scenarios
+    from deepcomp_amd.actor import FcnetActor
+    from deepcomp_amd.entities import build_from_scenario
+    from deepcomp_amd.env import BatchedMobileEnv
+    from deepcomp_amd.learner import PPOLearner
+    from deepcomp_amd.policy_set import PerUEActor, PerUELearner
+    from deepcomp_amd.sampler import collect
+    kind, E, U, B, T, H, compact = {'update_c2': ('central', 4096, 10, 5, 2, 256, False), 'update_c3s': ('multi', 1024, 32, 10, 2, 256, True),
+                                    'update_per_ue': ('multi', 256, 10, 5, 4, 64, False)}[w]
+    m, bs, ues = build_from_scenario(scenarios.grid_map(B, 'mixed').with_ues(num_slow=U))
+    env = BatchedMobileEnv(m, bs, ues, kind, num_envs=E, seed=42, episode_length=100, rng='philox', rand_episodes=True, device=dev)
+    if w == 'update_per_ue':
+        actor = PerUEActor.random(U, B, hidden=H, seed=3, bias_std=0.1, device=dev)
+        mb = E * T // 4                                    # per policy: E x T rows
+        learner, kw = PerUELearner(actor, lr=1e-5, max_rows=mb), {'grouped': True}
+    else:
+        actor = FcnetActor(kind, U, B, FcnetActor.random_weights(kind, U, B, H, seed=1, bias_std=0.1), device=dev,
+                           value_weights=FcnetActor.random_value_weights(kind, U, B, H, seed=1, bias_std=0.1))
+        mb = E * T * (U if kind == 'multi' else 1) // 4
+        learner, kw = PPOLearner(actor, lr=1e-5, max_rows=mb), {}
+    batch = collect(env, actor, T, gamma=0.99, lam=0.95, compact=compact, dist_inputs=True)
+    ms = []
+    for i in range(2 + calls):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        learner.update(batch, num_sgd_iter=4, minibatch_rows=mb, seed=1, **kw)
+        torch.cuda.synchronize()
+        ms.append((time.perf_counter() - t0) * 1e3)
+    return statistics.median(ms[2:])
+
+
 def measure(a):
     sys.path.insert(0, REPO)
+    if os.environ.get('DCOMP_AB_PYTREE'):                  # (a `py:TREE` tag: that checkout's deepcomp_amd, this tree's bench and library)
+        sys.path.insert(0, os.environ['DCOMP_AB_PYTREE'])
     import torch
     import bench
     from deepcomp_amd import scenarios
@@ -172,6 +215,8 @@ def measure(a):
             out[w] = measure_actor(torch, dev, 'multi', 65536, 32, 10, 50)
         elif w == 'actor_c2':
             out[w] = measure_actor(torch, dev, 'central', 4096, 10, 5, 500)
+        elif w in UPDATES:
+            out[w] = measure_update(torch, dev, w)
         elif w in ('central10x5f', 'c3roll'):      # the fused rollout kernel forced onto a big batch, ONE step per launch
             os.environ['DCOMP_FUSE_MAX_WAVES'] = '100000000'
             E, U, B, kind = (65536, 10, 5, 'central') if w == 'central10x5f' else (65536, 32, 10, 'multi')
@@ -220,20 +265,20 @@ def run(a):
     res = {t: {} for t in a.tags}
     for r in range(a.rounds):
         for t in a.tags:
-            lib = os.path.join(VAR, f'libdcomp_hip_{t}.so') if t != 'tree' else os.path.join(CSRC, 'libdcomp_hip.so')
-            env = dict(os.environ, DCOMP_LIB=lib, DCOMP_AB_NO_BUILD='1')
+            lib = os.path.join(VAR, f'libdcomp_hip_{t}.so') if t != 'tree' and not t.startswith('py:') else os.path.join(CSRC, 'libdcomp_hip.so')
+            env = dict(os.environ, DCOMP_LIB=lib, DCOMP_AB_NO_BUILD='1', DCOMP_AB_PYTREE=os.path.abspath(t[3:]) if t.startswith('py:') else '')
             p = subprocess.run([sys.executable, os.path.abspath(__file__), 'measure'] + (['--only', a.only] if a.only else []), env=env,
                                stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
             line = [l for l in p.stdout.splitlines() if l.startswith('AB_RESULT ')]
             if not line:
                 print(t, 'FAILED', p.stdout[-1500:], flush=True)
-                continue
+                sys.exit(1)                                # (a child that died may have left the device in a bad state: start no more)
             for k, v in json.loads(line[-1][10:]).items():
                 res[t].setdefault(k, []).append(v)
             print(f'round {r} {t}: ' + '  '.join(f'{k} {v * 1e3:.2f}us' for k, v in json.loads(line[-1][10:]).items()), flush=True)
     ref = a.tags[0]
     print(f'\n{"workload":14s}' + ''.join(f'{t:>22s}' for t in a.tags))
-    for w in WORKLOADS:
+    for w in WORKLOADS + UPDATES:
         if w not in res[ref]:
             continue
         base = min(res[ref][w])
