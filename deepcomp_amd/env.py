@@ -13,12 +13,12 @@ observations living in device tensors (``pos[E*U,2] f64``, ``mv[E*U] i64``, ``co
   device tensors (zero-copy for a learner on the same GPU).
 """
 import ctypes
-import os
 
 import numpy as np
 import torch
 
 from . import _lib, rng as _rng, spaces
+from .tape import draw_tape, uid_fields
 
 # The reference's classes ARE gym / RLlib classes (single_ue/base.py:20 `class MobileEnv(gym.Env)`, multi_ue/multi_agent.py:6
 # `class MultiAgentMobileEnv(RelNormEnv, MultiAgentEnv)`), and its callers dispatch on that: `MultiAgentEnv in
@@ -58,9 +58,30 @@ SNR_THRESHOLD = 2e-8          # station.py:10
 MIN_UTILITY, MAX_UTILITY = -20, 20   # constants.py:40-41
 
 
+METRICS = ('sum_utility', 'ue_dr', 'ue_utility', 'reward_before')          # the optional outputs of a step, in dcomp_out's order
+FRAGMENT_KEYS = ('obs', 'obs_compact', 'reward') + METRICS
+
+
 def _fragment_obs(out):
     """The observation buffer of a rollout's `out` dict: the rows, or the compact record where the caller asked for that."""
     return out['obs'] if out.get('obs') is not None else out.get('obs_compact')
+
+
+def _fragment(out, t0, n):
+    """Steps t0 .. t0 + n of a rollout's `out` dict."""
+    return None if out is None else {k: out[k][t0:t0 + n] for k in FRAGMENT_KEYS if out.get(k) is not None}
+
+
+# The words of the device state, decoded in ONE place each (include/dcomp_types.h; the uid word: deepcomp_amd.tape.uid_fields).
+def mv_cursor(mv):
+    """Movement words (torch or numpy) -> the draw cursor: movement triples the UE has consumed in this episode."""
+    return (mv >> 48) & 0xFFFF
+
+
+def conn_mask(conn, conn_hi=None):
+    """Host copies of the connection words -> one mask per UE: uint32, or with the word of stations 32-63 uint64 (conn | conn_hi << 32)."""
+    conn = conn.astype(np.uint32)
+    return conn if conn_hi is None else conn.astype(np.uint64) | (conn_hi.astype(np.uint32).astype(np.uint64) << np.uint64(32))
 
 
 def _coord(v):
@@ -153,7 +174,6 @@ class BatchedMobileEnv:
         self.rng_mode = _lib.RNG_PHILOX if rng == 'philox' else _lib.RNG_TAPE
         if rng not in ('philox', 'reference'):
             raise ValueError("rng must be 'philox' (counter-based, in-kernel) or 'reference' (stdlib-random draw tape)")
-        self._tape_depth_arg = tape_depth
         self.seed_value = seed if seed is not None else int(np.random.SeedSequence().generate_state(1)[0])
         self.env_id_base = int(env_id_base)
         # env e of a batch gets base seed `seed + 20000*e` (UE i adds 100*(i+1), base.py:138-143)
@@ -161,8 +181,7 @@ class BatchedMobileEnv:
         self._seed_stride = max(20000, 100 * (len(ue_list) + 1))
         self._reseeded = False
         self._device_seed = self.seed_value    # the Philox key the DEVICE draws from (a seed() call stages a new one until reset())
-        self.env_seeds = (np.asarray(env_seeds, dtype=np.int64) if env_seeds is not None
-                          else self.seed_value + self._seed_stride * (self.env_id_base + np.arange(self.E, dtype=np.int64)))
+        self.env_seeds = np.asarray(env_seeds, dtype=np.int64) if env_seeds is not None else self._env_seeds_for(self.seed_value)
 
         U, B = self.U, self.B          # U: slots per env
         ent = parse_entities(map, bs_list, ue_list)
@@ -176,14 +195,14 @@ class BatchedMobileEnv:
         # steps and draws in the step it moves on (movement.py:158-181) -- every third step with the default pause of 2, EVERY
         # step with pause_duration 0 and a velocity that covers the distance.  UEs that arrive during an episode pause 2 steps.
         self._redraw_period = min([int(x) for x in self._pause] + ([2] if self.dynamic else [])) + 1
-        self.tape_depth = int(self._tape_depth_arg or (self.episode_length // self._redraw_period + 4))
+        self._tape_depth = int(tape_depth or (self.episode_length // self._redraw_period + 4))
 
         c = _lib.DcompCfg()
         c.num_envs, c.num_ue, c.num_bs = self.E, self.U0, B
         c.max_ues = self.U if self.dynamic else 0
         c.map_w, c.map_h = self.map_w, self.map_h
         c.env_kind, c.reward_agg = self.kind, _lib.REWARD[reward]
-        c.rng_mode, c.tape_depth = self.rng_mode, self.tape_depth
+        c.rng_mode, c.tape_depth = self.rng_mode, self._tape_depth
         c.device = self.device.index
         c.seed = int(self.seed_value) & 0xFFFFFFFFFFFFFFFF
         c.env_id_base = self.env_id_base
@@ -237,22 +256,32 @@ class BatchedMobileEnv:
                                    self.uid.data_ptr() if self.dynamic else None,
                                    self.orig_consumed.data_ptr() if self.dynamic else None,
                                    self.conn_hi.data_ptr() if self.conn_hi is not None else None)
-        self._dyn_streams = None
         self._ev_keep = None
         self._out = self._make_out(self.obs, self.reward)
         self._st_ref, self._out_ref = ctypes.byref(self._st), ctypes.byref(self._out)   # per-step ctypes work done once
+        # rng='reference': the owner of the draw tape on the host (deepcomp_amd.tape), and the tensors the device reads it from
+        self._tape = draw_tape(c, self.env_seeds, self._tape_depth, self._redraw_period, (self.map_w, self.map_h, self.vel_specs, self.init_xy),
+                               self._border, self.rand_episodes, self.max_id if self.dynamic else None) if self.rng_mode == _lib.RNG_TAPE else None
         self._tape_dev = None
-        self._streams = None
-        self._fixed_tape = None
-        self._live = None                    # seed(immediate=True) in a running fixed episode: (new env seeds, cursors at that time)
 
     # ------------------------------------------------------------------ helpers
-    def _make_out(self, obs, reward, packed=None):
-        m = self.log_metrics
-        return _lib.DcompOut(obs.data_ptr() if obs is not None else None, reward.data_ptr(), self.sum_utility.data_ptr() if m else None,
-                             self.ue_dr.data_ptr() if m else None, self.ue_utility.data_ptr() if m else None,
-                             self.reward_before.data_ptr() if self.want_reward_before else None,
+    def _make_out(self, obs, reward, packed=None, metrics=None):
+        """metrics: tensors (or None) in METRICS order, the per-step buffers of a rollout fragment; default: the env's own, as configured."""
+        if metrics is None:
+            metrics = (self.sum_utility, self.ue_dr, self.ue_utility) if self.log_metrics else (None, None, None)
+            metrics += (self.reward_before if self.want_reward_before else None,)
+        return _lib.DcompOut(obs.data_ptr() if obs is not None else None, reward.data_ptr(),
+                             *[t.data_ptr() if t is not None else None for t in metrics],
                              packed.data_ptr() if packed is not None else None)
+
+    def _env_seeds_for(self, seed):
+        """env e of the batch gets base seed `seed + stride * (env_id_base + e)`."""
+        return seed + self._seed_stride * (self.env_id_base + np.arange(self.E, dtype=np.int64))
+
+    @property
+    def tape_depth(self):
+        """Movement triples per UE on the draw tape: rng='reference' grows it with the episode (the ONE depth, the tape owner's)."""
+        return self._tape.depth if self._tape is not None else self._tape_depth
 
     def _stream(self):
         try:                                   # raw handle of torch's current stream without building a Stream object (~4 us)
@@ -294,134 +323,52 @@ class BatchedMobileEnv:
         seed = int(seed)
         if immediate and self.rng_mode == _lib.RNG_TAPE:
             return self._seed_live(seed)
-        self.seed_value = seed
-        self.env_seeds = self.seed_value + self._seed_stride * (self.env_id_base + np.arange(self.E, dtype=np.int64))
-        self._streams, self._fixed_tape, self._dyn_streams = None, None, None
-        self._live = None
+        self.seed_value, self.env_seeds = seed, self._env_seeds_for(seed)
+        if self._tape is not None:
+            self._tape.stage_seed(self.env_seeds)
         self._reseeded = True                         # reset() starts the new key's episode 0
 
     def _seed_live(self, seed):
         """seed(immediate=True), rng='reference': splice the new streams into the tape of the running episode."""
-        seeds = seed + self._seed_stride * (self.env_id_base + np.arange(self.E, dtype=np.int64))
-        live = self._tape_dev is not None
+        seeds = self._env_seeds_for(seed)
+        spliced = self._tape.reseed_live(seeds, **(self._tape_readback() if self._tape_dev is not None else {}))
+        if self._tape.seeds is seeds:                 # streams that are carried into the next episodes: the configured seed from here on
+            self.seed_value, self.env_seeds = seed, seeds         # (reset() of a fixed-episode env goes back to env_seeds, base.py:171-173)
+        if spliced is not None:
+            self._install_tape(*spliced)
+
+    def _tape_readback(self):
+        """What the tape's owner must know of the device state: the draw cursor per slot; where the UE list changes also the uid words,
+        the triples the initial UEs that left had consumed, and the length of the list."""
+        rb = {'cursor': mv_cursor(self.mv).cpu().numpy().reshape(self.E, self.U)}
         if self.dynamic:
-            if self._dyn_streams is None or not live:        # no episode yet
-                if self.rand_episodes:                       # ... the first reset() starts the new streams; a fixed-episode env re-seeds
-                    self.seed_value, self.env_seeds = seed, seeds        #     with the configured seed anyway (base.py:171-173)
-                return
-            E, U, n = self.E, self.U, self.num_ue
-            uid = self.uid.cpu().numpy().astype(np.uint16).reshape(E, U)
-            cur = ((self.mv >> 48) & 0xFFFF).cpu().numpy().reshape(E, U)
-            lists = [[(int(w & 0x7FFF), bool(w & 0x8000)) for w in uid[e, :n]] for e in range(E)]
-            pos0, trip = self._dyn_streams.reseed_live(seeds, lists, cur)
-            torch.cuda.current_stream(self.device).synchronize()       # steps in flight still read the old tape
-            old = self._tape_dev
-            tape = self._upload_tape(pos0, trip)
-            _lib.check(self._L.dcomp_set_tape(self._h, ctypes.byref(tape), int(trip.shape[1])))
-            del old
-            return
-        cursor = ((self.mv >> 48) & 0xFFFF).cpu().numpy().astype(np.int64) if live else None   # triples consumed so far, per (env, UE)
-        if self.rand_episodes:
-            self.seed_value, self.env_seeds = seed, seeds
-            if self._streams is None:                 # no reset() yet: the first one starts the new streams
-                return
-            spliced = self._streams.reseed_live(seeds, cursor)
-            if spliced is None:
-                return
-        else:                                         # reset() goes back to self.env_seeds (base.py:171-173): only the running episode changes
-            if not live:
-                return
-            self._live = (seeds, cursor)
-            spliced = self._live_fixed_tape(max(self._tape_depth_now, self.tape_depth))
-        pos0, trip = spliced
+            rb.update(uid=self.uid.cpu().numpy().reshape(self.E, self.U), num_ue=self.num_ue,
+                      orig_consumed=self.orig_consumed.cpu().numpy().reshape(self.E, self.U0))
+        return rb
+
+    def _draw_tape(self):
+        """(pos0, triples) of the next episode."""
+        return self._tape.new_episode(**(self._tape_readback() if self._tape.started else {}))
+
+    def _upload_tape(self, pos0, trip):
+        self._tape_dev = (torch.from_numpy(pos0).to(self.device), torch.from_numpy(trip.view(np.int16)).to(self.device))
+        return _lib.DcompTape(self._tape_dev[0].data_ptr(), self._tape_dev[1].data_ptr(), self.U0 + self.max_id if self.dynamic else 0)
+
+    def _install_tape(self, pos0, trip):
+        """Another tape for the episode that is running (grown, or spliced by a live re-seed)."""
         torch.cuda.current_stream(self.device).synchronize()       # steps in flight still read the old tape
         old = self._tape_dev
         tape = self._upload_tape(pos0, trip)
         _lib.check(self._L.dcomp_set_tape(self._h, ctypes.byref(tape), int(trip.shape[1])))
         del old
 
-    def _live_fixed_tape(self, depth):
-        """rand_episodes=False after a live re-seed: row (e, i) = the configured seed's triples up to the cursor at the time of
-        seed(), the new seed's stream from there on (both stateless: the C++ MT19937 draws any depth again)."""
-        pos0, trip = _rng.mt_tape(self._cfg, self.env_seeds, depth)
-        seeds, cursor = self._live
-        _, fresh = _rng.mt_tape(self._cfg, seeds, depth)
-        for i, c in enumerate(cursor):
-            c = int(c)
-            if c < depth:
-                trip[i, c:] = fresh[i, :depth - c]
-        return pos0, trip
-
-    def _draw_tape_dynamic(self):
-        """Reference-exact draws with UE arrival: see rng.DynamicStdlibStreams (initial UEs keep their generators)."""
-        first = self._dyn_streams is None
-        if first:
-            self._dyn_streams = _rng.DynamicStdlibStreams(self.env_seeds, self.map_w, self.map_h, self.vel_specs, self.init_xy,
-                                                         self.tape_depth, self.rand_episodes, self.max_id, border=self._border)
-            return self._dyn_streams.draw_episode()
-        E, U, U0 = self.E, self.U, self.U0
-        uid = self.uid.cpu().numpy().astype(np.uint16).reshape(E, U)
-        cursor = ((self.mv >> 48) & 0xFFFF).cpu().numpy().reshape(E, U)
-        left = self.orig_consumed.cpu().numpy().astype(np.uint16).reshape(E, U0)
-        n = self.num_ue
-        end_lists, consumed = [], []
-        for e in range(E):
-            end_lists.append([(int(w & 0x7FFF), bool(w & 0x8000)) for w in uid[e, :n]])
-            c = [int(x) for x in left[e]]                       # 0xFFFF: never left -> still listed, cursor of its slot
-            for slot in range(n):
-                w = int(uid[e, slot])
-                if not (w & 0x8000):
-                    c[(w & 0x7FFF) - 1] = int(cursor[e, slot])
-            consumed.append(c)
-        return self._dyn_streams.draw_episode(end_lists, consumed)
-
-    def _draw_tape(self):
-        if self.dynamic:
-            return self._draw_tape_dynamic()
-        if self.rand_episodes:
-            if self._streams is None:
-                self._streams = _rng.StdlibStreams(self.env_seeds, self.map_w, self.map_h, self.vel_specs, self.init_xy,
-                                                   self.tape_depth, border=self._border)
-                consumed = None
-            else:
-                consumed = ((self.mv >> 48) & 0xFFFF).cpu().numpy()
-            return self._streams.draw_episode(reseed=False, consumed=consumed)
-        self._live = None
-        if self._fixed_tape is None or self._fixed_tape[1].shape[1] < self.tape_depth:   # (a live re-seed extended only the spliced tape)
-            # re-seeded at every reset (base.py:171-173): same tape every episode
-            self._fixed_tape = _rng.mt_tape(self._cfg, self.env_seeds, self.tape_depth)
-        return self._fixed_tape
-
-    def _upload_tape(self, pos0, trip):
-        self._tape_dev = (torch.from_numpy(pos0).to(self.device), torch.from_numpy(trip.view(np.int16)).to(self.device))
-        self._tape_depth_now = int(trip.shape[1])
-        return _lib.DcompTape(self._tape_dev[0].data_ptr(), self._tape_dev[1].data_ptr(), self.U0 + self.max_id if self.dynamic else 0)
-
     def _ensure_tape(self, steps=1):
-        """rng='reference': the episode's draw tape must cover the next `steps` steps.  A UE redraws at most once per
-        (smallest configured pause_duration + 1) steps (arrive, pause, draw when it moves on: movement.py:158-181), so step t
-        needs at most t // period + 2 triples.  Episodes that outlive the tape -- the reference's done() is always None and
-        --cont-train never resets (main.py:48-51) -- get a longer one: the same draws, continued."""
+        """rng='reference': the episode's draw tape must cover the next `steps` steps (DrawTape.grown has the rule)."""
         if self.rng_mode != _lib.RNG_TAPE or self._tape_dev is None:
             return
-        need = (self.time + steps) // self._redraw_period + 3
-        if need <= self._tape_depth_now:
-            return
-        depth = max(need, 2 * self._tape_depth_now)
-        if self.dynamic:
-            pos0, trip = self._dyn_streams.extend(depth)
-        elif self.rand_episodes:
-            pos0, trip = self._streams.extend(depth)
-        elif self._live is not None:
-            pos0, trip = self._live_fixed_tape(depth)
-        else:
-            pos0, trip = self._fixed_tape = _rng.mt_tape(self._cfg, self.env_seeds, depth)     # stateless: same prefix, longer
-        torch.cuda.current_stream(self.device).synchronize()       # steps in flight still read the old tape
-        old = self._tape_dev
-        tape = self._upload_tape(pos0, trip)
-        _lib.check(self._L.dcomp_set_tape(self._h, ctypes.byref(tape), depth))
-        self.tape_depth = depth
-        del old
+        grown = self._tape.grown(self.time + steps)
+        if grown is not None:
+            self._install_tape(*grown)
 
     # ------------------------------------------------------------------ gym-like batched API
     def reset(self, _out=None):
@@ -464,19 +411,17 @@ class BatchedMobileEnv:
                                     self._out_ref if out is self._out else ctypes.byref(out), self._stream())
             if rc:
                 _lib.check(rc)
-            if self._policy_key is not None:
-                self._policy_launched()
-            return
-        t = self.time
-        n_rem, n_add = self.schedule[t] if t < len(self.schedule) else (0, 0)      # base.py:433-443
-        ev = _lib.DcompEvents(n_rem, n_add, None, None)
-        if (n_rem or n_add) and self.rng_mode == _lib.RNG_TAPE:
-            rem = torch.from_numpy(self._dyn_streams.departures(n_rem, self.num_ue)).to(self.device) if n_rem else None
-            add = torch.from_numpy(self._dyn_streams.arrivals(n_add)).to(self.device) if n_add else None
-            self._ev_keep = (rem, add)                         # keep the device buffers alive until the launch has run
-            ev = _lib.DcompEvents(n_rem, n_add, rem.data_ptr() if n_rem else None, add.data_ptr() if n_add else None)
-        _lib.check(self._L.dcomp_step_dyn(self._h, ctypes.byref(self._st), ctypes.c_void_p(action.data_ptr()),
-                                          ctypes.byref(out), ctypes.byref(ev), self._stream()))
+        else:
+            t = self.time
+            n_rem, n_add = self.schedule[t] if t < len(self.schedule) else (0, 0)      # base.py:433-443
+            ev = _lib.DcompEvents(n_rem, n_add, None, None)
+            if (n_rem or n_add) and self.rng_mode == _lib.RNG_TAPE:
+                rem = torch.from_numpy(self._tape.departures(n_rem, self.num_ue)).to(self.device) if n_rem else None
+                add = torch.from_numpy(self._tape.arrivals(n_add)).to(self.device) if n_add else None
+                self._ev_keep = (rem, add)                         # keep the device buffers alive until the launch has run
+                ev = _lib.DcompEvents(n_rem, n_add, rem.data_ptr() if n_rem else None, add.data_ptr() if n_add else None)
+            _lib.check(self._L.dcomp_step_dyn(self._h, ctypes.byref(self._st), ctypes.c_void_p(action.data_ptr()),
+                                              ctypes.byref(out), ctypes.byref(ev), self._stream()))
         if self._policy_key is not None:
             self._policy_launched()
 
@@ -553,22 +498,28 @@ class BatchedMobileEnv:
         L = int(horizon or 0)
         if new_episode_draws is None:
             new_episode_draws = self.rand_episodes
-        if L and self.rng_mode == _lib.RNG_TAPE and (self.rand_episodes or new_episode_draws or self.dynamic or self._live is not None) and not _policy_steps:
-            # rng='reference' with streams that continue across episodes (or UEs re-seeded by list position at reset, or a fixed-episode
-            # env whose RUNNING episode was re-seeded with seed(immediate=True): its tape is a splice that only reset() replaces with
-            # the configured seed's again, base.py:171-173): every episode
-            # needs a tape the HOST draws from where the previous one stopped, so the rollout is cut at the episode boundaries --
-            # one launch per stretch, reset() (cursors read back, new tape) in between.  Same sequence as `if time == L: reset()`
-            # before every step, like the in-kernel reset of the other modes.
-            keys = ('obs', 'obs_compact', 'reward', 'sum_utility', 'ue_dr', 'ue_utility', 'reward_before')
-            t0 = 0
-            while t0 < T:
-                if self.time >= L:
-                    self.reset()
-                n = min(T - t0, L - self.time)
-                self.rollout(actions[t0:t0 + n], out=None if out is None else {k: out[k][t0:t0 + n] for k in keys if out.get(k) is not None})
-                t0 += n
-            return (self.obs, self.reward) if out is None else (_fragment_obs(out), out['reward'])
+        if L and self.rng_mode == _lib.RNG_TAPE and (new_episode_draws or self._tape.needs_host_reset()):
+            # rng='reference' where every episode needs a tape the HOST draws (DrawTape.needs_host_reset): the rollout is cut at the
+            # episode boundaries -- one launch per stretch, reset() (cursors read back, new tape) in between.  Same sequence as
+            # `if time == L: reset()` before every step, like the in-kernel reset of the other modes.
+            for t0, n in self._stretches(T, L):
+                acts = self.next_action.view(1, self.E, self.U) if _policy_steps else actions[t0:t0 + n]
+                self.rollout(acts, out=_fragment(out, t0, n), _policy_steps=n if _policy_steps else 0)
+        else:
+            self._rollout_launch(actions, T, L, out, new_episode_draws, _policy_steps)
+        return (self.obs, self.reward) if out is None else (_fragment_obs(out), out['reward'])
+
+    def _stretches(self, T, L):
+        """(t0, n): the stretches of T steps cut at the horizon L, with the reset() in between."""
+        t0 = 0
+        while t0 < T:
+            if self.time >= L:
+                self.reset()
+            n = min(T - t0, L - self.time)
+            yield t0, n
+            t0 += n
+
+    def _rollout_launch(self, actions, T, L, out, new_episode_draws, policy_loop):
         o = self._out
         if out is not None:
             packed = out.get('obs_compact')          # the compact record of every step instead of the rows (see step_compact)
@@ -579,18 +530,13 @@ class BatchedMobileEnv:
             else:
                 self._require(out['obs'], torch.float32, T * self.obs.numel(), "out['obs']")
             self._require(out['reward'], torch.float32, T * self.reward.numel(), "out['reward']")
-            ptr = {}
-            for k, n in (('sum_utility', self.E), ('ue_dr', self.E * self.U), ('ue_utility', self.E * self.U),
-                         ('reward_before', self.E * self.U)):
+            for k, n in zip(METRICS, (self.E, self.E * self.U, self.E * self.U, self.E * self.U)):
                 if out.get(k) is not None:
                     self._require(out[k], torch.float32, T * n, f"out['{k}']")
-                    ptr[k] = out[k].data_ptr()
-            o = _lib.DcompOut(None if packed is not None else out['obs'].data_ptr(), out['reward'].data_ptr(), ptr.get('sum_utility'),
-                              ptr.get('ue_dr'), ptr.get('ue_utility'), ptr.get('reward_before'),
-                              packed.data_ptr() if packed is not None else None)
+            o = self._make_out(None if packed is not None else out['obs'], out['reward'], packed, tuple(out.get(k) for k in METRICS))
         if self.rng_mode == _lib.RNG_TAPE:
             self._ensure_tape(min(T, L - self.time) if L else T)
-        opts = _lib.DcompRolloutOpts(1 if out is not None else 0, L, 1 if new_episode_draws else 0, 1 if _policy_steps else 0)
+        opts = _lib.DcompRolloutOpts(1 if out is not None else 0, L, 1 if new_episode_draws else 0, 1 if policy_loop else 0)
         if self.dynamic:
             keep = self._rollout_events(T, L, opts)          # host / device arrays the call reads: alive until it has been enqueued
         with torch.cuda.device(self.device):
@@ -598,7 +544,6 @@ class BatchedMobileEnv:
                                                 ctypes.byref(opts), self._stream()))
         if self._policy_key is not None:
             self._policy_launched()
-        return (self.obs, self.reward) if out is None else (_fragment_obs(out), out['reward'])
 
     def _rollout_events(self, T, L, opts):
         """UE departures / arrivals of the next T steps (base.py:433-443) for dcomp_rollout_ex's event feed: the schedule is
@@ -615,9 +560,9 @@ class BatchedMobileEnv:
             n_rem[t], n_add[t] = r, a
             if self.rng_mode == _lib.RNG_TAPE:
                 if r:
-                    rem_blocks.append(self._dyn_streams.departures(r, cur).astype(np.int32).reshape(-1))
+                    rem_blocks.append(self._tape.departures(r, cur).astype(np.int32).reshape(-1))
                 if a:
-                    add_blocks.append(self._dyn_streams.arrivals(a).astype(np.int32).reshape(-1))
+                    add_blocks.append(self._tape.arrivals(a).astype(np.int32).reshape(-1))
             cur += a - r
             t_env += 1
         keep = [n_rem, n_add]
@@ -640,22 +585,9 @@ class BatchedMobileEnv:
         buffers of every step."""
         if self._policy_key is None or not self._next_action_fresh:
             raise RuntimeError("rollout_policy() needs set_policy() and a reset() / step() after it")
-        L = int(horizon or 0)
-        T, t0 = int(num_steps), 0
-        keys = ('obs', 'obs_compact', 'reward', 'sum_utility', 'ue_dr', 'ue_utility', 'reward_before')
         if out is not None and out.get('obs_compact') is not None:
-            self._require_compact(out['obs_compact'], T)
-        host_resets = L and self.rng_mode == _lib.RNG_TAPE and (self.rand_episodes or self.dynamic or self._live is not None)   # a fresh host-drawn tape per episode
-        if not host_resets:
-            return self.rollout(self.next_action.view(1, self.E, self.U), out=out, horizon=L, _policy_steps=T)
-        while t0 < T:
-            if self.time >= L:
-                self.reset()
-            n = min(T - t0, L - self.time)
-            frag = None if out is None else {k: out[k][t0:t0 + n] for k in keys if out.get(k) is not None}
-            self.rollout(self.next_action.view(1, self.E, self.U), out=frag, _policy_steps=n)
-            t0 += n
-        return (self.obs, self.reward) if out is None else (_fragment_obs(out), out['reward'])
+            self._require_compact(out['obs_compact'], int(num_steps))
+        return self.rollout(self.next_action.view(1, self.E, self.U), out=out, horizon=horizon, _policy_steps=int(num_steps))
 
     def heuristic_actions(self, policy, epsilon=0.0, cluster_mask=None, obs=None, out=None):
         """The reference's heuristic baselines (deepcomp/agent/heuristics.py) for every (env, UE) in one launch
@@ -667,6 +599,13 @@ class BatchedMobileEnv:
         if out is None:
             out = torch.empty((self.E, self.U), dtype=torch.uint8, device=self.device)
         self._require(out, torch.uint8, self.E * self.U, 'out')
+        p = self._policy_struct(policy, epsilon, cluster_mask)
+        with torch.cuda.device(self.device):
+            _lib.check(self._L.dcomp_heuristic_actions(ctypes.byref(p), obs.data_ptr(), out.data_ptr(), self._stream()))
+        return out
+
+    def _policy_struct(self, policy, epsilon, cluster_mask):
+        """The DcompPolicy of a heuristic for the UEs listed now: validated, the cluster mask's device pointer included."""
         if policy not in _lib.POLICY:
             raise ValueError(f"policy must be one of {sorted(_lib.POLICY)}")
         cm = None
@@ -675,10 +614,7 @@ class BatchedMobileEnv:
                 raise ValueError("policy 'cluster' needs cluster_mask")
             self._require(cluster_mask, torch.int32, self.B * (1 if self.B <= _lib.MASK32_MAX_BS else 2), 'cluster_mask')   # > 32 stations: [B, 2] words (lo, hi)
             cm = cluster_mask.data_ptr()
-        p = _lib.DcompPolicy(_lib.POLICY[policy], self.kind, self.E, self.U, self.B, self.num_ue, float(epsilon), cm)
-        with torch.cuda.device(self.device):
-            _lib.check(self._L.dcomp_heuristic_actions(ctypes.byref(p), obs.data_ptr(), out.data_ptr(), self._stream()))
-        return out
+        return _lib.DcompPolicy(_lib.POLICY[policy], self.kind, self.E, self.U, self.B, self.num_ue, float(epsilon), cm)
 
     def set_policy(self, policy, epsilon=0.0, cluster_mask=None):
         """Heuristic policy INSIDE the step (dcomp_set_policy): from now on every reset / step / rollout launch also writes
@@ -691,18 +627,10 @@ class BatchedMobileEnv:
             _lib.check(self._L.dcomp_set_policy(self._h, None, None))
             self._policy_key, self.next_action = None, None
             return True
-        if policy not in _lib.POLICY:
-            raise ValueError(f"policy must be one of {sorted(_lib.POLICY)}")
-        cm = None
-        if policy == 'cluster':
-            if cluster_mask is None:
-                raise ValueError("policy 'cluster' needs cluster_mask")
-            self._require(cluster_mask, torch.int32, self.B * (1 if self.B <= _lib.MASK32_MAX_BS else 2), 'cluster_mask')   # > 32 stations: [B, 2] words (lo, hi)
-            cm = cluster_mask.data_ptr()
+        p = self._policy_struct(policy, epsilon, cluster_mask)
         # two buffers, written alternately: the tensor handed to step() stays what the caller read until the step after
         # (and with UE arrival / departure slots shift, so a step must not write the tensor it reads its actions from)
         bufs = [torch.zeros((self.E, self.U), dtype=torch.uint8, device=self.device) for _ in range(2)]
-        p = _lib.DcompPolicy(_lib.POLICY[policy], self.kind, self.E, self.U, self.B, self.num_ue, float(epsilon), cm)
         rc = self._L.dcomp_set_policy(self._h, ctypes.byref(p), bufs[0].data_ptr())
         if rc == _lib.EUNSUPPORTED:
             self._policy_key, self.next_action = None, None
@@ -710,7 +638,7 @@ class BatchedMobileEnv:
         _lib.check(rc)
         self._policy_bufs, self._policy_p, self._policy_cm, self._policy_flip = bufs, p, cluster_mask, 0
         self.next_action = bufs[0]
-        self._policy_key = (policy, float(epsilon), cm)
+        self._policy_key = (policy, float(epsilon), p.cluster_mask)
         self._next_action_fresh = False              # valid once a reset / step has run with the policy set
         return True
 
@@ -806,7 +734,7 @@ class BatchedMobileEnv:
             self.seed(sd['pending_seed'])
         elif self._reseeded:                            # a seed staged in THIS env is not part of the checkpointed run
             self.seed_value = self._device_seed
-            self.env_seeds = self.seed_value + self._seed_stride * (self.env_id_base + np.arange(self.E, dtype=np.int64))
+            self.env_seeds = self._env_seeds_for(self.seed_value)
             self._reseeded = False
         if self._policy_key is not None:
             if sd.get('next_action') is not None:
@@ -862,12 +790,7 @@ class BatchedMobileEnv:
         return {name: h[o:o + cnt].reshape(shape) for name, (o, cnt, shape) in self._sections.items()}
 
     def obs_views_host(self, host):
-        B, U = self.B, self.U
-        o = host['obs']
-        if self.kind == _lib.MULTI:
-            return {'connected': o[..., 0:B], 'dr': o[..., B:2 * B], 'ues_at_bs': o[..., 2 * B:3 * B],
-                    'util_at_bs': o[..., 3 * B:4 * B], 'utility': o[..., 4 * B:4 * B + 1]}
-        return {'connected': o[..., 0:U * B], 'dr': o[..., U * B:2 * U * B], 'utility': o[..., 2 * U * B:]}
+        return self.obs_views(host['obs'])
 
     def check(self):
         """Synchronise and raise what the reference would have asserted (bad action, UE outside the map)."""
@@ -893,7 +816,7 @@ class BatchedMobileEnv:
             fixed = self._vel_num >= 0
             vel[:, fixed] = self._vel_num[fixed]
             return vel
-        ids, born = (uid & 0x7FFF).astype(np.int64), (uid & 0x8000) != 0
+        ids, born = uid_fields(uid)
         num = np.where((ids >= 1) & (ids <= self.U0) & ~born, self._vel_num[np.clip(ids - 1, 0, self.U0 - 1)], -1.0)
         return np.where(num >= 0, num, vel)
 
@@ -905,16 +828,14 @@ class BatchedMobileEnv:
             'pos': self.pos.cpu().numpy().reshape(E, U, 2),
             'wp': np.stack([(mv & 0xFFFF).astype(np.float64), ((mv >> 16) & 0xFFFF).astype(np.float64)], -1).reshape(E, U, 2),
             'vel': self._vel_host(((mv >> 32) & 0xFF).astype(np.float64).reshape(E, U),
-                                  self.uid.cpu().numpy().astype(np.uint16).reshape(E, U) if self.dynamic else None),
+                                  self.uid.cpu().numpy().reshape(E, U) if self.dynamic else None),
             'pausing': ((mv >> 47) & 1).astype(np.int32).reshape(E, U),
             'curr_pause': ((mv >> 40) & 0x7F).astype(np.int32).reshape(E, U),
-            'cursor': ((mv >> 48) & 0xFFFF).astype(np.int32).reshape(E, U),
-            # one mask per UE: uint32, or uint64 with more than 32 stations (conn | conn_hi << 32)
-            'conn': (self.conn.cpu().numpy().astype(np.uint32).reshape(E, U) if self.B <= _lib.MASK32_MAX_BS else
-                     (self.conn.cpu().numpy().astype(np.uint32).astype(np.uint64) |
-                      (self.conn_hi.cpu().numpy().astype(np.uint32).astype(np.uint64) << np.uint64(32))).reshape(E, U)),
+            'cursor': mv_cursor(mv).astype(np.int32).reshape(E, U),
+            # one mask per UE: uint32, or uint64 with more than 32 stations
+            'conn': conn_mask(self.conn.cpu().numpy(), self.conn_hi.cpu().numpy() if self.B > _lib.MASK32_MAX_BS else None).reshape(E, U),
             'ewma': self.ewma.cpu().numpy().reshape(E, U),
-            'uid': (self.uid.cpu().numpy().astype(np.uint16).reshape(E, U) & 0x7FFF) if self.dynamic else
+            'uid': uid_fields(self.uid.cpu().numpy())[0].astype(np.uint16).reshape(E, U) if self.dynamic else
                    np.tile(np.arange(1, U + 1, dtype=np.uint16), (E, 1)),
         }
 
@@ -997,9 +918,7 @@ class _RefSurfaceEnv(_GymEnv):
     def _host_view(self):
         if self._view_cache is None:
             c = self.core
-            conn = c.conn[:c.U].cpu().numpy().astype(np.uint32).astype(np.uint64)
-            if c.conn_hi is not None:
-                conn = conn | (c.conn_hi[:c.U].cpu().numpy().astype(np.uint32).astype(np.uint64) << np.uint64(32))
+            conn = conn_mask(c.conn[:c.U].cpu().numpy(), None if c.conn_hi is None else c.conn_hi[:c.U].cpu().numpy()).astype(np.uint64)
             self._view_cache = {
                 'pos': c.pos[:c.U].cpu().numpy(), 'ewma': c.ewma[:c.U].cpu().numpy().tolist(),
                 'curr_dr': self._host['ue_dr'][0].tolist(), 'utility': self._host['ue_utility'][0].tolist(),
@@ -1030,11 +949,10 @@ class _RefSurfaceEnv(_GymEnv):
         if not self.core.dynamic:
             return
         from .entities import RandomWaypoint, User
-        words = self.core.uid[:self.core.U].cpu().numpy().astype(np.uint16)[:self.core.num_ue]
+        ids, arrived = uid_fields(self.core.uid[:self.core.U].cpu().numpy()[:self.core.num_ue])
         pos = self.core.pos[:self.core.U].cpu().numpy()
         lst = []
-        for slot, w in enumerate(words):
-            uid, born = int(w & 0x7FFF), bool(w & 0x8000)
+        for slot, (uid, born) in enumerate(zip(ids.tolist(), arrived.tolist())):
             if not born:
                 ue = self.original_ue_list[uid - 1]
             else:

@@ -10,6 +10,7 @@ tape.  Two producers of the same tape:
   reference re-seeds at every reset, base.py:171-173);
 * ``StdlibStreams`` -- the stdlib generator itself, kept alive across episodes for ``rand_episodes=True``
   (streams continue where the previous episode stopped).
+``deepcomp_amd.tape`` decides which producer an env draws from and owns the tape they fill.
 """
 import ctypes
 import random
@@ -18,11 +19,13 @@ import numpy as np
 
 from . import _lib
 
+SLOW, NEW_UE_BORDER = (1, 3), 10     # UEs that arrive during an episode: 'slow', default border (base.py:597-599)
+
 
 def vel_range(v):
     """Velocity spec -> inclusive draw range (movement.py:112-117)."""
     if v == 'slow':
-        return 1, 3
+        return SLOW
     if v == 'fast':
         return 5, 10
     return int(v), int(v)
@@ -38,6 +41,17 @@ def mt_tape(cfg_struct, seeds, depth):
     _lib.check(L.dcomp_mt_draw_tape(ctypes.byref(cfg_struct), seeds.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)), E, depth,
                                     pos0.ctypes.data, trip.ctypes.data))
     return pos0, trip
+
+
+def draw_rows(gen, row, k0, k1, vel, border, w, h, states=None):
+    """Triples k0 .. k1 of ONE UE's tape row (row[depth, 4]) from its movement generator, as RandomWaypoint.reset draws them
+    (movement.py:110-130): a velocity where the spec is a range, then the waypoint inside the border.  states: a list that gets
+    the generator's state after every triple (what the next episode, which continues the stream, is set back to)."""
+    lo, hi = vel
+    for k in range(k0, k1):
+        row[k, :3] = (gen.randint(lo, hi) if lo != hi else lo, gen.randint(border, w - border), gen.randint(border, h - border))
+        if states is not None:
+            states.append(gen.getstate())
 
 
 class StdlibStreams:
@@ -59,6 +73,15 @@ class StdlibStreams:
         self.pos_rng = [[random.Random(s + 100 * (i + 1)) for i in range(self.U)] for s in self.seeds]
         self.mov_rng = [[random.Random(s + 100 * (i + 1)) for i in range(self.U)] for s in self.seeds]
 
+    def _draw(self, trip, k0, k1, fresh=True):
+        """Triples k0[e*U+i] .. k1 of every UE's row from its movement stream; fresh: the recorded states start over here."""
+        if fresh:
+            self._states = [[[mr.getstate()] for mr in env] for env in self.mov_rng]
+        for e, env in enumerate(self.mov_rng):
+            for i, mr in enumerate(env):
+                r = e * self.U + i
+                draw_rows(mr, trip[r], k0[r], k1, self.vel[i], self.border[i], self.w, self.h, self._states[e][i])
+
     def reseed_live(self, seeds, consumed=None):
         """MobileEnv.seed() on a live env (base.py:132-143): BOTH streams of every UE start over at once, from the new seeds.
         What a UE still draws in the running episode comes from the start of its new movement stream: returns the episode's
@@ -69,24 +92,10 @@ class StdlibStreams:
         if self._trip is None:
             self._states = None
             return None
-        E, U, D = len(self.seeds), self.U, self.depth
-        trip = self._trip.copy()
-        self._states, self._shift = [], [int(c) for c in consumed]
-        for e in range(E):
-            st_e = []
-            for i in range(U):
-                mr = self.mov_rng[e][i]
-                lo, hi = self.vel[i]
-                st = [mr.getstate()]
-                for k in range(self._shift[e * U + i], D):
-                    trip[e * U + i, k, 0] = mr.randint(lo, hi) if lo != hi else lo
-                    trip[e * U + i, k, 1] = mr.randint(self.border[i], self.w - self.border[i])
-                    trip[e * U + i, k, 2] = mr.randint(self.border[i], self.h - self.border[i])
-                    st.append(mr.getstate())
-                st_e.append(st)
-            self._states.append(st_e)
-        self._trip = trip
-        return self._pos0, trip
+        self._trip = self._trip.copy()
+        self._shift = [int(c) for c in consumed]
+        self._draw(self._trip, self._shift, self.depth)
+        return self._pos0, self._trip
 
     def draw_episode(self, reseed, consumed=None):
         """consumed[E*U]: movement triples the previous episode used (the cursor field of the state)."""
@@ -101,43 +110,22 @@ class StdlibStreams:
                     self.mov_rng[e][i].setstate(self._states[e][i][int(consumed[e * U + i]) - shift])
         self._shift = None
         pos0 = np.zeros((E * U, 2), dtype=np.int32)
-        trip = np.zeros((E * U, D, 4), dtype=np.uint16)
-        self._states = []
         for e in range(E):
-            st_e = []
-            for i in range(U):
-                ix, iy = self.init_xy[i]
-                pr, mr = self.pos_rng[e][i], self.mov_rng[e][i]
-                pos0[e * U + i, 0] = pr.randint(0, self.w) if ix < 0 else ix
-                pos0[e * U + i, 1] = pr.randint(0, self.h) if iy < 0 else iy
-                lo, hi = self.vel[i]
-                st = [mr.getstate()]
-                for k in range(D):
-                    v = mr.randint(lo, hi) if lo != hi else lo
-                    trip[e * U + i, k, 0] = v
-                    trip[e * U + i, k, 1] = mr.randint(self.border[i], self.w - self.border[i])
-                    trip[e * U + i, k, 2] = mr.randint(self.border[i], self.h - self.border[i])
-                    st.append(mr.getstate())
-                st_e.append(st)
-            self._states.append(st_e)
+            for i, (ix, iy) in enumerate(self.init_xy):
+                pr = self.pos_rng[e][i]
+                pos0[e * U + i] = (pr.randint(0, self.w) if ix < 0 else ix, pr.randint(0, self.h) if iy < 0 else iy)
+        trip = np.zeros((E * U, D, 4), dtype=np.uint16)
+        self._draw(trip, [0] * (E * U), D)
         self._pos0, self._trip = pos0, trip
         return pos0, trip
 
     def extend(self, new_depth):
         """Continue every movement stream beyond the tape drawn by draw_episode (an episode that runs longer than the
         tape was sized for: --cont-train never resets, main.py:48-51).  The generators still stand where the tape ended."""
-        E, U, D = len(self.seeds), self.U, self.depth
-        trip = np.zeros((E * U, new_depth, 4), dtype=np.uint16)
+        rows, D = len(self._trip), self.depth
+        trip = np.zeros((rows, new_depth, 4), dtype=np.uint16)
         trip[:, :D] = self._trip
-        for e in range(E):
-            for i in range(U):
-                mr, st = self.mov_rng[e][i], self._states[e][i]
-                lo, hi = self.vel[i]
-                for k in range(D, new_depth):
-                    trip[e * U + i, k, 0] = mr.randint(lo, hi) if lo != hi else lo
-                    trip[e * U + i, k, 1] = mr.randint(self.border[i], self.w - self.border[i])
-                    trip[e * U + i, k, 2] = mr.randint(self.border[i], self.h - self.border[i])
-                    st.append(mr.getstate())
+        self._draw(trip, [D] * rows, new_depth, fresh=False)
         self.depth, self._trip = new_depth, trip
         return self._pos0, trip
 
@@ -198,11 +186,24 @@ class DynamicStdlibStreams:
         self._shift = None          # [e][i]: triples initial UE i had drawn before a live re-seed (reseed_live)
         self._live_born = {}        # (e, id) -> (seed, cursor): arrived UEs re-seeded live, for extend()
 
-    def _born_row(self, trip, row, seed, cursor, upto):
-        """Row of an arrived UE re-seeded live: 'slow', default border (base.py:597-599), new stream from `cursor` on."""
-        r = random.Random(seed)
-        for k in range(cursor, upto):
-            trip[row, k, :3] = (r.randint(1, 3), r.randint(10, self.w - 10), r.randint(10, self.h - 10))
+    def _draw(self, trip, e, i, k0, k1, fresh=True):
+        """Triples k0 .. k1 of initial UE i of env e from its movement stream; fresh: its recorded states start over here."""
+        mr = self.mov_rng[e][i]
+        if fresh:
+            self._states[e][i] = [mr.getstate()]
+        draw_rows(mr, trip[e * (self.U0 + self.max_id) + i], k0, k1, self.vel[i], self.border[i], self.w, self.h, self._states[e][i])
+
+    def _born_row(self, trip, e, uid, seed, k0, k1):
+        """Triples k0 .. k1 of the UE that arrives in env e with id `uid`: a stream of its own, stateless (drawn again at any depth)."""
+        draw_rows(random.Random(seed), trip[e * (self.U0 + self.max_id) + self.U0 + uid - 1], k0, k1, SLOW, NEW_UE_BORDER, self.w, self.h)
+
+    def _born_rows(self, trip, e, depth):
+        """The rows of every id that may arrive in env e: the configured seed's stream (base.py:601-604), behind the cursor of a live
+        re-seed the stream of the list position the UE had then."""
+        for uid in range(1, self.max_id + 1):
+            self._born_row(trip, e, uid, self.seeds[e] + 100 * uid, 0, depth)
+            if (e, uid) in self._live_born:
+                self._born_row(trip, e, uid, *self._live_born[(e, uid)], depth)
 
     def reseed_live(self, seeds, lists, cursors):
         """MobileEnv.seed() while an episode with a changing UE list runs (base.py:132-143).  Per env: the global generator
@@ -213,7 +214,6 @@ class DynamicStdlibStreams:
         env_seed), initial UEs that have left keep their old stream, and reset() of a rand_episodes=False env re-seeds with the
         configured seed as always (self.seeds is not touched)."""
         E, U0, D = len(self.seeds), self.U0, self.depth
-        ids = U0 + self.max_id
         trip = self._trip.copy()
         if self._shift is None:
             self._shift = [[0] * U0 for _ in range(E)]
@@ -225,19 +225,12 @@ class DynamicStdlibStreams:
                 sd, cur = s + 100 * (pos + 1), int(cursors[e][pos])
                 if born:
                     self._live_born[(e, uid)] = (sd, cur)
-                    self._born_row(trip, e * ids + U0 + uid - 1, sd, cur, D)
+                    self._born_row(trip, e, uid, sd, cur, D)
                     continue
-                i = uid - 1
-                self.pos_rng[e][i].seed(sd)
-                mr = self.mov_rng[e][i]
-                mr.seed(sd)
-                lo, hi = self.vel[i]
-                st = [mr.getstate()]
-                for k in range(cur, D):
-                    trip[e * ids + i, k, :3] = (mr.randint(lo, hi) if lo != hi else lo, mr.randint(self.border[i], self.w - self.border[i]),
-                                                mr.randint(self.border[i], self.h - self.border[i]))
-                    st.append(mr.getstate())
-                self._states[e][i], self._shift[e][i] = st, cur
+                self.pos_rng[e][uid - 1].seed(sd)
+                self.mov_rng[e][uid - 1].seed(sd)
+                self._draw(trip, e, uid - 1, cur, D)
+                self._shift[e][uid - 1] = cur
         self._trip = trip
         return self._pos0, trip
 
@@ -260,52 +253,27 @@ class DynamicStdlibStreams:
                     if not born:
                         self.pos_rng[e][uid - 1].seed(s + 100 * (pos + 1))
                         self.mov_rng[e][uid - 1].seed(s + 100 * (pos + 1))
-        ids = U0 + self.max_id
         pos0 = np.zeros((E * U0, 2), dtype=np.int32)
-        trip = np.zeros((E * ids, D, 4), dtype=np.uint16)
-        self._states = []
-        for e, s in enumerate(self.seeds):
-            st_e = []
-            for i in range(U0):
-                ix, iy = self.init_xy[i]
-                pr, mr = self.pos_rng[e][i], self.mov_rng[e][i]
+        trip = np.zeros((E * (U0 + self.max_id), D, 4), dtype=np.uint16)
+        self._states = [[None] * U0 for _ in range(E)]
+        for e in range(E):
+            for i, (ix, iy) in enumerate(self.init_xy):
+                pr = self.pos_rng[e][i]
                 pos0[e * U0 + i] = (pr.randint(0, self.w) if ix < 0 else ix, pr.randint(0, self.h) if iy < 0 else iy)
-                lo, hi = self.vel[i]
-                st = [mr.getstate()]
-                for k in range(D):
-                    trip[e * ids + i, k, :3] = (mr.randint(lo, hi) if lo != hi else lo, mr.randint(self.border[i], self.w - self.border[i]),
-                                                mr.randint(self.border[i], self.h - self.border[i]))
-                    st.append(mr.getstate())
-                st_e.append(st)
-            self._states.append(st_e)
-            for j in range(self.max_id):                      # arriving UE with id j+1: fresh stream, 'slow'
-                mr = random.Random(s + 100 * (j + 1))
-                for k in range(D):
-                    trip[e * ids + U0 + j, k, :3] = (mr.randint(1, 3), mr.randint(10, self.w - 10), mr.randint(10, self.h - 10))
+                self._draw(trip, e, i, 0, D)
+            self._born_rows(trip, e, D)
         self._pos0, self._trip = pos0, trip
         return pos0, trip
 
     def extend(self, new_depth):
         """As StdlibStreams.extend: initial UEs continue their generators, the (stateless) tapes of arriving ids are redrawn."""
-        E, U0, D = len(self.seeds), self.U0, self.depth
-        ids = U0 + self.max_id
-        trip = np.zeros((E * ids, new_depth, 4), dtype=np.uint16)
+        E, D = len(self.seeds), self.depth
+        trip = np.zeros((len(self._trip), new_depth, 4), dtype=np.uint16)
         trip[:, :D] = self._trip
-        for e, s in enumerate(self.seeds):
-            for i in range(U0):
-                mr, st = self.mov_rng[e][i], self._states[e][i]
-                lo, hi = self.vel[i]
-                for k in range(D, new_depth):
-                    trip[e * ids + i, k, :3] = (mr.randint(lo, hi) if lo != hi else lo, mr.randint(self.border[i], self.w - self.border[i]),
-                                                mr.randint(self.border[i], self.h - self.border[i]))
-                    st.append(mr.getstate())
-            for j in range(self.max_id):
-                mr = random.Random(s + 100 * (j + 1))
-                for k in range(new_depth):
-                    trip[e * ids + U0 + j, k, :3] = (mr.randint(1, 3), mr.randint(10, self.w - 10), mr.randint(10, self.h - 10))
-                if (e, j + 1) in self._live_born:               # an arrived UE that seed() re-seeded while the episode ran
-                    sd, cur = self._live_born[(e, j + 1)]
-                    self._born_row(trip, e * ids + U0 + j, sd, cur, new_depth)
+        for e in range(E):
+            for i in range(self.U0):
+                self._draw(trip, e, i, D, new_depth, fresh=False)
+            self._born_rows(trip, e, new_depth)
         self.depth, self._trip = new_depth, trip
         return self._pos0, trip
 

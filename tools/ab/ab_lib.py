@@ -16,7 +16,9 @@ central, 100 steps per launch, every step's outputs), one GPU's share of config 
 PPOLearner grads + apply on one minibatch of 65 536 x 32 multi rows / 4 096 central rows (libraries from round 9 on); actor_c3 / actor_c2:
 dcomp_actor_actions_v (actions, logp and the value of a trunk of its own, sampled) at 65 536 x 32 x 10 multi / 4 096 x 10 x 5 central
 (libraries from round 8 on); update_c2 / update_c3s / update_per_ue: the host side of the learners' update() at launch-bound shapes
-(profiles/r18_sgd_phase.txt) -- wall-clock ms per call, not kernel time.  A tag `py:TREE` times the working tree's library under the
+(profiles/r18_sgd_phase.txt) -- wall-clock ms per call, not kernel time; step_philox / step_reference / step_philox_dyn and the compat_*
+loops: the host side of BatchedMobileEnv.step() and of the single-env classes (profiles/r19_env_tape.txt), wall clock as well.  For the
+wall-clock workloads `run` also prints the median over the rounds and their spread (max - min).  A tag `py:TREE` times the working tree's library under the
 Python package of another checkout (TREE/deepcomp_amd, e.g. `git archive <ref> deepcomp_amd | tar -x -C TREE`): a host-side A/B."""
 import argparse
 import json
@@ -72,6 +74,9 @@ def build(a):
 WORKLOADS = ['big64', 'big40c', 'c3', 'c2roll', 'c5', 'c5mid', 'c5big', 'c4share', 'c4big', 'central10x5', 'central10x5roll', 'central10x5f', 'central32x10', 'c2policy', 'c3rf', 'c3roll',
              'learner_c3', 'learner_c2', 'actor_c3', 'actor_c2']
 UPDATES = ['update_c2', 'update_c3s', 'update_per_ue']        # run on request only (--only): wall clock, and a collect() batch each
+ENV_STEPS = {'step_philox': dict(rng='philox'), 'step_reference': dict(rng='reference'), 'step_philox_dyn': dict(rng='philox', new_ue_interval=25)}
+COMPAT = {'compat_multi32x10': 'multi 32x10', 'compat_central10x5': 'central 10x5', 'compat_central3x3': 'central 3x3'}     # tools/compat_rate.py's loops
+WALL = UPDATES + list(ENV_STEPS) + list(COMPAT)               # all of them on request only
 
 
 def measure_actor(torch, dev, kind, E, U, B, n):
@@ -171,7 +176,31 @@ def measure_update(torch, dev, w, calls=12):
     return statistics.median(ms[2:])
 
 
+def measure_env_step(torch, dev, w, calls=2000):
+    """BatchedMobileEnv.step() at 64 x 32 x 10 multi, host-bound: wall clock per call in ms over `calls` calls (a reset() every 100, the
+    episode length, timed with them) after 100 warm-up calls, one synchronise at the end."""
+    import time
+    from deepcomp_amd import scenarios
+    from deepcomp_amd.entities import build_from_scenario
+    from deepcomp_amd.env import BatchedMobileEnv
+    m, bs, ues = build_from_scenario(scenarios.grid_map(10, 'mixed').with_ues(num_slow=32))
+    env = BatchedMobileEnv(m, bs, ues, 'multi', num_envs=64, seed=42, episode_length=100, device=dev, **ENV_STEPS[w])
+    g = torch.Generator(device=dev).manual_seed(7)
+    pool = torch.randint(0, 11, (4, 64, env.U), generator=g, device=dev, dtype=torch.uint8)
+    for timed in (False, True):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        for i in range(calls if timed else 100):
+            if i % 100 == 0:
+                env.reset()
+            env.step(pool[i & 3])
+        torch.cuda.synchronize()
+    env.check()
+    return (time.perf_counter() - t0) * 1e3 / calls
+
+
 def measure(a):
+    sys.path.insert(0, os.path.join(REPO, 'tools'))
     sys.path.insert(0, REPO)
     if os.environ.get('DCOMP_AB_PYTREE'):                  # (a `py:TREE` tag: that checkout's deepcomp_amd, this tree's bench and library)
         sys.path.insert(0, os.environ['DCOMP_AB_PYTREE'])
@@ -217,6 +246,11 @@ def measure(a):
             out[w] = measure_actor(torch, dev, 'central', 4096, 10, 5, 500)
         elif w in UPDATES:
             out[w] = measure_update(torch, dev, w)
+        elif w in ENV_STEPS:
+            out[w] = measure_env_step(torch, dev, w)
+        elif w in COMPAT:
+            import compat_rate
+            out[w] = compat_rate.loop(COMPAT[w]) * 1e3
         elif w in ('central10x5f', 'c3roll'):      # the fused rollout kernel forced onto a big batch, ONE step per launch
             os.environ['DCOMP_FUSE_MAX_WAVES'] = '100000000'
             E, U, B, kind = (65536, 10, 5, 'central') if w == 'central10x5f' else (65536, 32, 10, 'multi')
@@ -278,7 +312,7 @@ def run(a):
             print(f'round {r} {t}: ' + '  '.join(f'{k} {v * 1e3:.2f}us' for k, v in json.loads(line[-1][10:]).items()), flush=True)
     ref = a.tags[0]
     print(f'\n{"workload":14s}' + ''.join(f'{t:>22s}' for t in a.tags))
-    for w in WORKLOADS + UPDATES:
+    for w in WORKLOADS + WALL:
         if w not in res[ref]:
             continue
         base = min(res[ref][w])
@@ -290,6 +324,12 @@ def run(a):
             else:
                 row += f'{"-":>22s}'
         print(row)
+    import statistics
+    wall = [w for w in WALL if w in res[ref]]
+    if wall:
+        print(f'\nwall clock, median of {a.rounds} rounds (max - min), us')
+    for w in wall:
+        print(f'{w:20s}' + ''.join(f'{t}: {statistics.median(res[t][w]) * 1e3:10.2f} ({(max(res[t][w]) - min(res[t][w])) * 1e3:8.2f})   ' for t in a.tags if w in res[t]))
 
 
 if __name__ == '__main__':
