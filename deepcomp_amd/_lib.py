@@ -170,6 +170,10 @@ ACCUM_EXPORTS = ['dcomp_learner_flat_size', 'dcomp_learner_accumulate', 'dcomp_s
 ACCUM_SUMS = 8
 
 
+# include/dcomp_learner_group_accum.h: the accumulators of all learners of a group, [P][flat] / [P][8], in one launch round
+GROUP_ACCUM_EXPORTS = ['dcomp_learner_group_accumulate', 'dcomp_learner_group_accum_finish']
+
+
 class DcompPpoHyper(ctypes.Structure):
     _fields_ = [('struct_size', ctypes.c_int32), ('clip_param', ctypes.c_float), ('vf_clip_param', ctypes.c_float),
                 ('vf_loss_coeff', ctypes.c_float), ('entropy_coeff', ctypes.c_float), ('kl_coeff', ctypes.c_float)]
@@ -291,6 +295,11 @@ def load():
         L.dcomp_sgd_accumulate.argtypes = [vp, ctypes.POINTER(DcompSgdBatch), ctypes.POINTER(DcompPpoHyper), vp, vp, vp]
         L.dcomp_learner_accum_finish.argtypes = [vp, vp, vp, ctypes.POINTER(DcompPpoHyper), ctypes.c_float, vp, vp, vp]
         for name in ACCUM_EXPORTS:
+            getattr(L, name)
+    if hasattr(L, 'dcomp_learner_group_accumulate') or not os.environ.get('DCOMP_LIB'):
+        L.dcomp_learner_group_accumulate.argtypes = [vp, ctypes.POINTER(DcompGroupBatch), ctypes.POINTER(DcompPpoHyper), vp, vp, vp]
+        L.dcomp_learner_group_accum_finish.argtypes = [vp, vp, vp, ctypes.POINTER(DcompPpoHyper), _fp, _ip, vp, vp, vp]
+        for name in GROUP_ACCUM_EXPORTS:
             getattr(L, name)
     for name in EXPORTS:
         getattr(L, name)

@@ -37,9 +37,10 @@ def b_list():
 def _sources():
     return [os.path.join(CSRC, f) for f in ('dcomp_device.h', 'dcomp_wide.h', 'dcomp_dyn.h', 'dcomp_blist.h', 'dcomp_inst.hip', 'dcomp_api.hip', 'dcomp_fragment.h',
                                             'dcomp_big.h', 'dcomp_big.hip', 'dcomp_actor.hip', 'dcomp_actor_impl.h', 'dcomp_fcnet_plan.h', 'dcomp_learner.hip', 'dcomp_learner_tiles.inc',
-                                            'dcomp_learner_reduce.inc', 'dcomp_learner_adam.inc')] + \
+                                            'dcomp_learner_reduce.inc', 'dcomp_learner_adam.inc', 'dcomp_learner_accumulate.inc', 'dcomp_learner_norm.inc',
+                                            'dcomp_learner_finish.inc')] + \
         [os.path.join(os.path.dirname(HERE), 'include', f) for f in ('dcomp.h', 'dcomp_types.h', 'dcomp_learner.h', 'dcomp_learner_indexed.h', 'dcomp_policy_set.h',
-                                                                            'dcomp_learner_group.h', 'dcomp_learner_accum.h')]
+                                                                            'dcomp_learner_group.h', 'dcomp_learner_accum.h', 'dcomp_learner_group_accum.h')]
 
 
 def _dev_flags():
@@ -145,8 +146,9 @@ def build(force=False, jobs=None, extra_flags=()):
                 continue
             if f.endswith(('dcomp_actor_impl.h', 'dcomp_fcnet_plan.h')) and not t[0].endswith(('dcomp_actor.o', 'dcomp_learner.o')):
                 continue
-            if f.endswith(('dcomp_learner.hip', 'dcomp_learner_tiles.inc', 'dcomp_learner_reduce.inc', 'dcomp_learner_adam.inc', 'dcomp_learner.h',
-                           'dcomp_learner_indexed.h', 'dcomp_learner_group.h', 'dcomp_learner_accum.h')) and not t[0].endswith('dcomp_learner.o'):
+            if f.endswith(('dcomp_learner.hip', 'dcomp_learner_tiles.inc', 'dcomp_learner_reduce.inc', 'dcomp_learner_adam.inc', 'dcomp_learner_accumulate.inc',
+                           'dcomp_learner_norm.inc', 'dcomp_learner_finish.inc', 'dcomp_learner.h', 'dcomp_learner_indexed.h', 'dcomp_learner_group.h',
+                           'dcomp_learner_accum.h', 'dcomp_learner_group_accum.h')) and not t[0].endswith('dcomp_learner.o'):
                 continue
             if f.endswith(('dcomp_big.h', 'dcomp_big.hip')) and not t[0].endswith(('dcomp_api.o', 'dcomp_big.o')):
                 continue

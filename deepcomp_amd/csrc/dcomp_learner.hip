@@ -2,9 +2,10 @@
 // its minibatches picked through a row index out of a whole sample batch, rows or compact record (include/dcomp_learner_indexed.h);
 // and the learners of a per-UE policy set trained in one launch round (include/dcomp_learner_group.h): the same four kernels with the
 // policy as a grid dimension, behind the per-learner ones below; and the gradients as a running sum the caller owns, for micro-batches
-// and data-parallel ranks (include/dcomp_learner_accum.h): accumulate_kernel in reduce_kernel's place, then norm_kernel / finish_kernel.
+// and data-parallel ranks (include/dcomp_learner_accum.h): accumulate_kernel in reduce_kernel's place, then norm_kernel / finish_kernel;
+// and those three with the policy as a grid dimension, for the accumulators of a whole group (include/dcomp_learner_group_accum.h).
 // The bodies the per-learner and grouped forms share are text (dcomp_learner_tiles.inc, dcomp_learner_reduce.inc,
-// dcomp_learner_adam.inc), included in each kernel.
+// dcomp_learner_adam.inc, dcomp_learner_accumulate.inc, dcomp_learner_norm.inc, dcomp_learner_finish.inc), included in each kernel.
 //
 // Four kernels per minibatch, all deterministic (no floating-point atomics; every sum has an order fixed by the row count):
 //   learner_kernel   forward + loss + backward-data.  The shape of actor_kernel: a wavefront owns 32 decision rows on its lanes and
@@ -42,6 +43,7 @@
 #include "../../include/dcomp_learner_indexed.h"
 #include "../../include/dcomp_learner_group.h"
 #include "../../include/dcomp_learner_accum.h"
+#include "../../include/dcomp_learner_group_accum.h"
 #include "dcomp_actor_impl.h"       // the forward-pass helpers, the fragment layout, Net and struct dcomp_actor, fail / HIP_TRY: shared with dcomp_actor.hip
 
 namespace dlearn {
@@ -313,32 +315,7 @@ __global__ __launch_bounds__(256) void adam_kernel(const AParams p)
 // (micro-)batch on one stream: a thread owns its entry of acc, thread 0 of block 0 owns sums -- no atomics.
 __global__ __launch_bounds__(256) void accumulate_kernel(const AParams p, float *acc, double *sums)
 {
-    const int e = blockIdx.x * 256 + threadIdx.x;
-    if (e < p.total) {
-        const int ai = find_array(p, e);
-        const ADesc d = p.a[ai];
-        const int idx = e - d.off, k = idx / d.nout, o = idx - k * d.nout;
-        const size_t stride = d.is_bias ? (size_t)d.out_p : (size_t)d.in_p * d.out_p, at = (size_t)k * d.out_p + o;
-        float s = acc[e];
-        for (int c = 0; c < p.nchunks; c++) s += d.part[c * stride + at];             // chunk order
-        acc[e] = s;
-    }
-    if (blockIdx.x == 0) {
-        __shared__ double sh[256][4];
-        const int64_t per = (p.tiles + 255) / 256, lo = threadIdx.x * per, hi = lo + per < p.tiles ? lo + per : p.tiles;
-        double s0 = 0., s1 = 0., s2 = 0., s3 = 0.;
-        for (int64_t t = lo; t < hi; t++) {
-            const double *v = p.tile_part + 4 * t;
-            s0 += v[0]; s1 += v[1]; s2 += v[2]; s3 += v[3];
-        }
-        sh[threadIdx.x][0] = s0; sh[threadIdx.x][1] = s1; sh[threadIdx.x][2] = s2; sh[threadIdx.x][3] = s3;
-        __syncthreads();
-        if (threadIdx.x == 0) {
-            double t0 = 0., t1 = 0., t2 = 0., t3 = 0.;
-            for (int i = 0; i < 256; i++) { t0 += sh[i][0]; t1 += sh[i][1]; t2 += sh[i][2]; t3 += sh[i][3]; }
-            sums[0] += t0; sums[1] += t1; sums[2] += t2; sums[3] += t3; sums[4] += p.count;
-        }
-    }
+#include "dcomp_learner_accumulate.inc"
 }
 
 struct FParams {
@@ -357,56 +334,14 @@ __device__ __forceinline__ float accum_scale(const double *sums) { return sums[4
 // the squares of the scaled gradients, in double: a thread its 16 entries in order, a fixed tree over the block, one partial per block
 __global__ __launch_bounds__(256) void norm_kernel(const FParams p)
 {
-    __shared__ double sh[256];
-    const float scale = accum_scale(p.sums);
-    double s = 0.;
-    for (int i = 0; i < NORM_SPAN / 256; i++) {
-        const int e = blockIdx.x * NORM_SPAN + i * 256 + threadIdx.x;
-        if (e < p.total) {
-            const float g = p.acc[e] * scale;
-            s += (double)g * (double)g;
-        }
-    }
-    sh[threadIdx.x] = s;
-    __syncthreads();
-    for (int o = 128; o > 0; o >>= 1) {
-        if ((int)threadIdx.x < o) sh[threadIdx.x] += sh[threadIdx.x + o];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) p.norm_part[blockIdx.x] = sh[0];
+#include "dcomp_learner_norm.inc"
 }
 
 // g = acc / N (x the clip coefficient), and the statistics from sums as reduce_kernel forms them from its totals.  Every block adds
 // the norm partials itself, in block order: the same number in every block.
 __global__ __launch_bounds__(256) void finish_kernel(const FParams p)
 {
-    __shared__ float coef_sh;
-    const float scale = accum_scale(p.sums);
-    float coef = 1.f;
-    if (p.want_norm) {
-        if (threadIdx.x == 0) {
-            double s = 0.;
-            for (int i = 0; i < p.nparts; i++) s += p.norm_part[i];
-            const double norm = sqrt(s), c = (double)p.clip / (norm + 1e-6);
-            coef_sh = p.clip > 0.f ? (float)(c < 1.0 ? c : 1.0) : 1.f;
-            if (blockIdx.x == 0 && p.grad_norm) *p.grad_norm = (float)norm;
-        }
-        __syncthreads();
-        coef = coef_sh;
-    }
-    const int e = blockIdx.x * 256 + threadIdx.x;
-    if (e < p.total) {
-        float g = p.acc[e] * scale;
-        if (p.clip > 0.f) g = g * coef;
-        p.g[e] = g;
-    }
-    if (p.stats && blockIdx.x == 0 && threadIdx.x == 0) {
-        const double t0 = p.sums[0], t1 = p.sums[1], t2 = p.sums[2], t3 = p.sums[3], count = p.sums[4];
-        const double inv = count > 0. ? 1.0 / count : 0.0;
-        const float pol = (float)(-t0 * inv), kl = (float)(t1 * inv), ent = (float)(t2 * inv), vfl = (float)(t3 * inv);
-        p.stats[0] = pol + p.kl_coeff * kl + p.vf_coeff * vfl - p.ent_coeff * ent;
-        p.stats[1] = pol; p.stats[2] = vfl; p.stats[3] = kl; p.stats[4] = ent;
-    }
+#include "dcomp_learner_finish.inc"
 }
 
 // ---------------------------------------------------------------- all learners of a group in one launch (include/dcomp_learner_group.h)
@@ -426,6 +361,8 @@ struct GEntry {
     int32_t total, ntask;
     float beta1, omb1, beta2, omb2, eps;
     int32_t reserved;
+    double *norm_part;                    // appended (the offsets above stay put): the member's norm workspace, for finish_group_kernel
+    int32_t norm_parts, reserved2;
 };
 typedef const GEntry __attribute__((address_space(4))) *gentry_ptr;
 __device__ __forceinline__ gentry_ptr group_entry(const GEntry *table, int i) { return (gentry_ptr)(uintptr_t)(table + i); }
@@ -586,7 +523,73 @@ __global__ __launch_bounds__(256) void adam_group_kernel(const GAParams gp)
     }
 }
 
-static_assert(sizeof(GLParams) <= 4096 && sizeof(GWParams) <= 4096 && sizeof(GRParams) <= 4096 && sizeof(GAParams) <= 4096,
+// accumulate_kernel per policy (blockIdx.y) on the policy's slices of the caller's [P][flat] / [P][DCOMP_ACCUM_SUMS] accumulators: the
+// split and the count from the row count, as reduce_group_kernel has them
+struct GCParams {
+    const GEntry *table;
+    float *acc;                           // of the slice's first policy, as table is
+    double *sums;
+    int32_t rows[GROUP_SLICE];            // 0: the policy sits this call out, its slices are not touched
+};
+
+__global__ __launch_bounds__(256) void accumulate_group_kernel(const GCParams gp)
+{
+    const int pol = blockIdx.y;
+    const int32_t nrows = gp.rows[pol];
+    if (nrows == 0) return;
+    GAView p = group_view(gp.table, pol);
+    const RowSplit rs = row_split(nrows);
+    p.nchunks = rs.nchunks; p.tiles = rs.tiles; p.count = (double)nrows;
+    float *acc = gp.acc + (size_t)pol * (size_t)p.total;
+    double *sums = gp.sums + DCOMP_ACCUM_SUMS * pol;
+    {
+#include "dcomp_learner_accumulate.inc"
+    }
+}
+
+// norm_kernel / finish_kernel per policy (blockIdx.y): the policy's FParams from its table entry and the per-call arrays
+struct GFParams {
+    const GEntry *table;
+    const float *acc;                     // of the slice's first policy
+    const double *sums;
+    float *stats, *grad_norm;             // [policy of the slice][DCOMP_PPO_NUM_STATS], [policy of the slice]; may be NULL
+    int32_t active[GROUP_SLICE], want_norm[GROUP_SLICE];
+    float clip[GROUP_SLICE], vf_coeff[GROUP_SLICE], ent_coeff[GROUP_SLICE], kl_coeff[GROUP_SLICE];
+};
+__device__ __forceinline__ FParams group_finish_params(const GFParams &gp, int pol)
+{
+    const gentry_ptr en = group_entry(gp.table, pol);
+    FParams p;
+    p.total = en->total; p.nparts = en->norm_parts; p.g = en->g; p.norm_part = en->norm_part;
+    p.acc = gp.acc + (size_t)pol * (size_t)p.total; p.sums = gp.sums + DCOMP_ACCUM_SUMS * pol;
+    p.stats = gp.stats ? gp.stats + DCOMP_PPO_NUM_STATS * pol : nullptr; p.grad_norm = gp.grad_norm ? gp.grad_norm + pol : nullptr;
+    p.want_norm = gp.want_norm[pol]; p.clip = gp.clip[pol];
+    p.vf_coeff = gp.vf_coeff[pol]; p.ent_coeff = gp.ent_coeff[pol]; p.kl_coeff = gp.kl_coeff[pol];
+    return p;
+}
+
+__global__ __launch_bounds__(256) void norm_group_kernel(const GFParams gp)
+{
+    const int pol = blockIdx.y;
+    if (!gp.active[pol] || !gp.want_norm[pol]) return;
+    const FParams p = group_finish_params(gp, pol);
+    {
+#include "dcomp_learner_norm.inc"
+    }
+}
+
+__global__ __launch_bounds__(256) void finish_group_kernel(const GFParams gp)
+{
+    const int pol = blockIdx.y;
+    if (!gp.active[pol]) return;
+    const FParams p = group_finish_params(gp, pol);
+    {
+#include "dcomp_learner_finish.inc"
+    }
+}
+
+static_assert(sizeof(GLParams) <= 4096 && sizeof(GWParams) <= 4096 && sizeof(GRParams) <= 4096 && sizeof(GAParams) <= 4096 &&
+              sizeof(GCParams) <= 4096 && sizeof(GFParams) <= 4096,
               "the kernel arguments of a grouped launch: lower DCOMP_GROUP_SLICE");
 static_assert(DCOMP_GROUP_SLICE >= 64 && DCOMP_GROUP_SLICE <= 65535, "a slice is a grid's y / z extent");
 
@@ -1075,6 +1078,7 @@ extern "C" int dcomp_learner_group_create(const dcomp_learner_group_cfg *cfg, dc
         e.total = m->plan.total; e.ntask = m->plan.ntask;
         e.beta1 = m->beta1; e.beta2 = m->beta2; e.eps = m->eps;
         e.omb1 = (float)(1.0 - (double)m->beta1); e.omb2 = (float)(1.0 - (double)m->beta2);      // (as launch_adam)
+        e.norm_part = m->norm_part; e.norm_parts = m->norm_parts;
     }
     dcomp_learner_group *g = new dcomp_learner_group();
     g->members.assign(cfg->learners, cfg->learners + P);
@@ -1100,11 +1104,13 @@ extern "C" int dcomp_learner_group_destroy(dcomp_learner_group *g)
     return e == hipSuccess ? DCOMP_OK : fail(DCOMP_EHIP, "dcomp_learner_group_destroy: hipFree failed: %s", hipGetErrorString(e));
 }
 
-extern "C" int dcomp_learner_group_grads(dcomp_learner_group *g, const dcomp_group_batch *b, const dcomp_ppo_hyper *hyper, float *stats_dev, void *stream)
+// the grads and accumulate calls of a group: every check on the host first.  acc / sums (dcomp_learner_group_accum.h, both or neither):
+// the chunk partials go into the caller's [P][flat] running sums instead of the handles' gradients; the callers have checked their
+// own pointers (stats_dev stands for sums_dev there: non-NULL by then)
+static int group_launch(const char *fn, dcomp_learner_group *g, const dcomp_group_batch *b, const dcomp_ppo_hyper *hyper, float *stats_dev, void *stream,
+                        float *acc = nullptr, double *sums = nullptr)
 {
     using namespace dlearn;
-    const char *fn = "dcomp_learner_group_grads";
-    if (!g || !b || !hyper || !stats_dev) return fail(DCOMP_EINVAL, "%s: group, batch, hyper and stats_dev must not be NULL", fn);
     if (int rc = check_struct(fn, "dcomp_group_batch", b->struct_size, sizeof(dcomp_group_batch))) return rc;
     if (!b->rows || !b->index) return fail(DCOMP_EINVAL, "%s: batch.rows and batch.index must not be NULL", fn);
     const int P = (int)g->members.size();
@@ -1134,13 +1140,14 @@ extern "C" int dcomp_learner_group_grads(dcomp_learner_group *g, const dcomp_gro
         GLParams lp;
         GWParams wp;
         GRParams rp;
-        memset(&lp, 0, sizeof(lp)); memset(&wp, 0, sizeof(wp)); memset(&rp, 0, sizeof(rp));
+        GCParams cp;
+        memset(&lp, 0, sizeof(lp)); memset(&wp, 0, sizeof(wp)); memset(&rp, 0, sizeof(rp)); memset(&cp, 0, sizeof(cp));
         int64_t max_rows = 0;
         int nactive = 0;
         for (int i = 0; i < n; i++) {
             const int64_t r = b->rows[first + i];
             const dcomp_ppo_hyper &hy = hyper[first + i];
-            lp.rows[i] = wp.rows[i] = rp.rows[i] = (int32_t)r;                       // (<= max_rows <= 2^28)
+            lp.rows[i] = wp.rows[i] = rp.rows[i] = cp.rows[i] = (int32_t)r;          // (<= max_rows <= 2^28)
             lp.clip[i] = hy.clip_param; lp.vf_clip[i] = hy.vf_clip_param;
             lp.vf_coeff[i] = rp.vf_coeff[i] = hy.vf_loss_coeff; lp.ent_coeff[i] = rp.ent_coeff[i] = hy.entropy_coeff; lp.kl_coeff[i] = rp.kl_coeff[i] = hy.kl_coeff;
             rp.scale[i] = r > 0 ? (float)(1.0 / (double)r) : 0.f;                   // learner_launch's 1 / N: indexed, every position counts
@@ -1154,7 +1161,7 @@ extern "C" int dcomp_learner_group_grads(dcomp_learner_group *g, const dcomp_gro
         const int max_chunks = group_chunks(b->rows + first, n);
         lp.obs = static_cast<const float *>(b->obs); lp.actions = b->actions; lp.old_logp = b->old_logp; lp.old_logits = b->old_logits;
         lp.adv = b->advantages; lp.vtarg = b->value_targets; lp.old_vf = b->old_vf;
-        lp.table = wp.table = rp.table = g->table + first;
+        lp.table = wp.table = rp.table = cp.table = g->table + first;
         lp.index = b->index + (int64_t)first * b->index_stride; lp.index_stride = b->index_stride; lp.source_rows = b->source_rows;
         lp.compact = b->obs_format == DCOMP_ACTOR_COMPACT; lp.num_active = a->net.U;
         rp.stats = stats_dev + (size_t)first * DCOMP_PPO_NUM_STATS;
@@ -1162,7 +1169,80 @@ extern "C" int dcomp_learner_group_grads(dcomp_learner_group *g, const dcomp_gro
         HIP_TRY(hipGetLastError());
         hipLaunchKernelGGL(wgrad_group_kernel, dim3((f->plan.ntask + WAVES - 1) / WAVES, max_chunks, n), dim3(BLOCK), 0, s, wp);
         HIP_TRY(hipGetLastError());
-        hipLaunchKernelGGL(reduce_group_kernel, dim3((f->plan.total + 255) / 256, n), dim3(256), 0, s, rp);
+        if (acc) {
+            cp.acc = acc + (size_t)first * (size_t)f->plan.total; cp.sums = sums + (size_t)first * DCOMP_ACCUM_SUMS;
+            hipLaunchKernelGGL(accumulate_group_kernel, dim3((f->plan.total + 255) / 256, n), dim3(256), 0, s, cp);
+        } else {
+            hipLaunchKernelGGL(reduce_group_kernel, dim3((f->plan.total + 255) / 256, n), dim3(256), 0, s, rp);
+        }
+        HIP_TRY(hipGetLastError());
+    }
+    return DCOMP_OK;
+}
+
+extern "C" int dcomp_learner_group_grads(dcomp_learner_group *g, const dcomp_group_batch *b, const dcomp_ppo_hyper *hyper, float *stats_dev, void *stream)
+{
+    const char *fn = "dcomp_learner_group_grads";
+    if (!g || !b || !hyper || !stats_dev) return fail(DCOMP_EINVAL, "%s: group, batch, hyper and stats_dev must not be NULL", fn);
+    return group_launch(fn, g, b, hyper, stats_dev, stream);
+}
+
+// ---------------------------------------------------------------- include/dcomp_learner_group_accum.h
+extern "C" int dcomp_learner_group_accumulate(dcomp_learner_group *g, const dcomp_group_batch *b, const dcomp_ppo_hyper *hyper, float *acc_dev,
+                                              double *sums_dev, void *stream)
+{
+    const char *fn = "dcomp_learner_group_accumulate";
+    if (!g || !b || !hyper) return fail(DCOMP_EINVAL, "%s: group, batch and hyper must not be NULL", fn);
+    if (!acc_dev || !sums_dev) return fail(DCOMP_EINVAL, "%s: acc_dev and sums_dev must not be NULL", fn);
+    return group_launch(fn, g, b, hyper, reinterpret_cast<float *>(sums_dev), stream, acc_dev, sums_dev);
+}
+
+extern "C" int dcomp_learner_group_accum_finish(dcomp_learner_group *g, const float *acc_dev, const double *sums_dev, const dcomp_ppo_hyper *hyper,
+                                                const float *grad_clip, const int32_t *active, float *stats_dev, float *grad_norm_dev, void *stream)
+{
+    using namespace dlearn;
+    const char *fn = "dcomp_learner_group_accum_finish";
+    if (!g) return fail(DCOMP_EINVAL, "%s: group must not be NULL", fn);
+    if (!acc_dev || !sums_dev) return fail(DCOMP_EINVAL, "%s: acc_dev and sums_dev must not be NULL", fn);
+    if (!hyper) return fail(DCOMP_EINVAL, "%s: hyper must not be NULL", fn);
+    const int P = (int)g->members.size();
+    int nactive = 0;
+    for (int i = 0; i < P; i++) {
+        if (active && !active[i]) continue;
+        nactive++;
+        if (int rc = check_struct(fn, "dcomp_ppo_hyper", hyper[i].struct_size, sizeof(dcomp_ppo_hyper))) return rc;
+        if (grad_clip && !(grad_clip[i] >= 0.f)) return fail(DCOMP_EINVAL, "%s: grad_clip[%d] %g must be >= 0 (0: no clipping)", fn, i, grad_clip[i]);
+    }
+    if (!nactive) return fail(DCOMP_EINVAL, "%s: no member is active", fn);
+    if (int rc = check_device(fn, "the group lives", g->device)) return rc;
+
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const dcomp_learner *f = g->members[0];
+    const int total = f->plan.total;
+    for (int first = 0; first < P; first += GROUP_SLICE) {
+        const int n = P - first < GROUP_SLICE ? P - first : GROUP_SLICE;
+        GFParams fp;
+        memset(&fp, 0, sizeof(fp));
+        bool any = false, any_norm = false;
+        for (int i = 0; i < n; i++) {
+            if (active && !active[first + i]) continue;
+            const dcomp_ppo_hyper &hy = hyper[first + i];
+            const float clip = grad_clip ? grad_clip[first + i] : 0.f;
+            fp.active[i] = 1; any = true;
+            fp.clip[i] = clip; fp.want_norm[i] = clip > 0.f || grad_norm_dev;        // (dcomp_learner_accum_finish's rule)
+            fp.vf_coeff[i] = hy.vf_loss_coeff; fp.ent_coeff[i] = hy.entropy_coeff; fp.kl_coeff[i] = hy.kl_coeff;
+            any_norm = any_norm || fp.want_norm[i];
+        }
+        if (!any) continue;
+        fp.table = g->table + first;
+        fp.acc = acc_dev + (size_t)first * (size_t)total; fp.sums = sums_dev + (size_t)first * DCOMP_ACCUM_SUMS;
+        fp.stats = stats_dev ? stats_dev + (size_t)first * DCOMP_PPO_NUM_STATS : nullptr;
+        fp.grad_norm = grad_norm_dev ? grad_norm_dev + first : nullptr;
+        if (any_norm) {
+            hipLaunchKernelGGL(norm_group_kernel, dim3(f->norm_parts, n), dim3(256), 0, s, fp);
+            HIP_TRY(hipGetLastError());
+        }
+        hipLaunchKernelGGL(finish_group_kernel, dim3((total + 255) / 256, n), dim3(256), 0, s, fp);
         HIP_TRY(hipGetLastError());
     }
     return DCOMP_OK;

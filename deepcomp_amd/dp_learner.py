@@ -14,7 +14,13 @@ The update is written once, as local phases separated by all-reduce points: ``up
 ``(tensor, op)`` wherever the ranks meet and goes on once the tensor holds the reduction.  ``update`` drives it with the process
 group's all-reduce (``nccl``: the device tensor in place; ``gloo``: staged through the host; no group: the identity, torch.distributed
 is not touched); ``run_lockstep`` drives R of them in ONE process, summing each yielded tensor in rank order and writing the sum back
-to every rank -- the same code the ranks run, testable on one GPU."""
+to every rank -- the same code the ranks run, testable on one GPU.
+
+``DataParallelPerUELearner`` is the same for a per-UE policy set (deepcomp_amd.policy_set.PerUELearner, D3-CoMP): one rank's set on
+one rank's shard, the same phases through the same drivers.  The policies' accumulators are one [P, flat] and one [P, 8] tensor
+(include/dcomp_learner_group_accum.h), so the ranks meet exactly twice per minibatch round whatever P is, and a round is the grouped
+update's launch round.  No run on more than one GPU exists yet for either class: lockstep ranks and gloo ranks on one device are what
+has been run."""
 import hashlib
 import math
 import time
@@ -22,7 +28,8 @@ import time
 import numpy as np
 import torch
 
-from .learner import ARRAYS, SUM, close_out, flatten_batch, minibatch_plan, minibatch_stats, sgd_epochs
+from .learner import ARRAYS, SUM, close_out, flatten_batch, minibatch_plan, minibatch_stats, sgd_epochs, standardize
+from .policy_set import group_plan
 
 MIN, MAX = 'min', 'max'
 
@@ -50,24 +57,29 @@ def standardize_phases(adv):
     return standardize_with(adv, m)
 
 
-def shard_agreement_phases(local_rows, minibatch_rows, world, device=None):
+def shard_agreement_phases(local_rows, minibatch_rows, world, device=None, policies=False):
     """Every rank holds the same number of rows and the GLOBAL minibatch divides by the world size: ValueError otherwise, on every
     rank.  One small SUM: of (n, n^2) -- the ranks agree exactly when world x sum n^2 == (sum n)^2 (exact in float64 below 2^26
-    rows).  Returns the rows of this rank's share of a minibatch."""
-    n = int(local_rows)
-    if n < 1 or n >= 1 << 26:
-        raise ValueError(f"a rank's shard has {n} rows: outside [1, 2^26)")
-    t = torch.tensor([float(n), float(n) * float(n)], dtype=torch.float64, device=device)
+    rows).  Returns the rows of this rank's share of a minibatch.  policies: local_rows is a list, the rows of every policy of a
+    per-UE set on this rank (0: a policy without slots, on every rank); the one SUM is of a [P, 2] tensor, the policy that differs
+    is named, and the share returned is the common one, before a policy's own row count caps it (None: whole batches)."""
+    ns = [int(n) for n in local_rows] if policies else [int(local_rows)]
+    for n in ns:
+        if n < (0 if policies else 1) or n >= 1 << 26:
+            raise ValueError(f"a rank's shard has {n} rows: outside [1, 2^26)")
+    t = torch.tensor([[float(n), float(n) * float(n)] for n in ns], dtype=torch.float64, device=device)
+    t = t if policies else t[0]
     yield t, SUM
-    s1, s2 = t.tolist()
-    if world * s2 != s1 * s1:
-        raise ValueError(f"the ranks hold different numbers of rows (this rank {n}, mean {s1 / world:g}): a data-parallel update needs equal shards")
+    for p, (n, (s1, s2)) in enumerate(zip(ns, t.reshape(-1, 2).tolist())):
+        if world * s2 != s1 * s1:
+            raise ValueError(f"the ranks hold different numbers of rows{f' of policy {p}' if policies else ''} (this rank {n}, mean {s1 / world:g}): "
+                             "a data-parallel update needs equal shards")
     if minibatch_rows is None:
-        return n
+        return None if policies else ns[0]
     mb = int(minibatch_rows)
     if mb < world or mb % world:
         raise ValueError(f"minibatch_rows {mb} is the GLOBAL minibatch: it must be a positive multiple of the world size {world}")
-    return min(mb // world, n)
+    return mb // world if policies else min(mb // world, ns[0])
 
 
 def drive(phases, reduce):
@@ -181,6 +193,66 @@ class DataParallelLearner:
     def check_sync(self):
         """Raise RuntimeError when the ranks' master weights differ; returns this rank's sha256 of them."""
         return drive(self.check_sync_phases(), self._reduce)
+
+
+class DataParallelPerUELearner(DataParallelLearner):
+    """One rank of a data-parallel per-UE policy set.  per_ue_learner: this rank's PerUELearner (every rank built from the same
+    weights and hyper-parameters); group, rank, world as DataParallelLearner takes them.  The same drivers run it: update() with the
+    process group's all-reduce, run_lockstep() R of them in one process."""
+
+    def __init__(self, per_ue_learner, group=None, rank=None, world=None):
+        super().__init__(per_ue_learner, group, rank, world)
+        self.set = per_ue_learner
+
+    def update_phases(self, batch, num_sgd_iter=30, minibatch_rows=None, micro_rows=None, seed=0, grad_clip=None):
+        """update() as a generator of local phases (DataParallelLearner.update_phases).  Returns update()'s result."""
+        S, dev = self.set, self.set.device
+        P, first = len(S.learners), S.learners[0]
+        src, N, compact = flatten_batch(first.actor, batch)
+        rows = S.rows_of(N)
+        n_of = [int(r.numel()) for r in rows]
+        share = yield from shard_agreement_phases(n_of, minibatch_rows, self.world, dev, policies=True)
+        plan = group_plan(n_of, share, [ln.max_rows for ln in S.learners], micro_rows, grad_clip, accumulate=True,
+                          noun="a rank's share of a policy's minibatch is {} rows", hint=": give micro_rows")
+        adv = torch.zeros_like(src['advantages'])
+        mine = [src['advantages'].index_select(0, rows[p]) for p in range(P)]
+        if self.world == 1:                                      # nobody to add moments with: the set's own rule, the grouped update's bits
+            done = [standardize(a) if a.numel() else a for a in mine]
+        else:                                                    # per policy over the global rows: ONE SUM of the [P, 3] moments
+            moments = torch.stack([advantage_moments(a) for a in mine])
+            yield moments, SUM
+            done = [standardize_with(a, m) if a.numel() else a for a, m in zip(mine, moments.cpu())]
+        for p in range(P):
+            adv.index_copy_(0, rows[p], done[p])
+        # each rank shuffles its own rows of each policy; the statistics come from the reduced sums: the same numbers, and so the
+        # same kl_coeff per policy, on every rank
+        seeds = [int(seed) + p + P * self.rank for p in range(P)]
+        return (yield from S.grouped_phases(src, rows, adv, plan, int(num_sgd_iter), seeds, grad_clip, lap=self._lap))
+
+    def update(self, batch, num_sgd_iter=30, minibatch_rows=None, micro_rows=None, seed=0, grad_clip=None):
+        """PerUELearner.update(grouped=True) on this rank's shard of a collect(env, per_ue_actor, ..., dist_inputs=True) batch, in
+        step with the other ranks.  Per policy the ranks must hold equally many rows; minibatch_rows is the GLOBAL per-policy
+        minibatch (a multiple of the world size; default: a policy's whole batch), of which each rank trains its 1 / world;
+        micro_rows as in PerUELearner.update, per rank.  The advantages are standardised per policy over the global rows (one SUM of
+        a [P, 3] moments tensor); policy p on rank r permutes its rows with a generator seeded seed + p + P r -- a world of one is
+        the grouped update, bit for bit, and standardises as it does; per minibatch round: zeroed [P, flat] / [P, 8] accumulators,
+        one grouped accumulate per micro-batch round, all-reduce of acc and of sums, grouped finish (1 / N of the global count per
+        policy, grad_clip per policy's gradient), grouped apply.  kl_coeff is adapted per policy from the global statistics.  Returns
+        one dict per policy (None for a policy no slot maps to)."""
+        return drive(self.update_phases(batch, num_sgd_iter, minibatch_rows, micro_rows, seed, grad_clip), self._reduce)
+
+    def check_sync_phases(self):
+        """One MIN and one MAX over the ranks of [P, 4] checksum words (62 bits each of the sha256 of a policy's master weights):
+        RuntimeError naming the policies whose weights differ.  Returns this rank's sha256 per policy."""
+        digests = [bytes.fromhex(weights_checksum(ln.read('weights'))) for ln in self.set.learners]
+        lo = torch.tensor([[int.from_bytes(d[8 * i:8 * i + 8], 'little') >> 2 for i in range(4)] for d in digests], dtype=torch.int64, device=self.set.device)
+        hi = lo.clone()
+        yield lo, MIN
+        yield hi, MAX
+        differ = torch.nonzero((lo != hi).any(1)).reshape(-1).tolist()
+        if differ:
+            raise RuntimeError(f"rank {self.rank}: the ranks' master weights differ for policy {', '.join(map(str, differ))}")
+        return [d.hex() for d in digests]
 
 
 def run_lockstep(dp_learners, batches=None, *, phases='update', host_staged=False, seconds=None, **kw):

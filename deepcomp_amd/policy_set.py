@@ -13,6 +13,13 @@ launch gives each wavefront 32 envs of ONE UE slot with that slot's weights and 
 so ``sampler.collect``, the advantages and the env step are the shared policy's.  The set copies no weights: it holds pointers into
 its members' device images, and a member's learner rewrites those in place -- the set's next launch runs the trained weights.
 
+``update(grouped=True)`` trains all policies in one launch round per minibatch round (include/dcomp_learner_group.h), and
+``update(micro_rows=, grad_clip=)`` trains minibatches larger than the handles micro-batch by micro-batch and clips each policy's
+gradient by its global norm, sequential or grouped (include/dcomp_learner_group_accum.h: the policies' accumulators are one [P, flat]
+and one [P, 8] tensor, a micro-batch round and a finish are one launch round each).  ``group_plan`` lays the policies' minibatches and
+micro-batches side by side; ``PerUELearner.grouped_phases`` is the one grouped SGD loop, which ``update`` drains and
+deepcomp_amd.dp_learner.DataParallelPerUELearner drives across the ranks of a data-parallel set.
+
 Members are ``multi`` actors of one shape (UE slots, stations, hidden width, activation, device), all without a value function or
 all with a value trunk of their own; attach value functions BEFORE building the set -- its table holds the trunks the members have then,
 and once a member gets one afterwards every call on the set raises ValueError (build a new set).  Central members (one network by construction) and a shared value function are refused
@@ -24,7 +31,7 @@ import torch
 
 from . import _lib
 from .actor import FcnetActor, _ActorLaunch
-from .learner import INPUT, INPUTS, PPOLearner, close_out, field_pointers, fill, flatten_batch, minibatch_plan, sgd_epochs, standardize
+from .learner import INPUT, INPUTS, SUM, PPOLearner, close_out, field_pointers, fill, flatten_batch, minibatch_plan, sgd_epochs, standardize
 
 
 def default_slot_policy(num_ue, num_policies):
@@ -40,6 +47,33 @@ def policy_rows(num_rows, num_ue, slot_policy, num_policies, device=None):
         raise ValueError(f"slot_policy has {sp.numel()} entries, the env {num_ue} UE slots")
     of_row = sp[torch.arange(int(num_rows), device=device) % int(num_ue)]
     return [torch.nonzero(of_row == p).reshape(-1) for p in range(int(num_policies))]
+
+
+def group_plan(n_of, minibatch_rows, max_rows_of, micro_rows=None, grad_clip=None, accumulate=False, **wording):
+    """The launch rounds of a grouped SGD iteration over P policies with n_of[p] rows each: minibatch_plan() per policy (its checks,
+    its refusals; wording: its noun / hint), then the policies' minibatches and micro-batches side by side.  Returns (accumulated,
+    taken, rounds): whether the minibatches go through the accumulators (micro_rows, grad_clip or accumulate given); per policy the
+    minibatch rounds it takes part in (0: a policy without rows); and per minibatch round k the pair (rows, micro) -- rows[p] the
+    positions of policy p's k-th minibatch (0: it has none left and sits the round out), micro the round's launches, each (offset,
+    rows): policy p trains positions [offset, offset + rows[p]) of its own permutation.  Policy p's positions are the ones its own
+    PPOLearner.update(rows=..., micro_rows=...) takes: minibatch k at k mb_p, micro-batch j of it at j micro_p behind that.  One offset
+    serves all policies because a policy's minibatch is the common `step` rows unless it has fewer rows than that (then it is its one
+    minibatch, in round 0), and its micro-batch the common one unless its minibatch is smaller (then it is its one micro-batch)."""
+    P = len(n_of)
+    mb_of, micro_of, accumulated = [0] * P, [0] * P, bool(accumulate)
+    for p in range(P):
+        if n_of[p]:
+            mb_of[p], micro_of[p], acc_p = minibatch_plan(n_of[p], minibatch_rows, max_rows_of[p], micro_rows, grad_clip, **wording)
+            accumulated = accumulated or acc_p
+    step, micro_step = max(mb_of), max(micro_of)
+    taken = [(n_of[p] + mb_of[p] - 1) // mb_of[p] if mb_of[p] else 0 for p in range(P)]
+    rounds = []
+    for k in range(max(taken)):
+        rows = [max(0, min(mb_of[p], n_of[p] - k * step)) if mb_of[p] else 0 for p in range(P)]
+        launches = max((rows[p] + micro_of[p] - 1) // micro_of[p] for p in range(P) if rows[p])
+        rounds.append((rows, [(k * step + j * micro_step, [max(0, min(micro_of[p], rows[p] - j * micro_step)) if rows[p] else 0 for p in range(P)])
+                              for j in range(launches)]))
+    return accumulated, taken, rounds
 
 
 class PerUEActor(_ActorLaunch):
@@ -130,7 +164,9 @@ class PerUELearner:
     should be a policy's minibatch, not the batch.  ``update`` runs the P updates one after the other, P x minibatches x (gathers +
     four launches), so small per-policy batches are bound by launches; ``update(grouped=True)`` trains all policies in one launch
     round per minibatch round (include/dcomp_learner_group.h) and leaves every learner in the same state, bit for bit.  The two can
-    be mixed with each other and with calls on a member learner."""
+    be mixed with each other and with calls on a member learner.  ``update(micro_rows=, grad_clip=)`` are PPOLearner.update's, per
+    policy, on both paths: grouped, the policies' accumulators are one [P, flat] and one [P, 8] tensor and a micro-batch round is one
+    launch round (include/dcomp_learner_group_accum.h); with micro_rows the workspaces are sized by the micro-batch, P times over."""
 
     def __init__(self, actor, **ppo_kwargs):
         if not isinstance(actor, PerUEActor):
@@ -159,7 +195,7 @@ class PerUELearner:
             self._split = {num_rows: policy_rows(num_rows, a.U, a.slot_policy, a.num_policies, self.device)}
         return self._split[num_rows]
 
-    def update(self, batch, num_sgd_iter=30, minibatch_rows=None, seed=0, grouped=False):
+    def update(self, batch, num_sgd_iter=30, minibatch_rows=None, seed=0, grouped=False, micro_rows=None, grad_clip=None):
         """PPO's SGD phase on one collect(env, per_ue_actor, ..., dist_inputs=True) batch, rows or compact record: policy p's
         PPOLearner.update on the source rows whose UE slot maps to p (rows=), with seed + p.  Returns one statistics dict per policy
         (None for a policy no slot maps to, whose state stays untouched).
@@ -168,11 +204,20 @@ class PerUELearner:
         advantage standardisation, its own permutations (a generator seeded seed + p), its own minibatch boundaries, Adam state and
         kl_coeff; round k hands every policy its k-th minibatch through one [P, rows] index into the batch where it lies (both batch
         formats), and a policy with fewer minibatches sits the later rounds out.  One synchronisation at the end.  The learners'
-        states and the returned statistics are those of grouped=False, bit for bit."""
+        states and the returned statistics are those of grouped=False, bit for bit.
+
+        micro_rows / grad_clip (both None: the paths above, unchanged) are PPOLearner.update's, per policy: a minibatch is trained as
+        zeroed accumulators, one accumulate per micro-batch of micro_rows positions, finish (1 / N of the policy's minibatch, the
+        global-norm clip of that policy's gradient) and apply; a policy's minibatch may then be larger than max_rows.  Sequential,
+        the two are handed to every member's update.  Grouped, a minibatch round zeroes the [P, flat] / [P, 8] accumulators, makes one
+        dcomp_learner_group_accumulate per micro-batch round (a policy whose minibatch is exhausted sits it out), one
+        dcomp_learner_group_accum_finish and one dcomp_learner_group_apply: the sequential update with the same arguments, bit for
+        bit."""
         rows = self.rows_of(int(batch['actions'].numel()))
         if grouped:
-            return self._update_grouped(batch, rows, int(num_sgd_iter), minibatch_rows, int(seed))
-        return [ln.update(batch, num_sgd_iter=num_sgd_iter, minibatch_rows=minibatch_rows, seed=int(seed) + p, rows=rows[p], check_rows=False)
+            return self._update_grouped(batch, rows, int(num_sgd_iter), minibatch_rows, int(seed), micro_rows, grad_clip)
+        return [ln.update(batch, num_sgd_iter=num_sgd_iter, minibatch_rows=minibatch_rows, seed=int(seed) + p, rows=rows[p], check_rows=False,
+                          micro_rows=micro_rows, grad_clip=grad_clip)
                 if rows[p].numel() else None                     # (check_rows: policy_rows() built them, distinct and in range)
                 for p, ln in enumerate(self.learners)]
 
@@ -187,49 +232,161 @@ class PerUELearner:
             self._group = h
         return self._group
 
-    def _update_grouped(self, batch, rows, num_sgd_iter, minibatch_rows, seed):
-        L, dev = self.actor._L, self.device
-        first, P = self.learners[0], len(self.learners)
-        src, N, compact = flatten_batch(first.actor, batch)
-        obs, fmt, _ = first._source_obs(src)
-        live = [p for p in range(P) if rows[p].numel()]
-        # every policy's advantages standardised over its own rows (PPOLearner.update's rule), back in source order in ONE tensor: the
-        # row sets are disjoint
-        adv = torch.zeros_like(src['advantages'])
-        n_of, mb_of = [int(rows[p].numel()) for p in range(P)], [0] * P
-        for p in live:
-            mb_of[p] = minibatch_plan(n_of[p], minibatch_rows, self.learners[p].max_rows)[0]
-            adv.index_copy_(0, rows[p], standardize(src['advantages'].index_select(0, rows[p])))
-        ptr = field_pointers(first.actor, dict({n: src[n] for n in INPUTS}, advantages=adv), {INPUT: N})
-        # round k: positions [k step, k step + mb_p) of every policy that has that many.  A policy's minibatch is `step` rows unless
-        # it has fewer rows than that -- then it is its one minibatch, in round 0
-        step = max(mb_of)
-        taken = {p: (n_of[p] + mb_of[p] - 1) // mb_of[p] for p in live}
-        rounds = max(taken.values())
-        stride = max(n_of)
-        index = torch.zeros((P, stride), dtype=torch.int32, device=dev)
-        stats = torch.zeros((rounds, P, _lib.PPO_NUM_STATS), dtype=torch.float32, device=dev)
-        epochs = {p: sgd_epochs(n_of[p], num_sgd_iter, seed + p, dev) for p in live}
-        hyper = (_lib.DcompPpoHyper * P)(*[ln._hyper_struct() for ln in self.learners])
-        lr = (ctypes.c_float * P)(*[ln.lr for ln in self.learners])
-        round_rows = [(ctypes.c_int64 * P)(*[max(0, min(mb_of[p], n_of[p] - k * step)) if mb_of[p] else 0 for p in range(P)]) for k in range(rounds)]
-        round_active = [(ctypes.c_int32 * P)(*[1 if r else 0 for r in rr]) for rr in round_rows]
-        g = self._group_handle()
-        b = fill(_lib.DcompGroupBatch, obs_format=fmt, source_rows=N, obs=obs.data_ptr(), index_stride=stride, **ptr)
-        with torch.cuda.device(dev):
-            stream = first.actor._stream()
-            for _ in range(num_sgd_iter):
-                for p in live:
-                    index[p, :n_of[p]] = rows[p].index_select(0, next(epochs[p]))
-                for k in range(rounds):
-                    b.index, b.rows = index.data_ptr() + 4 * k * step, round_rows[k]
-                    _lib.check(L.dcomp_learner_group_grads(g, ctypes.byref(b), hyper, ctypes.c_void_p(stats[k].data_ptr()), stream))
-                    _lib.check(L.dcomp_learner_group_apply(g, lr, round_active[k], stream))
+    # ------------------------------------------------------------------ the group's calls (include/dcomp_learner_group.h, dcomp_learner_group_accum.h)
+    @property
+    def flat_size(self):
+        """Elements of a member's flat gradient array (the members have one shape)."""
+        return self.learners[0].flat_size
+
+    def new_accumulators(self):
+        """(acc float32 [P, flat_size], sums float64 [P, 8]) on the set's device, zeroed: row p is policy p's PPOLearner.new_accumulators()."""
+        P = len(self.learners)
+        return (torch.zeros((P, self.flat_size), dtype=torch.float32, device=self.device),
+                torch.zeros((P, _lib.ACCUM_SUMS), dtype=torch.float64, device=self.device))
+
+    def _accumulators(self, acc, sums):
+        P, a = len(self.learners), self.learners[0].actor
+        a._check(acc, torch.float32, P * self.flat_size, 'acc')
+        a._check(sums, torch.float64, P * _lib.ACCUM_SUMS, 'sums')
+        return ctypes.c_void_p(acc.data_ptr()), ctypes.c_void_p(sums.data_ptr())
+
+    def _per_policy(self, ctype, values, what):
+        """A host array [P] of a per-policy argument: one number for all, or one per policy."""
+        P = len(self.learners)
+        values = [values] * P if not isinstance(values, (list, tuple)) else list(values)
+        if len(values) != P:
+            raise ValueError(f"{what} has {len(values)} entries for {P} policies")
+        return (ctype * P)(*values)
+
+    def group_batch(self, source, index):
+        """The batch of the group's calls: source a dict of the flattened sample-batch tensors as PPOLearner.grads_indexed takes it
+        ('obs' or 'obs_compact', and the six per-row inputs, the advantages standardised by the caller), index a contiguous int32
+        [P, stride] device tensor: row p holds policy p's positions -> source rows.  The tensors must outlive the calls made with it."""
+        first = self.learners[0]
+        obs, fmt, N = first._source_obs(source)
+        if not isinstance(index, torch.Tensor) or index.dim() != 2 or index.shape[0] != len(self.learners) or index.shape[1] < 1:
+            raise ValueError(f"index must be a contiguous int32 [{len(self.learners)}, stride] device tensor")
+        first.actor._check(index, torch.int32, index.numel(), 'index')
+        ptr = field_pointers(first.actor, {n: source.get(n) for n in INPUTS}, {INPUT: N})
+        return fill(_lib.DcompGroupBatch, obs_format=fmt, source_rows=N, obs=obs.data_ptr(), index=index.data_ptr(), index_stride=int(index.shape[1]), **ptr)
+
+    def _hypers(self):
+        """The HOST array of the policies' hyper-parameters as they are now (kl_coeff adapts per policy, at the end of an update)."""
+        return (_lib.DcompPpoHyper * len(self.learners))(*[ln._hyper_struct() for ln in self.learners])
+
+    def _active(self, active):
+        return active if active is None or isinstance(active, ctypes.Array) else self._per_policy(ctypes.c_int32, [1 if x else 0 for x in active], 'active')
+
+    def _group_call(self, entry, gb, rows, offset, *args, hyper=None):
+        """grads or accumulate on positions [offset, offset + rows[p]) of every policy's index row."""
+        rows = rows if isinstance(rows, ctypes.Array) else self._per_policy(ctypes.c_int64, [int(r) for r in rows], 'rows')
+        if offset < 0 or offset + max(rows) > gb.index_stride:
+            raise ValueError(f"offset {offset} + rows reaches past the index's stride {gb.index_stride}")
+        b = type(gb).from_buffer_copy(gb)                        # (the stride stays: policy p's row begins p strides behind the pointer)
+        b.index, b.rows = gb.index + 4 * int(offset), rows
+        with torch.cuda.device(self.device):
+            _lib.check(getattr(self.actor._L, entry)(self._group_handle(), ctypes.byref(b), hyper or self._hypers(), *args, self.learners[0].actor._stream()))
+
+    def accumulate_grouped(self, gb, rows, acc, sums, offset=0, hyper=None):
+        """PPOLearner.accumulate_indexed for every policy with rows[p] > 0, in one launch round: policy p's positions [offset, offset
+        + rows[p]) of its row of the index of gb (group_batch()) are added to acc[p] / sums[p].  Nothing else is written."""
+        self._group_call('dcomp_learner_group_accumulate', gb, rows, offset, *self._accumulators(acc, sums), hyper=hyper)
+
+    def finish_grouped(self, acc, sums, grad_clip=None, active=None, stats=None, grad_norm=None, hyper=None):
+        """PPOLearner.finish for every policy with active[p] (None: all), in one launch round: policy p's gradients from acc[p] /
+        sums[p], clipped by grad_clip (a number for all or one per policy; None / 0: no clipping), its statistics into stats[p] (a
+        float32 [P, 5] device tensor, returned; allocated when None), its gradient norm into grad_norm[p] (float32 [P], optional).
+        An inactive policy keeps its gradients, its row of stats and its entry of grad_norm.  acc and sums are read only."""
+        P, a = len(self.learners), self.learners[0].actor
+        clip = grad_clip
+        if not isinstance(clip, ctypes.Array):
+            each = grad_clip if isinstance(grad_clip, (list, tuple)) else [grad_clip] * P
+            clip = self._per_policy(ctypes.c_float, [0.0 if c is None else float(c) for c in each], 'grad_clip')
+        if not all(c >= 0.0 for c in clip):
+            raise ValueError(f"grad_clip {grad_clip!r} must be >= 0 (None or 0: no clipping)")
+        pa, ps = self._accumulators(acc, sums)
+        if stats is None:
+            stats = torch.zeros((P, _lib.PPO_NUM_STATS), dtype=torch.float32, device=self.device)
+        a._check(stats, torch.float32, P * _lib.PPO_NUM_STATS, 'stats')
+        if grad_norm is not None:
+            a._check(grad_norm, torch.float32, P, 'grad_norm')
+        with torch.cuda.device(self.device):
+            _lib.check(self.actor._L.dcomp_learner_group_accum_finish(self._group_handle(), pa, ps, hyper or self._hypers(), clip, self._active(active), ctypes.c_void_p(stats.data_ptr()),
+                                                                      ctypes.c_void_p(grad_norm.data_ptr()) if grad_norm is not None else None, a._stream()))
+        return stats
+
+    def apply_grouped(self, active=None, lr=None):
+        """PPOLearner.apply for every policy with active[p] (None: all), each with its own lr, in one launch."""
+        lr = lr or self._per_policy(ctypes.c_float, [ln.lr for ln in self.learners], 'lr')
+        with torch.cuda.device(self.device):
+            _lib.check(self.actor._L.dcomp_learner_group_apply(self._group_handle(), lr, self._active(active), self.learners[0].actor._stream()))
+
+    # ------------------------------------------------------------------ the grouped training step
+    def grouped_phases(self, src, rows, adv, plan, num_sgd_iter, seeds, grad_clip=None, lap=lambda name=None: None):
+        """The grouped SGD phase as a generator: src the flattened batch (flatten_batch()), rows the policies' source rows, adv every
+        policy's standardised advantages in source order, plan = group_plan(...), seeds[p] the seed of policy p's permutations.  Per
+        minibatch round of an accumulated plan: zeroed accumulators, one accumulate_grouped per micro-batch round, then (acc, SUM) and
+        (sums, SUM) are yielded -- where the ranks of a data-parallel set add theirs together; one set just goes on -- then
+        finish_grouped and apply_grouped with the round's active mask.  A plan that is not accumulated makes one
+        dcomp_learner_group_grads and one apply per round and yields nothing.  Returns update()'s result."""
+        dev, P = self.device, len(self.learners)
+        accumulated, taken, rounds = plan
+        n_of = [int(rows[p].numel()) for p in range(P)]
+        live = [p for p in range(P) if n_of[p]]
+        index = torch.zeros((P, max(n_of)), dtype=torch.int32, device=dev)
+        gb = self.group_batch(dict(src, advantages=adv), index)
+        stats = torch.zeros((len(rounds), P, _lib.PPO_NUM_STATS), dtype=torch.float32, device=dev)
+        epochs = {p: sgd_epochs(n_of[p], num_sgd_iter, seeds[p], dev) for p in live}
+        as_rows = lambda rr: (ctypes.c_int64 * P)(*rr)         # noqa: E731
+        round_active = [(ctypes.c_int32 * P)(*[1 if r else 0 for r in rr]) for rr, _ in rounds]
+        launches = [[(off, as_rows(rr)) for off, rr in micro] for _, micro in rounds]
+        hyper, lr = self._hypers(), self._per_policy(ctypes.c_float, [ln.lr for ln in self.learners], 'lr')
+        if accumulated:
+            acc, sums = self.new_accumulators()
+            grad_clip = self._per_policy(ctypes.c_float, 0.0 if grad_clip is None else float(grad_clip), 'grad_clip')
+        for _ in range(num_sgd_iter):
+            for p in live:
+                index[p, :n_of[p]] = rows[p].index_select(0, next(epochs[p]))
+            for k in range(len(rounds)):
+                lap()
+                if accumulated:
+                    acc.zero_()
+                    sums.zero_()
+                    for off, rr in launches[k]:
+                        self.accumulate_grouped(gb, rr, acc, sums, off, hyper)
+                    lap('accumulate')
+                    yield acc, SUM
+                    yield sums, SUM
+                    lap('reduce')
+                    self.finish_grouped(acc, sums, grad_clip, round_active[k], stats[k], hyper=hyper)
+                    lap('finish')
+                else:
+                    (off, rr), = launches[k]
+                    self._group_call('dcomp_learner_group_grads', gb, rr, off, ctypes.c_void_p(stats[k].data_ptr()), hyper=hyper)
+                self.apply_grouped(round_active[k], lr)
+                lap('apply')
         # a policy's mean over the rounds it took part in: PPOLearner.update's own reduction of its own [minibatches, 5] tensor
         out = [None] * P
         for p, st in zip(live, close_out([self.learners[p] for p in live], torch.stack([stats[:taken[p], p].contiguous().mean(0) for p in live]))):
             out[p] = st
         return out
+
+    def _update_grouped(self, batch, rows, num_sgd_iter, minibatch_rows, seed, micro_rows=None, grad_clip=None):
+        first, P = self.learners[0], len(self.learners)
+        src, N, compact = flatten_batch(first.actor, batch)
+        # every policy's advantages standardised over its own rows (PPOLearner.update's rule), back in source order in ONE tensor: the
+        # row sets are disjoint
+        adv = torch.zeros_like(src['advantages'])
+        plan = group_plan([int(rows[p].numel()) for p in range(P)], minibatch_rows, [ln.max_rows for ln in self.learners], micro_rows, grad_clip)
+        for p in range(P):
+            if rows[p].numel():
+                adv.index_copy_(0, rows[p], standardize(src['advantages'].index_select(0, rows[p])))
+        phases = self.grouped_phases(src, rows, adv, plan, num_sgd_iter, [seed + p for p in range(P)], grad_clip)
+        try:
+            while True:
+                next(phases)                                     # (one set: nothing to add together)
+        except StopIteration as stop:
+            return stop.value
 
     def get_weights(self):
         """[(weights, value_weights)] per policy; refreshes the members' host copies (PPOLearner.get_weights)."""
@@ -250,4 +407,4 @@ class PerUELearner:
             ln.load_state_dict(st)
 
 
-__all__ = ['PerUEActor', 'PerUELearner', 'policy_rows', 'default_slot_policy']
+__all__ = ['PerUEActor', 'PerUELearner', 'policy_rows', 'default_slot_policy', 'group_plan']

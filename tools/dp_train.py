@@ -2,7 +2,7 @@
 """One data-parallel PPO step end to end: env shards, collect, DataParallelLearner.update, check_sync.
 
     python tools/dp_train.py --world 2 [--backend nccl|gloo] [--same-device] [--envs 64 --ues 4 --bs 5 --steps 8 --hidden 32]
-                             [--sgd-iters 1] [--minibatch GLOBAL_ROWS] [--micro-rows ROWS] [--grad-clip NORM] [--compact]
+                             [--sgd-iters 1] [--minibatch GLOBAL_ROWS] [--micro-rows ROWS] [--grad-clip NORM] [--compact] [--per-ue]
     python tools/dp_train.py --lockstep 2 [...]
 
 --world N: this command starts N ranks as fresh child processes (RANK / WORLD_SIZE / MASTER_* in their environment), each with a
@@ -13,7 +13,11 @@ sha256 of its master weights (equal, or check_sync has raised), the statistics a
 uses cuda:0 (a dry run on one GPU; with --backend gloo the reductions are staged through the host).
 
 --lockstep R: the same R ranks in ONE process on one GPU through deepcomp_amd.dp_learner.run_lockstep, the reductions staged through
-the host: the same phases, the same bits (a sum of two f32 terms does not depend on the order), no process group."""
+the host: the same phases, the same bits (a sum of two f32 terms does not depend on the order), no process group.
+
+--per-ue: one policy per UE slot (deepcomp_amd.policy_set: a PerUEActor collects, a DataParallelPerUELearner trains the set's policies
+together); --minibatch is then the GLOBAL minibatch PER POLICY, the statistics are a list with one entry per policy, and a rank's
+sha256 is taken over its policies' sha256 in order."""
 import argparse
 import json
 import os
@@ -40,6 +44,7 @@ def parse():
     ap.add_argument('--micro-rows', type=int, default=0, help='rows per micro-batch of a rank (a multiple of 2048)')
     ap.add_argument('--grad-clip', type=float, default=0.0)
     ap.add_argument('--compact', action='store_true', help='collect the compact record and train on it through the row index')
+    ap.add_argument('--per-ue', action='store_true', help='one policy per UE slot, trained as a data-parallel per-UE set')
     ap.add_argument('--seed', type=int, default=0)
     ap.add_argument('--lr', type=float, default=1e-3)
     ap.add_argument('--timeout', type=float, default=300.0, help='seconds a child may take')
@@ -107,17 +112,31 @@ def make_rank(a, rank, world, dev):
         raise SystemExit('dp_train.py: build the HIP extension first (python -m deepcomp_amd.build)')
     scn = scenarios.grid_map(a.bs, 'mixed').with_ues(num_slow=a.ues)
     env = make_sharded_env(scn, 'multi', a.envs * world, rank, world, device=dev, seed=42, episode_length=100, rng='philox', rand_episodes=True)
+    local_rows = a.envs * a.steps * (1 if a.per_ue else a.ues)       # (per policy: every UE slot has its own)
+    share = min(a.minibatch // world, local_rows) if a.minibatch else local_rows
+    if a.per_ue:
+        from deepcomp_amd.policy_set import PerUEActor, PerUELearner
+        return env, PerUELearner(PerUEActor.random(a.ues, a.bs, a.hidden, 'tanh', seed=1, bias_std=0.1, device=dev), lr=a.lr, max_rows=a.micro_rows or share)
     w = FcnetActor.random_weights('multi', a.ues, a.bs, a.hidden, seed=1, bias_std=0.1)
     vw = FcnetActor.random_value_weights('multi', a.ues, a.bs, a.hidden, seed=1, bias_std=0.1)
     actor = FcnetActor('multi', a.ues, a.bs, w, activation='tanh', device=dev, value_weights=vw)
-    local_rows = a.envs * a.ues * a.steps
-    share = min(a.minibatch // world, local_rows) if a.minibatch else local_rows
     return env, PPOLearner(actor, lr=a.lr, max_rows=a.micro_rows or share)
 
 
 def update_args(a):
     return dict(num_sgd_iter=a.sgd_iters, minibatch_rows=a.minibatch or None, micro_rows=a.micro_rows or None, seed=a.seed,
                 grad_clip=a.grad_clip or None)
+
+
+def dp_of(a, learner, **kw):
+    from deepcomp_amd.dp_learner import DataParallelLearner, DataParallelPerUELearner
+    return (DataParallelPerUELearner if a.per_ue else DataParallelLearner)(learner, **kw)
+
+
+def one_sha(sha):
+    """check_sync's result as one sha256: a set's is taken over its policies' in order."""
+    import hashlib
+    return sha if isinstance(sha, str) else hashlib.sha256(''.join(sha).encode()).hexdigest()
 
 
 def report(a, mode, world, shas, stats, seconds, t_collect, t_update):
@@ -129,7 +148,6 @@ def report(a, mode, world, shas, stats, seconds, t_collect, t_update):
 def child(a):
     import torch
     import torch.distributed as dist
-    from deepcomp_amd.dp_learner import DataParallelLearner
     from deepcomp_amd.sampler import collect
     rank, world = int(os.environ['RANK']), int(os.environ['WORLD_SIZE'])
     if not a.same_device and torch.cuda.device_count() < world:
@@ -147,12 +165,12 @@ def child(a):
         batch = collect(env, learner.actor, a.steps, 0.99, 0.95, dist_inputs=True, compact=a.compact)
         torch.cuda.synchronize(dev)
         t1 = time.perf_counter()
-        dp = DataParallelLearner(learner, group=dist.group.WORLD)
+        dp = dp_of(a, learner, group=dist.group.WORLD)
         dp.profile = True
         stats = dp.update(batch, **update_args(a))
         torch.cuda.synchronize(dev)
         t2 = time.perf_counter()
-        sha = dp.check_sync()
+        sha = one_sha(dp.check_sync())
         # every rank's sha256 on rank 0: one SUM of a [world, 32] table in which a rank fills its own row
         table = torch.zeros((world, 32), dtype=torch.int64, device=dev)
         table[rank] = torch.tensor(list(bytes.fromhex(sha)), dtype=torch.int64, device=dev)
@@ -166,7 +184,7 @@ def child(a):
 
 def lockstep(a):
     import torch
-    from deepcomp_amd.dp_learner import DataParallelLearner, run_lockstep
+    from deepcomp_amd.dp_learner import run_lockstep
     from deepcomp_amd.sampler import collect
     R = a.lockstep
     dev = torch.device('cuda', 0)
@@ -177,14 +195,14 @@ def lockstep(a):
     batches = [collect(env, learner.actor, a.steps, 0.99, 0.95, dist_inputs=True, compact=a.compact) for env, learner in ranks]
     torch.cuda.synchronize(dev)
     t1 = time.perf_counter()
-    dps = [DataParallelLearner(learner, rank=r, world=R) for r, (_, learner) in enumerate(ranks)]
+    dps = [dp_of(a, learner, rank=r, world=R) for r, (_, learner) in enumerate(ranks)]
     for d in dps:
         d.profile = True
     reduce_s = {}
     stats = run_lockstep(dps, batches, host_staged=True, seconds=reduce_s, **update_args(a))
     torch.cuda.synchronize(dev)
     t2 = time.perf_counter()
-    shas = run_lockstep(dps, phases='check_sync', host_staged=True)
+    shas = [one_sha(s) for s in run_lockstep(dps, phases='check_sync', host_staged=True)]
     # per rank: the local phases; the reductions: the driver's clock (a rank's own also sees the other ranks' phases)
     seconds = {k: sum(d.seconds[k] for d in dps) / R for k in ('accumulate', 'finish', 'apply')}
     seconds['reduce'] = reduce_s.get('reduce', 0.0)
