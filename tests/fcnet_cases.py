@@ -11,14 +11,16 @@ log-sum-exp walk and of the loss epilogue, which show that the stated bounds are
 
 To extend: a new template parameter or dispatch branch gets its number in the plan header, a cell in cells(), a line in REQUIRED, and
 the smallest case that reaches it.  Pure numpy / torch on the CPU; nothing here touches the device (dcomp_fcnet_describe makes no
-HIP call)."""
+HIP call).
+
+The shape tables and integer nets of the per-feature tests (tests/test_actor_gpu.py ... tests/test_learner_accum_gpu.py) are here too,
+with HYPER, so that every file reads them from one place; what runs the device is in tests/fcnet_support.py, which imports this
+module.  Neither imports a test module."""
 import ctypes
 import functools
 import os
 
 import numpy as np
-
-from tests import test_actor_gpu as tag
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -119,9 +121,71 @@ def tiles_of(kind, E, U):
     return describe(*_ANY, rows=rows_of(kind, E, U)).split.tiles
 
 
+# ------------------------------------------------------------------------------------------------------------ primitive builders
+def dims(kind, U, B):
+    from deepcomp_amd.actor import layer_shapes
+    nin, heads, nout, _ = layer_shapes(kind, U, B, 32)
+    return nin, heads, nout
+
+
+def sparse_pm1(rng, nin, nout, nnz):
+    """[nin, nout] with at most nnz entries of -1 / +1 per column at random positions."""
+    w = np.zeros((nin, nout), dtype=np.float32)
+    for c in range(nout):
+        rows = rng.choice(nin, size=min(nnz, nin), replace=False)
+        w[rows, c] = rng.choice([-1.0, 1.0], size=len(rows))
+    return w
+
+
+def int_weights(kind, U, B, H, seed):
+    rng = np.random.default_rng(seed)
+    nin, _, nout = dims(kind, U, B)
+    ib = lambda n: rng.integers(-2, 3, size=n).astype(np.float32)      # noqa: E731
+    return {'w1': sparse_pm1(rng, nin, H, 8), 'b1': ib(H), 'w2': sparse_pm1(rng, H, H, 8), 'b2': ib(H),
+            'w3': sparse_pm1(rng, H, nout, 4), 'b3': ib(nout)}
+
+
+def int_value_weights(kind, U, B, H, seed, form):
+    rng = np.random.default_rng(1000 + seed)
+    nin, _, _ = dims(kind, U, B)
+    ib = lambda n: rng.integers(-2, 3, size=n).astype(np.float32)      # noqa: E731
+    v = {'wv': sparse_pm1(rng, H, 1, 4)[:, 0], 'bv': ib(1)}
+    if form == 'own':
+        v.update({'w1': sparse_pm1(rng, nin, H, 8), 'b1': ib(H), 'w2': sparse_pm1(rng, H, H, 8), 'b2': ib(H)})
+    return v
+
+
+def obs_shape(kind, E, U, B):
+    nin, _, _ = dims(kind, U, B)
+    return (E, U, nin) if kind == 'multi' else (E, nin)
+
+
 # ------------------------------------------------------------------------------------------------------------ the cases
 ACTIVATIONS = ('relu', 'tanh')
 VF_OF = {None: 0, 'own': 1, 'shared': 2}                      # the value form of a launch -> the kernel's VF
+FORMS = ['own', 'shared']                                      # the value forms tests/test_critic_gpu.py runs
+
+# tests/test_actor_gpu.py and test_critic_gpu.py: (kind, E, U, B, hidden): partial tile / K = 13; 256 wide; K = 129 and N = 33 cross a
+# tile; K = 257 (two input chunks), N = 65, two mask words; central with 10 and 32 heads (K = 672: five chunks); more rows than one
+# round of the grid's waves takes
+BASE_SHAPES = [('multi', 3, 7, 3, 32), ('multi', 5, 32, 10, 256), ('multi', 9, 5, 32, 64), ('multi', 4, 6, 64, 256),
+               ('central', 9, 10, 5, 256), ('central', 3, 32, 10, 64), ('multi', 1300, 32, 10, 256)]
+# the persistent grid is at most two workgroups of four waves per CU (2 048 tiles a round on 256 CUs): 2 200 tiles of 32 rows
+BASE_LOOP_SHAPE = ('multi', 2200, 32, 10, 32)
+BASE_IDS = [f'{k}{e}x{u}x{b}h{h}' for k, e, u, b, h in BASE_SHAPES]
+
+CHUNK = 2048                      # dcomp_learner.hip CHUNK_UNIT: rows of a weight-gradient chunk (while the batch has <= 128 of them)
+# tests/test_learner_gpu.py: (kind, E, U, B, hidden); the last: 6 400 rows = three chunks and a partial one
+LEARNER_BASE_SHAPES = [('multi', 3, 7, 3, 32), ('multi', 5, 32, 10, 256), ('multi', 9, 5, 32, 64), ('central', 9, 10, 5, 256),
+                       ('central', 3, 32, 10, 64), ('multi', 4, 6, 10, 96), ('multi', 200, 32, 10, 256)]
+LEARNER_BASE_IDS = [f'{k}{e}x{u}x{b}h{h}' for k, e, u, b, h in LEARNER_BASE_SHAPES]
+assert 3 * CHUNK < 200 * 32 < 4 * CHUNK
+
+# tests/test_policy_set_gpu.py: U, B, hidden, activation, E
+SET_SHAPES = {'a': (5, 3, 32, 'tanh', 70), 'b': (3, 36, 64, 'relu', 33), 'c': (4, 10, 256, 'tanh', 40)}
+SET_SLOTS = {'a': [0, 1, 1, 0, 1], 'b': [0, 1, 2], 'c': [0, 1, 2, 3]}
+SET_GUARD = 97
+SET_T = 5
 
 # (kind, E, U, B, hidden).  Every one runs relu and tanh, without a value, with a trunk of its own and with the shared value.
 ACTOR_SHAPES = [('multi', 3, 7, 3, 96), ('multi', 3, 7, 3, 128), ('multi', 3, 7, 3, 160), ('multi', 3, 7, 3, 224),      # MT 4 and 8, padded widths
@@ -152,6 +216,12 @@ INDEXED = dict(kind='multi', E=16, U=5, B=4, T=2)  # x hidden 32 / 64 / 128 / 25
 INDEXED_HIDDEN = (32, 64, 128, 256)
 REUSE_SHAPE = ('multi', 200, 32, 10, 256)          # tests/test_learner_gpu.py's 6 400-row case
 EPILOGUE_SHAPES = [('multi', 5, 32, 10, 64), ('central', 9, 10, 5, 64)]
+# tests/test_learner_accum_gpu.py: (kind, E, U, B, hidden, T)
+ACCUM_MULTI = ('multi', 101, 4, 5, 32, 16)      # 6 464 source rows
+ACCUM_CENTRAL = ('central', 404, 10, 5, 64, 16)  # EPILOGUE_SHAPES[1]'s net: 6 464 source rows
+assert EPILOGUE_SHAPES[1][0] == 'central' and EPILOGUE_SHAPES[1][2:] == ACCUM_CENTRAL[2:5]
+ACCUM_ROWS = 6444                                # three full chunks and a partial one
+ACCUM_LOCK = ('multi', 96, 4, 5, 32, 8)         # 3 072 rows: 1 536 per rank of two, 1 024 per rank of three
 
 
 def sid(shape):
@@ -243,13 +313,12 @@ def actor_int_case(shape, seed, wide=False):
     wide: b3 drawn from the integers in [-150, 150] instead.  As the recipe stands its logits stay below 34 at every shape of the
     table (the 330 is the worst case of the construction, never met), inside expf's float32 range; with the wide head bias the
     logits of one head lie more than 88.7 apart and reach past +-100, and they are still integers below 2^24: exact."""
-    from tests.test_critic_gpu import _int_value_weights
     kind, E, U, B, H = shape
     rows = rows_of(kind, E, U)
-    w = tag._int_weights(kind, U, B, H, seed)
+    w = int_weights(kind, U, B, H, seed)
     if wide:
         w['b3'] = np.random.default_rng(700 + seed).integers(-WIDE_B3, WIDE_B3 + 1, size=w['b3'].shape).astype(np.float32)
-    x = np.random.default_rng(100 + seed).integers(0, 2, size=tag._obs_shape(kind, E, U, B)).astype(np.float32)
+    x = np.random.default_rng(100 + seed).integers(0, 2, size=obs_shape(kind, E, U, B)).astype(np.float32)
     x2 = x.reshape(rows, -1).astype(np.float64)
     out = dict(w=w, x=x, rows=rows, v={}, vf={})
 
@@ -262,7 +331,7 @@ def actor_int_case(shape, seed, wide=False):
     out['logits'] = h @ w['w3'] + w['b3']
     assert np.abs(out['logits']).max() <= 330
     for form in ('own', 'shared'):
-        v = _int_value_weights(kind, U, B, H, seed, form)
+        v = int_value_weights(kind, U, B, H, seed, form)
         hv = trunk(v) if form == 'own' else h
         out['v'][form] = v
         out['vf'][form] = hv @ v['wv'].astype(np.float64) + float(v['bv'][0])
@@ -271,8 +340,8 @@ def actor_int_case(shape, seed, wide=False):
 
 
 def learner_int_reference(w, v, x, dl, dv):
-    """The float64 reference of all twelve gradients from upstream gradients, with the conditions tests/test_learner_gpu.py's
-    _int_case asserts (integers of magnitude <= 256 everywhere, every sum below 2^24: exact in f32 in any order)."""
+    """The float64 reference of all twelve gradients from upstream gradients, with the conditions learner_int_case
+    asserts (integers of magnitude <= 256 everywhere, every sum below 2^24: exact in f32 in any order)."""
     grads = {}
     x = x.astype(np.float64)
     rows, H = len(x), w['w1'].shape[1]
@@ -294,15 +363,46 @@ def learner_int_reference(w, v, x, dl, dv):
     return grads
 
 
+def learner_int_case(kind, E, U, B, H, seed):
+    """relu, inputs in {0, 1}, sparse +-1 weights and small integer biases in both trunks, dlogits with <= 2 entries of +-1 per row,
+    dvalue in {-1, 0, 1}; the float64 reference of all twelve gradients, with both exactness bounds asserted."""
+    rng = np.random.default_rng(500 + seed)
+    rows = rows_of(kind, E, U)
+    nin, _, n3 = dims(kind, U, B)
+    w, v = int_weights(kind, U, B, H, seed), int_value_weights(kind, U, B, H, seed, 'own')
+    x = rng.integers(0, 2, size=(rows, nin)).astype(np.float64)
+    dl = np.zeros((rows, n3))
+    for r in range(rows):
+        cols = rng.choice(n3, size=min(2, n3), replace=False)
+        dl[r, cols] = rng.choice([-1.0, 0.0, 1.0], size=len(cols))
+    dv = rng.integers(-1, 2, size=rows).astype(np.float64)
+    grads = {}
+
+    def trunk(t, w3, d3, names):
+        h1 = np.maximum(x @ t['w1'] + t['b1'], 0)
+        h2 = np.maximum(h1 @ t['w2'] + t['b2'], 0)
+        d2 = (d3 @ w3.T) * (h2 > 0)
+        d1 = (d2 @ t['w2'].astype(np.float64).T) * (h1 > 0)
+        for a in (h1, h2, d1, d2, d3):
+            assert np.array_equal(a, np.round(a)) and np.abs(a).max() <= 256          # integers, exact in bf16
+        for (a, d), (wn, bn) in zip(((x, d1), (h1, d2), (h2, d3)), names):
+            assert (np.abs(a).T @ np.abs(d)).max() < 2 ** 24                          # exact in f32 in any order
+            assert np.abs(d).sum(0).max() < 2 ** 24
+            grads[wn], grads[bn] = a.T @ d, d.sum(0)
+    trunk(w, w['w3'].astype(np.float64), dl, (('w1', 'b1'), ('w2', 'b2'), ('w3', 'b3')))
+    trunk(v, v['wv'].astype(np.float64).reshape(H, 1), dv.reshape(rows, 1), (('vw1', 'vb1'), ('vw2', 'vb2'), ('wv', 'bv')))
+    grads['wv'] = grads['wv'].reshape(-1)
+    return w, v, x.astype(np.float32), dl.astype(np.float32), dv.astype(np.float32), grads
+
+
 def mult2_int_case(seed=1):
-    """tests/test_learner_gpu.py's _int_case for MULT2_SHAPE with dlogits built vectorised (two distinct columns per row, entries in
+    """learner_int_case for MULT2_SHAPE with dlogits built vectorised (two distinct columns per row, entries in
     {-1, 0, 1}) instead of row by row: (weights, value weights, x, dlogits, dvalue, the twelve float64 gradients)."""
-    from tests.test_critic_gpu import _int_value_weights
     kind, E, U, B, H = MULT2_SHAPE
     rng = np.random.default_rng(500 + seed)
     rows = rows_of(kind, E, U)
-    nin, _, n3 = tag._dims(kind, U, B)
-    w, v = tag._int_weights(kind, U, B, H, seed), _int_value_weights(kind, U, B, H, seed, 'own')
+    nin, _, n3 = dims(kind, U, B)
+    w, v = int_weights(kind, U, B, H, seed), int_value_weights(kind, U, B, H, seed, 'own')
     x = rng.integers(0, 2, size=(rows, nin)).astype(np.float32)
     c0 = rng.integers(0, n3, size=rows)
     c1 = (c0 + 1 + rng.integers(0, n3 - 1, size=rows)) % n3
@@ -368,7 +468,7 @@ EPILOGUE_ADV = {'kl': False, 'entropy': False, 'surrogate': True, 'all': True}  
 def epilogue_case(shape, seed=1):
     """The relu integer net of a shape driven through the REAL loss.  The forward pass is exact, so the float64 reference of every
     per-row output follows from the integer logits alone: actions random, old_logits = logits + integer noise in [-3, 3], old_logp =
-    float64 logp - log(RATIOS[i % 4]) / heads, advantages and value inputs as tests/test_learner_gpu.py's _old_policy_inputs places
+    float64 logp - log(RATIOS[i % 4]) / heads, advantages and value inputs as tests/fcnet_support.py's old_policy_inputs places
     them (around the exact value here)."""
     kind, E, U, B, H = shape
     c = actor_int_case(shape, seed)

@@ -8,7 +8,8 @@ needs at least 4), 5 where UEs arrive and depart so that a slot dies after havin
 """
 from collections import namedtuple
 
-from tests.test_threshold_gpu import ARRIVAL, _slots
+from tests import threshold_cases as tc
+from tests.threshold_cases import ARRIVAL
 
 PHASES = (0, 4, 8, 12)          # bytes into a 16-byte line at which a float / int32 output starts
 
@@ -49,7 +50,7 @@ ALLOW = {}
 
 def slots(case):
     """UE slots per env: the list, or max_ues of the arrival schedule."""
-    return _slots(case.U, case.mode)
+    return tc.slots(case.U, case.mode)
 
 
 def steps(case):

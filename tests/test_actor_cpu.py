@@ -2,22 +2,13 @@
 host before the first HIP call, the ctypes mirrors match the header, RLlib's weight names map onto the six arrays, and the two
 forms of the reference arithmetic agree within the bf16 chain's error.  No GPU compute is called here."""
 import ctypes
-import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
 
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-OK, EINVAL, EUNSUPPORTED, EABI = 0, -1, -6, -7
-
-
-@pytest.fixture(scope='module')
-def lib():
-    from deepcomp_amd import build, _lib
-    build.build()                      # hipcc cross-compiles gfx950 on a GPU-less host
-    return _lib.load()
+from tests import c_surface as cs
+from tests.c_surface import EABI, EINVAL, EUNSUPPORTED, OK, lib  # noqa: F401  (lib: the fixture)
 
 
 def _cfg(kind=1, U=4, B=5, H=64, act=0, size=None, keep=None, null=()):
@@ -70,14 +61,12 @@ def test_actor_struct_size_mismatch_is_an_abi_error(lib):
 
 def test_actor_ctypes_mirrors_match_the_header():
     from deepcomp_amd import _lib
-    txt = re.sub(r'/\*.*?\*/', '', open(os.path.join(REPO, 'include', 'dcomp_types.h')).read(), flags=re.S)
     for cname, mirror in (('dcomp_actor_cfg', _lib.DcompActorCfg), ('dcomp_actor_run', _lib.DcompActorRun)):
-        body = re.search(r'typedef struct %s \{(.*?)\} %s;' % (cname, cname), txt, flags=re.S).group(1)
-        members = [re.split(r'[\s*]+', m.strip())[-1] for decl in body.split(';') if decl.strip() for m in decl.split(',')]
+        members = cs.struct_members(cs.header('dcomp_types.h'), cname)
         assert members == [f[0] for f in mirror._fields_], (cname, members)
     assert ctypes.sizeof(_lib.DcompActorCfg) == 24 + 6 * ctypes.sizeof(ctypes.c_void_p)
     assert ctypes.sizeof(_lib.DcompActorRun) == 56
-    hdr = open(os.path.join(REPO, 'include', 'dcomp.h')).read()
+    hdr = open(cs.header('dcomp.h')).read()
     assert '#define DCOMP_ABI_VERSION 3' in hdr                          # the new structs carry their own size: no version bump
     for name in ('dcomp_actor_create', 'dcomp_actor_destroy', 'dcomp_actor_actions'):
         assert name in _lib.EXPORTS and re.search(r'\b%s\s*\(' % name, hdr)
@@ -148,13 +137,12 @@ def test_gumbel_noise_uses_the_documented_counter_layout():
 
 
 def test_header_with_the_actor_entry_points_is_c99(tmp_path):
-    src = tmp_path / 'actor_hdr.c'
-    src.write_text('#include "dcomp.h"\n'
-                   'int f(const float *w, dcomp_actor **a) {\n'
-                   '    dcomp_actor_cfg c = {0};\n'
-                   '    dcomp_actor_run r = {0};\n'
-                   '    c.struct_size = (int32_t)sizeof c; c.obs_kind = DCOMP_MULTI; c.activation = DCOMP_ACT_TANH; c.w1 = w;\n'
-                   '    r.struct_size = (int32_t)sizeof r; r.obs_format = DCOMP_ACTOR_COMPACT;\n'
-                   '    return dcomp_actor_create(&c, a) + dcomp_actor_actions(*a, &r, 0, 0, 0) + dcomp_actor_destroy(*a);\n'
-                   '}\n')
-    subprocess.run(['gcc', '-std=c99', '-Wall', '-Wextra', '-Werror', '-pedantic', '-fsyntax-only', '-I', os.path.join(REPO, 'include'), str(src)], check=True)
+    cs.compiles_as_c99(tmp_path, 'actor_hdr', [
+        '#include "dcomp.h"\n'
+        'int f(const float *w, dcomp_actor **a) {\n'
+        '    dcomp_actor_cfg c = {0};\n'
+        '    dcomp_actor_run r = {0};\n'
+        '    c.struct_size = (int32_t)sizeof c; c.obs_kind = DCOMP_MULTI; c.activation = DCOMP_ACT_TANH; c.w1 = w;\n'
+        '    r.struct_size = (int32_t)sizeof r; r.obs_format = DCOMP_ACTOR_COMPACT;\n'
+        '    return dcomp_actor_create(&c, a) + dcomp_actor_actions(*a, &r, 0, 0, 0) + dcomp_actor_destroy(*a);\n'
+        '}\n'])

@@ -9,62 +9,13 @@ env.step.  Measured kernel errors: profiles/r07_actor_numerics.txt."""
 import numpy as np
 import pytest
 
+from tests import fcnet_cases as fc
+from tests import fcnet_support as fs
+from tests.fcnet_support import torch_cuda  # noqa: F401  (the fixture)
+
 pytestmark = pytest.mark.gpu
 
-# (kind, E, U, B, hidden): partial tile / K = 13; 256 wide; K = 129 and N = 33 cross a tile; K = 257 (two input chunks), N = 65, two
-# mask words; central with 10 and 32 heads (K = 672: five chunks); more rows than one round of the grid's waves takes
-SHAPES = [('multi', 3, 7, 3, 32), ('multi', 5, 32, 10, 256), ('multi', 9, 5, 32, 64), ('multi', 4, 6, 64, 256),
-          ('central', 9, 10, 5, 256), ('central', 3, 32, 10, 64), ('multi', 1300, 32, 10, 256)]
-# the persistent grid is at most two workgroups of four waves per CU (2 048 tiles a round on 256 CUs): 2 200 tiles of 32 rows
-LOOP_SHAPE = ('multi', 2200, 32, 10, 32)
-IDS = [f'{k}{e}x{u}x{b}h{h}' for k, e, u, b, h in SHAPES]
-
-
-@pytest.fixture(scope='module')
-def torch_cuda():
-    import torch
-    assert torch.cuda.is_available(), "these tests need the MI355X"
-    return torch
-
-
-def _dims(kind, U, B):
-    from deepcomp_amd.actor import layer_shapes
-    nin, heads, nout, _ = layer_shapes(kind, U, B, 32)
-    return nin, heads, nout
-
-
-def _sparse_pm1(rng, nin, nout, nnz):
-    """[nin, nout] with at most nnz entries of -1 / +1 per column at random positions."""
-    w = np.zeros((nin, nout), dtype=np.float32)
-    for c in range(nout):
-        rows = rng.choice(nin, size=min(nnz, nin), replace=False)
-        w[rows, c] = rng.choice([-1.0, 1.0], size=len(rows))
-    return w
-
-
-def _int_weights(kind, U, B, H, seed):
-    rng = np.random.default_rng(seed)
-    nin, _, nout = _dims(kind, U, B)
-    ib = lambda n: rng.integers(-2, 3, size=n).astype(np.float32)      # noqa: E731
-    return {'w1': _sparse_pm1(rng, nin, H, 8), 'b1': ib(H), 'w2': _sparse_pm1(rng, H, H, 8), 'b2': ib(H),
-            'w3': _sparse_pm1(rng, H, nout, 4), 'b3': ib(nout)}
-
-
-def _obs_shape(kind, E, U, B):
-    nin, _, _ = _dims(kind, U, B)
-    return (E, U, nin) if kind == 'multi' else (E, nin)
-
-
-def _run(torch, actor, obs, rows, **kw):
-    logits = torch.full((rows, actor.num_logits), float('nan'), device='cuda')
-    logp = torch.full((rows, actor.heads), float('nan'), device='cuda')
-    act = actor.actions(obs, logits=logits, logp=logp, **kw)
-    torch.cuda.synchronize()
-    return act.cpu().numpy(), logits.cpu().numpy(), logp.cpu().numpy()
-
-
-def _rows(kind, E, U):
-    return E * U if kind == 'multi' else E
+SHAPES, LOOP_SHAPE, IDS = fc.BASE_SHAPES, fc.BASE_LOOP_SHAPE, fc.BASE_IDS
 
 
 @pytest.mark.parametrize('shape', SHAPES + [LOOP_SHAPE], ids=IDS + ['loop2200x32x10h32'])
@@ -74,10 +25,10 @@ def test_integer_data_exact(torch_cuda, shape):
     torch = torch_cuda
     from deepcomp_amd.actor import FcnetActor
     kind, E, U, B, H = shape
-    rows = _rows(kind, E, U)
+    rows = fc.rows_of(kind, E, U)
     for seed in (1, 2, 3):
-        w = _int_weights(kind, U, B, H, seed)
-        x = np.random.default_rng(100 + seed).integers(0, 2, size=_obs_shape(kind, E, U, B)).astype(np.float32)
+        w = fc.int_weights(kind, U, B, H, seed)
+        x = np.random.default_rng(100 + seed).integers(0, 2, size=fc.obs_shape(kind, E, U, B)).astype(np.float32)
         x2 = x.reshape(rows, -1).astype(np.float64)
         h = np.maximum(x2 @ w['w1'] + w['b1'], 0)
         h = np.maximum(h @ w['w2'] + w['b2'], 0)
@@ -85,7 +36,7 @@ def test_integer_data_exact(torch_cuda, shape):
         ref = h @ w['w3'] + w['b3']
         assert np.abs(ref).max() <= 330
         actor = FcnetActor(kind, U, B, w, activation='relu')
-        act, logits, _ = _run(torch, actor, torch.from_numpy(x).cuda(), rows, sample=False)
+        act, logits, _ = fs.actor_run(torch, actor, torch.from_numpy(x).cuda(), rows, sample=False)
         bad = np.argwhere(logits != ref.astype(np.float32))
         assert bad.size == 0, f'seed {seed}: {len(bad)} of {ref.size} logits differ, first at (row, logit) {bad[0]}: {logits[tuple(bad[0])]} != {ref[tuple(bad[0])]}'
         first = ref.reshape(rows, actor.heads, B + 1).argmax(axis=-1)            # np.argmax: the first maximum
@@ -93,63 +44,14 @@ def test_integer_data_exact(torch_cuda, shape):
 
 
 # ---------------------------------------------------------------------------------------------------------------- real observations
-def _env(kind, E, U, B, **kw):
-    from deepcomp_amd import scenarios
-    from deepcomp_amd.entities import build_from_scenario
-    from deepcomp_amd.env import BatchedMobileEnv
-    m, bs, ues = build_from_scenario(scenarios.grid_map(B, 'mixed').with_ues(num_slow=U))
-    return BatchedMobileEnv(m, bs, ues, kind, num_envs=E, seed=42, episode_length=100, rng='philox', rand_episodes=True, **kw)
-
-
-_CASES = {}
-
-
-def _case(torch, shape):
-    """Per shape, computed once and left unchanged: observation rows of a real env (reset + 3 steps of random actions), a tanh
-    actor with random-init weights (N(0, 1 / fan_in) kernels, N(0, 0.1) biases), the kernel's greedy run, the float64 reference
-    and the CPU chain's own error against it."""
-    if shape in _CASES:
-        return _CASES[shape]
-    from deepcomp_amd.actor import FcnetActor
-    kind, E, U, B, H = shape
-    env = _env(kind, E, U, B)
-    env.reset()
-    g = torch.Generator(device='cuda').manual_seed(5)
-    for _ in range(3):
-        env.step(torch.randint(0, B + 1, (E, U), generator=g, device='cuda', dtype=torch.uint8))
-    env.check()
-    obs = env.obs.clone()
-    w = FcnetActor.random_weights(kind, U, B, H, seed=7, bias_std=0.1)
-    actor = FcnetActor(kind, U, B, w, activation='tanh')
-    rows = _rows(kind, E, U)
-    act, logits, logp = _run(torch, actor, obs, rows, sample=False)
-    x = obs.cpu().numpy().reshape(rows, -1)
-    ref64 = actor.reference_logits(x, form='float64').numpy()
-    chain = actor.reference_logits(x, form='bf16').numpy().astype(np.float64)
-    c = dict(actor=actor, obs=obs, rows=rows, act=act, logits=logits, logp=logp, ref64=ref64,
-             err_chain=float(np.abs(chain - ref64).max()), err_kernel=float(np.abs(logits.astype(np.float64) - ref64).max()))
-    _CASES[shape] = c
-    return c
-
-
 @pytest.mark.parametrize('shape', SHAPES, ids=IDS)
 def test_tanh_numerics(torch_cuda, shape):
-    """Kernel logits against the float64 model: allowed 2 x the max abs error the CPU bf16 / f32 chain has on the same inputs (the
-    factor covers the accumulation order and a device tanh that flips individual bf16 roundings).  Measured on the MI355X
-    (profiles/r07_actor_numerics.txt): the kernel's max abs error equals the chain's to four digits at all seven shapes, 1.2e-3 ... 2.9e-3."""
-    c = _case(torch_cuda, shape)
-    print(f'actor numerics {shape}: logit std {c["ref64"].std():.3f}  CPU chain max abs err {c["err_chain"]:.3e}  kernel {c["err_kernel"]:.3e}  '
-          f'ratio {c["err_kernel"] / c["err_chain"]:.2f}')
-    assert np.isfinite(c['logits']).all()
-    assert c['err_kernel'] <= 2 * c['err_chain'], (c['err_kernel'], c['err_chain'])
+    fs.check_tanh_numerics(torch_cuda, shape)
 
 
 @pytest.mark.parametrize('shape', SHAPES, ids=IDS)
 def test_greedy_is_first_maximum_of_own_logits(torch_cuda, shape):
-    c = _case(torch_cuda, shape)
-    B = shape[3]
-    own = c['logits'].reshape(c['rows'], c['actor'].heads, B + 1).argmax(axis=-1)
-    assert np.array_equal(c['act'].reshape(c['rows'], c['actor'].heads), own)
+    fs.check_greedy_is_first_maximum_of_own_logits(torch_cuda, shape)
 
 
 @pytest.mark.parametrize('kind', ['multi', 'central'])
@@ -159,7 +61,7 @@ def test_unlisted_slots_get_action_zero(torch_cuda, kind):
     torch = torch_cuda
     from deepcomp_amd.actor import FcnetActor
     E, U0, B = 6, 4, 5
-    env = _env(kind, E, U0, B, ue_arrival={2: 2, 4: -1})
+    env = fs.env(kind, E, U0, B, ue_arrival={2: 2, 4: -1})
     U = env.U
     actor = FcnetActor.random(kind, U, B, hidden=64, seed=3, bias_std=0.1)
     env.reset()
@@ -167,7 +69,7 @@ def test_unlisted_slots_get_action_zero(torch_cuda, kind):
     for t in range(6):
         n = env.num_ue
         seen.add(n)
-        rows = _rows(kind, E, U)
+        rows = fc.rows_of(kind, E, U)
         logits = torch.empty((rows, actor.num_logits), device='cuda')
         for sample in (False, True):
             act = actor.act(env, sample=sample)
@@ -195,11 +97,11 @@ def test_sampled_action_matches_host_gumbel(torch_cuda, shape):
     from deepcomp_amd.actor import gumbel_noise
     from oracle import oracle as orc
     kind, E, U, B, H = shape
-    c = _case(torch, shape)
+    c = fs.actor_case(torch, shape)
     actor, Es = c['actor'], _sub(shape)
-    rows = _rows(kind, Es, U)
+    rows = fc.rows_of(kind, Es, U)
     seed, step, row_base = 0x1234ABCD5678, 77, 1000
-    act, logits, _ = _run(torch, actor, c['obs'][:Es].contiguous(), rows, sample=True, seed=seed, step=step, row_base=row_base)
+    act, logits, _ = fs.actor_run(torch, actor, c['obs'][:Es].contiguous(), rows, sample=True, seed=seed, step=step, row_base=row_base)
     assert np.array_equal(logits, c['logits'][:rows])
     g = gumbel_noise(orc.philox4x32_10, seed, step, row_base + np.arange(rows), actor.heads, B + 1)
     y = logits.astype(np.float64).reshape(rows, actor.heads, B + 1) + g
@@ -219,13 +121,13 @@ def test_logp_is_log_softmax_of_chosen_action(torch_cuda, shape):
     torch = torch_cuda
     from deepcomp_amd.actor import FcnetActor
     kind, E, U, B, H = shape
-    c = _case(torch, shape)
+    c = fs.actor_case(torch, shape)
     s = 9.9 / float(np.abs(c['logits']).max())
     w = dict(c['actor'].weights)
     w['w3'], w['b3'] = w['w3'] * np.float32(s), w['b3'] * np.float32(s)
     actor = FcnetActor(kind, U, B, w, activation='tanh')
     for sample in (True, False):
-        act, logits, logp = _run(torch, actor, c['obs'], c['rows'], sample=sample, seed=9, step=3)
+        act, logits, logp = fs.actor_run(torch, actor, c['obs'], c['rows'], sample=sample, seed=9, step=3)
         assert np.abs(logits).max() <= 10.0
         lg = logits.astype(np.float64).reshape(c['rows'], actor.heads, B + 1)
         ls = lg - (np.log(np.exp(lg - lg.max(-1, keepdims=True)).sum(-1, keepdims=True)) + lg.max(-1, keepdims=True))
@@ -239,7 +141,7 @@ def test_logp_is_log_softmax_of_chosen_action(torch_cuda, shape):
 def test_keying(torch_cuda, shape):
     torch = torch_cuda
     kind, E, U, B, H = shape
-    c = _case(torch, shape)
+    c = fs.actor_case(torch, shape)
     actor, obs = c['actor'], c['obs']
     a0 = actor.actions(obs, seed=11, step=5).cpu().numpy()
     assert np.array_equal(a0, actor.actions(obs, seed=11, step=5).cpu().numpy())
@@ -263,7 +165,7 @@ def test_sampled_actions_follow_softmax(torch_cuda):
     torch = torch_cuda
     from scipy import stats
     shape = SHAPES[1]
-    c = _case(torch, shape)
+    c = fs.actor_case(torch, shape)
     actor = c['actor']
     U, B = shape[2], shape[3]
     E = 65536 // U
@@ -281,17 +183,13 @@ def test_sampled_actions_follow_softmax(torch_cuda):
         assert chi < limit
 
 
-def _bits(a):
-    return np.ascontiguousarray(a).view(np.int32)
-
-
 @pytest.mark.parametrize('E,U,B,H', [(300, 32, 10, 256), (9, 5, 32, 64)])
 def test_compact_record_from_the_step(torch_cuda, E, U, B, H):
     """(a) the rows one env writes with step_into and the record its twin writes with step_compact from equal state: logits and
     actions bit-identical."""
     torch = torch_cuda
     from deepcomp_amd.actor import FcnetActor
-    rows_env, comp_env = _env('multi', E, U, B), _env('multi', E, U, B)
+    rows_env, comp_env = fs.env('multi', E, U, B), fs.env('multi', E, U, B)
     actor = FcnetActor.random('multi', U, B, hidden=H, seed=4, bias_std=0.1)
     packed = torch.zeros((E, comp_env.compact_words), dtype=torch.int32, device='cuda')
     obs, rew, rew2 = torch.zeros_like(rows_env.obs), torch.zeros_like(rows_env.reward), torch.zeros_like(rows_env.reward)
@@ -301,9 +199,9 @@ def test_compact_record_from_the_step(torch_cuda, E, U, B, H):
     for t in range(4):
         rows_env.step_into(a, obs, rew)
         comp_env.step_compact(a, packed, rew2)
-        ra, rl, rp = _run(torch, actor, obs, E * U, sample=True, seed=5, step=t)
-        ca, cl, cp = _run(torch, actor, packed, E * U, compact=True, sample=True, seed=5, step=t)
-        assert np.array_equal(_bits(rl), _bits(cl)) and np.array_equal(ra, ca) and np.array_equal(_bits(rp), _bits(cp)), t
+        ra, rl, rp = fs.actor_run(torch, actor, obs, E * U, sample=True, seed=5, step=t)
+        ca, cl, cp = fs.actor_run(torch, actor, packed, E * U, compact=True, sample=True, seed=5, step=t)
+        assert np.array_equal(fs.bits(rl), fs.bits(cl)) and np.array_equal(ra, ca) and np.array_equal(fs.bits(rp), fs.bits(cp)), t
         a = torch.from_numpy(ra).cuda()
     rows_env.check(); comp_env.check()
 
@@ -330,9 +228,9 @@ def test_compact_record_from_pack_fragment(torch_cuda, B):
     assert torch.equal(codec.unpack(packed).view(torch.int32), obs.view(torch.int32))
     actor = FcnetActor.random('multi', U, B, hidden=64, seed=B, bias_std=0.1)
     for sample in (False, True):
-        ra, rl, rp = _run(torch, actor, obs, E * U, sample=sample, seed=8, step=2, num_active=listed)
-        ca, cl, cp = _run(torch, actor, packed, E * U, compact=True, sample=sample, seed=8, step=2, num_active=listed)
-        assert np.array_equal(_bits(rl), _bits(cl)) and np.array_equal(ra, ca) and np.array_equal(_bits(rp), _bits(cp))
+        ra, rl, rp = fs.actor_run(torch, actor, obs, E * U, sample=sample, seed=8, step=2, num_active=listed)
+        ca, cl, cp = fs.actor_run(torch, actor, packed, E * U, compact=True, sample=sample, seed=8, step=2, num_active=listed)
+        assert np.array_equal(fs.bits(rl), fs.bits(cl)) and np.array_equal(ra, ca) and np.array_equal(fs.bits(rp), fs.bits(cp))
         assert (ra[:, listed:] == 0).all()
 
 
@@ -351,12 +249,12 @@ def test_actor_drives_the_env(torch_cuda, kind, E, U, B):
     computes the logits.  With N(0, 4) the band holds about a quarter of that."""
     torch = torch_cuda
     from deepcomp_amd.actor import FcnetActor
-    dev_env, ref_env, sampled = _env(kind, E, U, B), _env(kind, E, U, B), _env(kind, E, U, B)
+    dev_env, ref_env, sampled = fs.env(kind, E, U, B), fs.env(kind, E, U, B), fs.env(kind, E, U, B)
     w = FcnetActor.random_weights(kind, U, B, 256, seed=21, bias_std=0.1)
     w['b3'] = np.random.default_rng(21).normal(0.0, 4.0, size=w['b3'].shape).astype(np.float32)
     actor = FcnetActor(kind, U, B, w)
     dev_env.reset(); ref_env.reset(); sampled.reset()
-    rows = _rows(kind, E, U)
+    rows = fc.rows_of(kind, E, U)
     close = changed = 0
     for t in range(20):
         sampled.step(actor.act(sampled, sample=True))

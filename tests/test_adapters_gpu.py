@@ -7,7 +7,8 @@ import os
 import numpy as np
 import pytest
 
-from tests.test_parity_gpu import ATOL_OBS, ATOL_UTIL, GOLDEN, RTOL_RATE, _entities_from_fixture
+from tests.env_support import GOLDEN, entities_from_fixture
+from tests.parity import ATOL_OBS, ATOL_UTIL, RTOL_RATE
 
 pytestmark = pytest.mark.gpu
 
@@ -24,7 +25,7 @@ def _load(stack):
 
 
 def _env_config(g, num_envs):
-    m, bs, ues = _entities_from_fixture(g)
+    m, bs, ues = entities_from_fixture(g)
     return {'map': m, 'bs_list': bs, 'ue_list': ues, 'seed': int(g['cfg_seed']), 'episode_length': int(g['cfg_eps_len']),
             'reward': {0: 'avg', 1: 'sum', 2: 'min'}[int(g['cfg_reward'])], 'rand_episodes': bool(g['cfg_rand_episodes']),
             'num_envs': num_envs, 'rng': 'reference'}

@@ -11,7 +11,8 @@ deepcomp_amd/csrc/dcomp_big.h (run-time B, per-UE rows in LDS, the connection se
 import numpy as np
 import pytest
 
-from tests import parity
+from tests import env_support, parity
+from tests.env_support import bigb_scenario as _scenario
 
 pytestmark = pytest.mark.gpu
 
@@ -21,17 +22,6 @@ def torch_cuda():
     import torch
     assert torch.cuda.is_available(), "these tests need the MI355X"
     return torch
-
-
-def _scenario(U, B, sharing, pitch=45):
-    from deepcomp_amd import scenarios
-    n_static = max(1, U // 8)
-    scn = scenarios.grid_map(B, 'mixed' if sharing == 'mixed' else sharing, pitch=pitch, border=25).with_ues(
-        num_static=n_static, num_slow=U - n_static - U // 4, num_fast=U // 4)
-    if sharing == 'max-cap':                                  # a few other models among the max-cap stations, one of them beyond 31
-        for b, m in ((1, 'resource-fair'), (B - 1, 'rate-fair'), (B - 2, 'proportional-fair')):
-            scn.bs_sharing[b] = m
-    return scn
 
 
 def _oracle_batch(scn, kind, reward, E, seed):
@@ -454,10 +444,9 @@ def test_generic_kernel_on_the_reference_run_ue_arrival_fixtures(torch_cuda, nam
     """DCOMP_FORCE_BIG=1: the reference-run dyn_* / reseeddyn_* fixtures (<= 7 stations; tape mode: host-drawn departures and border points,
     MobileEnv.seed() on a live env) through the GENERIC kernel's event phase -- the same assertions as on the specialised dynamic kernel.
     (dyn_dense40_* / dyn_dense36_* take the generic kernel by themselves: 40 / 36 stations.)"""
-    from tests import test_parity_gpu as tp
     monkeypatch.setenv('DCOMP_FORCE_BIG', '1')
-    tp.test_golden_dynamic_ue_trajectory(torch_cuda, name, False)
-    tp.test_golden_dynamic_ue_trajectory(torch_cuda, name, True)
+    env_support.check_golden_dynamic_ue_trajectory(torch_cuda, name, False)
+    env_support.check_golden_dynamic_ue_trajectory(torch_cuda, name, True)
 
 
 @pytest.mark.parametrize('U,B,E,arrival', [(32, 64, 40, None), (12, 40, 64, None), (7, 33, 50, {2: 3, 5: -2, 9: 2}), (130, 48, 3, None), (300, 36, 2, None)])

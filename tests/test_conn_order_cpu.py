@@ -16,9 +16,9 @@ import numpy as np
 import pytest
 
 from tests import parity
-from tests.test_bigb_gpu import _scenario as _bigb_scenario
+from tests.env_support import CONN_ORDER_ARRIVAL as ARRIVAL
+from tests.env_support import bigb_scenario as _bigb_scenario
 
-ARRIVAL = {2: 3, 5: -2, 9: 4, 14: -3, 20: 2, 21: 2, 30: -4, 33: 5, 37: -6}
 TAMPERS = ['no_stamp', 'row_not_moved', 'wrong_neighbour', 'stamp_off_by_one']
 
 

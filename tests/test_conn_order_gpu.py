@@ -15,8 +15,8 @@ import numpy as np
 import pytest
 
 from tests import parity
-from tests.test_bigb_gpu import _scenario
-from tests.test_conn_order_cpu import ARRIVAL
+from tests.env_support import CONN_ORDER_ARRIVAL as ARRIVAL
+from tests.env_support import bigb_scenario as _scenario
 
 pytestmark = pytest.mark.gpu
 

@@ -4,28 +4,20 @@ first HIP call, the ctypes mirrors match the header, RLlib's value-branch names 
 RLlib's compute_advantages.  No GPU compute is called here.  The two refusals that need a live handle -- a handle without a value
 function, a second dcomp_actor_set_value -- are in tests/test_critic_gpu.py: a handle cannot be created without a device."""
 import ctypes
-import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
 
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-OK, EINVAL, EABI = 0, -1, -7
+from tests import c_surface as cs
+from tests.c_surface import EABI, EINVAL, lib  # noqa: F401  (lib: the fixture)
+
 NEW = ('dcomp_actor_set_value', 'dcomp_actor_actions_v', 'dcomp_gae')
-
-
-@pytest.fixture(scope='module')
-def lib():
-    from deepcomp_amd import build, _lib
-    build.build()                      # hipcc cross-compiles gfx950 on a GPU-less host
-    return _lib.load()
 
 
 def test_symbols_are_exported_and_declared(lib):
     from deepcomp_amd import _lib
-    hdr = open(os.path.join(REPO, 'include', 'dcomp.h')).read()
+    hdr = open(cs.header('dcomp.h')).read()
     for name in NEW:
         assert name in _lib.EXPORTS and re.search(r'\b%s\s*\(' % name, hdr)
         getattr(lib, name)
@@ -108,14 +100,12 @@ def test_gae_refuses_bad_arguments_on_the_host(lib):
 def test_ctypes_mirrors_match_the_header(tmp_path):
     """Member names from the header text, sizes from a C program compiled against it."""
     from deepcomp_amd import _lib
-    txt = re.sub(r'/\*.*?\*/', '', open(os.path.join(REPO, 'include', 'dcomp_types.h')).read(), flags=re.S)
     mirrors = (('dcomp_actor_value_cfg', _lib.DcompActorValueCfg), ('dcomp_gae_args', _lib.DcompGaeArgs))
     for cname, mirror in mirrors:
-        body = re.search(r'typedef struct %s \{(.*?)\} %s;' % (cname, cname), txt, flags=re.S).group(1)
-        members = [re.split(r'[\s*]+', m.strip())[-1] for decl in body.split(';') if decl.strip() for m in decl.split(',')]
+        members = cs.struct_members(cs.header('dcomp_types.h'), cname)
         assert members == [f[0] for f in mirror._fields_], (cname, members)
-    src = tmp_path / 'sizes.c'
-    src.write_text('#include <stdio.h>\n#include "dcomp.h"\n'
+    sizes, = cs.c_program_output(
+        tmp_path, '#include <stdio.h>\n#include "dcomp.h"\n'
                    'int f(dcomp_actor *a, const dcomp_actor_run *r, float *vf) {\n'
                    '    dcomp_actor_value_cfg c = {0};\n'
                    '    dcomp_gae_args g = {0};\n'
@@ -126,12 +116,7 @@ def test_ctypes_mirrors_match_the_header(tmp_path):
                    'int main(void) {\n'
                    '    printf("%zu %zu %zu %zu\\n", sizeof(dcomp_actor_value_cfg), sizeof(dcomp_gae_args), sizeof(dcomp_actor_cfg), sizeof(dcomp_actor_run));\n'
                    '    return 0;\n'
-                   '}\n')
-    inc = os.path.join(REPO, 'include')
-    subprocess.run(['gcc', '-std=c99', '-Wall', '-Wextra', '-Werror', '-pedantic', '-fsyntax-only', '-I', inc, str(src)], check=True)
-    exe = tmp_path / 'sizes'
-    subprocess.run(['gcc', '-std=c99', '-I', inc, '-Wl,--unresolved-symbols=ignore-all', '-o', str(exe), str(src)], check=True)
-    sizes = [int(x) for x in subprocess.run([str(exe)], check=True, stdout=subprocess.PIPE, text=True).stdout.split()]
+                   '}\n', link=['-Wl,--unresolved-symbols=ignore-all'])
     assert sizes == [ctypes.sizeof(_lib.DcompActorValueCfg), ctypes.sizeof(_lib.DcompGaeArgs), ctypes.sizeof(_lib.DcompActorCfg),
                      ctypes.sizeof(_lib.DcompActorRun)]
     assert sizes[2:] == [24 + 6 * ctypes.sizeof(ctypes.c_void_p), 56]     # the existing structs stay as they are

@@ -12,44 +12,28 @@ import ctypes
 import numpy as np
 import pytest
 
-from tests import test_actor_gpu as tag
+from tests import fcnet_cases as fc
+from tests import fcnet_support as fs
+from tests.fcnet_support import torch_cuda  # noqa: F401  (the fixture)
 
 pytestmark = pytest.mark.gpu
 
-SHAPES, IDS = tag.SHAPES, tag.IDS
-FORMS = ['own', 'shared']
-
-
-@pytest.fixture(scope='module')
-def torch_cuda():
-    import torch
-    assert torch.cuda.is_available(), "these tests need the MI355X"
-    return torch
-
-
-def _int_value_weights(kind, U, B, H, seed, form):
-    rng = np.random.default_rng(1000 + seed)
-    nin, _, _ = tag._dims(kind, U, B)
-    ib = lambda n: rng.integers(-2, 3, size=n).astype(np.float32)      # noqa: E731
-    v = {'wv': tag._sparse_pm1(rng, H, 1, 4)[:, 0], 'bv': ib(1)}
-    if form == 'own':
-        v.update({'w1': tag._sparse_pm1(rng, nin, H, 8), 'b1': ib(H), 'w2': tag._sparse_pm1(rng, H, H, 8), 'b2': ib(H)})
-    return v
+SHAPES, IDS, FORMS = fc.BASE_SHAPES, fc.BASE_IDS, fc.FORMS
 
 
 @pytest.mark.parametrize('form', FORMS)
-@pytest.mark.parametrize('shape', SHAPES + [tag.LOOP_SHAPE], ids=IDS + ['loop2200x32x10h32'])
+@pytest.mark.parametrize('shape', SHAPES + [fc.BASE_LOOP_SHAPE], ids=IDS + ['loop2200x32x10h32'])
 def test_value_integer_data_exact(torch_cuda, shape, form):
     """relu, inputs in {0, 1}, <= 8 entries of +-1 per column of each trunk matrix, wv with <= 4 entries of +-1, integer biases in
     [-2, 2]: every intermediate is an integer of magnitude <= 82 (exact in bf16), every value <= 4 * 82 + 2 (exact in f32)."""
     torch = torch_cuda
     from deepcomp_amd.actor import FcnetActor
     kind, E, U, B, H = shape
-    rows = tag._rows(kind, E, U)
+    rows = fc.rows_of(kind, E, U)
     for seed in (1, 2, 3):
-        w = tag._int_weights(kind, U, B, H, seed)
-        v = _int_value_weights(kind, U, B, H, seed, form)
-        x = np.random.default_rng(100 + seed).integers(0, 2, size=tag._obs_shape(kind, E, U, B)).astype(np.float32)
+        w = fc.int_weights(kind, U, B, H, seed)
+        v = fc.int_value_weights(kind, U, B, H, seed, form)
+        x = np.random.default_rng(100 + seed).integers(0, 2, size=fc.obs_shape(kind, E, U, B)).astype(np.float32)
         x2 = x.reshape(rows, -1).astype(np.float64)
         t = v if form == 'own' else w
         h = np.maximum(x2 @ t['w1'] + t['b1'], 0)
@@ -66,77 +50,22 @@ def test_value_integer_data_exact(torch_cuda, shape, form):
         assert bad.size == 0, f'seed {seed}: {len(bad)} of {rows} values differ, first at row {bad[0]}: {got[tuple(bad[0])]} != {ref[tuple(bad[0])]}'
 
 
-_VCASES = {}
-
-
-def _vcase(torch, shape, form):
-    """Per (shape, form), computed once and left unchanged: the observation rows and tanh actor weights of test_actor_gpu's case,
-    random-init value weights (N(0, 0.1) biases), and the kernel's runs -- without vf, with vf, value only; greedy and sampled."""
-    if (shape, form) in _VCASES:
-        return _VCASES[(shape, form)]
-    from deepcomp_amd.actor import FcnetActor
-    kind, E, U, B, H = shape
-    base = tag._case(torch, shape)
-    obs, rows = base['obs'], base['rows']
-    v = FcnetActor.random_value_weights(kind, U, B, H, seed=7, bias_std=0.1, shared=form == 'shared')
-    actor = FcnetActor(kind, U, B, base['actor'].weights, activation='tanh', value_weights=v)
-    c = dict(actor=actor, obs=obs, rows=rows)
-    for sample in (False, True):
-        kw = dict(sample=sample, seed=0xC0FFEE, step=12, row_base=64)
-        c['plain', sample] = tag._run(torch, actor, obs, rows, **kw)
-        vf = torch.full((rows,), float('nan'), device='cuda')
-        c['with', sample] = tag._run(torch, actor, obs, rows, vf=vf, **kw)
-        c['vf', sample] = vf.cpu().numpy()
-    only = torch.full((rows,), float('nan'), device='cuda')
-    assert actor.value(obs, out=only) is only
-    c['only'] = only.cpu().numpy()
-    x = obs.cpu().numpy().reshape(rows, -1)
-    ref64 = actor.reference_value(x, form='float64').numpy()
-    chain = actor.reference_value(x, form='bf16').numpy().astype(np.float64)
-    c['ref64'] = ref64
-    c['err_chain'] = float(np.abs(chain - ref64).max())
-    c['err_kernel'] = float(np.abs(c['vf', False].astype(np.float64) - ref64).max())
-    _VCASES[(shape, form)] = c
-    return c
-
-
 @pytest.mark.parametrize('form', FORMS)
 @pytest.mark.parametrize('shape', SHAPES, ids=IDS)
 def test_value_tanh_numerics(torch_cuda, shape, form):
-    """Kernel vf against the float64 model on real observations: allowed 2 x the max abs error the CPU bf16 / f32 chain has on the
-    same inputs (the factor covers the accumulation order and a device tanh that flips individual bf16 roundings).  Measured on the
-    MI355X: profiles/r08_critic_numerics.txt."""
-    c = _vcase(torch_cuda, shape, form)
-    print(f'critic numerics {shape} {form}: value std {c["ref64"].std():.3f}  CPU chain max abs err {c["err_chain"]:.3e}  kernel {c["err_kernel"]:.3e}  '
-          f'ratio {c["err_kernel"] / c["err_chain"]:.2f}')
-    assert np.isfinite(c['vf', False]).all()
-    assert c['err_chain'] > 0
-    assert c['err_kernel'] <= 2 * c['err_chain'], (c['err_kernel'], c['err_chain'])
+    fs.check_value_tanh_numerics(torch_cuda, shape, form)
 
 
 @pytest.mark.parametrize('form', FORMS)
 @pytest.mark.parametrize('shape', SHAPES, ids=IDS)
 def test_policy_outputs_are_bit_identical_with_vf(torch_cuda, shape, form):
-    """actions, logits and logp of actions(..., vf=...) == those of the call without vf, greedy and sampled; and they are those of
-    the actor without a value function (test_actor_gpu's case: the same weights, greedy)."""
-    c = _vcase(torch_cuda, shape, form)
-    for sample in (False, True):
-        (a0, l0, p0), (a1, l1, p1) = c['plain', sample], c['with', sample]
-        assert np.array_equal(a0, a1), sample
-        assert np.array_equal(tag._bits(l0), tag._bits(l1)), sample
-        assert np.array_equal(tag._bits(p0), tag._bits(p1)), sample
-    base = tag._case(torch_cuda, shape)
-    assert np.array_equal(tag._bits(c['with', False][1]), tag._bits(base['logits'])) and np.array_equal(c['with', False][0], base['act'])
-    assert not np.array_equal(c['with', False][0], c['with', True][0])            # (the sampled run did sample)
+    fs.check_policy_outputs_are_bit_identical_with_vf(torch_cuda, shape, form)
 
 
 @pytest.mark.parametrize('form', FORMS)
 @pytest.mark.parametrize('shape', SHAPES, ids=IDS)
 def test_value_only_call_is_bit_identical(torch_cuda, shape, form):
-    c = _vcase(torch_cuda, shape, form)
-    assert np.isfinite(c['only']).all()
-    assert np.array_equal(tag._bits(c['only']), tag._bits(c['vf', False]))
-    assert np.array_equal(tag._bits(c['only']), tag._bits(c['vf', True]))         # the draws do not touch the value
+    fs.check_value_only_call_is_bit_identical(torch_cuda, shape, form)
 
 
 @pytest.mark.parametrize('form', FORMS)
@@ -145,7 +74,7 @@ def test_compact_record_gives_bit_identical_vf(torch_cuda, E, U, B, H, form):
     """The rows one env writes with step_into and the record its twin writes with step_compact from equal state."""
     torch = torch_cuda
     from deepcomp_amd.actor import FcnetActor
-    rows_env, comp_env = tag._env('multi', E, U, B), tag._env('multi', E, U, B)
+    rows_env, comp_env = fs.env('multi', E, U, B), fs.env('multi', E, U, B)
     v = FcnetActor.random_value_weights('multi', U, B, H, seed=4, bias_std=0.1, shared=form == 'shared')
     actor = FcnetActor('multi', U, B, FcnetActor.random_weights('multi', U, B, H, seed=4, bias_std=0.1), value_weights=v)
     packed = torch.zeros((E, comp_env.compact_words), dtype=torch.int32, device='cuda')
@@ -157,11 +86,11 @@ def test_compact_record_gives_bit_identical_vf(torch_cuda, E, U, B, H, form):
         rows_env.step_into(a, obs, rew)
         comp_env.step_compact(a, packed, rew2)
         rv, cv = torch.full((E * U,), float('nan'), device='cuda'), torch.full((E * U,), float('nan'), device='cuda')
-        ra, rl, rp = tag._run(torch, actor, obs, E * U, sample=True, seed=5, step=t, vf=rv)
-        ca, cl, cp = tag._run(torch, actor, packed, E * U, compact=True, sample=True, seed=5, step=t, vf=cv)
+        ra, rl, rp = fs.actor_run(torch, actor, obs, E * U, sample=True, seed=5, step=t, vf=rv)
+        ca, cl, cp = fs.actor_run(torch, actor, packed, E * U, compact=True, sample=True, seed=5, step=t, vf=cv)
         assert torch.isfinite(rv).all()
         assert torch.equal(rv.view(torch.int32), cv.view(torch.int32)), t
-        assert np.array_equal(ra, ca) and np.array_equal(tag._bits(rl), tag._bits(cl)) and np.array_equal(tag._bits(rp), tag._bits(cp)), t
+        assert np.array_equal(ra, ca) and np.array_equal(fs.bits(rl), fs.bits(cl)) and np.array_equal(fs.bits(rp), fs.bits(cp)), t
         assert torch.equal(actor.value(packed, compact=True).view(torch.int32), rv.view(torch.int32)), t
         a = torch.from_numpy(ra).cuda()
     rows_env.check(); comp_env.check()
@@ -172,7 +101,7 @@ def test_compact_record_gives_bit_identical_vf(torch_cuda, E, U, B, H, form):
 def test_rows_beyond_the_batch_are_never_stored(torch_cuda, shape, form):
     """The last tile is partial at both shapes (21 and 9 rows): a vf buffer of rows + 64 floats filled with NaN keeps its last 64."""
     torch = torch_cuda
-    c = _vcase(torch, shape, form)
+    c = fs.value_case(torch, shape, form)
     rows = c['rows']
     for only in (False, True):
         buf = torch.full((rows + 64,), float('nan'), device='cuda')
@@ -182,7 +111,7 @@ def test_rows_beyond_the_batch_are_never_stored(torch_cuda, shape, form):
             c['actor'].actions(c['obs'], sample=False, vf=buf[:rows])
         got = buf.cpu().numpy()
         assert np.isnan(got[rows:]).all(), only
-        assert np.array_equal(tag._bits(got[:rows]), tag._bits(c['only'])), only
+        assert np.array_equal(fs.bits(got[:rows]), fs.bits(c['only'])), only
 
 
 def test_refusals_that_need_a_handle(torch_cuda):

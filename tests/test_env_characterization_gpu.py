@@ -5,7 +5,7 @@ it to a RECORDING of itself, tests/golden/env_characterization.json, on the host
 after a splice, rollouts cut into stretches after a splice, the order of the library calls.  Written by this module's own entry with
 env.py and rng.py as they stood before the draw tape got one owner (the parent commit's):
 
-    python -m tests.test_env_characterization_gpu --write            (on an MI355X)
+    python -m tests.<this module> --write            (on an MI355X, from the repository root)
 
 Per public call of a script the recording holds (1) the library calls it makes, in order, through a forwarding proxy around the ``_L``
 the env holds: the entry point; for dcomp_reset whether a tape was given and its num_ids, for dcomp_set_tape the depth, for both the

@@ -8,13 +8,12 @@ import numpy as np
 import pytest
 
 from tests import fcnet_cases as fc
-from tests import test_learner_gpu as tlg
 
 
 def test_constants_are_the_librarys():
     assert (fc.KC, fc.TILE, fc.WAVES) == (144, 32, 4)
     assert (fc.CHUNK_UNIT, fc.MAX_CHUNKS) == (2048, 128)
-    assert fc.CHUNK_UNIT == tlg.CHUNK
+    assert fc.CHUNK_UNIT == fc.CHUNK
     assert fc.GRID_TILES == 2048                                  # tests/test_actor_gpu.py: "2 048 tiles a round on 256 CUs"
     assert fc.grid_tiles(256) == 2048 and fc.grid_tiles(0) == 2048 and fc.grid_tiles(64) == 512      # (0: the library's fallback)
 
@@ -129,11 +128,11 @@ def test_the_logits_go_past_the_float32_range_of_exp():
 
 @pytest.mark.parametrize('shape', fc.LEARNER_SHAPES, ids=[fc.sid(s) for s in fc.LEARNER_SHAPES])
 def test_learner_integer_references_are_exact(shape):
-    """tests/test_learner_gpu.py's _int_case asserts its own conditions while it builds the reference (seeds 1 and 2: the ones
+    """fc.learner_int_case asserts its own conditions while it builds the reference (seeds 1 and 2: the ones
     test_backward_integer_data_exact runs)."""
     kind, E, U, B, H = shape
     for seed in (1, 2):
-        w, v, x, dl, dv, ref = tlg._int_case(kind, E, U, B, H, seed)
+        w, v, x, dl, dv, ref = fc.learner_int_case(kind, E, U, B, H, seed)
         again = fc.learner_int_reference(w, v, x, dl, dv)
         assert all(np.array_equal(ref[n], again[n]) for n in ref)
         assert any(np.abs(ref[n]).max() > 0 for n in ('w1', 'vw1'))

@@ -1,10 +1,11 @@
 """GPU tests of the fcnet kernels over tests/fcnet_cases.py: every instantiation of actor_kernel<MT, RELU, VF, PER>, learner_kernel<MT,
 RELU, IDX>, wgrad_block<MB, NB> and wgrad_bias<NB>, and the host-side branches on shape, held to a reference.
 
-The bars are the project's existing ones and the constructions are imported from the tests that introduced them:
+The bars are the project's existing ones and the constructions are those of the tests that introduced them
+(tests/fcnet_support.py and tests/fcnet_cases.py hold what both run):
   relu   integer data (tests/test_actor_gpu.py, test_critic_gpu.py, test_learner_gpu.py): logits, values and all twelve gradient arrays
          equal the float64 reference EXACTLY, the action is the first maximum
-  tanh   random-init weights on the rows of a real env (reset + 3 steps, tag._case's recipe -- the env takes every shape of the
+  tanh   random-init weights on the rows of a real env (reset + 3 steps, fs.actor_case's recipe -- the env takes every shape of the
          table, 63 and 64 stations and 1 024 UE slots included, so no case uses synthetic rows): within 2 x the error the CPU bf16 chain
          itself has against the float64 model
   sets   a slot's rows equal its member's own launch bit for bit (the member's launch is held to the reference above)
@@ -16,28 +17,14 @@ import numpy as np
 import pytest
 
 from tests import fcnet_cases as fc
-from tests import test_actor_gpu as tag
-from tests import test_critic_gpu as tcg
-from tests import test_learner_gpu as tlg
-from tests import test_learner_indexed_gpu as tli
-from tests import test_policy_set_gpu as tps
+from tests import fcnet_support as fs
+from tests.fcnet_cases import HYPER
+from tests.fcnet_support import torch_cuda  # noqa: F401  (the fixture)
 
 pytestmark = pytest.mark.gpu
 
-HYPER = tlg.HYPER
 IDS = [fc.sid(s) for s in fc.ACTOR_SHAPES]
 LIDS = [fc.sid(s) for s in fc.LEARNER_SHAPES]
-
-
-@pytest.fixture(scope='module')
-def torch_cuda():
-    import torch
-    assert torch.cuda.is_available(), "these tests need the MI355X"
-    return torch
-
-
-def _bits(a):
-    return np.ascontiguousarray(a).view(np.int32)
 
 
 # ================================================================================================ actor and value head
@@ -69,16 +56,16 @@ def _relu_exact(torch, shape, variant, forms):
         actor = FcnetActor(kind, U, B, c['w'], activation='relu', value_weights=c['v'][form])
         assert actor.value_shared == (form == 'shared')
         if base is None:                                                              # VF = 0: dcomp_actor_actions
-            base = tag._run(torch, actor, obs, rows, sample=False)
+            base = fs.actor_run(torch, actor, obs, rows, sample=False)
             _exact(base[1], c['logits'], f'{form} logits without vf')
             assert np.array_equal(base[0].reshape(rows, -1), first)
             _logp_check(shape, variant, c, base[0], base[2], 'VF 0')
         vf = torch.full((rows,), float('nan'), device='cuda')
-        act, logits, logp = tag._run(torch, actor, obs, rows, sample=False, vf=vf)
+        act, logits, logp = fs.actor_run(torch, actor, obs, rows, sample=False, vf=vf)
         _exact(logits, c['logits'], f'{form} logits with vf')
         _exact(vf.cpu().numpy(), c['vf'][form], f'{form} vf')
         assert np.array_equal(act.reshape(rows, -1), first)
-        assert np.array_equal(_bits(logp), _bits(base[2]))                           # (the walk is the same code on the same logits)
+        assert np.array_equal(fs.bits(logp), fs.bits(base[2]))                           # (the walk is the same code on the same logits)
         only = torch.full((rows + 64,), float('nan'), device='cuda')
         actor.value(obs, out=only[:rows])
         got = only.cpu().numpy()
@@ -107,23 +94,23 @@ def test_actor_tanh_numerics(torch_cuda, shape):
     """tanh x VF 0 / 1 / 2 on the rows of a real env: the assertions of test_actor_gpu's test_tanh_numerics and
     test_greedy_is_first_maximum_of_own_logits, and per value form those of test_critic_gpu's test_value_tanh_numerics,
     test_policy_outputs_are_bit_identical_with_vf and test_value_only_call_is_bit_identical, at this shape."""
-    tag.test_tanh_numerics(torch_cuda, shape)
-    tag.test_greedy_is_first_maximum_of_own_logits(torch_cuda, shape)
-    for form in tcg.FORMS:
-        tcg.test_value_tanh_numerics(torch_cuda, shape, form)
-        tcg.test_policy_outputs_are_bit_identical_with_vf(torch_cuda, shape, form)
-        tcg.test_value_only_call_is_bit_identical(torch_cuda, shape, form)
+    fs.check_tanh_numerics(torch_cuda, shape)
+    fs.check_greedy_is_first_maximum_of_own_logits(torch_cuda, shape)
+    for form in fc.FORMS:
+        fs.check_value_tanh_numerics(torch_cuda, shape, form)
+        fs.check_policy_outputs_are_bit_identical_with_vf(torch_cuda, shape, form)
+        fs.check_value_only_call_is_bit_identical(torch_cuda, shape, form)
 
 
 def test_num_active_zero(torch_cuda):
     """num_active = 0: every action is 0 and logp is the log-softmax of the kernel's own logits at action 0."""
     torch = torch_cuda
     shape = fc.NO_ACTIVE_SHAPE
-    c = tag._case(torch, shape)
+    c = fs.actor_case(torch, shape)
     for sample in (False, True):
-        act, logits, logp = tag._run(torch, c['actor'], c['obs'], c['rows'], sample=sample, seed=3, step=1, num_active=0)
+        act, logits, logp = fs.actor_run(torch, c['actor'], c['obs'], c['rows'], sample=sample, seed=3, step=1, num_active=0)
         assert not act.any()
-        assert np.array_equal(_bits(logits), _bits(c['logits']))
+        assert np.array_equal(fs.bits(logits), fs.bits(c['logits']))
         lg = logits.astype(np.float64).reshape(c['rows'], -1, shape[3] + 1)
         err = np.abs(logp.astype(np.float64) - fc.log_softmax64(lg)[..., 0]).max()
         assert err <= fc.lse_bound(shape[3] + 1, np.abs(lg).max()), err
@@ -137,19 +124,19 @@ def test_1024_slots_rows_and_compact_record_agree(torch_cuda):
     shape = fc.COMPACT_SHAPE
     kind, E, U, B, H = shape
     codec = FragmentCodec(U, B)
-    for form in tcg.FORMS:
-        c = tcg._vcase(torch, shape, form)
+    for form in fc.FORMS:
+        c = fs.value_case(torch, shape, form)
         packed = codec.pack(c['obs']).clone()
         codec.check()
         assert torch.equal(codec.unpack(packed).view(torch.int32), c['obs'].view(torch.int32))
         for sample in (False, True):
             kw = dict(sample=sample, seed=0xC0FFEE, step=12, row_base=64)
             vf = torch.full((c['rows'],), float('nan'), device='cuda')
-            got = tag._run(torch, c['actor'], packed, c['rows'], compact=True, vf=vf, **kw)
+            got = fs.actor_run(torch, c['actor'], packed, c['rows'], compact=True, vf=vf, **kw)
             for x, y in zip(got, c['with', sample]):
-                assert np.array_equal(_bits(x) if x.dtype == np.float32 else x, _bits(y) if y.dtype == np.float32 else y)
-            assert np.array_equal(_bits(vf.cpu().numpy()), _bits(c['vf', sample]))
-        assert np.array_equal(_bits(c['actor'].value(packed, compact=True).cpu().numpy()), _bits(c['only']))
+                assert np.array_equal(fs.bits(x) if x.dtype == np.float32 else x, fs.bits(y) if y.dtype == np.float32 else y)
+            assert np.array_equal(fs.bits(vf.cpu().numpy()), fs.bits(c['vf', sample]))
+        assert np.array_equal(fs.bits(c['actor'].value(packed, compact=True).cpu().numpy()), fs.bits(c['only']))
 
 
 # ================================================================================================ policy set
@@ -158,7 +145,7 @@ _SET_OBS = {}
 
 def _set_obs(torch, U, B, E):
     if (U, B, E) not in _SET_OBS:
-        env = tag._env('multi', E, U, B)
+        env = fs.env('multi', E, U, B)
         env.reset()
         g = torch.Generator(device='cuda').manual_seed(5)
         for _ in range(3):
@@ -178,9 +165,9 @@ def _set_against_members(torch, pset, obs, modes):
     for mode in modes:
         kws = [{}] if mode == 'v' else [dict(sample=True, seed=7, step=3), dict(sample=False)]
         for kw in kws:
-            got = tps._run(torch, pset, obs, False, mode, guard=tps.GUARD, **kw)
+            got = fs.set_run(torch, pset, obs, False, mode, guard=fc.SET_GUARD, **kw)
             for p, rows in by_member.items():
-                tps._same(torch, got, tps._run(torch, pset.members[p], obs, False, mode, **kw), rows=torch.cat(rows))
+                fs.set_same(torch, got, fs.set_run(torch, pset.members[p], obs, False, mode, **kw), rows=torch.cat(rows))
             for k, t in got.items():
                 if t.dtype.is_floating_point:
                     assert bool(torch.isfinite(t).all()), k
@@ -194,13 +181,13 @@ def test_policy_set_every_instantiation(torch_cuda, H, activation, value):
     torch = torch_cuda
     from deepcomp_amd.policy_set import PerUEActor
     ps = fc.POLICY_SET
-    assert (ps['U'], ps['B'], ps['E']) == (tps.SHAPES['a'][0], tps.SHAPES['a'][1], tps.SHAPES['a'][4]) and ps['slots'] == tps.SLOTS['a']
+    assert (ps['U'], ps['B'], ps['E']) == (fc.SET_SHAPES['a'][0], fc.SET_SHAPES['a'][1], fc.SET_SHAPES['a'][4]) and ps['slots'] == fc.SET_SLOTS['a']
     obs = _set_obs(torch, ps['U'], ps['B'], ps['E'])
-    members = [tps._member('a', 10 + p, value, H=H, activation=activation) for p in range(max(ps['slots']) + 1)]
+    members = [fs.set_member('a', 10 + p, value, H=H, activation=activation) for p in range(max(ps['slots']) + 1)]
     pset = PerUEActor(members, ps['slots'])
     _set_against_members(torch, pset, obs, ('a', 'av', 'v') if value else ('a',))
     # the comparison discriminates: the two members disagree on the same rows
-    a0, a1 = (tps._run(torch, m, obs, False, 'a', sample=False)['logits'] for m in members)
+    a0, a1 = (fs.set_run(torch, m, obs, False, 'a', sample=False)['logits'] for m in members)
     assert not torch.equal(a0, a1)
 
 
@@ -210,7 +197,7 @@ def test_policy_set_1024_slots(torch_cuda):
     from deepcomp_amd.policy_set import PerUEActor
     pw = fc.POLICY_SET_WIDE
     obs = _set_obs(torch, pw['U'], pw['B'], pw['E'])
-    members = [tps._member('a', 10 + p, True, U=pw['U'], B=pw['B'], H=pw['H'], activation='tanh') for p in range(pw['P'])]
+    members = [fs.set_member('a', 10 + p, True, U=pw['U'], B=pw['B'], H=pw['H'], activation='tanh') for p in range(pw['P'])]
     pset = PerUEActor(members, [u % pw['P'] for u in range(pw['U'])])
     _set_against_members(torch, pset, obs, ('a', 'av', 'v'))
 
@@ -219,7 +206,7 @@ def test_policy_set_1024_slots(torch_cuda):
 @pytest.mark.parametrize('shape', fc.LEARNER_SHAPES, ids=LIDS)
 def test_learner_backward_integer_data_exact(torch_cuda, shape):
     """test_learner_gpu's test_backward_integer_data_exact at this shape: all twelve arrays equal the float64 reference exactly."""
-    tlg.test_backward_integer_data_exact(torch_cuda, shape)
+    fs.check_backward_integer_data_exact(torch_cuda, shape)
 
 
 @pytest.mark.parametrize('shape', fc.LEARNER_SHAPES, ids=LIDS)
@@ -227,14 +214,14 @@ def test_learner_tanh_numerics(torch_cuda, shape):
     """test_learner_gpu's test_loss_and_gradient_numerics at this shape: statistics and gradients within 2 x the chain's error.
     (At multi4x6x64h128 -- 24 rows, 65 logits -- the entropy statistic was one f32 step off, 3.47e-07 against the chain's 1.30e-07,
     while the tile's row terms were summed in f32: profiles/r13_fcnet_matrix.txt.)"""
-    tlg.test_loss_and_gradient_numerics(torch_cuda, shape)
+    fs.check_loss_and_gradient_numerics(torch_cuda, shape)
 
 
 @pytest.mark.parametrize('shape', fc.LEARNER_SHAPES, ids=LIDS)
 def test_learner_repacked_weights(torch_cuda, shape):
     """test_learner_gpu's test_repacked_weights_are_what_create_packs at this shape: after three updates the handle's actor equals
     a fresh FcnetActor from the master weights bit for bit."""
-    tlg.test_repacked_weights_are_what_create_packs(torch_cuda, shape)
+    fs.check_repacked_weights_are_what_create_packs(torch_cuda, shape)
 
 
 def test_learner_row_split_with_mult_2(torch_cuda):
@@ -247,7 +234,7 @@ def test_learner_row_split_with_mult_2(torch_cuda):
     assert fc.row_split(len(x)) == dict(mult=2, chunk_rows=4096, nchunks=65)
     actor = FcnetActor(kind, U, B, w, activation='relu', value_weights=v)
     learner = PPOLearner(actor, max_rows=len(x))
-    stats = learner.grads(tlg._cuda(torch, x), dlogits=tlg._cuda(torch, dl), dvalue=tlg._cuda(torch, dv))
+    stats = learner.grads(fs.cuda(torch, x), dlogits=fs.cuda(torch, dl), dvalue=fs.cuda(torch, dv))
     got = learner.read('grads')
     assert np.array_equal(stats.cpu().numpy(), np.zeros(5, dtype=np.float32))
     for n in ARRAYS:
@@ -273,23 +260,23 @@ def test_learner_indexed_every_instantiation(torch_cuda, H, activation, compact)
     from deepcomp_amd.learner import ARRAYS
     ix = fc.INDEXED
     kind, E, U, B, T = ix['kind'], ix['E'], ix['U'], ix['B'], ix['T']
-    w, vw, batch = tli._collected(torch, kind, E, U, B, H, activation, T, compact)
-    learner = tli._learner(kind, U, B, w, vw, activation, max_rows=E * U * T)
-    src = tli._source(batch, learner.actor)
+    w, vw, batch = fs.collected(torch, kind, E, U, B, H, activation, T, compact)
+    learner = fs.ppo_learner(kind, U, B, w, vw, activation, max_rows=E * U * T)
+    src = fs.source(batch, learner.actor)
     n_src = E * U * T
     assert ('obs_compact' in src) == compact
-    idx = tli._shuffled(torch, n_src, 70, 11)
-    _, _, want = tli._check_against_gathered(torch, learner, src, idx)
+    idx = fs.shuffled(torch, n_src, 70, 11)
+    _, _, want = fs.check_against_gathered(torch, learner, src, idx)
     bad = _bad_entry(torch, idx, n_src)
-    got = tli._outputs(torch, 70, 1)
+    got = fs.outputs(torch, 70, 1)
     stats = learner.grads_indexed(src, bad, **got)
     grads = learner.read('grads')
     assert bool(torch.isfinite(stats).all()) and all(np.isfinite(grads[n]).all() for n in ARRAYS)
     others = torch.ones(70, dtype=torch.bool, device='cuda')
     others[35] = False
-    for k in tli.OUTS:
+    for k in fs.OUTS:
         assert bool((got[k][~others] == 0).all()), k
-        assert torch.equal(tli._bits(torch, got[k][others]), tli._bits(torch, want[k][others])), k
+        assert torch.equal(fs.tbits(torch, got[k][others]), fs.tbits(torch, want[k][others])), k
 
 
 def test_learner_handle_reused_across_calls(torch_cuda):
@@ -300,8 +287,8 @@ def test_learner_handle_reused_across_calls(torch_cuda):
     torch = torch_cuda
     from deepcomp_amd import learner as lm
     shape = fc.REUSE_SHAPE
-    assert shape == tlg.SHAPES[6]
-    c = tlg._case(torch, shape)
+    assert shape == fc.LEARNER_BASE_SHAPES[6]
+    c = fs.learner_case(torch, shape)
     rows, actor, dev = c['rows'], c['actor'], c['dev']
     assert rows == 6400
     small = {k: t[:37].contiguous() for k, t in dev.items()}
@@ -312,7 +299,7 @@ def test_learner_handle_reused_across_calls(torch_cuda):
     source = dict(dev)
 
     def outs(n):
-        return {k: torch.full((n, actor.heads) if k == 'logp' else (n,), float('nan'), device='cuda') for k in tli.OUTS}
+        return {k: torch.full((n, actor.heads) if k == 'logp' else (n,), float('nan'), device='cuda') for k in fs.OUTS}
 
     def step(learner, i):
         """-> (tensors to compare, gradient arrays or None)"""
@@ -338,10 +325,10 @@ def test_learner_handle_reused_across_calls(torch_cuda):
         got_t, got_g = step(one, i)
         want_t, want_g = step(lm.PPOLearner(actor, max_rows=rows, **HYPER), i)
         for j, (x, y) in enumerate(zip(got_t, want_t)):
-            assert torch.equal(tli._bits(torch, x), tli._bits(torch, y)), (i, j)
+            assert torch.equal(fs.tbits(torch, x), fs.tbits(torch, y)), (i, j)
         if got_g is not None:
             for n in lm.ARRAYS:
-                assert np.array_equal(_bits(got_g[n]), _bits(want_g[n])), (i, n)
+                assert np.array_equal(fs.bits(got_g[n]), fs.bits(want_g[n])), (i, n)
                 assert np.isfinite(got_g[n]).all(), (i, n)
         if i == 1:
             first = (got_t, got_g)
@@ -349,9 +336,9 @@ def test_learner_handle_reused_across_calls(torch_cuda):
         if i == 5:
             assert bool((got_t[1][[7, 31]] == 0).all())                              # (entropy of the two positions that read nothing)
     for x, y in zip(got_t, first[0]):
-        assert torch.equal(tli._bits(torch, x), tli._bits(torch, y))
+        assert torch.equal(fs.tbits(torch, x), fs.tbits(torch, y))
     for n in lm.ARRAYS:
-        assert np.array_equal(_bits(got_g[n]), _bits(first[1][n])), n
+        assert np.array_equal(fs.bits(got_g[n]), fs.bits(first[1][n])), n
 
 
 @pytest.mark.parametrize('run', list(fc.EPILOGUE_RUNS))
@@ -373,8 +360,8 @@ def test_loss_epilogue_on_exact_logits(torch_cuda, shape, run):
     rows, heads = c['rows'], c['heads']
     actor = FcnetActor(kind, U, B, c['w'], activation='relu', value_weights=c['v']['own'])
     learner = PPOLearner(actor, max_rows=rows, **hy)
-    out = {k: torch.full((rows, heads) if k == 'logp' else (rows,), float('nan'), device='cuda') for k in tli.OUTS}
-    cu = lambda a: tlg._cuda(torch, a)      # noqa: E731
+    out = {k: torch.full((rows, heads) if k == 'logp' else (rows,), float('nan'), device='cuda') for k in fs.OUTS}
+    cu = lambda a: fs.cuda(torch, a)      # noqa: E731
     stats = learner.grads(cu(c['x'].reshape(rows, -1)), cu(c['actions']), cu(c['old_logp']), cu(c['old_logits']), cu(adv), cu(c['value_targets']),
                           cu(c['old_vf']), **out)
     got = {k: t.cpu().numpy().astype(np.float64) for k, t in out.items()}

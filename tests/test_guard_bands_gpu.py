@@ -20,7 +20,7 @@ import pytest
 
 from tests import guard, parity
 from tests import guard_cases as gc
-from tests.test_threshold_gpu import _oracle
+from tests.threshold_cases import oracle_batch as _oracle
 
 pytestmark = pytest.mark.gpu
 

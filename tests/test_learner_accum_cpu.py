@@ -8,24 +8,20 @@ import ctypes
 import math
 import os
 import re
-import subprocess
 
 import pytest
 import torch
 
-from tests.test_sharded_gloo import _free_port
+from tests import c_surface as cs
+from tests.c_surface import EABI, EINVAL, EUNSUPPORTED, lib  # noqa: F401  (lib: the fixture)
+from tests.c_surface import LOSS_INPUTS as _LOSS_INPUTS
+from tests.c_surface import ppo_batch as _ppo
+from tests.c_surface import ppo_hyper as _hyper
+from tests.c_surface import sgd_batch as _sgd
+from tests.env_support import free_port as _free_port
 
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-OK, EINVAL, EUNSUPPORTED, EABI = 0, -1, -6, -7
-HEADER = os.path.join(REPO, 'include', 'dcomp_learner_accum.h')
+HEADER = cs.header('dcomp_learner_accum.h')
 NAMES = ['dcomp_learner_flat_size', 'dcomp_learner_accumulate', 'dcomp_sgd_accumulate', 'dcomp_learner_accum_finish']
-
-
-@pytest.fixture(scope='module')
-def lib():
-    from deepcomp_amd import build, _lib
-    build.build()                      # hipcc cross-compiles gfx950 on a GPU-less host
-    return _lib.load()
 
 
 def test_symbols_are_exported_and_declared(lib, tmp_path):
@@ -41,35 +37,11 @@ def test_symbols_are_exported_and_declared(lib, tmp_path):
     # the surfaces the existing tests pin are as they were
     assert len(_lib.LEARNER_EXPORTS) == 7 and len(_lib.EXPORTS) == 42 and len(_lib.SGD_EXPORTS) == 2 and len(_lib.GROUP_EXPORTS) == 4
     for other in ('dcomp_learner.h', 'dcomp_learner_indexed.h', 'dcomp_learner_group.h'):
-        assert not re.search(r'_accum|_flat_size', open(os.path.join(REPO, 'include', other)).read())
+        assert not re.search(r'_accum|_flat_size', open(cs.header(other)).read())
     # the header as C99, alone and behind the others
-    gcc = ['gcc', '-std=c99', '-Wall', '-Wextra', '-Werror', '-pedantic', '-I', os.path.join(REPO, 'include'), '-fsyntax-only']
-    for n, text in enumerate(('#include "dcomp_learner_accum.h"\n', '#include "dcomp.h"\n#include "dcomp_learner_group.h"\n#include "dcomp_learner_accum.h"\n')):
-        src = tmp_path / f'accum{n}.c'
-        src.write_text(text + 'int main(void) { return DCOMP_ACCUM_SUMS == 8 && DCOMP_EABI == -7 ? 0 : 1; }\n')
-        subprocess.run(gcc + [str(src)], check=True)
-
-
-_PPO_FIELDS = ('obs', 'actions', 'old_logp', 'old_logits', 'advantages', 'value_targets', 'old_vf', 'logp', 'entropy', 'kl', 'vf', 'ratio', 'dlogits', 'dvalue')
-_SGD_FIELDS = ('obs', 'actions', 'old_logp', 'old_logits', 'advantages', 'value_targets', 'old_vf', 'dlogits', 'dvalue', 'logp', 'entropy', 'kl', 'vf', 'ratio')
-_LOSS_INPUTS = _PPO_FIELDS[:7]
-
-
-def _ppo(given=_LOSS_INPUTS, size=None, fmt=0, rows=8):
-    from deepcomp_amd import _lib
-    return _lib.DcompPpoBatch(ctypes.sizeof(_lib.DcompPpoBatch) if size is None else size, fmt, rows, 1, 0,
-                              *[4096 if n in given else None for n in _PPO_FIELDS])     # (never dereferenced)
-
-
-def _sgd(given=_LOSS_INPUTS, size=None, fmt=0, rows=8, source_rows=64, index=4096):
-    from deepcomp_amd import _lib
-    return _lib.DcompSgdBatch(ctypes.sizeof(_lib.DcompSgdBatch) if size is None else size, fmt, rows, source_rows, index, 1, 0,
-                              *[4096 if n in given else None for n in _SGD_FIELDS])
-
-
-def _hyper(size=None, clip=0.3, vf_clip=10.0):
-    from deepcomp_amd import _lib
-    return _lib.DcompPpoHyper(ctypes.sizeof(_lib.DcompPpoHyper) if size is None else size, clip, vf_clip, 1.0, 0.0, 0.2)
+    main = 'int main(void) { return DCOMP_ACCUM_SUMS == 8 && DCOMP_EABI == -7 ? 0 : 1; }\n'
+    cs.compiles_as_c99(tmp_path, 'accum', [text + main for text in (
+        '#include "dcomp_learner_accum.h"\n', '#include "dcomp.h"\n#include "dcomp_learner_group.h"\n#include "dcomp_learner_accum.h"\n')])
 
 
 @pytest.mark.parametrize('surface', ['ppo', 'sgd'])

@@ -21,17 +21,12 @@ import numpy as np
 import pytest
 
 from tests import fcnet_cases as fc
-from tests import test_learner_gpu as tlg
-from tests import test_learner_indexed_gpu as tlig
+from tests import fcnet_support as fs
 
 pytestmark = pytest.mark.gpu
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-MULTI = ('multi', 101, 4, 5, 32, 16)            # (kind, E, U, B, hidden, T): 6 464 source rows
-CENTRAL = ('central', 404, 10, 5, 64, 16)       # fc.EPILOGUE_SHAPES[1]'s net: 6 464 source rows
-assert fc.EPILOGUE_SHAPES[1][0] == 'central' and fc.EPILOGUE_SHAPES[1][2:] == CENTRAL[2:5]
-ROWS = 6444                                      # three full chunks and a partial one
-CHUNK = 2048
+MULTI, CENTRAL, ROWS, CHUNK, LOCK = fc.ACCUM_MULTI, fc.ACCUM_CENTRAL, fc.ACCUM_ROWS, fc.CHUNK, fc.ACCUM_LOCK
 ALIGNED = [(2048, 2048, 2348), (4096, 2348)]
 UNALIGNED = (1000, 5444)
 
@@ -44,30 +39,9 @@ def torch_cuda():
     return torch
 
 
-_WHOLE = {}
-
-
-def _whole(torch, shape, compact=False):
-    """Per shape and source format, computed once and left unchanged: the collect() batch, a shuffled index of ROWS positions, the
-    rows it picks (gathered), and grads() on all of them by a learner with max_rows = ROWS: statistics and gradients."""
-    key = (shape, compact)
-    if key not in _WHOLE:
-        kind, E, U, B, H, T = shape
-        w, vw, batch = tlig._collected(torch, kind, E, U, B, H, 'tanh', T, compact)
-        learner = tlig._learner(kind, U, B, w, vw, 'tanh', max_rows=ROWS)
-        src = tlig._source(batch, learner.actor)
-        n_src = src['actions'].shape[0]
-        assert n_src == 6464
-        index = tlig._shuffled(torch, n_src, ROWS, 7)
-        gathered = {k: t.index_select(0, index.long()).contiguous() for k, t in tlig._as_rows(src, learner.actor).items()}
-        stats = learner.grads(**gathered).cpu().numpy()
-        _WHOLE[key] = dict(w=w, vw=vw, learner=learner, src=src, index=index, gathered=gathered, stats=stats, grads=learner.read('grads'))
-    return _WHOLE[key]
-
-
 def _twin(shape, c, max_rows, **kw):
     kind, E, U, B, H, T = shape
-    return tlig._learner(kind, U, B, c['w'], c['vw'], 'tanh', max_rows=max_rows, **kw)
+    return fs.ppo_learner(kind, U, B, c['w'], c['vw'], 'tanh', max_rows=max_rows, **kw)
 
 
 def _split(sizes):
@@ -89,36 +63,6 @@ def _accumulate(learner, c, sizes, surface):
     return acc, sums
 
 
-def _flat(grads):
-    from deepcomp_amd.learner import ARRAYS
-    return np.concatenate([grads[n].reshape(-1) for n in ARRAYS])
-
-
-_TERMS = {}
-
-
-def _row_terms(c, shape):
-    """mean |per-row term| of the five statistics, from the float64 model on the gathered rows (computed once per shape)."""
-    if shape not in _TERMS:
-        from deepcomp_amd import learner as lm
-        host = {k: t.cpu().numpy() for k, t in c['gathered'].items()}
-        ref64 = lm.ppo_loss_reference(c['w_now'], c['vw_now'], host, tlig.HYPER, 'tanh', 'float64')
-        r = {k: ref64[2][k].numpy() for k in ('surr', 'kl', 'entropy', 'vf_loss')}
-        hy = tlig.HYPER
-        total = -r['surr'] + hy['kl_coeff'] * r['kl'] + hy['vf_loss_coeff'] * r['vf_loss'] - hy['entropy_coeff'] * r['entropy']
-        _TERMS[shape] = (ref64, {'total_loss': np.abs(total).mean(), 'policy_loss': np.abs(r['surr']).mean(), 'vf_loss': np.abs(r['vf_loss']).mean(),
-                                 'kl': np.abs(r['kl']).mean(), 'entropy': np.abs(r['entropy']).mean()})
-    return _TERMS[shape]
-
-
-def _now(c):
-    """The weights the case's learner runs (perturbed against the ones the batch was collected with), as the references take them."""
-    if 'w_now' not in c:
-        from deepcomp_amd import learner as lm
-        c['w_now'], c['vw_now'] = lm.split_weights(c['learner'].read('weights'))
-    return c
-
-
 # ---------------------------------------------------------------------------------------------- (1) micro-batches equal the whole
 @pytest.mark.parametrize('case', ['multi-rows', 'multi-indexed', 'multi-compact', 'central-rows', 'central-indexed'])
 def test_micro_batches_equal_the_whole_bit_for_bit(torch_cuda, case):
@@ -136,11 +80,11 @@ def test_micro_batches_equal_the_whole_bit_for_bit(torch_cuda, case):
     from deepcomp_amd import learner as lm
     shape = MULTI if case.startswith('multi') else CENTRAL
     surface = case.split('-')[1]
-    c = _now(_whole(torch, shape, compact=surface == 'compact'))
-    rows_c = _now(_whole(torch, shape))                      # (the per-row terms: from the rows of the same index)
-    _, terms = _row_terms(rows_c, shape)
+    c = fs.now(fs.whole(torch, shape, compact=surface == 'compact'))
+    rows_c = fs.now(fs.whole(torch, shape))                      # (the per-row terms: from the rows of the same index)
+    _, terms = fs.row_terms(rows_c, shape)
     micro = _twin(shape, c, 4096)
-    assert micro.flat_size == _flat(c['grads']).size
+    assert micro.flat_size == fs.flat(c['grads']).size
     for sizes in ALIGNED:
         assert all(n % CHUNK == 0 for n in sizes[:-1])
         acc, sums = _accumulate(micro, c, sizes, 'rows' if surface == 'rows' else 'indexed')
@@ -163,26 +107,26 @@ def test_a_split_that_is_not_chunk_aligned_meets_the_whole_batch_bars(torch_cuda
     array).  The statistics are not re-associated by the split beyond test (1)'s bound and are held to the whole batch's."""
     torch = torch_cuda
     from deepcomp_amd import learner as lm
-    c = _now(_whole(torch, shape))
-    ref64, _ = _row_terms(c, shape)
+    c = fs.now(fs.whole(torch, shape))
+    ref64, _ = fs.row_terms(c, shape)
     host = {k: t.cpu().numpy() for k, t in c['gathered'].items()}
-    chain = lm.ppo_loss_reference(c['w_now'], c['vw_now'], host, tlig.HYPER, 'tanh', 'bf16')
+    chain = lm.ppo_loss_reference(c['w_now'], c['vw_now'], host, fc.HYPER, 'tanh', 'bf16')
     learner = _twin(shape, c, ROWS)
     assert UNALIGNED[0] % CHUNK
     acc, sums = _accumulate(learner, c, UNALIGNED, 'rows')
     stats = learner.finish(acc, sums).cpu().numpy()
     got = learner.read('grads')
     worst = []
-    for name, ek, ec in tlg._errors(lm, stats, got, ref64, chain):
+    for name, ek, ec in fs.errors(lm, stats, got, ref64, chain):
         print(f'unaligned split {shape[0]} {name}: CPU chain max abs err {ec:.3e}  kernel {ek:.3e}')
         if name in lm.ARRAYS and not ek <= 2 * ec:           # the gradients: what the split re-associates
             worst.append((name, ek, ec))
     assert not worst, worst
     # the whole batch's gradients are inside the same bars, and the split did change bits: neither comparison is vacuous
-    assert all(ek <= 2 * ec for name, ek, ec in tlg._errors(lm, c['stats'], c['grads'], ref64, chain) if name in lm.ARRAYS)
+    assert all(ek <= 2 * ec for name, ek, ec in fs.errors(lm, c['stats'], c['grads'], ref64, chain) if name in lm.ARRAYS)
     assert any(not np.array_equal(got[n], c['grads'][n]) for n in lm.ARRAYS)
     # the statistics do not depend on where a call ends: test (1)'s bar against the whole batch
-    _, terms = _row_terms(c, shape)
+    _, terms = fs.row_terms(c, shape)
     for i, n in enumerate(lm.STATS):
         assert abs(float(stats[i]) - float(c['stats'][i])) <= float(np.spacing(np.abs(c['stats'][i]))) + 2.0 ** -40 * terms[n], n
 
@@ -202,7 +146,7 @@ def _same(torch, lm, p1, p2):
     for x, y in zip(p1[0], p2[0]):
         assert torch.equal(x, y)
     assert bool(torch.isfinite(p1[0][1]).all())
-    tlig._same_state(lm, p1[1], p2[1])
+    fs.same_state(p1[1], p2[1])
 
 
 @pytest.mark.parametrize('R', [2, 3])
@@ -213,7 +157,7 @@ def test_ranks_equal_the_whole_bit_for_bit(torch_cuda, R):
     the R x 2 048 rows in a row."""
     torch = torch_cuda
     from deepcomp_amd import learner as lm
-    c = _whole(torch, MULTI)
+    c = fs.whole(torch, MULTI)
     n = R * CHUNK
     rows = {k: t[:n] for k, t in c['gathered'].items()}
     one = _twin(MULTI, c, n, lr=1e-3)
@@ -237,7 +181,7 @@ def test_ranks_equal_the_whole_bit_for_bit(torch_cuda, R):
         ln.apply()
     obs = rows['obs'][:300]
     want = _probe(torch, one, obs)
-    assert want[1]['step'] == 1 and np.abs(want[1]['weights']['w2'] - lm.join_weights(*tlig._perturbed(c['w'], c['vw']))['w2']).max() > 1e-4
+    assert want[1]['step'] == 1 and np.abs(want[1]['weights']['w2'] - lm.join_weights(*fs.perturbed(c['w'], c['vw']))['w2']).max() > 1e-4
     for ln in ranks:
         _same(torch, lm, _probe(torch, ln, obs), want)
     # the backward fragments: the next gradients, on rows none of the ranks has seen
@@ -255,7 +199,7 @@ def test_ranks_equal_the_whole_bit_for_bit(torch_cuda, R):
 def test_nothing_else_is_written_and_repeats_are_identical(torch_cuda):
     torch = torch_cuda
     from deepcomp_amd import learner as lm
-    c = _whole(torch, MULTI)
+    c = fs.whole(torch, MULTI)
     learner = _twin(MULTI, c, ROWS)
     F = learner.flat_size
     first = {k: t[:700] for k, t in c['gathered'].items()}
@@ -292,7 +236,7 @@ def test_nothing_else_is_written_and_repeats_are_identical(torch_cuda):
         assert torch.equal(again, stats)
         for n in lm.ARRAYS:
             assert np.array_equal(learner.read('grads')[n], got[n]), n
-        runs.append((acc0.cpu().numpy(), sums0.cpu().numpy(), stats.cpu().numpy(), _flat(got), norm.cpu().numpy()[1]))
+        runs.append((acc0.cpu().numpy(), sums0.cpu().numpy(), stats.cpu().numpy(), fs.flat(got), norm.cpu().numpy()[1]))
         learner.grads(**first, stats=kept_stats)             # the handle's gradients as before the next run
     for x, y in zip(*runs):
         assert np.array_equal(x, y)
@@ -305,18 +249,18 @@ def test_global_norm_clipping(torch_cuda):
     kernel's double norm is a different order of the same sum), one for the product.  Below the clip: unchanged bit for bit."""
     torch = torch_cuda
     from deepcomp_amd import learner as lm
-    c = _whole(torch, MULTI)
+    c = fs.whole(torch, MULTI)
     learner = _twin(MULTI, c, 4096)
     acc, sums = _accumulate(learner, c, ALIGNED[1], 'rows')
     learner.finish(acc, sums)
-    g = _flat(learner.read('grads'))
-    assert np.array_equal(g, _flat(c['grads']))
+    g = fs.flat(learner.read('grads'))
+    assert np.array_equal(g, fs.flat(c['grads']))
     norm64 = float(np.sqrt((g.astype(np.float64) ** 2).sum()))
     for clip, clipped in ((0.5 * norm64, True), (2.0 * norm64, False)):
         assert (norm64 > clip) == clipped                    # from the read-back unclipped gradient
         norm = torch.full((1,), float('nan'), device='cuda')
         learner.finish(acc, sums, grad_clip=clip, grad_norm=norm)
-        got = _flat(learner.read('grads'))
+        got = fs.flat(learner.read('grads'))
         want, want_norm = lm.clip_reference(g, clip)
         assert learner.clip_reference is lm.clip_reference
         print(f'clip {clip:.6e}: grad_norm {float(norm):.9e} float64 norm {norm64:.9e} |diff| {abs(float(norm) - norm64):.3e} ulp {float(np.spacing(np.float32(norm64))):.3e}')
@@ -332,7 +276,7 @@ def test_global_norm_clipping(torch_cuda):
     for none in (0.0, None):
         norm = torch.full((1,), float('nan'), device='cuda')
         learner.finish(acc, sums, grad_clip=none, grad_norm=norm)
-        assert np.array_equal(_flat(learner.read('grads')), g)
+        assert np.array_equal(fs.flat(learner.read('grads')), g)
         assert abs(float(norm) - norm64) <= float(np.spacing(np.float32(norm64)))
     with pytest.raises(ValueError):
         learner.finish(acc, sums, grad_clip=-1.0)
@@ -349,18 +293,18 @@ def test_update_with_micro_rows_equals_update(torch_cuda, compact):
     torch = torch_cuda
     from deepcomp_amd import learner as lm
     kind, E, U, B, H, T = MULTI
-    w, vw, batch = tlig._collected(torch, kind, E, U, B, H, 'tanh', T, compact)
-    mk = lambda max_rows: tlig._learner(kind, U, B, w, vw, 'tanh', max_rows=max_rows, perturb=False, lr=1e-3)      # noqa: E731
+    w, vw, batch = fs.collected(torch, kind, E, U, B, H, 'tanh', T, compact)
+    mk = lambda max_rows: fs.ppo_learner(kind, U, B, w, vw, 'tanh', max_rows=max_rows, perturb=False, lr=1e-3)      # noqa: E731
     whole, micro, loop = mk(4096), mk(CHUNK), mk(4096)
     out_w = whole.update(batch, num_sgd_iter=2, minibatch_rows=4096, seed=3)
     out_m = micro.update(batch, num_sgd_iter=2, minibatch_rows=4096, seed=3, micro_rows=CHUNK)
     s_w, s_m = whole.state_dict(), micro.state_dict()
     assert s_w['step'] == 4 and np.abs(s_w['weights']['w2'] - w['w2']).max() > 1e-4
-    tlig._same_state(lm, s_w, s_m)
+    fs.same_state(s_w, s_m)
     for n in lm.STATS:                                       # means of two minibatches' float32 statistics, each within an ulp (test (1))
         assert abs(out_w[n] - out_m[n]) <= 2.0 ** -22 * max(1.0, abs(out_w[n])), n
-    tlig._gathered_update(torch, loop, batch if not compact else tlig._rows_batch(torch, batch, U, B), 2, 4096, 3)
-    tlig._same_state(lm, s_w, dict(loop.state_dict(), kl_coeff=s_w['kl_coeff']))
+    fs.gathered_update(torch, loop, batch if not compact else fs.rows_batch(batch, U, B), 2, 4096, 3)
+    fs.same_state(s_w, dict(loop.state_dict(), kl_coeff=s_w['kl_coeff']))
     # the refusals of update's new arguments
     for bad in (1000, CHUNK + 1, 0):
         with pytest.raises(ValueError, match='multiple'):
@@ -379,12 +323,12 @@ def test_update_with_grad_clip_clips(torch_cuda):
     torch = torch_cuda
     from deepcomp_amd import learner as lm
     kind, E, U, B, H, T = MULTI
-    w, vw, batch = tlig._collected(torch, kind, E, U, B, H, 'tanh', T, False)
-    mk = lambda: tlig._learner(kind, U, B, w, vw, 'tanh', max_rows=4096, perturb=False, lr=1e-3)      # noqa: E731
+    w, vw, batch = fs.collected(torch, kind, E, U, B, H, 'tanh', T, False)
+    mk = lambda: fs.ppo_learner(kind, U, B, w, vw, 'tanh', max_rows=4096, perturb=False, lr=1e-3)      # noqa: E731
     clipped, loop, free = mk(), mk(), mk()
     clipped.update(batch, num_sgd_iter=1, minibatch_rows=4096, seed=3, grad_clip=0.01)
     free.update(batch, num_sgd_iter=1, minibatch_rows=4096, seed=3)
-    src = tlig._source(batch, loop.actor)
+    src = fs.source(batch, loop.actor)
     adv = src['advantages']
     src['advantages'] = (adv - adv.mean()) / adv.std(unbiased=False).clamp_min(1e-4)
     N = src['obs'].shape[0]
@@ -402,25 +346,15 @@ def test_update_with_grad_clip_clips(torch_cuda):
         norms.append(float(norm))
         loop.apply()
     assert min(norms) > 0.01                                 # every step was clipped
-    tlig._same_state(lm, clipped.state_dict(), dict(loop.state_dict(), kl_coeff=clipped.hyper['kl_coeff']))
+    fs.same_state(clipped.state_dict(), dict(loop.state_dict(), kl_coeff=clipped.hyper['kl_coeff']))
     assert not np.array_equal(clipped.read('m')['w2'], free.read('m')['w2'])
 
 
 # ---------------------------------------------------------------------------------------------- (6) lockstep
-LOCK = ('multi', 96, 4, 5, 32, 8)               # 3 072 rows: 1 536 per rank of two, 1 024 per rank of three
-
-
-def _shard(batch, r, R, E, U, T):
-    """Rank r's envs of a rows batch: every per-row tensor is [T, E, U, ...] flattened."""
-    lo, hi = r * E // R, (r + 1) * E // R
-    keys = ('obs', 'actions', 'action_logp', 'action_dist_inputs', 'advantages', 'value_targets', 'vf_preds')
-    return {k: batch[k].reshape(T, E, U, -1)[:, lo:hi].reshape(T, (hi - lo) * U, -1).contiguous() for k in keys}
-
-
 def _dp_ranks(torch, R, w, vw, max_rows):
     from deepcomp_amd.dp_learner import DataParallelLearner
     kind, E, U, B, H, T = LOCK
-    return [DataParallelLearner(tlig._learner(kind, U, B, w, vw, 'tanh', max_rows=max_rows, perturb=False, lr=1e-3), rank=r, world=R) for r in range(R)]
+    return [DataParallelLearner(fs.ppo_learner(kind, U, B, w, vw, 'tanh', max_rows=max_rows, perturb=False, lr=1e-3), rank=r, world=R) for r in range(R)]
 
 
 @pytest.mark.parametrize('R', [2, 3])
@@ -429,8 +363,8 @@ def test_lockstep_ranks_stay_identical(torch_cuda, R):
     from deepcomp_amd import learner as lm
     from deepcomp_amd.dp_learner import run_lockstep
     kind, E, U, B, H, T = LOCK
-    w, vw, batch = tlig._collected(torch, kind, E, U, B, H, 'tanh', T, False)
-    shards = [_shard(batch, r, R, E, U, T) for r in range(R)]
+    w, vw, batch = fs.collected(torch, kind, E, U, B, H, 'tanh', T, False)
+    shards = [fs.shard(batch, r, R, E, U, T) for r in range(R)]
     n = E * U * T // R
     dps = _dp_ranks(torch, R, w, vw, max_rows=n // 2)
     obs = shards[0]['obs'].reshape(-1, 4 * B + 1)[:200]
@@ -459,13 +393,13 @@ def test_lockstep_of_one_rank_is_the_phases_written_out(torch_cuda):
     from deepcomp_amd import learner as lm
     from deepcomp_amd.dp_learner import DataParallelLearner, run_lockstep
     kind, E, U, B, H, T = LOCK
-    w, vw, batch = tlig._collected(torch, kind, E, U, B, H, 'tanh', T, False)
+    w, vw, batch = fs.collected(torch, kind, E, U, B, H, 'tanh', T, False)
     dp = _dp_ranks(torch, 1, w, vw, max_rows=CHUNK)[0]
     out = run_lockstep([dp], [batch], num_sgd_iter=2, minibatch_rows=CHUNK, micro_rows=CHUNK, seed=21)[0]
-    assert out == DataParallelLearner(tlig._learner(kind, U, B, w, vw, 'tanh', max_rows=CHUNK, perturb=False, lr=1e-3)).update(
+    assert out == DataParallelLearner(fs.ppo_learner(kind, U, B, w, vw, 'tanh', max_rows=CHUNK, perturb=False, lr=1e-3)).update(
         batch, num_sgd_iter=2, minibatch_rows=CHUNK, micro_rows=CHUNK, seed=21)          # (no group: update() alone is the same thing)
-    ref = tlig._learner(kind, U, B, w, vw, 'tanh', max_rows=CHUNK, perturb=False, lr=1e-3)
-    src = tlig._source(batch, ref.actor)
+    ref = fs.ppo_learner(kind, U, B, w, vw, 'tanh', max_rows=CHUNK, perturb=False, lr=1e-3)
+    src = fs.source(batch, ref.actor)
     a = src['advantages'].double()
     n = a.numel()
     mean = float(a.sum()) / n
@@ -485,9 +419,9 @@ def test_lockstep_of_one_rank_is_the_phases_written_out(torch_cuda):
             ref.finish(acc, sums, stats=stats[i])
             ref.apply()
     kl = float(stats.mean(0)[3])
-    want_coeff = lm.adapt_kl_coeff(tlig.HYPER['kl_coeff'], kl, ref.kl_target)
+    want_coeff = lm.adapt_kl_coeff(fc.HYPER['kl_coeff'], kl, ref.kl_target)
     assert out['kl'] == kl and out['kl_coeff'] == want_coeff
-    tlig._same_state(lm, dp.learner.state_dict(), dict(ref.state_dict(), kl_coeff=want_coeff))
+    fs.same_state(dp.learner.state_dict(), dict(ref.state_dict(), kl_coeff=want_coeff))
     assert dp.learner.state_dict()['step'] == 4
 
 
@@ -495,18 +429,18 @@ def test_lockstep_refuses_unequal_shards_before_any_launch(torch_cuda):
     torch = torch_cuda
     from deepcomp_amd.dp_learner import run_lockstep
     kind, E, U, B, H, T = LOCK
-    w, vw, batch = tlig._collected(torch, kind, E, U, B, H, 'tanh', T, False)
+    w, vw, batch = fs.collected(torch, kind, E, U, B, H, 'tanh', T, False)
     dps = _dp_ranks(torch, 2, w, vw, max_rows=CHUNK)
     before = [d.learner.state_dict() for d in dps]
-    lo = {k: batch[k].reshape(T, E, U, -1)[:, :40].reshape(T, 40 * U, -1).contiguous() for k in _shard(batch, 0, 2, E, U, T)}
+    lo = {k: batch[k].reshape(T, E, U, -1)[:, :40].reshape(T, 40 * U, -1).contiguous() for k in fs.shard(batch, 0, 2, E, U, T)}
     hi = {k: batch[k].reshape(T, E, U, -1)[:, 40:].reshape(T, 56 * U, -1).contiguous() for k in lo}
     with pytest.raises(ValueError, match='different numbers of rows'):
         run_lockstep(dps, [lo, hi], num_sgd_iter=1)
     with pytest.raises(ValueError, match='world size'):
-        run_lockstep(dps, [_shard(batch, r, 2, E, U, T) for r in range(2)], num_sgd_iter=1, minibatch_rows=1025)
+        run_lockstep(dps, [fs.shard(batch, r, 2, E, U, T) for r in range(2)], num_sgd_iter=1, minibatch_rows=1025)
     from deepcomp_amd import learner as lm
     for d, s in zip(dps, before):                            # nothing ran: no step, the weights as they were
-        tlig._same_state(lm, d.learner.state_dict(), s)
+        fs.same_state(d.learner.state_dict(), s)
         assert d.learner.state_dict()['step'] == 0
 
 

@@ -4,27 +4,21 @@ one is never dereferenced), and the specification -- ppo_loss_reference, adam_re
 names -- is what it claims to be.  No GPU compute is called here.  Refusals that need a live handle (rows > max_rows, an actor
 without a value trunk, a shared value) are in tests/test_learner_gpu.py."""
 import ctypes
-import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
 
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-OK, EINVAL, EUNSUPPORTED, EABI = 0, -1, -6, -7
-
-
-@pytest.fixture(scope='module')
-def lib():
-    from deepcomp_amd import build, _lib
-    build.build()                      # hipcc cross-compiles gfx950 on a GPU-less host
-    return _lib.load()
+from tests import c_surface as cs
+from tests.c_surface import EABI, EINVAL, EUNSUPPORTED, OK, lib  # noqa: F401  (lib: the fixture)
+from tests.c_surface import LOSS_INPUTS as _LOSS_INPUTS
+from tests.c_surface import ppo_batch as _batch
+from tests.c_surface import ppo_hyper as _hyper
 
 
 def test_symbols_are_exported_and_declared(lib):
     from deepcomp_amd import _lib
-    hdr = open(os.path.join(REPO, 'include', 'dcomp_learner.h')).read()
+    hdr = open(cs.header('dcomp_learner.h')).read()
     assert len(_lib.LEARNER_EXPORTS) == 7 and len(set(_lib.LEARNER_EXPORTS)) == 7
     for name in _lib.LEARNER_EXPORTS:
         assert re.search(r'\bint %s\s*\(' % name, hdr), name
@@ -32,35 +26,27 @@ def test_symbols_are_exported_and_declared(lib):
         assert name not in _lib.EXPORTS                                   # EXPORTS stays what include/dcomp.h declares
     assert sorted(re.findall(r'\bint (dcomp_learner_\w+)\s*\(', hdr)) == sorted(_lib.LEARNER_EXPORTS)
     assert len(_lib.EXPORTS) == 42
-    assert '#include "dcomp_types.h"' in hdr and 'DCOMP_ABI_VERSION 3' in open(os.path.join(REPO, 'include', 'dcomp.h')).read()
+    assert '#include "dcomp_types.h"' in hdr and 'DCOMP_ABI_VERSION 3' in open(cs.header('dcomp.h')).read()
 
 
 def test_ctypes_mirrors_match_the_header(tmp_path):
     """Member names from the header text, sizes from a C program compiled against it (C99, pedantic)."""
     from deepcomp_amd import _lib
-    txt = re.sub(r'/\*.*?\*/', '', open(os.path.join(REPO, 'include', 'dcomp_learner.h')).read(), flags=re.S)
     mirrors = (('dcomp_learner_arrays', _lib.DcompLearnerArrays), ('dcomp_learner_cfg', _lib.DcompLearnerCfg),
                ('dcomp_ppo_batch', _lib.DcompPpoBatch), ('dcomp_ppo_hyper', _lib.DcompPpoHyper))
     for cname, mirror in mirrors:
-        body = re.search(r'typedef struct %s \{(.*?)\} %s;' % (cname, cname), txt, flags=re.S).group(1)
-        members = [re.split(r'[\s*]+', m.strip())[-1] for decl in body.split(';') if decl.strip() for m in decl.split(',')]
+        members = cs.struct_members(cs.header('dcomp_learner.h'), cname)
         assert members == [f[0] for f in mirror._fields_], (cname, members)
     assert tuple(f[0] for f in _lib.DcompLearnerArrays._fields_[2:]) == _lib.LEARNER_ARRAYS
-    src = tmp_path / 'sizes.c'
-    src.write_text('#include <stdio.h>\n#include "dcomp_learner.h"\n'
+    sizes, = cs.c_program_output(
+        tmp_path, '#include <stdio.h>\n#include "dcomp_learner.h"\n'
                    'int main(void) {\n'
                    '    printf("%zu %zu %zu %zu %d %d\\n", sizeof(dcomp_learner_arrays), sizeof(dcomp_learner_cfg), sizeof(dcomp_ppo_batch),\n'
                    '           sizeof(dcomp_ppo_hyper), DCOMP_PPO_NUM_STATS, DCOMP_LEARNER_ADAM_V);\n'
                    '    return 0;\n'
                    '}\n')
-    inc = os.path.join(REPO, 'include')
-    subprocess.run(['gcc', '-std=c99', '-Wall', '-Wextra', '-Werror', '-pedantic', '-fsyntax-only', '-I', inc, str(src)], check=True)
-    both = tmp_path / 'both.c'                                            # the two public headers side by side
-    both.write_text('#include "dcomp.h"\n#include "dcomp_learner.h"\nint main(void) { return DCOMP_EABI == -7 ? 0 : 1; }\n')
-    subprocess.run(['gcc', '-std=c99', '-Wall', '-Wextra', '-Werror', '-pedantic', '-fsyntax-only', '-I', inc, str(both)], check=True)
-    exe = tmp_path / 'sizes'
-    subprocess.run(['gcc', '-std=c99', '-I', inc, '-o', str(exe), str(src)], check=True)
-    sizes = [int(x) for x in subprocess.run([str(exe)], check=True, stdout=subprocess.PIPE, text=True).stdout.split()]
+    # the two public headers side by side
+    cs.compiles_as_c99(tmp_path, 'both', ['#include "dcomp.h"\n#include "dcomp_learner.h"\nint main(void) { return DCOMP_EABI == -7 ? 0 : 1; }\n'])
     assert sizes == [ctypes.sizeof(_lib.DcompLearnerArrays), ctypes.sizeof(_lib.DcompLearnerCfg), ctypes.sizeof(_lib.DcompPpoBatch),
                      ctypes.sizeof(_lib.DcompPpoHyper), _lib.PPO_NUM_STATS, _lib.LEARNER_ADAM_V]
     assert len(_lib.PPO_STATS) == _lib.PPO_NUM_STATS
@@ -105,22 +91,6 @@ def test_create_refuses_bad_arguments_on_the_host(lib):
     assert lib.dcomp_learner_create(fake, ctypes.byref(_cfg(keep, weights=bad)), ctypes.byref(out)) == EABI
     assert b'dcomp_learner_arrays' in lib.dcomp_last_error()
     assert lib.dcomp_learner_destroy(None) == OK
-
-
-_BATCH_FIELDS = ('obs', 'actions', 'old_logp', 'old_logits', 'advantages', 'value_targets', 'old_vf', 'logp', 'entropy', 'kl', 'vf', 'ratio',
-                 'dlogits', 'dvalue')
-_LOSS_INPUTS = _BATCH_FIELDS[:7]
-
-
-def _batch(given=_LOSS_INPUTS, size=None, fmt=0, rows=8, num_active=1):
-    from deepcomp_amd import _lib
-    return _lib.DcompPpoBatch(ctypes.sizeof(_lib.DcompPpoBatch) if size is None else size, fmt, rows, num_active, 0,
-                              *[4096 if n in given else None for n in _BATCH_FIELDS])          # (never dereferenced)
-
-
-def _hyper(size=None, clip=0.3, vf_clip=10.0):
-    from deepcomp_amd import _lib
-    return _lib.DcompPpoHyper(ctypes.sizeof(_lib.DcompPpoHyper) if size is None else size, clip, vf_clip, 1.0, 0.0, 0.2)
 
 
 def test_grads_refuses_bad_arguments_on_the_host(lib):

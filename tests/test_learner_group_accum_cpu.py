@@ -10,42 +10,17 @@ of a member its max_rows (the second 64-bit word of the handle).  Everything els
 import ctypes
 import os
 import re
-import subprocess
 
 import pytest
 
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-OK, EINVAL, EUNSUPPORTED, EABI = 0, -1, -6, -7
-HEADER = os.path.join(REPO, 'include', 'dcomp_learner_group_accum.h')
+from tests import c_surface as cs
+from tests.c_surface import EABI, EINVAL, REPO, lib  # noqa: F401  (lib: the fixture)
+from tests.c_surface import group_batch as _batch
+from tests.c_surface import ppo_hypers as _hypers
+from tests.group_cases import CALL, CALL_ROWS, CHUNK, FINISH, GROUP_CASES, LOCK, LOCK4, PLANS, UPDATE, group_slice
+
+HEADER = cs.header('dcomp_learner_group_accum.h')
 NAMES = ['dcomp_learner_group_accumulate', 'dcomp_learner_group_accum_finish']
-CHUNK = 2048
-
-# The shapes of the GPU tests: (U, B, hidden, E, T, slot_policy).
-CALL = (5, 3, 32, 70, 13, [0, 1, 2, 0, 1])            # GROUP_CASES['a-rows']'s shape with T raised: 4 550 source rows for indices of 4 500
-CALL_ROWS = [4500, 2250, 0]                           # 3 and 2 weight-gradient chunks; the third member sits the calls out
-FINISH = {32: (4, 5, 32, 40, 2, [0, 1, 2, 3]), 64: (4, 5, 64, 40, 2, [0, 1, 2, 3])}
-UPDATE = (4, 5, 32, 100, 23, [0, 0, 1, 2])            # 4 600 / 2 300 / 2 300 rows per policy, max_rows 2 048
-LOCK = (4, 5, 32, 32, 8, [0, 1, 0, 1])                # per rank: 32 envs, 512 rows per policy
-LOCK4 = (4, 5, 32, 32, 8, [0, 1, 2, 3])
-# (n_of per policy, minibatch_rows, max_rows, micro_rows, grad_clip) of every grouped update the GPU tests run
-PLANS = {
-    'whole-batch': ([4600, 2300, 2300], None, 2048, 2048, 0.5),
-    'two-rounds': ([4600, 2300, 2300], 3000, 2048, 2048, 0.5),
-    'no-clip': ([4600, 2300, 2300], 3000, 2048, 2048, None),
-    'clip-only': ([4600, 2300, 2300], 3000, 4600, None, 0.5),
-    'mix': ([4600, 2300, 2300], 2048, 2048, None, 1.0),
-    'lock-1': ([512, 512], 256, 2048, None, 5.0),
-    'lock-2': ([512, 512], 128, 2048, None, 5.0),
-    'idle-policy': ([4600, 0, 2300], 3000, 2048, 2048, None),
-    'plain': ([700, 1050], 64, 64, None, None),
-}
-
-
-@pytest.fixture(scope='module')
-def lib():
-    from deepcomp_amd import build, _lib
-    build.build()                      # hipcc cross-compiles gfx950 on a GPU-less host
-    return _lib.load()
 
 
 def test_symbols_are_exported_and_declared_and_the_header_is_c(lib, tmp_path):
@@ -58,13 +33,11 @@ def test_symbols_are_exported_and_declared_and_the_header_is_c(lib, tmp_path):
         assert not any(name in lst for lst in (_lib.EXPORTS, _lib.LEARNER_EXPORTS, _lib.SGD_EXPORTS, _lib.GROUP_EXPORTS, _lib.ACCUM_EXPORTS))
     assert sorted(re.findall(r'\bint (dcomp_\w+)\s*\(', hdr)) == sorted(NAMES)
     assert '#include "dcomp_learner_group.h"' in hdr and '#include "dcomp_learner_accum.h"' in hdr
-    gcc = ['gcc', '-std=c99', '-Wall', '-Wextra', '-Werror', '-pedantic', '-I', os.path.join(REPO, 'include'), '-fsyntax-only']
     every = ''.join(f'#include "{h}"\n' for h in ('dcomp.h', 'dcomp_learner.h', 'dcomp_learner_indexed.h', 'dcomp_policy_set.h', 'dcomp_learner_group.h',
                                                    'dcomp_learner_accum.h', 'dcomp_learner_group_accum.h'))
-    for n, text in enumerate(('#include "dcomp_learner_group_accum.h"\n', every, '#include "dcomp_learner_group_accum.h"\n' + every)):
-        src = tmp_path / f'group_accum{n}.c'
-        src.write_text(text + 'int main(void) { return DCOMP_ACCUM_SUMS == 8 && DCOMP_GROUP_SLICE >= 64 && DCOMP_EABI == -7 ? 0 : 1; }\n')
-        subprocess.run(gcc + [str(src)], check=True)
+    main = 'int main(void) { return DCOMP_ACCUM_SUMS == 8 && DCOMP_GROUP_SLICE >= 64 && DCOMP_EABI == -7 ? 0 : 1; }\n'
+    cs.compiles_as_c99(tmp_path, 'group_accum', [text + main for text in (
+        '#include "dcomp_learner_group_accum.h"\n', every, '#include "dcomp_learner_group_accum.h"\n' + every)])
     # both of the build's header lists name it: the source list and dcomp_learner.o's dependency rule
     assert open(os.path.join(REPO, 'deepcomp_amd', 'build.py')).read().count("'dcomp_learner_group_accum.h'") == 2
 
@@ -84,23 +57,6 @@ class _FakeGroup:
         self.image[0] = ctypes.addressof(self.list)
         self.image[1] = self.image[2] = ctypes.addressof(self.list) + 8 * P
         self.handle = ctypes.c_void_p(ctypes.addressof(self.image))
-
-
-def _hypers(P, size=None, bad=None):
-    from deepcomp_amd import _lib
-    hy = (_lib.DcompPpoHyper * P)(*[_lib.DcompPpoHyper(ctypes.sizeof(_lib.DcompPpoHyper), 0.3, 10.0, 1.0, 0.0, 0.2) for _ in range(P)])
-    if bad is not None:
-        hy[bad].struct_size = size
-    return hy
-
-
-def _batch(rows=None, size=None, stride=64, index=4096, given=True, source_rows=640):
-    from deepcomp_amd import _lib
-    ptr = 4096 if given else None                                                      # (never dereferenced)
-    arr = (ctypes.c_int64 * len(rows))(*rows) if rows is not None else None
-    b = _lib.DcompGroupBatch(ctypes.sizeof(_lib.DcompGroupBatch) if size is None else size, 0, source_rows, ptr, ptr, ptr, ptr, ptr, ptr, ptr, index, stride, arr)
-    b._keep = arr
-    return b
 
 
 def test_accumulate_refuses_in_the_documented_order(lib):
@@ -224,7 +180,6 @@ def _flat(U, B, H):
 
 def test_the_shapes_reach_what_the_gpu_tests_claim(lib):
     from tests import fcnet_cases as fc
-    from tests.test_learner_group_cpu import GROUP_CASES, group_slice
     assert fc.CHUNK_UNIT == CHUNK
     # finish: fewer entries than one 4 096-entry norm block and no multiple of 256; three norm partials and 46 blocks of 256
     for U in (1, 4, 9):

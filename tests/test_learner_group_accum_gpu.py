@@ -8,7 +8,7 @@ per-learner kernels' own text and every order of summation depends on that polic
 torch.equal on accumulators, np.array_equal on state_dict() and gradients, == on the statistics dicts.  The one place where two
 DIFFERENT paths are compared (test 5: accumulated against unaccumulated) says what is exact there and why the rest is not.
 
-Shapes: tests/test_learner_group_accum_cpu.py's tables (the CPU test shows what they reach).  A sample batch is collected once per
+Shapes: tests/group_cases.py's tables (tests/test_learner_group_accum_cpu.py shows what they reach).  A sample batch is collected once per
 shape and left unchanged."""
 import ctypes
 import json
@@ -19,37 +19,23 @@ import sys
 import numpy as np
 import pytest
 
-from tests import test_learner_group_accum_cpu as ac
-from tests import test_learner_group_gpu as tlgg
-from tests.test_learner_accum_gpu import _shard
-from tests.test_learner_indexed_gpu import _same_state as _same_bits
-from tests.test_policy_set_gpu import _same_state
+from tests import fcnet_support as fs
+from tests import group_cases as ac
+from tests.fcnet_cases import HYPER
+from tests.fcnet_support import torch_cuda  # noqa: F401  (the fixture)
 
 pytestmark = pytest.mark.gpu
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HYPER = tlgg.HYPER
 CHUNK = ac.CHUNK
 PATTERN = 0x5A5A5A5A                                      # as float32 1.536e16: finite, so a gradient can hold it
-
-
-@pytest.fixture(scope='module')
-def torch_cuda():
-    import torch
-    assert torch.cuda.is_available(), "these tests need the MI355X"
-    return torch
 
 
 def _case(shape, compact=False, key=None):
     """(batch, two PerUELearner twins' factory) of a shape of the CPU table."""
     U, B, H, E, T, slots = shape
-    batch = tlgg._batch(('group-accum', key, tuple(slots), U, B, H, E, T, compact), U, B, H, 'tanh', E, T, slots, compact)
-    return batch, lambda max_rows: tlgg._learner(tlgg._set(U, B, H, 'tanh', slots), max_rows)
-
-
-def _flat(grads):
-    from deepcomp_amd.learner import ARRAYS
-    return np.concatenate([grads[n].reshape(-1) for n in ARRAYS])
+    batch = fs.group_collected(('group-accum', key, tuple(slots), U, B, H, E, T, compact), U, B, H, 'tanh', E, T, slots, compact)
+    return batch, lambda max_rows: fs.per_ue_learner(fs.policy_set(U, B, H, 'tanh', slots), max_rows)
 
 
 def _pattern_gradients(torch, learner):
@@ -58,7 +44,7 @@ def _pattern_gradients(torch, learner):
     acc.view(torch.int32).fill_(PATTERN)
     sums[4] = 1.0
     learner.finish(acc, sums)
-    got = _flat(learner.read('grads'))
+    got = fs.flat(learner.read('grads'))
     assert np.all(got.view(np.int32) == PATTERN)
     return got
 
@@ -80,15 +66,15 @@ def test_group_accumulate_is_p_sgd_accumulate_calls(torch_cuda, compact):
     U, B, H, E, T, slots = ac.CALL
     batch, _ = _case(ac.CALL, compact)
     mk = lambda: [PPOLearner(m, max_rows=max(ac.CALL_ROWS), **dict(HYPER, lr=1e-3, kl_coeff=0.2 + 0.1 * p))      # noqa: E731
-                  for p, m in enumerate(tlgg._set(U, B, H, 'tanh', slots).members)]
+                  for p, m in enumerate(fs.policy_set(U, B, H, 'tanh', slots).members)]
     grp, seq = mk(), mk()
-    src = tlgg._source(torch, batch, grp[0].actor)
+    src = fs.source(batch, grp[0].actor, own_advantages=True)
     N = src['actions'].shape[0]
     index = _index(torch, 3, max(ac.CALL_ROWS), N, 9)
     kept_stats = [ln.grads_indexed(src, index[p, :50].contiguous()) for p, ln in enumerate(grp)]      # gradients and statistics of an earlier call
     kept_bits = [s.clone() for s in kept_stats]
-    kept = [_flat(ln.read('grads')) for ln in grp]
-    rc, h, msg = tlgg._group(grp)
+    kept = [fs.flat(ln.read('grads')) for ln in grp]
+    rc, h, msg = fs.c_group(grp)
     assert rc == 0, msg
     L = _lib.load()
     F = grp[0].flat_size
@@ -97,9 +83,9 @@ def test_group_accumulate_is_p_sgd_accumulate_calls(torch_cuda, compact):
     acc[2].view(torch.int32).fill_(PATTERN)
     sums[2].view(torch.int64).fill_(PATTERN)
     twin = [ln.new_accumulators() for ln in seq]
-    hy = tlgg._hypers(grp)
+    hy = fs.c_hypers(grp)
     for rows in (ac.CALL_ROWS, [ac.CALL_ROWS[1], ac.CALL_ROWS[0], 0]):
-        b = tlgg._group_batch(src, index, rows, compact)
+        b = fs.c_group_batch(src, index, rows, compact)
         assert L.dcomp_learner_group_accumulate(h, ctypes.byref(b), hy, ctypes.c_void_p(acc.data_ptr()), ctypes.c_void_p(sums.data_ptr()),
                                                 grp[0].actor._stream()) == 0, L.dcomp_last_error()
         for p in (0, 1):
@@ -109,7 +95,7 @@ def test_group_accumulate_is_p_sgd_accumulate_calls(torch_cuda, compact):
     assert not torch.equal(acc[0], acc[1])
     assert bool((acc[2].view(torch.int32) == PATTERN).all()) and bool((sums[2].view(torch.int64) == PATTERN).all())
     for p, ln in enumerate(grp):
-        assert np.array_equal(_flat(ln.read('grads')), kept[p]), p
+        assert np.array_equal(fs.flat(ln.read('grads')), kept[p]), p
         assert torch.equal(kept_stats[p], kept_bits[p])
     assert L.dcomp_learner_group_destroy(h) == 0
 
@@ -128,7 +114,7 @@ def test_group_finish_is_p_accum_finish_calls(torch_cuda, H):
     for s in (grp, seq):
         for p, ln in enumerate(s.learners):
             ln.hyper['kl_coeff'] = 0.2 + 0.1 * p
-    src = tlgg._source(torch, batch, grp.learners[0].actor)
+    src = fs.source(batch, grp.learners[0].actor, own_advantages=True)
     index = _index(torch, P, 100, src['actions'].shape[0], 5)
     rows = [100, 77, 50, 64]
     acc, sums = grp.new_accumulators()
@@ -148,7 +134,7 @@ def test_group_finish_is_p_accum_finish_calls(torch_cuda, H):
         norm = torch.full((P,), -777.0, device='cuda')
         assert grp.finish_grouped(acc, sums, clips, [1, 1, 1, 0], stats, norm) is stats
         assert torch.equal(acc, acc0) and torch.equal(sums, sums0)
-        got = [_flat(ln.read('grads')) for ln in grp.learners]
+        got = [fs.flat(ln.read('grads')) for ln in grp.learners]
         runs.append((stats.cpu().numpy(), norm.cpu().numpy(), got))
     assert all(np.array_equal(x, y) for x, y in zip(runs[0][2], runs[1][2])) and all(np.array_equal(runs[0][i], runs[1][i]) for i in (0, 1))
     stats, norm, got = runs[0]
@@ -157,7 +143,7 @@ def test_group_finish_is_p_accum_finish_calls(torch_cuda, H):
         want = seq.learners[p].finish(acc[p], sums[p], grad_clip=clips[p], grad_norm=n).cpu().numpy()
         assert np.array_equal(stats[p], want) and np.all(np.isfinite(want)), p
         assert norm[p] == float(n) == np.float32(norms[p]), p
-        assert np.array_equal(got[p], _flat(seq.learners[p].read('grads'))), p
+        assert np.array_equal(got[p], fs.flat(seq.learners[p].read('grads'))), p
     unclipped = [acc0[p].cpu().numpy() * np.float32(1.0 / rows[p]) for p in range(3)]
     assert norms[0] > clips[0] and not np.array_equal(got[0], unclipped[0]) and np.abs(got[0]).max() < np.abs(unclipped[0]).max()
     assert norms[1] < clips[1] and np.array_equal(got[1], unclipped[1]) and np.array_equal(got[2], unclipped[2])
@@ -165,7 +151,7 @@ def test_group_finish_is_p_accum_finish_calls(torch_cuda, H):
     # without a norm anywhere (no clip, none asked for) the norm launch is skipped: the gradients are the unclipped ones
     grp.finish_grouped(acc, sums, None, [1, 1, 1, 0])
     for p in range(3):
-        assert np.array_equal(_flat(grp.learners[p].read('grads')), unclipped[p]), p
+        assert np.array_equal(fs.flat(grp.learners[p].read('grads')), unclipped[p]), p
     with pytest.raises(ValueError, match='grad_clip'):
         grp.finish_grouped(acc, sums, [0.0, -1.0, 0.0, 0.0])
     with pytest.raises(ValueError):
@@ -178,12 +164,11 @@ def test_more_members_than_one_launch_slice(torch_cuda):
     first of the first slice among them; the one member of the second slice takes part.  Accumulate (two calls) + finish + apply
     through the group equal the per-member calls: accumulators, statistics, norms and state_dict()."""
     torch = torch_cuda
-    from tests.test_learner_group_cpu import group_slice
-    P = group_slice() + 1
+    P = ac.group_slice() + 1
     shape = (P, 2, 32, 4, 2, list(range(P)))
     batch, mk = _case(shape)
     grp, seq = mk(32), mk(32)
-    src = tlgg._source(torch, batch, grp.learners[0].actor)
+    src = fs.source(batch, grp.learners[0].actor, own_advantages=True)
     index = _index(torch, P, 32, src['actions'].shape[0], 3)
     rows = [0 if p % 5 == 0 else 1 + (7 * p) % 32 for p in range(P)]
     assert rows[0] == 0 and rows[P - 1] > 0 and max(rows) == 32 and len(set(rows)) > 20
@@ -210,7 +195,7 @@ def test_more_members_than_one_launch_slice(torch_cuda):
         ln.apply()
         assert torch.equal(acc[p], a) and torch.equal(sums[p], s), p
         assert np.array_equal(stats[p], want) and norm[p] == float(n), p
-        _same_state(grp.learners[p].state_dict(), ln.state_dict())
+        fs.same_state(grp.learners[p].state_dict(), ln.state_dict(), stepped=True)
 
 
 # ---------------------------------------------------------------------------------------------- 4: update(grouped, micro_rows, grad_clip)
@@ -245,7 +230,7 @@ def test_grouped_update_with_micro_rows_and_grad_clip_equals_the_sequential_upda
     _spy_norms(torch, grp, log)
     got = grp.update(batch, num_sgd_iter=2, minibatch_rows=minibatch, seed=4, grouped=True, micro_rows=CHUNK, grad_clip=clip)
     want = seq.update(batch, num_sgd_iter=2, minibatch_rows=minibatch, seed=4, micro_rows=CHUNK, grad_clip=clip)
-    tlgg._same_run(got, want, grp, seq)
+    fs.same_run(got, want, grp, seq)
     rounds = 1 if minibatch is None else 2
     assert len(log) == 2 * rounds and [a for _, a in log] == ([[1, 1, 1]] if rounds == 1 else [[1, 1, 1], [1, 0, 0]]) * 2
     assert [ln.state_dict()['step'] for ln in grp.learners] == [2 * rounds, 2, 2]
@@ -267,7 +252,7 @@ def test_grouped_micro_batches_equal_the_grouped_update_on_learners_that_hold_th
     got = micro.update(batch, num_sgd_iter=2, minibatch_rows=3000, seed=7, grouped=True, micro_rows=CHUNK)
     want = whole.update(batch, num_sgd_iter=2, minibatch_rows=3000, seed=7, grouped=True)
     for p in range(3):
-        _same_state(micro.learners[p].state_dict(), whole.learners[p].state_dict())
+        fs.same_state(micro.learners[p].state_dict(), whole.learners[p].state_dict(), stepped=True)
         assert got[p]['kl_coeff'] == want[p]['kl_coeff']
         for k in want[p]:
             print(f'policy {p} {k}: accumulated {got[p][k]!r} whole {want[p][k]!r}')
@@ -294,7 +279,7 @@ def test_grouped_sequential_member_and_accumulated_calls_mix(torch_cuda):
     assert one.update(batch, seed=1, grouped=True, **kw) == members(1)
     assert one.update(batch, seed=2, grouped=False, micro_rows=CHUNK, **kw) == members(2, micro_rows=CHUNK)
     # the group's own calls: 300 positions of every policy's rows in order, each policy its own clip
-    src = tlgg._source(torch, batch, one.learners[0].actor)
+    src = fs.source(batch, one.learners[0].actor, own_advantages=True)
     for p in range(3):
         src['advantages'].index_copy_(0, rows[p], standardize(src['advantages'].index_select(0, rows[p])))
     index = torch.stack([rows[p][:300].to(torch.int32) for p in range(3)]).contiguous()
@@ -311,7 +296,7 @@ def test_grouped_sequential_member_and_accumulated_calls_mix(torch_cuda):
     assert one.update(batch, num_sgd_iter=1, minibatch_rows=CHUNK, seed=3, grouped=True) == \
         [ln.update(batch, num_sgd_iter=1, minibatch_rows=CHUNK, seed=3 + p, rows=rows[p], check_rows=False) for p, ln in enumerate(two.learners)]
     for a, b in zip(one.state_dict(), two.state_dict()):
-        _same_state(a, b)
+        fs.same_state(a, b, stepped=True)
     assert [s['step'] for s in one.state_dict()] == [3 + 3 + 1 + 3, 2 + 2 + 1 + 2, 2 + 2 + 2 + 2]
 
 
@@ -322,7 +307,7 @@ def _ranks(torch, shape, R, max_rows=CHUNK, key='lock'):
     from deepcomp_amd.dp_learner import DataParallelPerUELearner
     U, B, H, E, T, slots = shape
     batch, mk = _case((U, B, H, E * R, T, slots), key=key)
-    shards = [_shard(batch, r, R, E * R, U, T) for r in range(R)]
+    shards = [fs.shard(batch, r, R, E * R, U, T) for r in range(R)]
     return shards, [DataParallelPerUELearner(mk(max_rows), rank=r, world=R) for r in range(R)]
 
 
@@ -337,7 +322,7 @@ def test_lockstep_ranks_stay_identical(torch_cuda, R):
         for p in range(2):
             assert len({d.set.learners[p].hyper['kl_coeff'] for d in dps}) == 1 and outs[0][p]['kl_coeff'] == dps[0].set.learners[p].hyper['kl_coeff']
             for d in dps[1:]:
-                _same_state(d.set.learners[p].state_dict(), dps[0].set.learners[p].state_dict())
+                fs.same_state(d.set.learners[p].state_dict(), dps[0].set.learners[p].state_dict(), stepped=True)
         assert [s['step'] for s in dps[0].set.state_dict()] == [4 * (it + 1)] * 2
         shas = run_lockstep(dps, phases='check_sync')
         assert all(s == shas[0] for s in shas) and len(shas[0]) == 2 and shas[0][0] != shas[0][1] and len(shas[0][0]) == 64
@@ -355,10 +340,10 @@ def test_lockstep_of_one_rank_is_the_grouped_update(torch_cuda):
     kw = dict(num_sgd_iter=2, minibatch_rows=256, micro_rows=CHUNK, seed=21, grad_clip=5.0)
     assert run_lockstep([dp], shards, **kw)[0] == ref.update(shards[0], grouped=True, **kw)
     for a, b in zip(dp.set.state_dict(), ref.state_dict()):
-        _same_state(a, b)
+        fs.same_state(a, b, stepped=True)
     assert dp.update(shards[0], **kw) == ref.update(shards[0], grouped=True, **kw)       # (no group: update() alone is the same thing)
     for a, b in zip(dp.set.state_dict(), ref.state_dict()):
-        _same_state(a, b)
+        fs.same_state(a, b, stepped=True)
     assert [s['step'] for s in ref.state_dict()] == [8, 8]
 
 
@@ -376,7 +361,7 @@ def test_lockstep_of_two_ranks_is_the_phases_written_out(torch_cuda):
     outs = run_lockstep(dps, shards, num_sgd_iter=2, minibatch_rows=R * mb, seed=seed, grad_clip=CLIP)
     _, mk = _case(ac.LOCK, key='lock')
     refs = [mk(CHUNK) for _ in range(R)]
-    srcs = [tlgg._source(torch, s, refs[0].learners[0].actor) for s in shards]
+    srcs = [fs.source(s, refs[0].learners[0].actor, own_advantages=True) for s in shards]
     rows = refs[0].rows_of(srcs[0]['actions'].shape[0])
     n = int(rows[0].numel())
     assert n == 512 == int(rows[1].numel())
@@ -413,7 +398,7 @@ def test_lockstep_of_two_ranks_is_the_phases_written_out(torch_cuda):
         coeff = lm.adapt_kl_coeff(HYPER['kl_coeff'], kl, refs[0].learners[p].kl_target)
         assert outs[0][p]['kl'] == kl and outs[0][p]['kl_coeff'] == coeff and outs[1][p] == outs[0][p]
         for r in range(R):
-            _same_bits(lm, dps[r].set.learners[p].state_dict(), dict(refs[r].learners[p].state_dict(), kl_coeff=coeff))
+            fs.same_state(dps[r].set.learners[p].state_dict(), dict(refs[r].learners[p].state_dict(), kl_coeff=coeff))
     assert [s['step'] for s in dps[0].set.state_dict()] == [8, 8]
 
 

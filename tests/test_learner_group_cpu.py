@@ -3,42 +3,14 @@ points exist and are declared, the two ctypes mirrors match the header, every ar
 handle is refused on the host before the first HIP call, and the table of grouped cases tests/test_learner_group_gpu.py runs reaches
 every grouped instantiation and every weight-gradient form.  No GPU compute is called here."""
 import ctypes
-import os
 import re
 import subprocess
 
-import pytest
+from tests import c_surface as cs
+from tests.c_surface import EABI, EINVAL, OK, REPO, lib  # noqa: F401  (lib: the fixture)
+from tests.group_cases import GROUP_CASES, group_slice
 
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-OK, EINVAL, EUNSUPPORTED, EABI = 0, -1, -6, -7
-HEADER = os.path.join(REPO, 'include', 'dcomp_learner_group.h')
-
-# The grouped cases of the GPU tests: (U, B, hidden, activation, E, T, slot_policy, compact).  Each is the smallest shape that reaches
-# its cell; every one trains with minibatches of 64 rows per policy.
-GROUP_CASES = {
-    'a-rows': (5, 3, 32, 'tanh', 70, 5, [0, 1, 1, 0, 1], False),         # the uneven split: 700 against 1 050 rows
-    'a-compact': (5, 3, 32, 'tanh', 70, 5, [0, 1, 1, 0, 1], True),
-    'b-compact': (3, 36, 64, 'relu', 33, 2, [0, 1, 2], True),            # 36 stations: two connection words, two staging chunks; <2, 1>
-    'c-rows': (4, 10, 256, 'tanh', 40, 2, [0, 1, 2, 3], False),          # the widest instantiation; <2, 4>, bias<4>
-    'h128-b5': (4, 5, 128, 'tanh', 40, 2, [0, 1, 0, 1], False),          # one input tile, four output tiles: <1, 4>
-    'h128-b10': (4, 10, 128, 'relu', 40, 2, [0, 1, 0, 1], True),         # two input tiles: <2, 4>
-    'h32-relu': (5, 3, 32, 'relu', 70, 2, [0, 1, 1, 0, 1], True),
-    'h64-tanh': (5, 3, 64, 'tanh', 70, 2, [0, 1, 1, 0, 1], False),       # dW2 / dW3 through <2, 1>
-    'h256-relu': (4, 10, 256, 'relu', 40, 2, [0, 1, 2, 3], True),
-}
-UNEVEN = ('a-rows', 'a-compact')
-
-
-def group_slice():
-    """DCOMP_GROUP_SLICE as the header has it."""
-    return int(re.search(r'#define\s+DCOMP_GROUP_SLICE\s+(\d+)', open(HEADER).read()).group(1))
-
-
-@pytest.fixture(scope='module')
-def lib():
-    from deepcomp_amd import build, _lib
-    build.build()                      # hipcc cross-compiles gfx950 on a GPU-less host
-    return _lib.load()
+HEADER = cs.header('dcomp_learner_group.h')
 
 
 def test_symbols_are_exported_and_declared(lib):
@@ -53,34 +25,22 @@ def test_symbols_are_exported_and_declared(lib):
     assert group_slice() >= 64
     assert -(-128 // group_slice()) <= 2                                               # config 5's 128 policies: at most two launch rounds
     for other in ('dcomp.h', 'dcomp_types.h', 'dcomp_learner.h', 'dcomp_learner_indexed.h', 'dcomp_policy_set.h'):
-        assert not re.search(r'dcomp_learner_group', open(os.path.join(REPO, 'include', other)).read()), other
-
-
-def _members(txt, name):
-    body = re.search(r'typedef struct %s \{(.*?)\} %s;' % (name, name), txt, flags=re.S).group(1)
-    return [re.split(r'[\s*]+', m.strip())[-1] for decl in body.split(';') if decl.strip() for m in decl.split(',')]
+        assert not re.search(r'dcomp_learner_group', open(cs.header(other)).read()), other
 
 
 def test_ctypes_mirrors_match_the_header(tmp_path):
     """Member names from the header text, sizes and offsets from a C program compiled against it (C99, pedantic)."""
     from deepcomp_amd import _lib
-    txt = re.sub(r'/\*.*?\*/', '', open(HEADER).read(), flags=re.S)
     mirrors = {'dcomp_learner_group_cfg': _lib.DcompLearnerGroupCfg, 'dcomp_group_batch': _lib.DcompGroupBatch}
     prints = []
     for name, S in mirrors.items():
-        names = _members(txt, name)
+        names = cs.struct_members(HEADER, name)
         assert names == [f[0] for f in S._fields_], names
         prints.append('    printf("%%zu", sizeof(%s));\n' % name + ''.join('    printf(" %%zu", offsetof(%s, %s));\n' % (name, m) for m in names) + '    printf("\\n");\n')
-    inc = os.path.join(REPO, 'include')
-    src = tmp_path / 'sizes.c'
-    src.write_text('#include <stdio.h>\n#include <stddef.h>\n#include "dcomp_learner_group.h"\nint main(void) {\n' + ''.join(prints) +
-                   '    return DCOMP_EABI == -7 && DCOMP_GROUP_SLICE >= 64 ? 0 : 1;\n}\n')
-    subprocess.run(['gcc', '-std=c99', '-Wall', '-Wextra', '-Werror', '-pedantic', '-I', inc, '-fsyntax-only', str(src)], check=True)
-    exe = tmp_path / 'sizes'
-    subprocess.run(['gcc', '-std=c99', '-I', inc, '-o', str(exe), str(src)], check=True)
-    lines = subprocess.run([str(exe)], check=True, stdout=subprocess.PIPE, text=True).stdout.strip().split('\n')
+    lines = cs.c_program_output(tmp_path, '#include <stdio.h>\n#include <stddef.h>\n#include "dcomp_learner_group.h"\nint main(void) {\n' + ''.join(prints) +
+                                '    return DCOMP_EABI == -7 && DCOMP_GROUP_SLICE >= 64 ? 0 : 1;\n}\n')
     for line, S in zip(lines, mirrors.values()):
-        assert [int(x) for x in line.split()] == [ctypes.sizeof(S)] + [getattr(S, f[0]).offset for f in S._fields_], S
+        assert line == [ctypes.sizeof(S)] + [getattr(S, f[0]).offset for f in S._fields_], S
 
 
 def _cfg(num_learners=2, learners='fake', size=None):
@@ -119,7 +79,7 @@ def test_grads_and_apply_refuse_nulls_and_a_wrong_struct_size(lib):
     err = lib.dcomp_last_error
     fake = ctypes.c_void_p(4096)
     batch = lambda size=None: _lib.DcompGroupBatch(ctypes.sizeof(_lib.DcompGroupBatch) if size is None else size)      # noqa: E731
-    hyper = _lib.DcompPpoHyper(ctypes.sizeof(_lib.DcompPpoHyper), 0.3, 10.0, 1.0, 0.0, 0.2)
+    hyper = cs.ppo_hyper()
     grads = lambda g, b, h, s: lib.dcomp_learner_group_grads(g, ctypes.byref(b) if b is not None else None, ctypes.byref(h) if h is not None else None, s, None)      # noqa: E731
     for args in ((None, batch(), hyper, fake), (fake, None, hyper, fake), (fake, batch(), None, fake), (fake, batch(), hyper, None)):
         assert grads(*args) == EINVAL and b'dcomp_learner_group_grads:' in err() and b'NULL' in err()

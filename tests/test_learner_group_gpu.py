@@ -4,69 +4,21 @@ The reference is the existing sequential path -- PerUELearner.update, P PPOLearn
 tests hold to the float64 model.  A policy's arithmetic is unchanged and its row split depends on its own row count alone, so every
 comparison here is EXACT: np.array_equal on state_dict() (weights, m, v, step, kl_coeff) and == on the statistics dicts.
 
-Shapes: tests/test_learner_group_cpu.py's GROUP_CASES (the CPU test shows that they reach every grouped instantiation and every
+Shapes: tests/group_cases.py's GROUP_CASES (tests/test_learner_group_cpu.py shows that they reach every grouped instantiation and every
 weight-gradient form).  A sample batch is collected once per case and left unchanged."""
 import ctypes
 
 import numpy as np
 import pytest
 
-from tests import test_actor_gpu as tag
-from tests import test_learner_gpu as tlg
-from tests import test_learner_group_cpu as cases
-from tests.test_policy_set_gpu import _same_state
+from tests import fcnet_support as fs
+from tests import group_cases as cases
+from tests.fcnet_cases import HYPER
+from tests.fcnet_support import torch_cuda  # noqa: F401  (the fixture)
 
 pytestmark = pytest.mark.gpu
 
-HYPER = tlg.HYPER
 EINVAL, EUNSUPPORTED = -1, -6
-
-
-@pytest.fixture(scope='module')
-def torch_cuda():
-    import torch
-    assert torch.cuda.is_available(), "these tests need the MI355X"
-    return torch
-
-
-def _set(U, B, H, act, slots, seed=10):
-    from deepcomp_amd.actor import FcnetActor
-    from deepcomp_amd.policy_set import PerUEActor
-    members = [FcnetActor('multi', U, B, FcnetActor.random_weights('multi', U, B, H, seed=seed + p, bias_std=0.1), activation=act,
-                          value_weights=FcnetActor.random_value_weights('multi', U, B, H, seed=seed + p, bias_std=0.1))
-               for p in range(max(slots) + 1)]
-    return PerUEActor(members, slots)
-
-
-def _learner(pset, max_rows=64):
-    from deepcomp_amd.policy_set import PerUELearner
-    return PerUELearner(pset, max_rows=max_rows, **dict(HYPER, lr=1e-3))
-
-
-_BATCH = {}
-
-
-def _batch(key, U, B, H, act, E, T, slots, compact):
-    """One collect() batch of the shape, driven by a set of distinct members; computed once per key."""
-    if key not in _BATCH:
-        from deepcomp_amd.sampler import collect
-        _BATCH[key] = collect(tag._env('multi', E, U, B), _set(U, B, H, act, slots), T, gamma=0.99, lam=0.95, compact=compact, dist_inputs=True)
-    return _BATCH[key]
-
-
-def _same_run(got, want, learner_g, learner_s):
-    assert len(got) == len(want)
-    for p, (g, w) in enumerate(zip(got, want)):
-        assert g == w, p
-        if g is not None:
-            assert all(np.isfinite(v) for v in g.values())
-            _same_state(learner_g.learners[p].state_dict(), learner_s.learners[p].state_dict())
-
-
-def _twins(name, max_rows=64):
-    U, B, H, act, E, T, slots, compact = cases.GROUP_CASES[name]
-    batch = _batch(name, U, B, H, act, E, T, slots, compact)
-    return batch, _learner(_set(U, B, H, act, slots), max_rows), _learner(_set(U, B, H, act, slots), max_rows)
 
 
 # ---------------------------------------------------------------------------------------------- 1: the uneven split
@@ -74,10 +26,10 @@ def _twins(name, max_rows=64):
 def test_uneven_split_equals_the_sequential_update(torch_cuda, name):
     """Policy 0 has 700 rows and policy 1 has 1 050: 11 against 17 minibatch rounds (policy 0 sits six out), last minibatches of 60
     and 26 rows, and from the second iteration on the policies' Adam steps differ."""
-    batch, grp, seq = _twins(name)
+    batch, grp, seq = fs.twins(name)
     got = grp.update(batch, num_sgd_iter=2, minibatch_rows=64, seed=4, grouped=True)
     want = seq.update(batch, num_sgd_iter=2, minibatch_rows=64, seed=4)
-    _same_run(got, want, grp, seq)
+    fs.same_run(got, want, grp, seq)
     assert [ln.state_dict()['step'] for ln in grp.learners] == [22, 34]
     w = [ln.read('weights')['w1'] for ln in grp.learners]
     assert not np.array_equal(w[0], w[1])
@@ -86,10 +38,10 @@ def test_uneven_split_equals_the_sequential_update(torch_cuda, name):
 # ---------------------------------------------------------------------------------------------- 2: the other cells
 @pytest.mark.parametrize('name', [n for n in cases.GROUP_CASES if n not in cases.UNEVEN])
 def test_every_other_cell_equals_the_sequential_update(torch_cuda, name):
-    batch, grp, seq = _twins(name)
+    batch, grp, seq = fs.twins(name)
     got = grp.update(batch, num_sgd_iter=2, minibatch_rows=64, seed=2, grouped=True)
     want = seq.update(batch, num_sgd_iter=2, minibatch_rows=64, seed=2)
-    _same_run(got, want, grp, seq)
+    fs.same_run(got, want, grp, seq)
 
 
 # ---------------------------------------------------------------------------------------------- 3: weight-gradient chunks per policy
@@ -97,11 +49,11 @@ def test_several_weight_gradient_chunks_that_differ_per_policy(torch_cuda):
     """U 3, slots [0, 0, 1], E 450, T 5, minibatch_rows = max_rows = 4 500: policy 0 gets one minibatch of 4 500 rows (3 chunks, the
     last one partial), policy 1 one of 2 250 rows (2 chunks)."""
     U, B, H, act, E, T, slots = 3, 3, 32, 'tanh', 450, 5, [0, 0, 1]
-    batch = _batch('chunks', U, B, H, act, E, T, slots, True)
-    grp, seq = _learner(_set(U, B, H, act, slots), 4500), _learner(_set(U, B, H, act, slots), 4500)
+    batch = fs.group_collected('chunks', U, B, H, act, E, T, slots, True)
+    grp, seq = fs.per_ue_learner(fs.policy_set(U, B, H, act, slots), 4500), fs.per_ue_learner(fs.policy_set(U, B, H, act, slots), 4500)
     got = grp.update(batch, num_sgd_iter=2, minibatch_rows=4500, seed=1, grouped=True)
     want = seq.update(batch, num_sgd_iter=2, minibatch_rows=4500, seed=1)
-    _same_run(got, want, grp, seq)
+    fs.same_run(got, want, grp, seq)
     assert [ln.state_dict()['step'] for ln in grp.learners] == [2, 2]
 
 
@@ -116,14 +68,14 @@ def test_more_policies_than_one_launch_slice(torch_cuda, skip):
     slots = list(range(P))
     if skip:
         slots[P - 2] = P - 1
-    batch = _batch(('slice', skip), U, B, H, act, E, T, slots, False)
-    grp, seq = _learner(_set(U, B, H, act, slots), 32), _learner(_set(U, B, H, act, slots), 32)
+    batch = fs.group_collected(('slice', skip), U, B, H, act, E, T, slots, False)
+    grp, seq = fs.per_ue_learner(fs.policy_set(U, B, H, act, slots), 32), fs.per_ue_learner(fs.policy_set(U, B, H, act, slots), 32)
     if skip:                                                                           # (the members come from max(slots) + 1: all P)
         assert len(grp.learners) == P
         before = grp.learners[P - 2].state_dict()
     got = grp.update(batch, num_sgd_iter=2, minibatch_rows=32, seed=3, grouped=True)
     want = seq.update(batch, num_sgd_iter=2, minibatch_rows=32, seed=3)
-    _same_run(got, want, grp, seq)
+    fs.same_run(got, want, grp, seq)
     assert sum(g is None for g in got) == (1 if skip else 0)
     if skip:
         assert got[P - 2] is None
@@ -136,44 +88,6 @@ def test_more_policies_than_one_launch_slice(torch_cuda, skip):
 
 
 # ---------------------------------------------------------------------------------------------- 5: the C call directly
-def _source(torch, batch, actor):
-    src = {'actions': batch['actions'].reshape(-1, 1), 'old_logp': batch['action_logp'].reshape(-1, 1),
-           'old_logits': batch['action_dist_inputs'].reshape(-1, actor.num_logits), 'advantages': batch['advantages'].reshape(-1).clone(),
-           'value_targets': batch['value_targets'].reshape(-1), 'old_vf': batch['vf_preds'].reshape(-1)}
-    if 'obs' in batch:
-        src['obs'] = batch['obs'].reshape(-1, actor.num_in)
-    else:
-        src['obs_compact'] = batch['obs_compact'].reshape(-1, batch['obs_compact'].shape[-1])
-    return src
-
-
-def _group(learners):
-    from deepcomp_amd import _lib
-    L = _lib.load()
-    arr = (ctypes.c_void_p * len(learners))(*[ln._h.value for ln in learners])
-    cfg = _lib.DcompLearnerGroupCfg(ctypes.sizeof(_lib.DcompLearnerGroupCfg), len(learners), arr)
-    h = ctypes.c_void_p()
-    rc = L.dcomp_learner_group_create(ctypes.byref(cfg), ctypes.byref(h))
-    return rc, h, L.dcomp_last_error().decode()
-
-
-def _group_batch(src, index, rows, compact, source_rows=None):
-    from deepcomp_amd import _lib
-    obs = src['obs_compact' if compact else 'obs']
-    n = src['actions'].shape[0] if source_rows is None else source_rows
-    arr = (ctypes.c_int64 * len(rows))(*rows)
-    b = _lib.DcompGroupBatch(ctypes.sizeof(_lib.DcompGroupBatch), _lib.ACTOR_COMPACT if compact else _lib.ACTOR_ROWS, n, obs.data_ptr(),
-                             src['actions'].data_ptr(), src['old_logp'].data_ptr(), src['old_logits'].data_ptr(), src['advantages'].data_ptr(),
-                             src['value_targets'].data_ptr(), src['old_vf'].data_ptr(), index.data_ptr(), index.shape[1], arr)
-    b._keep = arr
-    return b
-
-
-def _hypers(learners):
-    from deepcomp_amd import _lib
-    return (_lib.DcompPpoHyper * len(learners))(*[ln._hyper_struct() for ln in learners])
-
-
 @pytest.mark.parametrize('compact', [False, True], ids=['rows', 'compact'])
 def test_group_grads_is_p_sgd_grads_calls(torch_cuda, compact):
     """One dcomp_learner_group_grads against dcomp_sgd_grads per policy on twins: all twelve gradient arrays and the [P][5] statistics.
@@ -183,10 +97,10 @@ def test_group_grads_is_p_sgd_grads_calls(torch_cuda, compact):
     from deepcomp_amd import _lib
     from deepcomp_amd.learner import ARRAYS, PPOLearner
     U, B, H, act, E, T, slots, _ = cases.GROUP_CASES['a-compact' if compact else 'a-rows']
-    batch = _batch('a-compact' if compact else 'a-rows', U, B, H, act, E, T, slots, compact)
-    mk = lambda: [PPOLearner(m, max_rows=128, **dict(HYPER, lr=1e-3, kl_coeff=0.2 + 0.1 * p)) for p, m in enumerate(_set(U, B, H, act, [0, 1, 2, 0, 1]).members)]      # noqa: E731
+    batch = fs.group_collected('a-compact' if compact else 'a-rows', U, B, H, act, E, T, slots, compact)
+    mk = lambda: [PPOLearner(m, max_rows=128, **dict(HYPER, lr=1e-3, kl_coeff=0.2 + 0.1 * p)) for p, m in enumerate(fs.policy_set(U, B, H, act, [0, 1, 2, 0, 1]).members)]      # noqa: E731
     grp, seq = mk(), mk()
-    src = _source(torch, batch, grp[0].actor)
+    src = fs.source(batch, grp[0].actor, own_advantages=True)
     N = src['actions'].shape[0]
     g = torch.Generator(device='cuda').manual_seed(9)
     index = torch.randint(0, N, (3, 130), generator=g, device='cuda', dtype=torch.int32)
@@ -196,13 +110,13 @@ def test_group_grads_is_p_sgd_grads_calls(torch_cuda, compact):
     for lns in (grp, seq):
         lns[2].grads_indexed(src, index[2, :50].contiguous())
     kept = grp[2].read('grads')
-    rc, h, msg = _group(grp)
+    rc, h, msg = fs.c_group(grp)
     assert rc == 0, msg
     L = _lib.load()
     GUARD = 33
     stats = torch.full((3 * _lib.PPO_NUM_STATS + GUARD,), -12345.0, dtype=torch.float32, device='cuda')
-    b = _group_batch(src, index, rows, compact)
-    hy = _hypers(grp)
+    b = fs.c_group_batch(src, index, rows, compact)
+    hy = fs.c_hypers(grp)
     stream = grp[0].actor._stream()
     for again in range(2):
         assert L.dcomp_learner_group_grads(h, ctypes.byref(b), hy, ctypes.c_void_p(stats.data_ptr()), stream) == 0, L.dcomp_last_error()
@@ -244,18 +158,18 @@ def test_chunk_counts_that_fall_as_the_rows_grow(torch_cuda):
     rows = [262176, 262144]
     assert [fc.row_split(r)['nchunks'] for r in rows] == [65, 128]
     U, B, H, act, E, T, slots, _ = cases.GROUP_CASES['a-rows']
-    batch = _batch('a-rows', U, B, H, act, E, T, slots, False)
-    mk = lambda: [PPOLearner(m, max_rows=rows[0], **dict(HYPER, lr=1e-3)) for m in _set(U, B, H, act, [0, 1, 0, 1, 0]).members]      # noqa: E731
+    batch = fs.group_collected('a-rows', U, B, H, act, E, T, slots, False)
+    mk = lambda: [PPOLearner(m, max_rows=rows[0], **dict(HYPER, lr=1e-3)) for m in fs.policy_set(U, B, H, act, [0, 1, 0, 1, 0]).members]      # noqa: E731
     grp, seq = mk(), mk()
-    src = _source(torch, batch, grp[0].actor)
+    src = fs.source(batch, grp[0].actor, own_advantages=True)
     g = torch.Generator(device='cuda').manual_seed(11)
     index = torch.randint(0, src['actions'].shape[0], (2, rows[0]), generator=g, device='cuda', dtype=torch.int32)
-    rc, h, msg = _group(grp)
+    rc, h, msg = fs.c_group(grp)
     assert rc == 0, msg
     L = _lib.load()
     stats = torch.zeros(2 * _lib.PPO_NUM_STATS, dtype=torch.float32, device='cuda')
-    b = _group_batch(src, index, rows, False)
-    assert L.dcomp_learner_group_grads(h, ctypes.byref(b), _hypers(grp), ctypes.c_void_p(stats.data_ptr()), grp[0].actor._stream()) == 0, L.dcomp_last_error()
+    b = fs.c_group_batch(src, index, rows, False)
+    assert L.dcomp_learner_group_grads(h, ctypes.byref(b), fs.c_hypers(grp), ctypes.c_void_p(stats.data_ptr()), grp[0].actor._stream()) == 0, L.dcomp_last_error()
     got = stats.cpu().numpy()
     for p in (0, 1):
         want = seq[p].grads_indexed(src, index[p, :rows[p]].contiguous()).cpu().numpy()
@@ -272,7 +186,7 @@ def test_grouped_sequential_and_member_calls_mix(torch_cuda):
     """grouped update -> one member's own PPOLearner.update -> grouped update equals the same sequence run all-sequentially; and
     state_dict -> a new set and learner -> load_state_dict -> grouped update equals the uninterrupted run."""
     from deepcomp_amd.policy_set import policy_rows
-    batch, grp, seq = _twins('a-compact')
+    batch, grp, seq = fs.twins('a-compact')
     U, _, _, _, E, T, slots, _ = cases.GROUP_CASES['a-compact']
     rows1 = policy_rows(T * E * U, U, slots, 2, 'cuda')[1]
     saved = None
@@ -283,13 +197,13 @@ def test_grouped_sequential_and_member_calls_mix(torch_cuda):
             saved = ln.state_dict()
         ln.update(batch, num_sgd_iter=1, minibatch_rows=64, seed=2, grouped=grouped)
     for s1, s2 in zip(grp.state_dict(), seq.state_dict()):
-        _same_state(s1, s2)
+        fs.same_state(s1, s2, stepped=True)
     assert [s['step'] for s in grp.state_dict()] == [22, 34 + 17]
-    _, _, resumed = _twins('a-compact')
+    _, _, resumed = fs.twins('a-compact')
     resumed.load_state_dict(saved)
     resumed.update(batch, num_sgd_iter=1, minibatch_rows=64, seed=2, grouped=True)
     for s1, s2 in zip(grp.state_dict(), resumed.state_dict()):
-        _same_state(s1, s2)
+        fs.same_state(s1, s2, stepped=True)
 
 
 # ---------------------------------------------------------------------------------------------- 7: refusals that need handles
@@ -306,37 +220,37 @@ def test_refusals_that_need_handles(torch_cuda):
         return PPOLearner(a, max_rows=max_rows, **HYPER)
     base = learner()
     for other, what in ((learner(H=64), 'hidden'), (learner(act='relu'), 'activation'), (learner(U=4), 'num_ue'), (learner(B=4), 'num_bs')):
-        rc, h, msg = _group([base, other])
+        rc, h, msg = fs.c_group([base, other])
         assert rc == EINVAL and h.value is None and 'dcomp_learner_group_create' in msg and what in msg, msg
-    rc, h, msg = _group([base, base])
+    rc, h, msg = fs.c_group([base, base])
     assert rc == EINVAL and 'learner 1 is learner 0 again' in msg
-    rc, h, msg = _group([base, PPOLearner(base.actor, max_rows=64, **HYPER)])
+    rc, h, msg = fs.c_group([base, PPOLearner(base.actor, max_rows=64, **HYPER)])
     assert rc == EINVAL and 'the same actor' in msg
-    rc, h, msg = _group([learner(kind='central'), learner(kind='central', seed=2)])
+    rc, h, msg = fs.c_group([learner(kind='central'), learner(kind='central', seed=2)])
     assert rc == EUNSUPPORTED and 'dcomp_learner_group_create' in msg and 'DCOMP_CENTRAL' in msg
-    rc, h, msg = _group([base, learner(kind='central')])
+    rc, h, msg = fs.c_group([base, learner(kind='central')])
     assert rc == EINVAL and 'obs_kind' in msg
 
     U, B, H, act, E, T, slots, _ = cases.GROUP_CASES['a-rows']
     second = learner(seed=2, max_rows=32)
-    rc, h, msg = _group([base, second])
+    rc, h, msg = fs.c_group([base, second])
     assert rc == 0, msg
-    rows_src = _source(torch, _batch('a-rows', U, B, H, act, E, T, slots, False), base.actor)
-    compact_src = _source(torch, _batch('a-compact', U, B, H, act, E, T, slots, True), base.actor)
+    rows_src = fs.source(fs.group_collected('a-rows', U, B, H, act, E, T, slots, False), base.actor, own_advantages=True)
+    compact_src = fs.source(fs.group_collected('a-compact', U, B, H, act, E, T, slots, True), base.actor, own_advantages=True)
     N = rows_src['actions'].shape[0]
     index = torch.zeros((2, 80), dtype=torch.int32, device='cuda')
     narrow = torch.zeros((2, 16), dtype=torch.int32, device='cuda')
     stats = torch.zeros(10, dtype=torch.float32, device='cuda')
-    hy = _hypers([base, second])
+    hy = fs.c_hypers([base, second])
 
     def grads(b):
         rc = L.dcomp_learner_group_grads(h, ctypes.byref(b), hy, ctypes.c_void_p(stats.data_ptr()), None)
         return rc, L.dcomp_last_error().decode()
-    for b, what in ((_group_batch(rows_src, index, [65, 10], False), 'rows[0] 65'), (_group_batch(rows_src, index, [10, 33], False), 'rows[1] 33'),
-                    (_group_batch(rows_src, index, [-1, 10], False), 'rows[0] -1'), (_group_batch(rows_src, narrow, [17, 10], False), 'index_stride'),
-                    (_group_batch(rows_src, index, [0, 0], False), 'at least one'),
-                    (_group_batch(compact_src, index, [10, 10], True, source_rows=N - 1), 'multiple of num_ue'),
-                    (_group_batch(rows_src, index, [10, 10], False, source_rows=0), 'source_rows')):
+    for b, what in ((fs.c_group_batch(rows_src, index, [65, 10], False), 'rows[0] 65'), (fs.c_group_batch(rows_src, index, [10, 33], False), 'rows[1] 33'),
+                    (fs.c_group_batch(rows_src, index, [-1, 10], False), 'rows[0] -1'), (fs.c_group_batch(rows_src, narrow, [17, 10], False), 'index_stride'),
+                    (fs.c_group_batch(rows_src, index, [0, 0], False), 'at least one'),
+                    (fs.c_group_batch(compact_src, index, [10, 10], True, source_rows=N - 1), 'multiple of num_ue'),
+                    (fs.c_group_batch(rows_src, index, [10, 10], False, source_rows=0), 'source_rows')):
         rc, msg = grads(b)
         assert rc == EINVAL and 'dcomp_learner_group_grads' in msg and what in msg, (what, msg)
     torch.cuda.synchronize()

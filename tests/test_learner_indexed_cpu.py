@@ -4,22 +4,17 @@ argument the library can judge without its handle is refused on the host before 
 never dereferenced.  The refusals that read the handle (rows > max_rows, the compact record with a central handle, source rows that
 are not whole envs, num_active of a multi-agent handle) are in tests/test_learner_indexed_gpu.py.  No GPU compute is called here."""
 import ctypes
-import os
 import re
-import subprocess
 
 import pytest
 
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-OK, EINVAL, EUNSUPPORTED, EABI = 0, -1, -6, -7
-HEADER = os.path.join(REPO, 'include', 'dcomp_learner_indexed.h')
+from tests import c_surface as cs
+from tests.c_surface import EABI, EINVAL, EUNSUPPORTED, lib  # noqa: F401  (lib: the fixture)
+from tests.c_surface import LOSS_INPUTS as _LOSS_INPUTS
+from tests.c_surface import ppo_hyper as _hyper
+from tests.c_surface import sgd_batch as _batch
 
-
-@pytest.fixture(scope='module')
-def lib():
-    from deepcomp_amd import build, _lib
-    build.build()                      # hipcc cross-compiles gfx950 on a GPU-less host
-    return _lib.load()
+HEADER = cs.header('dcomp_learner_indexed.h')
 
 
 def test_symbols_are_exported_and_declared(lib):
@@ -33,52 +28,28 @@ def test_symbols_are_exported_and_declared(lib):
     assert sorted(re.findall(r'\bint (dcomp_\w+)\s*\(', hdr)) == sorted(_lib.SGD_EXPORTS)
     # the surfaces the existing tests pin are as they were
     assert len(_lib.LEARNER_EXPORTS) == 7 and len(_lib.EXPORTS) == 42
-    assert not re.search(r'dcomp_sgd_', open(os.path.join(REPO, 'include', 'dcomp_learner.h')).read())
+    assert not re.search(r'dcomp_sgd_', open(cs.header('dcomp_learner.h')).read())
 
 
 def test_ctypes_mirror_matches_the_header(tmp_path):
     """Member names from the header text, sizes from a C program compiled against it (C99, pedantic); dcomp_ppo_batch keeps its size."""
     from deepcomp_amd import _lib
-    txt = re.sub(r'/\*.*?\*/', '', open(HEADER).read(), flags=re.S)
-    body = re.search(r'typedef struct dcomp_sgd_batch \{(.*?)\} dcomp_sgd_batch;', txt, flags=re.S).group(1)
-    members = [re.split(r'[\s*]+', m.strip())[-1] for decl in body.split(';') if decl.strip() for m in decl.split(',')]
+    members = cs.struct_members(HEADER, 'dcomp_sgd_batch')
     assert members == [f[0] for f in _lib.DcompSgdBatch._fields_], members
-    inc = os.path.join(REPO, 'include')
-    gcc = ['gcc', '-std=c99', '-Wall', '-Wextra', '-Werror', '-pedantic', '-I', inc]
-    src = tmp_path / 'sizes.c'
-    src.write_text('#include <stdio.h>\n#include <stddef.h>\n#include "dcomp_learner_indexed.h"\n'
+    sizes, = cs.c_program_output(                                                      # (compiled alone first)
+        tmp_path, '#include <stdio.h>\n#include <stddef.h>\n#include "dcomp_learner_indexed.h"\n'
                    'int main(void) {\n'
                    '    printf("%zu %zu %zu %zu %zu\\n", sizeof(dcomp_sgd_batch), sizeof(dcomp_ppo_batch), offsetof(dcomp_sgd_batch, index),\n'
                    '           offsetof(dcomp_sgd_batch, obs), offsetof(dcomp_sgd_batch, ratio));\n'
                    '    return 0;\n'
                    '}\n')
-    subprocess.run(gcc + ['-fsyntax-only', str(src)], check=True)                      # alone
-    for n, text in enumerate(('#include "dcomp.h"\n#include "dcomp_learner.h"\n#include "dcomp_learner_indexed.h"\n',
-                              '#include "dcomp_learner_indexed.h"\n#include "dcomp_learner.h"\n#include "dcomp.h"\n')):
-        both = tmp_path / f'both{n}.c'                                                 # with the other two public headers, either order
-        both.write_text(text + 'int main(void) { return DCOMP_EABI == -7 && DCOMP_ACTOR_COMPACT == 1 ? 0 : 1; }\n')
-        subprocess.run(gcc + ['-fsyntax-only', str(both)], check=True)
-    exe = tmp_path / 'sizes'
-    subprocess.run(['gcc', '-std=c99', '-I', inc, '-o', str(exe), str(src)], check=True)
-    sizes = [int(x) for x in subprocess.run([str(exe)], check=True, stdout=subprocess.PIPE, text=True).stdout.split()]
+    main = 'int main(void) { return DCOMP_EABI == -7 && DCOMP_ACTOR_COMPACT == 1 ? 0 : 1; }\n'
+    cs.compiles_as_c99(tmp_path, 'both', [text + main for text in (                    # with the other two public headers, either order
+        '#include "dcomp.h"\n#include "dcomp_learner.h"\n#include "dcomp_learner_indexed.h"\n',
+        '#include "dcomp_learner_indexed.h"\n#include "dcomp_learner.h"\n#include "dcomp.h"\n')])
     S = _lib.DcompSgdBatch
     assert sizes == [ctypes.sizeof(S), ctypes.sizeof(_lib.DcompPpoBatch), S.index.offset, S.obs.offset, S.ratio.offset]
     assert ctypes.sizeof(_lib.DcompPpoBatch) == 24 + 14 * 8                           # (as before this header existed)
-
-
-_FIELDS = ('obs', 'actions', 'old_logp', 'old_logits', 'advantages', 'value_targets', 'old_vf', 'dlogits', 'dvalue', 'logp', 'entropy', 'kl', 'vf', 'ratio')
-_LOSS_INPUTS = _FIELDS[:7]
-
-
-def _batch(given=_LOSS_INPUTS, size=None, fmt=0, rows=8, source_rows=64, index=4096, num_active=1):
-    from deepcomp_amd import _lib
-    return _lib.DcompSgdBatch(ctypes.sizeof(_lib.DcompSgdBatch) if size is None else size, fmt, rows, source_rows, index, num_active, 0,
-                              *[4096 if n in given else None for n in _FIELDS])          # (never dereferenced)
-
-
-def _hyper(size=None, clip=0.3, vf_clip=10.0):
-    from deepcomp_amd import _lib
-    return _lib.DcompPpoHyper(ctypes.sizeof(_lib.DcompPpoHyper) if size is None else size, clip, vf_clip, 1.0, 0.0, 0.2)
 
 
 def test_grads_refuses_bad_arguments_on_the_host(lib):

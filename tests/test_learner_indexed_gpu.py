@@ -16,116 +16,11 @@ import ctypes
 import numpy as np
 import pytest
 
-from tests import test_actor_gpu as tag
-from tests import test_learner_gpu as tlg
+from tests import fcnet_cases as fc
+from tests import fcnet_support as fs
+from tests.fcnet_support import OUTS, torch_cuda  # noqa: F401  (torch_cuda: the fixture)
 
 pytestmark = pytest.mark.gpu
-
-HYPER = tlg.HYPER
-OUTS = ('logp', 'entropy', 'kl', 'vf', 'ratio')
-
-
-@pytest.fixture(scope='module')
-def torch_cuda():
-    import torch
-    assert torch.cuda.is_available(), "these tests need the MI355X"
-    return torch
-
-
-_COLLECTED = {}
-
-
-def _collected(torch, kind, E, U, B, H, activation, T, compact):
-    """One collect(..., dist_inputs=True) batch per configuration, computed once and left unchanged: (weights, value weights, batch)."""
-    key = (kind, E, U, B, H, activation, T, compact)
-    if key not in _COLLECTED:
-        from deepcomp_amd.actor import FcnetActor
-        from deepcomp_amd.sampler import collect
-        w = FcnetActor.random_weights(kind, U, B, H, seed=1, bias_std=0.1)
-        vw = FcnetActor.random_value_weights(kind, U, B, H, seed=1, bias_std=0.1)
-        actor = FcnetActor(kind, U, B, w, activation=activation, value_weights=vw)
-        batch = collect(tag._env(kind, E, U, B), actor, T, gamma=0.99, lam=0.95, compact=compact, dist_inputs=True)
-        _COLLECTED[key] = (w, vw, batch)
-    return _COLLECTED[key]
-
-
-def _perturbed(w, vw, seed=5):
-    rng = np.random.default_rng(seed)
-    pert = lambda d: {n: (a + rng.normal(size=a.shape).astype(np.float32) * np.float32(0.25 * (a.std() + 0.02))) for n, a in d.items()}      # noqa: E731
-    return pert(w), pert(vw)
-
-
-def _learner(kind, U, B, w, vw, activation, max_rows, perturb=True, **kw):
-    from deepcomp_amd.actor import FcnetActor
-    from deepcomp_amd.learner import PPOLearner
-    if perturb:
-        w, vw = _perturbed(w, vw)
-    return PPOLearner(FcnetActor(kind, U, B, w, activation=activation, value_weights=vw), max_rows=max_rows, **dict(HYPER, **kw))
-
-
-def _source(batch, actor):
-    """The flattened sample-batch tensors of a collect() batch under grads' argument names."""
-    s = {'actions': batch['actions'].reshape(-1, actor.heads), 'old_logp': batch['action_logp'].reshape(-1, actor.heads),
-         'old_logits': batch['action_dist_inputs'].reshape(-1, actor.num_logits), 'advantages': batch['advantages'].reshape(-1),
-         'value_targets': batch['value_targets'].reshape(-1), 'old_vf': batch['vf_preds'].reshape(-1)}
-    if 'obs' in batch:
-        s['obs'] = batch['obs'].reshape(-1, actor.num_in)
-    else:
-        s['obs_compact'] = batch['obs_compact'].reshape(-1, batch['obs_compact'].shape[-1])
-    return s
-
-
-def _as_rows(source, actor):
-    """The same source with observation rows: a compact source unpacked record by record."""
-    if 'obs' in source:
-        return source
-    from deepcomp_amd.fragment import FragmentCodec
-    rows = dict(source)
-    rows['obs'] = FragmentCodec(actor.U, actor.B).unpack(rows.pop('obs_compact')).reshape(-1, actor.num_in)
-    return rows
-
-
-def _bits(torch, t):
-    return t.contiguous().view(torch.int32)
-
-
-def _outputs(torch, rows, heads, pad=0):
-    return {k: torch.full((rows + pad, heads) if k == 'logp' else (rows + pad,), float('nan'), device='cuda') for k in OUTS}
-
-
-def _check_against_gathered(torch, learner, source, index, num_active=None):
-    """grads_indexed / evaluate_indexed against grads / evaluate on the gathered rows; returns the indexed call's outputs."""
-    from deepcomp_amd.learner import ARRAYS
-    a = learner.actor
-    rows_src = _as_rows(source, a)
-    n_src = rows_src['obs'].shape[0]
-    pick = index.long() if index is not None else torch.arange(n_src, device='cuda')
-    n = int(pick.numel())
-    gathered = {k: t.index_select(0, pick).contiguous() for k, t in rows_src.items()}
-    want_out, got_out = _outputs(torch, n, a.heads), _outputs(torch, n, a.heads)
-    want_stats = learner.grads(**gathered, num_active=num_active, **want_out).clone()
-    want = learner.read('grads')
-    got_stats = learner.grads_indexed(source, index, num_active=num_active, **got_out)
-    got = learner.read('grads')
-    assert torch.equal(_bits(torch, got_stats), _bits(torch, want_stats)), (got_stats, want_stats)
-    for name in ARRAYS:
-        assert np.array_equal(got[name], want[name]), name
-        assert np.isfinite(got[name]).all(), name
-    assert any(np.abs(want[name]).max() > 0 for name in ('w1', 'vw1'))
-    for k in OUTS:
-        assert torch.equal(_bits(torch, got_out[k]), _bits(torch, want_out[k])), k
-    if 'actions' in gathered:
-        e_want = learner.evaluate(gathered['obs'], gathered['actions'], num_active=num_active)
-        e_got = learner.evaluate_indexed(source, index, num_active=num_active)
-        for x, y in zip(e_got, e_want):
-            assert torch.equal(_bits(torch, x), _bits(torch, y))
-    return got_stats, got, got_out
-
-
-def _shuffled(torch, n_src, n, seed):
-    g = torch.Generator(device='cuda')
-    g.manual_seed(seed)
-    return torch.randperm(n_src, generator=g, device='cuda')[:n].to(torch.int32).contiguous()
 
 
 # ---------------------------------------------------------------------------------------------- (1), (2) rows and compact, multi
@@ -135,20 +30,20 @@ def test_multi_indexed_equals_gathered(torch_cuda, compact):
     torch = torch_cuda
     from deepcomp_amd.learner import ARRAYS
     kind, E, U, B, H, T = 'multi', 64, 5, 4, 64, 5
-    w, vw, batch = _collected(torch, kind, E, U, B, H, 'tanh', T, compact)
-    learner = _learner(kind, U, B, w, vw, 'tanh', max_rows=E * U * T)
-    src = _source(batch, learner.actor)
+    w, vw, batch = fs.collected(torch, kind, E, U, B, H, 'tanh', T, compact)
+    learner = fs.ppo_learner(kind, U, B, w, vw, 'tanh', max_rows=E * U * T)
+    src = fs.source(batch, learner.actor)
     n_src = E * U * T
     assert ('obs_compact' in src) == compact and src['actions'].shape[0] == n_src == 1600
-    shuffled = _shuffled(torch, n_src, 512, 1)
+    shuffled = fs.shuffled(torch, n_src, 512, 1)
     assert int(shuffled.max()) - int(shuffled.min()) > 4 * E * U                  # (more than four time steps apart)
-    stats, grads, _ = _check_against_gathered(torch, learner, src, shuffled)
-    _check_against_gathered(torch, learner, src, _shuffled(torch, n_src, 70, 2))    # two tiles and a partial one
+    stats, grads, _ = fs.check_against_gathered(torch, learner, src, shuffled)
+    fs.check_against_gathered(torch, learner, src, fs.shuffled(torch, n_src, 70, 2))    # two tiles and a partial one
     repeated = torch.cat([shuffled[:100], shuffled[:60], shuffled[50:90]]).contiguous()
-    _check_against_gathered(torch, learner, src, repeated)
+    fs.check_against_gathered(torch, learner, src, repeated)
     # no index: every source row in order -- the gathered call is then learner.grads on the source itself
-    full_stats, full, _ = _check_against_gathered(torch, learner, src, None)
-    direct = learner.grads(**_as_rows(src, learner.actor))
+    full_stats, full, _ = fs.check_against_gathered(torch, learner, src, None)
+    direct = learner.grads(**fs.as_rows(src, learner.actor))
     assert torch.equal(full_stats, direct)
     got = learner.read('grads')
     assert all(np.array_equal(got[n], full[n]) for n in ARRAYS)
@@ -164,14 +59,14 @@ def test_two_connection_words_and_two_staging_chunks(torch_cuda, compact):
     4B + 1 = 161 inputs > the 144 staged at a time, so the value sweep fetches its rows again instead of reusing LDS."""
     torch = torch_cuda
     kind, E, U, B, H, T = 'multi', 16, 3, 40, 32, 2
-    w, vw, batch = _collected(torch, kind, E, U, B, H, 'relu', T, compact)
-    learner = _learner(kind, U, B, w, vw, 'relu', max_rows=E * U * T)
+    w, vw, batch = fs.collected(torch, kind, E, U, B, H, 'relu', T, compact)
+    learner = fs.ppo_learner(kind, U, B, w, vw, 'relu', max_rows=E * U * T)
     assert learner.actor.num_in == 161 > 144
-    src = _source(batch, learner.actor)
+    src = fs.source(batch, learner.actor)
     if compact:
         assert src['obs_compact'].shape[1] == U * (B + 3) + 2 * B
-    _check_against_gathered(torch, learner, src, _shuffled(torch, E * U * T, 70, 3))
-    _check_against_gathered(torch, learner, src, None)
+    fs.check_against_gathered(torch, learner, src, fs.shuffled(torch, E * U * T, 70, 3))
+    fs.check_against_gathered(torch, learner, src, None)
 
 
 # ---------------------------------------------------------------------------------------------- (4) several weight-gradient chunks
@@ -180,10 +75,10 @@ def test_several_weight_gradient_chunks(torch_cuda, compact):
     """6 400 of 8 000 source rows at hidden 96 (packed as 128): three weight-gradient chunks and a partial one."""
     torch = torch_cuda
     kind, E, U, B, H, T = 'multi', 160, 5, 4, 96, 10
-    assert 3 * tlg.CHUNK < 6400 < 4 * tlg.CHUNK and E * U * T == 8000
-    w, vw, batch = _collected(torch, kind, E, U, B, H, 'tanh', T, compact)
-    learner = _learner(kind, U, B, w, vw, 'tanh', max_rows=6400)
-    _check_against_gathered(torch, learner, _source(batch, learner.actor), _shuffled(torch, 8000, 6400, 4))
+    assert 3 * fc.CHUNK < 6400 < 4 * fc.CHUNK and E * U * T == 8000
+    w, vw, batch = fs.collected(torch, kind, E, U, B, H, 'tanh', T, compact)
+    learner = fs.ppo_learner(kind, U, B, w, vw, 'tanh', max_rows=6400)
+    fs.check_against_gathered(torch, learner, fs.source(batch, learner.actor), fs.shuffled(torch, 8000, 6400, 4))
 
 
 # ---------------------------------------------------------------------------------------------- (5) central
@@ -191,12 +86,12 @@ def test_central_indexed_equals_gathered_and_refuses_the_compact_record(torch_cu
     torch = torch_cuda
     from deepcomp_amd import _lib
     kind, E, U, B, H, T = 'central', 100, 4, 3, 64, 3
-    w, vw, batch = _collected(torch, kind, E, U, B, H, 'tanh', T, False)
-    learner = _learner(kind, U, B, w, vw, 'tanh', max_rows=E * T)
-    src = _source(batch, learner.actor)
-    idx = _shuffled(torch, E * T, 200, 5)
-    stats3, _, _ = _check_against_gathered(torch, learner, src, idx, num_active=3)
-    stats4, _, _ = _check_against_gathered(torch, learner, src, idx)
+    w, vw, batch = fs.collected(torch, kind, E, U, B, H, 'tanh', T, False)
+    learner = fs.ppo_learner(kind, U, B, w, vw, 'tanh', max_rows=E * T)
+    src = fs.source(batch, learner.actor)
+    idx = fs.shuffled(torch, E * T, 200, 5)
+    stats3, _, _ = fs.check_against_gathered(torch, learner, src, idx, num_active=3)
+    stats4, _, _ = fs.check_against_gathered(torch, learner, src, idx)
     assert not torch.equal(stats3, stats4)                                         # (the fourth head does count)
     words = torch.zeros((E * T, 64), dtype=torch.int32, device='cuda')
     compact = dict(src, obs_compact=words)
@@ -225,11 +120,11 @@ def test_upstream_gradients_through_an_index(torch_cuda):
     from deepcomp_amd.actor import FcnetActor
     from deepcomp_amd.learner import PPOLearner, ARRAYS
     kind, E, U, B, H = 'multi', 40, 7, 3, 32
-    w, v, x, dl, dv, _ = tlg._int_case(kind, E, U, B, H, seed=1)
+    w, v, x, dl, dv, _ = fc.learner_int_case(kind, E, U, B, H, seed=1)
     learner = PPOLearner(FcnetActor(kind, U, B, w, activation='relu', value_weights=v), max_rows=150)
-    src = {'obs': tlg._cuda(torch, x), 'dlogits': tlg._cuda(torch, dl), 'dvalue': tlg._cuda(torch, dv)}
-    idx = _shuffled(torch, E * U, 150, 6)
-    stats, got, _ = _check_against_gathered(torch, learner, src, idx)
+    src = {'obs': fs.cuda(torch, x), 'dlogits': fs.cuda(torch, dl), 'dvalue': fs.cuda(torch, dv)}
+    idx = fs.shuffled(torch, E * U, 150, 6)
+    stats, got, _ = fs.check_against_gathered(torch, learner, src, idx)
     assert np.array_equal(stats.cpu().numpy(), np.zeros(5, dtype=np.float32))
     pick = idx.cpu().numpy()
     x64, dl64 = x[pick].astype(np.float64), dl[pick].astype(np.float64)
@@ -248,14 +143,14 @@ def test_index_entries_outside_the_batch_are_not_read(torch_cuda, compact):
     torch = torch_cuda
     from deepcomp_amd.learner import ARRAYS
     kind, E, U, B, H, T = 'multi', 64, 5, 4, 64, 5
-    w, vw, batch = _collected(torch, kind, E, U, B, H, 'tanh', T, compact)
-    learner = _learner(kind, U, B, w, vw, 'tanh', max_rows=70)
-    src = _source(batch, learner.actor)
+    w, vw, batch = fs.collected(torch, kind, E, U, B, H, 'tanh', T, compact)
+    learner = fs.ppo_learner(kind, U, B, w, vw, 'tanh', max_rows=70)
+    src = fs.source(batch, learner.actor)
     n_src = E * U * T
-    valid = _shuffled(torch, n_src, 70, 7)
+    valid = fs.shuffled(torch, n_src, 70, 7)
     bad = valid.clone()
     bad[3], bad[40] = -1, n_src
-    want, got = _outputs(torch, 70, 1), _outputs(torch, 70, 1)
+    want, got = fs.outputs(torch, 70, 1), fs.outputs(torch, 70, 1)
     learner.grads_indexed(src, valid, **want)
     stats = learner.grads_indexed(src, bad, **got)
     grads = learner.read('grads')
@@ -264,28 +159,28 @@ def test_index_entries_outside_the_batch_are_not_read(torch_cuda, compact):
     others[3] = others[40] = False
     for k in OUTS:
         assert bool((got[k][~others] == 0).all()), k
-        assert torch.equal(_bits(torch, got[k][others]), _bits(torch, want[k][others])), k
+        assert torch.equal(fs.tbits(torch, got[k][others]), fs.tbits(torch, want[k][others])), k
         assert bool(torch.isfinite(want[k]).all()), k
     e = learner.evaluate_indexed(src, bad)
     e_valid = learner.evaluate_indexed(src, valid)
     for x, y in zip(e, e_valid):
-        assert bool((x[~others] == 0).all()) and torch.equal(_bits(torch, x[others]), _bits(torch, y[others]))
+        assert bool((x[~others] == 0).all()) and torch.equal(fs.tbits(torch, x[others]), fs.tbits(torch, y[others]))
 
 
 def test_nothing_is_written_past_the_minibatch(torch_cuda):
     """Per-row outputs with a guard of 64 sentinel elements behind the 70 positions (two tiles and a partial one)."""
     torch = torch_cuda
     kind, E, U, B, H, T = 'multi', 64, 5, 4, 64, 5
-    w, vw, batch = _collected(torch, kind, E, U, B, H, 'tanh', T, True)
-    learner = _learner(kind, U, B, w, vw, 'tanh', max_rows=70 + 64)
-    src = _source(batch, learner.actor)
-    idx = _shuffled(torch, E * U * T, 70, 8)
-    bufs = _outputs(torch, 70, 1, pad=64)
+    w, vw, batch = fs.collected(torch, kind, E, U, B, H, 'tanh', T, True)
+    learner = fs.ppo_learner(kind, U, B, w, vw, 'tanh', max_rows=70 + 64)
+    src = fs.source(batch, learner.actor)
+    idx = fs.shuffled(torch, E * U * T, 70, 8)
+    bufs = fs.outputs(torch, 70, 1, pad=64)
     learner.grads_indexed(src, idx, **{k: b[:70] for k, b in bufs.items()})
     for k, b in bufs.items():
         assert bool(torch.isnan(b[70:]).all()), k
         assert bool(torch.isfinite(b[:70]).all()), k
-    bufs = _outputs(torch, 70, 1, pad=64)
+    bufs = fs.outputs(torch, 70, 1, pad=64)
     learner.evaluate_indexed(src, idx)                                             # (allocates its own outputs)
     b = learner._sgd_batch(learner._sgd_source(src, idx), src, idx, None, ('actions',), {k: (bufs[k][:70], 1) for k in ('logp', 'entropy', 'vf')})
     from deepcomp_amd import _lib
@@ -295,82 +190,41 @@ def test_nothing_is_written_past_the_minibatch(torch_cuda):
 
 
 # ---------------------------------------------------------------------------------------------- (9)-(11) update
-def _same_state(lm, s1, s2):
-    assert s1['step'] == s2['step'] and s1['kl_coeff'] == s2['kl_coeff']
-    for k in ('weights', 'm', 'v'):
-        for n in lm.ARRAYS:
-            assert np.array_equal(s1[k][n], s2[k][n]), (k, n)
-
-
-def _gathered_update(torch, learner, batch, num_sgd_iter, minibatch_rows, seed, num_active=None):
-    """The SGD phase written out on rows: standardise, seeded randperm, index_select of all seven tensors per minibatch, grads, apply."""
-    a = learner.actor
-    src = _source(batch, a)
-    N = src['obs'].shape[0]
-    kernel_active = None
-    if num_active is not None and num_active < a.U:
-        if a.heads == 1:
-            keep = torch.nonzero(torch.arange(N, device='cuda') % a.U < num_active).reshape(-1)
-            src = {k: t.index_select(0, keep) for k, t in src.items()}
-            N = int(keep.numel())
-        else:
-            kernel_active = num_active
-    adv = src['advantages']
-    src['advantages'] = (adv - adv.mean()) / adv.std(unbiased=False).clamp_min(1e-4)
-    mb = min(minibatch_rows, N)
-    gen = torch.Generator(device='cuda')
-    gen.manual_seed(seed)
-    for _ in range(num_sgd_iter):
-        perm = torch.randperm(N, generator=gen, device='cuda')
-        for s in range(0, N, mb):
-            idx = perm[s:s + mb]
-            learner.grads(**{k: t.index_select(0, idx) for k, t in src.items()}, num_active=kernel_active)
-            learner.apply()
-
-
-def _rows_batch(torch, batch, U, B):
-    from deepcomp_amd.fragment import FragmentCodec
-    rows = {k: t for k, t in batch.items() if k != 'obs_compact'}
-    rows['obs'] = FragmentCodec(U, B).unpack(batch['obs_compact'])
-    return rows
-
-
 def test_update_agrees_on_rows_and_compact_and_with_the_gathered_loop(torch_cuda):
     """(9) one compact batch and the rows batch unpacked from it, two learners on twin actors: bit-identical state.  (10) a third
     twin through the gathered loop written out above: the same state again."""
     torch = torch_cuda
     from deepcomp_amd import learner as lm
     kind, E, U, B, H, T = 'multi', 64, 5, 4, 64, 5
-    w, vw, batch = _collected(torch, kind, E, U, B, H, 'tanh', T, True)
-    rows = _rows_batch(torch, batch, U, B)
+    w, vw, batch = fs.collected(torch, kind, E, U, B, H, 'tanh', T, True)
+    rows = fs.rows_batch(batch, U, B)
     assert 'obs' not in batch and rows['obs'].shape == (T, E, U, 4 * B + 1)
-    learners = [_learner(kind, U, B, w, vw, 'tanh', max_rows=512, perturb=False, lr=1e-3) for _ in range(3)]
+    learners = [fs.ppo_learner(kind, U, B, w, vw, 'tanh', max_rows=512, perturb=False, lr=1e-3) for _ in range(3)]
     out_c = learners[0].update(batch, num_sgd_iter=2, minibatch_rows=512, seed=3)
     out_r = learners[1].update(rows, num_sgd_iter=2, minibatch_rows=512, seed=3)
     assert out_c == out_r and all(np.isfinite(out_c[n]) for n in lm.STATS)
     s_c, s_r = learners[0].state_dict(), learners[1].state_dict()
     assert s_c['step'] == 8                                                        # 1 600 rows: three full minibatches and a partial one, twice
-    _same_state(lm, s_c, s_r)
+    fs.same_state(s_c, s_r)
     assert np.abs(s_c['weights']['w2'] - w['w2']).max() > 1e-4
-    _gathered_update(torch, learners[2], rows, 2, 512, 3)
+    fs.gathered_update(torch, learners[2], rows, 2, 512, 3)
     s_g = dict(learners[2].state_dict(), kl_coeff=s_r['kl_coeff'])                 # (the loop leaves kl_coeff alone)
-    _same_state(lm, s_r, s_g)
+    fs.same_state(s_r, s_g)
 
 
 @pytest.mark.parametrize('compact', [False, True], ids=['rows', 'compact'])
 def test_update_with_unlisted_slots_equals_the_gathered_loop_over_the_kept_rows(torch_cuda, compact):
     torch = torch_cuda
-    from deepcomp_amd import learner as lm
     kind, E, U, B, H, T = 'multi', 64, 5, 4, 64, 5
-    w, vw, batch = _collected(torch, kind, E, U, B, H, 'tanh', T, True)
-    rows = _rows_batch(torch, batch, U, B)
-    a, b = (_learner(kind, U, B, w, vw, 'tanh', max_rows=512, perturb=False, lr=1e-3) for _ in range(2))
+    w, vw, batch = fs.collected(torch, kind, E, U, B, H, 'tanh', T, True)
+    rows = fs.rows_batch(batch, U, B)
+    a, b = (fs.ppo_learner(kind, U, B, w, vw, 'tanh', max_rows=512, perturb=False, lr=1e-3) for _ in range(2))
     a.update(batch if compact else rows, num_sgd_iter=2, minibatch_rows=512, seed=9, num_active=3)
-    _gathered_update(torch, b, rows, 2, 512, 9, num_active=3)
+    fs.gathered_update(torch, b, rows, 2, 512, 9, num_active=3)
     s_a = a.state_dict()
     assert s_a['step'] == 4                                                        # 960 kept rows: one full minibatch and a partial one, twice
-    _same_state(lm, s_a, dict(b.state_dict(), kl_coeff=s_a['kl_coeff']))
-    full = _learner(kind, U, B, w, vw, 'tanh', max_rows=512, perturb=False, lr=1e-3)
+    fs.same_state(s_a, dict(b.state_dict(), kl_coeff=s_a['kl_coeff']))
+    full = fs.ppo_learner(kind, U, B, w, vw, 'tanh', max_rows=512, perturb=False, lr=1e-3)
     full.update(rows, num_sgd_iter=2, minibatch_rows=512, seed=9)
     assert not np.array_equal(full.state_dict()['weights']['w1'], s_a['weights']['w1'])      # (the unlisted rows are left out)
 
@@ -380,12 +234,12 @@ def test_refusals_that_need_a_handle(torch_cuda):
     torch = torch_cuda
     from deepcomp_amd import _lib
     kind, E, U, B, H, T = 'multi', 64, 5, 4, 64, 5
-    w, vw, batch = _collected(torch, kind, E, U, B, H, 'tanh', T, True)
-    learner = _learner(kind, U, B, w, vw, 'tanh', max_rows=64)
-    src = _source(batch, learner.actor)
-    rows_src = _as_rows(src, learner.actor)
+    w, vw, batch = fs.collected(torch, kind, E, U, B, H, 'tanh', T, True)
+    learner = fs.ppo_learner(kind, U, B, w, vw, 'tanh', max_rows=64)
+    src = fs.source(batch, learner.actor)
+    rows_src = fs.as_rows(src, learner.actor)
     n_src = E * U * T
-    idx = _shuffled(torch, n_src, 70, 1)
+    idx = fs.shuffled(torch, n_src, 70, 1)
     with pytest.raises(ValueError):
         learner.grads_indexed(src, idx)                                            # 70 rows > max_rows 64
     with pytest.raises(ValueError):

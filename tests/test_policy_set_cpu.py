@@ -4,22 +4,14 @@ export lists keep their lengths, every argument the library can judge without de
 before the first HIP call, and PerUELearner's row split is what the issue says.  The refusals that read the members are in
 tests/test_policy_set_gpu.py.  No GPU compute is called here."""
 import ctypes
-import os
 import re
-import subprocess
 
 import pytest
 
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-OK, EINVAL, EUNSUPPORTED, EABI = 0, -1, -6, -7
-HEADER = os.path.join(REPO, 'include', 'dcomp_policy_set.h')
+from tests import c_surface as cs
+from tests.c_surface import EABI, EINVAL, OK, lib  # noqa: F401  (lib: the fixture)
 
-
-@pytest.fixture(scope='module')
-def lib():
-    from deepcomp_amd import build, _lib
-    build.build()                      # hipcc cross-compiles gfx950 on a GPU-less host
-    return _lib.load()
+HEADER = cs.header('dcomp_policy_set.h')
 
 
 def test_symbols_are_exported_and_declared(lib):
@@ -34,34 +26,25 @@ def test_symbols_are_exported_and_declared(lib):
     # the surfaces the existing tests pin are as they were
     assert len(_lib.EXPORTS) == 42 and len(_lib.LEARNER_EXPORTS) == 7 and len(_lib.SGD_EXPORTS) == 2
     for other in ('dcomp.h', 'dcomp_types.h', 'dcomp_learner.h', 'dcomp_learner_indexed.h'):
-        assert not re.search(r'dcomp_policy_set', open(os.path.join(REPO, 'include', other)).read()), other
+        assert not re.search(r'dcomp_policy_set', open(cs.header(other)).read()), other
 
 
 def test_ctypes_mirror_matches_the_header(tmp_path):
     """Member names from the header text, size and offsets from a C program compiled against it (C99, pedantic)."""
     from deepcomp_amd import _lib
-    txt = re.sub(r'/\*.*?\*/', '', open(HEADER).read(), flags=re.S)
-    body = re.search(r'typedef struct dcomp_policy_set_cfg \{(.*?)\} dcomp_policy_set_cfg;', txt, flags=re.S).group(1)
-    members = [re.split(r'[\s*]+', m.strip())[-1] for decl in body.split(';') if decl.strip() for m in decl.split(',')]
+    members = cs.struct_members(HEADER, 'dcomp_policy_set_cfg')
     assert members == [f[0] for f in _lib.DcompPolicySetCfg._fields_], members
-    inc = os.path.join(REPO, 'include')
-    gcc = ['gcc', '-std=c99', '-Wall', '-Wextra', '-Werror', '-pedantic', '-I', inc]
-    src = tmp_path / 'sizes.c'
-    src.write_text('#include <stdio.h>\n#include <stddef.h>\n#include "dcomp_policy_set.h"\n'
+    sizes, = cs.c_program_output(                                                      # (compiled alone first)
+        tmp_path, '#include <stdio.h>\n#include <stddef.h>\n#include "dcomp_policy_set.h"\n'
                    'int main(void) {\n'
                    '    printf("%zu %zu %zu %zu\\n", sizeof(dcomp_policy_set_cfg), offsetof(dcomp_policy_set_cfg, num_policies),\n'
                    '           offsetof(dcomp_policy_set_cfg, members), offsetof(dcomp_policy_set_cfg, slot_policy));\n'
                    '    return DCOMP_EABI == -7 ? 0 : 1;\n'
                    '}\n')
-    subprocess.run(gcc + ['-fsyntax-only', str(src)], check=True)                      # alone
-    for n, text in enumerate(('#include "dcomp.h"\n#include "dcomp_policy_set.h"\n', '#include "dcomp_policy_set.h"\n#include "dcomp.h"\n')):
-        both = tmp_path / f'both{n}.c'                                                 # with dcomp.h, either order
-        both.write_text(text + 'int main(void) { dcomp_policy_set_cfg c; c.struct_size = (int32_t)sizeof c; '
-                               'return DCOMP_EABI == -7 && DCOMP_ACTOR_COMPACT == 1 && c.struct_size > 0 ? 0 : 1; }\n')
-        subprocess.run(gcc + ['-fsyntax-only', str(both)], check=True)
-    exe = tmp_path / 'sizes'
-    subprocess.run(['gcc', '-std=c99', '-I', inc, '-o', str(exe), str(src)], check=True)
-    sizes = [int(x) for x in subprocess.run([str(exe)], check=True, stdout=subprocess.PIPE, text=True).stdout.split()]
+    main = ('int main(void) { dcomp_policy_set_cfg c; c.struct_size = (int32_t)sizeof c; '
+            'return DCOMP_EABI == -7 && DCOMP_ACTOR_COMPACT == 1 && c.struct_size > 0 ? 0 : 1; }\n')
+    cs.compiles_as_c99(tmp_path, 'both', [text + main for text in (                    # with dcomp.h, either order
+        '#include "dcomp.h"\n#include "dcomp_policy_set.h"\n', '#include "dcomp_policy_set.h"\n#include "dcomp.h"\n')])
     S = _lib.DcompPolicySetCfg
     assert sizes == [ctypes.sizeof(S), S.num_policies.offset, S.members.offset, S.slot_policy.offset]
 

@@ -14,24 +14,16 @@ import ctypes
 import numpy as np
 import pytest
 
-from tests import test_actor_gpu as tag
-from tests import test_learner_gpu as tlg
+from tests import fcnet_cases as fc
+from tests import fcnet_support as fs
+from tests.fcnet_cases import HYPER
+from tests.fcnet_support import torch_cuda  # noqa: F401  (the fixture)
 
 pytestmark = pytest.mark.gpu
 
-SHAPES = {'a': (5, 3, 32, 'tanh', 70), 'b': (3, 36, 64, 'relu', 33), 'c': (4, 10, 256, 'tanh', 40)}      # U, B, hidden, activation, E
-SLOTS = {'a': [0, 1, 1, 0, 1], 'b': [0, 1, 2], 'c': [0, 1, 2, 3]}
+SHAPES, SLOTS, GUARD = fc.SET_SHAPES, fc.SET_SLOTS, fc.SET_GUARD
 FORMATS = [('a', False), ('a', True), ('b', False), ('b', True), ('c', False)]
 FORMAT_IDS = ['a-rows', 'a-compact', 'b-rows', 'b-compact', 'c-rows']
-HYPER = tlg.HYPER
-GUARD = 97
-
-
-@pytest.fixture(scope='module')
-def torch_cuda():
-    import torch
-    assert torch.cuda.is_available(), "these tests need the MI355X"
-    return torch
 
 
 _OBS = {}
@@ -42,7 +34,7 @@ def _obs(torch, name):
     if name not in _OBS:
         from deepcomp_amd.fragment import FragmentCodec
         U, B, _, _, E = SHAPES[name]
-        env = tag._env('multi', E, U, B)
+        env = fs.env('multi', E, U, B)
         env.reset()
         g = torch.Generator(device='cuda').manual_seed(5)
         for _ in range(3):
@@ -53,65 +45,6 @@ def _obs(torch, name):
         codec.check()
         _OBS[name] = {False: rows, True: packed}
     return _OBS[name]
-
-
-def _member(name, seed, value=True, **over):
-    from deepcomp_amd.actor import FcnetActor
-    U, B, H, act, _ = SHAPES[name]
-    U, B, H, act = over.get('U', U), over.get('B', B), over.get('H', H), over.get('activation', act)
-    w = FcnetActor.random_weights('multi', U, B, H, seed=seed, bias_std=0.1)
-    vw = FcnetActor.random_value_weights('multi', U, B, H, seed=seed, bias_std=0.1, shared=over.get('shared', False)) if value else None
-    return FcnetActor('multi', U, B, w, activation=act, value_weights=vw)
-
-
-def _distinct(name, value=True):
-    from deepcomp_amd.policy_set import PerUEActor
-    sp = SLOTS[name]
-    return PerUEActor([_member(name, 10 + p, value) for p in range(max(sp) + 1)], sp)
-
-
-def _run(torch, actor, obs, compact, mode, guard=0, **kw):
-    """One launch into fresh buffers: mode 'a' = actions, 'av' = actions with the value, 'v' = the value alone.  Floats start as NaN
-    (an unwritten element then equals nothing); guard > 0 puts that many pattern elements behind every output."""
-    E = obs.shape[0]
-    rows = E * actor.U
-    full = {}
-
-    def buf(key, n, dtype, fill):
-        t = torch.full((n + guard,), fill, dtype=dtype, device='cuda')
-        t[n:] = 0x5A if dtype == torch.uint8 else -12345.0
-        full[key] = (t, n)
-        return t[:n]
-    out = {}
-    if mode == 'v':
-        out['vf'] = buf('vf', rows, torch.float32, float('nan'))
-        actor.value(obs, compact=compact, out=out['vf'])
-    else:
-        out['act'] = buf('act', rows, torch.uint8, 0xEE).view(E, actor.U)
-        out['logits'] = buf('logits', rows * actor.num_logits, torch.float32, float('nan')).view(rows, actor.num_logits)
-        out['logp'] = buf('logp', rows * actor.heads, torch.float32, float('nan')).view(rows, actor.heads)
-        if mode == 'av':
-            out['vf'] = buf('vf', rows, torch.float32, float('nan'))
-        actor.actions(obs, compact=compact, out=out['act'], logits=out['logits'], logp=out['logp'], vf=out.get('vf'), **kw)
-    torch.cuda.synchronize()
-    for key, (t, n) in full.items():
-        tail = t[n:]
-        assert bool((tail == (0x5A if t.dtype == torch.uint8 else -12345.0)).all()), f'{key}: written past its end'
-    return out
-
-
-def _same(torch, got, want, rows=None):
-    """Every output of two launches equal, bit for bit (NaN, the initial fill, equals nothing); rows: at these decision rows only."""
-    assert got.keys() == want.keys()
-    for k in got:
-        a, b = got[k].reshape(_nrows(got), -1), want[k].reshape(_nrows(want), -1)
-        if rows is not None:
-            a, b = a[rows], b[rows]
-        assert torch.equal(a, b), k
-
-
-def _nrows(out):
-    return out['vf'].numel() if 'vf' in out else out['act'].numel()
 
 
 VARIANTS = [(mode, sample) for mode in ('a', 'av') for sample in (True, False)] + [('v', False)]
@@ -131,16 +64,16 @@ def test_equal_members_reproduce_the_shared_policy(torch_cuda, name, compact):
     from deepcomp_amd.policy_set import PerUEActor
     U = SHAPES[name][0]
     obs = _obs(torch, name)[compact]
-    single = _member(name, 1)
-    both = PerUEActor([_member(name, 1) for _ in range(U)])
+    single = fs.set_member(name, 1)
+    both = PerUEActor([fs.set_member(name, 1) for _ in range(U)])
     assert both.slot_policy == list(range(U)) and both.value_weights is not None and len(both.members) == U
     for mode, sample in VARIANTS:
-        want = _run(torch, single, obs, compact, mode, **_kw(mode, sample))
-        got = _run(torch, both, obs, compact, mode, guard=GUARD if name == 'a' else 0, **_kw(mode, sample))
-        _same(torch, got, want)
-    novalue = PerUEActor([_member(name, 1, value=False) for _ in range(U)])
+        want = fs.set_run(torch, single, obs, compact, mode, **_kw(mode, sample))
+        got = fs.set_run(torch, both, obs, compact, mode, guard=GUARD if name == 'a' else 0, **_kw(mode, sample))
+        fs.set_same(torch, got, want)
+    novalue = PerUEActor([fs.set_member(name, 1, value=False) for _ in range(U)])
     assert novalue.value_weights is None
-    _same(torch, _run(torch, novalue, obs, compact, 'a', **_kw('a', True)), _run(torch, single, obs, compact, 'a', **_kw('a', True)))
+    fs.set_same(torch, fs.set_run(torch, novalue, obs, compact, 'a', **_kw('a', True)), fs.set_run(torch, single, obs, compact, 'a', **_kw('a', True)))
 
 
 # ---------------------------------------------------------------------------------------------- 2: distinct members
@@ -152,22 +85,22 @@ def test_every_slot_runs_its_own_member(torch_cuda, name, compact):
     U, _, _, _, E = SHAPES[name]
     sp = SLOTS[name]
     obs = _obs(torch, name)[compact]
-    pset = _distinct(name)
+    pset = fs.set_distinct(name)
     slot_rows = [torch.arange(E, device='cuda') * U + u for u in range(U)]
     for kw in (dict(sample=True), dict(sample=True, row_base=3 * U, step=5, seed=0x123456789), dict(sample=False)):
-        got = _run(torch, pset, obs, compact, 'av', **kw)
-        alone = [_run(torch, m, obs, compact, 'av', **kw) for m in pset.members]
+        got = fs.set_run(torch, pset, obs, compact, 'av', **kw)
+        alone = [fs.set_run(torch, m, obs, compact, 'av', **kw) for m in pset.members]
         for u in range(U):
-            _same(torch, got, alone[sp[u]], rows=slot_rows[u])
+            fs.set_same(torch, got, alone[sp[u]], rows=slot_rows[u])
         # the comparison discriminates: on the rows of slot 1 the members of slots 0 and 1 disagree, so a kernel that ignored the
         # table could not have matched both
         assert sp[0] != sp[1]
         for k in ('logits', 'vf'):
             x, y = (alone[sp[s]][k].reshape(E * U, -1)[slot_rows[1]] for s in (0, 1))
             assert not torch.equal(x, y), k
-    gotv = _run(torch, pset, obs, compact, 'v')
+    gotv = fs.set_run(torch, pset, obs, compact, 'v')
     for u in range(U):
-        _same(torch, gotv, _run(torch, pset.members[sp[u]], obs, compact, 'v'), rows=slot_rows[u])
+        fs.set_same(torch, gotv, fs.set_run(torch, pset.members[sp[u]], obs, compact, 'v'), rows=slot_rows[u])
 
 
 # ---------------------------------------------------------------------------------------------- 3: unlisted slots
@@ -177,12 +110,12 @@ def test_unlisted_slots_get_action_zero_and_its_logp(torch_cuda, name):
     U, _, _, _, E = SHAPES[name]
     sp = SLOTS[name]
     obs = _obs(torch, name)[False]
-    pset = _distinct(name)
+    pset = fs.set_distinct(name)
     kw = dict(sample=True, seed=11, step=2, num_active=U - 2)
-    got = _run(torch, pset, obs, False, 'av', **kw)
+    got = fs.set_run(torch, pset, obs, False, 'av', **kw)
     for u in range(U):
         rows = torch.arange(E, device='cuda') * U + u
-        _same(torch, got, _run(torch, pset.members[sp[u]], obs, False, 'av', **kw), rows=rows)
+        fs.set_same(torch, got, fs.set_run(torch, pset.members[sp[u]], obs, False, 'av', **kw), rows=rows)
         if u >= U - 2:
             assert not bool(got['act'][:, u].any())
             lsm = torch.log_softmax(got['logits'][rows].double(), -1)[:, 0]
@@ -201,29 +134,29 @@ def test_the_set_runs_what_a_members_learner_wrote(torch_cuda):
     U, _, _, _, E = SHAPES[name]
     sp = SLOTS[name]
     obs = _obs(torch, name)[False]
-    pset = _distinct(name)
+    pset = fs.set_distinct(name)
     kw = dict(sample=True, seed=3, step=1)
-    before = _run(torch, pset, obs, False, 'av', **kw)
+    before = fs.set_run(torch, pset, obs, False, 'av', **kw)
     m = pset.members[1]
-    own = _run(torch, m, obs, False, 'av', **kw)
+    own = fs.set_run(torch, m, obs, False, 'av', **kw)
     learner = PPOLearner(m, max_rows=E * U, **dict(HYPER, lr=1e-2))
     g = torch.Generator(device='cuda').manual_seed(8)
     adv = torch.randn(E * U, generator=g, device='cuda')
     learner.grads(obs.reshape(E * U, -1), own['act'].reshape(E * U, 1), own['logp'], own['logits'], adv, own['vf'] + adv, own['vf'].clone())
     learner.apply()
-    after = _run(torch, pset, obs, False, 'av', **kw)
-    fresh = _run(torch, m, obs, False, 'av', **kw)
+    after = fs.set_run(torch, pset, obs, False, 'av', **kw)
+    fresh = fs.set_run(torch, m, obs, False, 'av', **kw)
     for u in range(U):
         rows = torch.arange(E, device='cuda') * U + u
         if sp[u] == 1:
-            _same(torch, after, fresh, rows=rows)
+            fs.set_same(torch, after, fresh, rows=rows)
             assert not torch.equal(after['logits'][rows], before['logits'][rows]) and not torch.equal(after['vf'][rows], before['vf'][rows])
         else:
-            _same(torch, after, before, rows=rows)
+            fs.set_same(torch, after, before, rows=rows)
 
 
 # ---------------------------------------------------------------------------------------------- 6: collect
-_T = 5
+_T = fc.SET_T
 
 
 def _equal_batches(torch, b1, b2):
@@ -238,32 +171,14 @@ def test_collect_with_a_set_of_equal_members_is_collect_with_the_shared_policy(t
     from deepcomp_amd.policy_set import PerUEActor
     from deepcomp_amd.sampler import collect
     U, B, _, _, E = SHAPES['a']
-    pset = PerUEActor([_member('a', 1) for _ in range(U)])
-    got = collect(tag._env('multi', E, U, B), pset, _T, gamma=0.99, lam=0.95, compact=compact, dist_inputs=True)
-    want = collect(tag._env('multi', E, U, B), _member('a', 1), _T, gamma=0.99, lam=0.95, compact=compact, dist_inputs=True)
+    pset = PerUEActor([fs.set_member('a', 1) for _ in range(U)])
+    got = collect(fs.env('multi', E, U, B), pset, _T, gamma=0.99, lam=0.95, compact=compact, dist_inputs=True)
+    want = collect(fs.env('multi', E, U, B), fs.set_member('a', 1), _T, gamma=0.99, lam=0.95, compact=compact, dist_inputs=True)
     _equal_batches(torch, got, want)
     assert bool(torch.isfinite(got['advantages']).all()) and bool(got['actions'].any())
 
 
 # ---------------------------------------------------------------------------------------------- 7: PPOLearner.update(rows=)
-_BATCH = {}
-
-
-def _batch(torch, compact):
-    """One collect() batch of (a)'s shape at T = 5 driven by the distinct set, computed once: (batch, the same with observation rows)."""
-    if compact not in _BATCH:
-        from deepcomp_amd.fragment import FragmentCodec
-        from deepcomp_amd.sampler import collect
-        U, B, _, _, E = SHAPES['a']
-        batch = collect(tag._env('multi', E, U, B), _distinct('a'), _T, gamma=0.99, lam=0.95, compact=compact, dist_inputs=True)
-        rows = batch
-        if compact:
-            rows = {k: t for k, t in batch.items() if k != 'obs_compact'}
-            rows['obs'] = FragmentCodec(U, B).unpack(batch['obs_compact'])
-        _BATCH[compact] = (batch, rows)
-    return _BATCH[compact]
-
-
 _FLAT = {'obs': 'num_in', 'actions': 'heads', 'action_logp': 'heads', 'action_dist_inputs': 'num_logits', 'advantages': None, 'value_targets': None,
          'vf_preds': None}
 
@@ -277,14 +192,6 @@ def _gathered(actor, rows_batch, rows):
     return out
 
 
-def _same_state(s1, s2):
-    from deepcomp_amd.learner import ARRAYS
-    assert s1['step'] == s2['step'] and s1['kl_coeff'] == s2['kl_coeff'] and s1['step'] > 0
-    for k in ('weights', 'm', 'v'):
-        for n in ARRAYS:
-            assert np.array_equal(s1[k][n], s2[k][n]), (k, n)
-
-
 def _ppo(actor, **kw):
     from deepcomp_amd.learner import PPOLearner
     return PPOLearner(actor, max_rows=64, **dict(HYPER, lr=1e-3, **kw))
@@ -294,20 +201,20 @@ def _ppo(actor, **kw):
 def test_update_on_given_rows_is_update_on_the_gathered_batch(torch_cuda, compact):
     torch = torch_cuda
     U, _, _, _, E = SHAPES['a']
-    batch, rows_batch = _batch(torch, compact)
+    batch, rows_batch = fs.set_batch(torch, compact)
     N = _T * E * U
     g = torch.Generator(device='cuda').manual_seed(21)
     subset = torch.randperm(N, generator=g, device='cuda')[:200].contiguous()           # distinct, in no order, across steps, envs and slots
-    a, b, full = (_ppo(_member('a', 1)) for _ in range(3))
+    a, b, full = (_ppo(fs.set_member('a', 1)) for _ in range(3))
     out_a = a.update(batch, num_sgd_iter=2, minibatch_rows=64, seed=3, rows=subset)
     out_b = b.update(_gathered(b.actor, rows_batch, subset), num_sgd_iter=2, minibatch_rows=64, seed=3)
     assert out_a == out_b and all(np.isfinite(v) for v in out_a.values())
     s_a = a.state_dict()
     assert s_a['step'] == 8                                                            # 200 rows: three minibatches of 64 and one of 8, twice
-    _same_state(s_a, b.state_dict())
-    c = _ppo(_member('a', 1))
+    fs.same_state(s_a, b.state_dict(), stepped=True)
+    c = _ppo(fs.set_member('a', 1))
     c.update(batch, num_sgd_iter=2, minibatch_rows=64, seed=3, rows=subset.to(torch.int32))      # int32 rows are the same rows
-    _same_state(s_a, c.state_dict())
+    fs.same_state(s_a, c.state_dict(), stepped=True)
     full.update(batch, num_sgd_iter=1, minibatch_rows=64, seed=3)                      # rows=None: the whole batch, as before
     assert full.state_dict()['step'] == -(-N // 64)
 
@@ -315,7 +222,7 @@ def test_update_on_given_rows_is_update_on_the_gathered_batch(torch_cuda, compac
 # ---------------------------------------------------------------------------------------------- 8, 9: PerUELearner
 def _per_ue(name='a'):
     from deepcomp_amd.policy_set import PerUELearner
-    pset = _distinct(name)
+    pset = fs.set_distinct(name)
     return pset, PerUELearner(pset, max_rows=64, **dict(HYPER, lr=1e-3))
 
 
@@ -325,29 +232,29 @@ def test_per_ue_update_is_the_loop_over_the_members_sub_batches(torch_cuda, comp
     from deepcomp_amd.policy_set import policy_rows
     U, _, _, _, E = SHAPES['a']
     sp = SLOTS['a']
-    batch, rows_batch = _batch(torch, compact)
+    batch, rows_batch = fs.set_batch(torch, compact)
     pset, learner = _per_ue()
     stats = learner.update(batch, num_sgd_iter=2, minibatch_rows=64, seed=4)
     assert len(stats) == 2 and all(np.isfinite(s['total_loss']) and 'kl_coeff' in s for s in stats)
     split = policy_rows(_T * E * U, U, sp, 2, 'cuda')
     assert [int(r.numel()) for r in split] == [2 * _T * E, 3 * _T * E]
     for p in range(2):                                                                 # the loop written out: fresh copies, gathered sub-batches, seed + p
-        twin = _ppo(_member('a', 10 + p))
+        twin = _ppo(fs.set_member('a', 10 + p))
         want = twin.update(_gathered(twin.actor, rows_batch, split[p]), num_sgd_iter=2, minibatch_rows=64, seed=4 + p)
         assert stats[p] == want
-        _same_state(learner.learners[p].state_dict(), twin.state_dict())
+        fs.same_state(learner.learners[p].state_dict(), twin.state_dict(), stepped=True)
     w = learner.get_weights()
     assert len(w) == 2 and len(learner.to_rllib_weights()) == 2 and not np.array_equal(w[0][0]['w1'], w[1][0]['w1'])
     obs = _obs(torch, 'a')[False]
-    got = _run(torch, pset, obs, False, 'av', sample=True, seed=5)
+    got = fs.set_run(torch, pset, obs, False, 'av', sample=True, seed=5)
     for u in range(U):
-        _same(torch, got, _run(torch, pset.members[sp[u]], obs, False, 'av', sample=True, seed=5), rows=torch.arange(E, device='cuda') * U + u)
+        fs.set_same(torch, got, fs.set_run(torch, pset.members[sp[u]], obs, False, 'av', sample=True, seed=5), rows=torch.arange(E, device='cuda') * U + u)
 
 
 def test_checkpoint_and_resume(torch_cuda):
     """state_dict -> a new set and learner -> load_state_dict -> one more update: the state of the uninterrupted run, bit for bit."""
     torch = torch_cuda
-    batch, _ = _batch(torch, True)
+    batch, _ = fs.set_batch(torch, True)
     _, run1 = _per_ue()
     run1.update(batch, num_sgd_iter=1, minibatch_rows=64, seed=1)
     saved = run1.state_dict()
@@ -356,7 +263,7 @@ def test_checkpoint_and_resume(torch_cuda):
     run2.load_state_dict(saved)
     run2.update(batch, num_sgd_iter=1, minibatch_rows=64, seed=2)
     for s1, s2 in zip(run1.state_dict(), run2.state_dict()):
-        _same_state(s1, s2)
+        fs.same_state(s1, s2, stepped=True)
     assert len(saved) == 2 and saved[0]['step'] > 0
     with pytest.raises(ValueError):
         run2.load_state_dict(saved[:1])
@@ -385,9 +292,9 @@ def test_refusals_that_need_handles(torch_cuda):
     from deepcomp_amd.actor import FcnetActor
     from deepcomp_amd.policy_set import PerUEActor, PerUELearner
     U, B, H, _, E = SHAPES['a']
-    base = _member('a', 1)
-    differing = {'num_bs': _member('a', 2, B=B + 1), 'hidden': _member('a', 2, H=64), 'activation': _member('a', 2, activation='relu'),
-                 'value function': _member('a', 2, value=False), 'num_ue': _member('a', 2, U=U + 1)}
+    base = fs.set_member('a', 1)
+    differing = {'num_bs': fs.set_member('a', 2, B=B + 1), 'hidden': fs.set_member('a', 2, H=64), 'activation': fs.set_member('a', 2, activation='relu'),
+                 'value function': fs.set_member('a', 2, value=False), 'num_ue': fs.set_member('a', 2, U=U + 1)}
     for field, other in differing.items():
         with pytest.raises(ValueError):
             PerUEActor([base, other])
@@ -400,7 +307,7 @@ def test_refusals_that_need_handles(torch_cuda):
     assert rc == _lib.EUNSUPPORTED and b'CENTRAL' in msg
     rc, msg = _c_create([base, central])
     assert rc == _lib.EINVAL and b'obs_kind' in msg                                    # (disagreement comes before the refusal of a form)
-    shared = _member('a', 1, shared=True)
+    shared = fs.set_member('a', 1, shared=True)
     with pytest.raises(NotImplementedError):
         PerUEActor([shared, shared])
     rc, msg = _c_create([shared, shared])
@@ -424,7 +331,7 @@ def test_refusals_that_need_handles(torch_cuda):
         pset.actions(obs[:, :, :-1].contiguous())
     with pytest.raises(ValueError):
         pset.actions(obs, vf=torch.zeros(E * U - 1, device='cuda'))
-    novalue = PerUEActor([_member('a', 1, value=False)])
+    novalue = PerUEActor([fs.set_member('a', 1, value=False)])
     with pytest.raises(ValueError):
         novalue.actions(obs, vf=torch.zeros(E * U, device='cuda'))
     run = _lib.DcompActorRun(ctypes.sizeof(_lib.DcompActorRun), 0, E, U, 0, 0, 0, 0, None, None)
@@ -432,8 +339,8 @@ def test_refusals_that_need_handles(torch_cuda):
     L = _lib.load()
     assert L.dcomp_policy_set_actions_v(novalue._h, ctypes.byref(run), obs.data_ptr(), None, vf.data_ptr(), None) == _lib.EINVAL
     assert b'dcomp_policy_set_actions_v' in L.dcomp_last_error() and b'no value function' in L.dcomp_last_error()
-    dyn = tag._env('multi', 6, 4, B, ue_arrival={2: 2, 4: -1})
-    dset = PerUEActor([_member('a', 1, U=dyn.U)])
+    dyn = fs.env('multi', 6, 4, B, ue_arrival={2: 2, 4: -1})
+    dset = PerUEActor([fs.set_member('a', 1, U=dyn.U)])
     dyn.reset()
     with pytest.raises(NotImplementedError):
         dset.act(dyn)
@@ -441,13 +348,13 @@ def test_refusals_that_need_handles(torch_cuda):
         PerUELearner(base)
     with pytest.raises(ValueError):
         PerUELearner(pset)                                                             # the same actor twice: two Adam states on one handle
-    lr = _ppo(_member('a', 1))
+    lr = _ppo(fs.set_member('a', 1))
     with pytest.raises(ValueError):
-        lr.update(_batch(torch, False)[0], num_sgd_iter=1, minibatch_rows=64, rows=torch.arange(64, device='cuda'), num_active=3)
+        lr.update(fs.set_batch(torch, False)[0], num_sgd_iter=1, minibatch_rows=64, rows=torch.arange(64, device='cuda'), num_active=3)
     for bad in (torch.arange(64), torch.arange(64, device='cuda').float(), torch.tensor([0, _T * E * U], device='cuda'), torch.tensor([3, 1, -1], device='cuda'),
                 torch.tensor([5, 9, 5], device='cuda'), torch.zeros(0, dtype=torch.int64, device='cuda')):
         with pytest.raises(ValueError):
-            lr.update(_batch(torch, False)[0], num_sgd_iter=1, minibatch_rows=64, rows=bad)
+            lr.update(fs.set_batch(torch, False)[0], num_sgd_iter=1, minibatch_rows=64, rows=bad)
     assert lr.state_dict()['step'] == 0
 
 
@@ -466,7 +373,7 @@ def test_a_value_function_attached_after_the_set_exists_is_refused_on_the_host(t
     run = _lib.DcompActorRun(ctypes.sizeof(_lib.DcompActorRun), 0, E, U, 0, 0, 0, 0, None, None)
     act, vf = torch.zeros((E, U), dtype=torch.uint8, device='cuda'), torch.zeros(E * U, device='cuda')
     for shared in (False, True):
-        members = [_member('a', 1, value=False), _member('a', 2, value=False)]
+        members = [fs.set_member('a', 1, value=False), fs.set_member('a', 2, value=False)]
         pset = PerUEActor(members)
         before = pset.actions(obs, sample=False).clone()
         for k, m in enumerate(members):
@@ -479,7 +386,7 @@ def test_a_value_function_attached_after_the_set_exists_is_refused_on_the_host(t
             with pytest.raises(ValueError):
                 pset.actions(obs)
             with pytest.raises(ValueError):
-                collect(tag._env('multi', E, U, B), pset, 2)
+                collect(fs.env('multi', E, U, B), pset, 2)
             for call in (lambda: L.dcomp_policy_set_actions_v(pset._h, ctypes.byref(run), obs.data_ptr(), act.data_ptr(), vf.data_ptr(), None),
                          lambda: L.dcomp_policy_set_actions_v(pset._h, ctypes.byref(run), obs.data_ptr(), None, vf.data_ptr(), None),
                          lambda: L.dcomp_policy_set_actions(pset._h, ctypes.byref(run), obs.data_ptr(), act.data_ptr(), None)):

@@ -4,7 +4,7 @@ The other learner tests hold the variants to EACH OTHER (grouped = sequential, m
 a change that moved all of them together would pass them.  This module holds every variant to a RECORDING of itself,
 tests/golden/sgd_characterization.json, written by this module's own entry at the commit that added it:
 
-    python -m tests.test_sgd_characterization_gpu --write            (on an MI355X)
+    python -m tests.<this module> --write            (on an MI355X, from the repository root)
 
 Per scenario the recording holds (1) the library calls the update makes, in order, through a forwarding proxy around the ``_L`` the
 learners hold: the entry point, the ``rows`` of its batch struct, ``source_rows`` and whether an index was given for the indexed and
@@ -22,9 +22,9 @@ import sys
 import numpy as np
 import pytest
 
-from tests import test_learner_accum_gpu as tlag
-from tests import test_learner_group_gpu as tlgg
-from tests import test_learner_indexed_gpu as tlig
+from tests import fcnet_cases as fc
+from tests import fcnet_support as fs
+from tests.fcnet_support import torch_cuda  # noqa: F401  (the fixture)
 
 pytestmark = pytest.mark.gpu
 
@@ -33,13 +33,6 @@ ITERS = 2
 MULTI = ('multi', 8, 3, 4, 32, 4)                # (kind, E, U, B, hidden, T): 96 source rows
 CENTRAL = ('central', 16, 3, 4, 32, 4)           # 64 source rows
 SLOTS = [0, 0, 1]                                # two policies: 64 and 32 rows
-
-
-@pytest.fixture(scope='module')
-def torch_cuda():
-    import torch
-    assert torch.cuda.is_available(), "these tests need the MI355X"
-    return torch
 
 
 # ---------------------------------------------------------------------------------------------- the recording
@@ -122,8 +115,8 @@ def _single(shape, compact, max_rows, **kw):
     """PPOLearner.update(batch, **kw) on the shape's collect() batch by a learner on the weights the batch was collected with."""
     def scenario(torch):
         kind, E, U, B, H, T = shape
-        w, vw, batch = tlig._collected(torch, kind, E, U, B, H, 'tanh', T, compact)
-        ln = tlig._learner(kind, U, B, w, vw, 'tanh', max_rows=max_rows, perturb=False, lr=1e-3)
+        w, vw, batch = fs.collected(torch, kind, E, U, B, H, 'tanh', T, compact)
+        ln = fs.ppo_learner(kind, U, B, w, vw, 'tanh', max_rows=max_rows, perturb=False, lr=1e-3)
         args = dict(kw)
         if args.pop('half', False):                                                    # rows=: a shuffled half of the source rows
             n = int(batch['actions'].numel())
@@ -137,31 +130,20 @@ def _single(shape, compact, max_rows, **kw):
 def _per_ue(compact, grouped):
     def scenario(torch):
         kind, E, U, B, H, T = MULTI
-        batch = tlgg._batch(('characterization', compact), U, B, H, 'tanh', E, T, SLOTS, compact)
-        ln = tlgg._learner(tlgg._set(U, B, H, 'tanh', SLOTS), max_rows=32)
+        batch = fs.group_collected(('characterization', compact), U, B, H, 'tanh', E, T, SLOTS, compact)
+        ln = fs.per_ue_learner(fs.policy_set(U, B, H, 'tanh', SLOTS), max_rows=32)
         return _record(torch, ln.learners, [batch], 6, [ln.actor] + ln.learners,
                        lambda: ln.update(batch, num_sgd_iter=ITERS, minibatch_rows=24, seed=6, grouped=grouped))
     return scenario
-
-
-def _shard(batch, r, R, E, U, T):
-    """Rank r's envs of a batch, rows (tests/test_learner_accum_gpu.py's _shard) or the compact record [T, E, words]."""
-    if 'obs' in batch:
-        return tlag._shard(batch, r, R, E, U, T)
-    lo, hi = r * E // R, (r + 1) * E // R
-    out = tlag._shard(dict(batch, obs=batch['actions']), r, R, E, U, T)
-    del out['obs']
-    out['obs_compact'] = batch['obs_compact'][:, lo:hi].contiguous()
-    return out
 
 
 def _lockstep(compact):
     def scenario(torch):
         from deepcomp_amd.dp_learner import DataParallelLearner, run_lockstep
         kind, E, U, B, H, T = MULTI
-        w, vw, batch = tlig._collected(torch, kind, E, U, B, H, 'tanh', T, compact)
-        shards = [_shard(batch, r, 2, E, U, T) for r in range(2)]
-        lns = [tlig._learner(kind, U, B, w, vw, 'tanh', max_rows=24, perturb=False, lr=1e-3) for _ in range(2)]
+        w, vw, batch = fs.collected(torch, kind, E, U, B, H, 'tanh', T, compact)
+        shards = [fs.shard(batch, r, 2, E, U, T) for r in range(2)]
+        lns = [fs.ppo_learner(kind, U, B, w, vw, 'tanh', max_rows=24, perturb=False, lr=1e-3) for _ in range(2)]
         dps = [DataParallelLearner(ln, rank=r, world=2) for r, ln in enumerate(lns)]
         return _record(torch, lns, shards, 8, lns, lambda: run_lockstep(dps, shards, num_sgd_iter=ITERS, minibatch_rows=48, seed=8))
     return scenario
@@ -175,9 +157,9 @@ for _c in (False, True):
     SCENARIOS[f'multi-{_f}-num_active'] = _single(MULTI, _c, 40, minibatch_rows=40, seed=4, num_active=2)
     SCENARIOS[f'multi-{_f}-rows'] = _single(MULTI, _c, 40, minibatch_rows=40, seed=5, half=True)
     # test_update_with_micro_rows_equals_update's shape: 6 464 rows in minibatches of 4 096 = 2 048 + 2 048, then 2 368 = 2 048 + 320
-    SCENARIOS[f'accum-{_f}-micro'] = _single(tlag.MULTI, _c, tlag.CHUNK, minibatch_rows=4096, seed=3, micro_rows=tlag.CHUNK)
-    SCENARIOS[f'accum-{_f}-micro-clip'] = _single(tlag.MULTI, _c, tlag.CHUNK, minibatch_rows=4096, seed=3, micro_rows=tlag.CHUNK, grad_clip=0.01)
-    SCENARIOS[f'accum-{_f}-clip-alone'] = _single(tlag.MULTI, _c, 4096, minibatch_rows=4096, seed=3, grad_clip=0.01)
+    SCENARIOS[f'accum-{_f}-micro'] = _single(fc.ACCUM_MULTI, _c, fc.CHUNK, minibatch_rows=4096, seed=3, micro_rows=fc.CHUNK)
+    SCENARIOS[f'accum-{_f}-micro-clip'] = _single(fc.ACCUM_MULTI, _c, fc.CHUNK, minibatch_rows=4096, seed=3, micro_rows=fc.CHUNK, grad_clip=0.01)
+    SCENARIOS[f'accum-{_f}-clip-alone'] = _single(fc.ACCUM_MULTI, _c, 4096, minibatch_rows=4096, seed=3, grad_clip=0.01)
     for _g in (False, True):
         SCENARIOS[f"per-ue-{_f}-{'grouped' if _g else 'sequential'}"] = _per_ue(_c, _g)
     SCENARIOS[f'lockstep-{_f}'] = _lockstep(_c)
@@ -197,7 +179,7 @@ def test_the_fixture_holds_exactly_the_scenarios():
 @pytest.mark.parametrize('name', sorted(SCENARIOS))
 def test_update_does_what_the_recording_did(torch_cuda, name):
     from deepcomp_amd.learner import chunk_unit
-    assert tlag.CHUNK == chunk_unit()                                                  # (the accumulated scenarios' micro_rows)
+    assert fc.CHUNK == chunk_unit()                                                  # (the accumulated scenarios' micro_rows)
     got, want = SCENARIOS[name](torch_cuda), _fixture()[name]
     if got == want:
         return

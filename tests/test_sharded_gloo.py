@@ -2,7 +2,6 @@
 (the same code runs on RCCL/xGMI with backend 'nccl').  Also: the oracle's Philox draws are keyed by the
 GLOBAL env id, so a sharded run equals the unsharded one."""
 import os
-import socket
 
 import numpy as np
 import pytest
@@ -10,21 +9,7 @@ import torch
 import torch.distributed as dist
 import torch.multiprocessing as mp
 
-
-def _free_port():
-    """Below the kernel's ephemeral range: a bind(0) port can be handed to any outgoing connection before rank 0 binds it."""
-    import random
-    for _ in range(64):
-        port = random.randrange(20000, 32000)
-        s = socket.socket()
-        try:
-            s.bind(('127.0.0.1', port))
-            return port
-        except OSError:
-            continue
-        finally:
-            s.close()
-    raise RuntimeError('no free port')
+from tests.env_support import free_port as _free_port
 
 
 def _worker(rank, world, port, total_envs, ret):

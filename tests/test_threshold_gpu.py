@@ -47,20 +47,6 @@ FAMILIES = [
     ('big_rollout_forced_10x5', 'central', 10, 5, 3, {'DCOMP_FORCE_BIG': '1'}, 'rollout', 'big_kernel'),
     ('big_dyn_6x40', 'multi', 6, 40, 3, {}, 'dyn', 'big_kernel'),
 ]
-ARRIVAL = {1: 2, 3: -1, 5: 1, 8: -2}            # UE arrival / departure while the threshold decisions are taken (base.py:433-443)
-
-
-def _slots(U, mode):
-    """UE slots per env: the list, or max_ues = the largest simultaneous count of the schedule (base.py:79-84)."""
-    if mode != 'dyn':
-        return U
-    n = peak = 0
-    for t in sorted(ARRIVAL):
-        n += ARRIVAL[t]
-        peak = max(peak, n)
-    return U + peak
-
-
 def _d_t():
     from oracle import oracle as orc
     return orc.connect_threshold_distance()
@@ -80,24 +66,12 @@ def _specs(vels, xy=None):
                  velocity=v, util_func='log', dr_req=1) for i, v in enumerate(vels)]
 
 
-def _oracle(scn, kind, E, seed, max_ues=None):
-    from oracle import oracle as orc
-    init_xy = [(s['pos_x'], s['pos_y']) if s['pos_x'] != 'random' else (-1, -1) for s in scn.ue_specs]
-    envs = []
-    for e in range(E):
-        o = orc.OracleEnv(int(scn.width), int(scn.height), scn.bs_pos, scn.bs_sharing, [s['velocity'] for s in scn.ue_specs],
-                          kind=orc.MULTI if kind == 'multi' else orc.CENTRAL, init_xy=init_xy, max_ues=max_ues)
-        o.set_philox(seed, e)
-        envs.append(o)
-    return orc.OracleBatch(envs)
-
-
 def _core(torch, scn, kind, E, seed, mode):
     from deepcomp_amd.entities import build_from_scenario
     from deepcomp_amd.env import BatchedMobileEnv
     m, bs, ues = build_from_scenario(scn)
     return BatchedMobileEnv(m, bs, ues, kind, num_envs=E, seed=seed, rng='philox', rand_episodes=True,
-                            ue_arrival=dict(ARRIVAL) if mode == 'dyn' else None)
+                            ue_arrival=dict(tc.ARRIVAL) if mode == 'dyn' else None)
 
 
 def _run(torch, scn, kind, E, seed, acts, mode, kernel_tag, msg):
@@ -109,8 +83,8 @@ def _run(torch, scn, kind, E, seed, acts, mode, kernel_tag, msg):
     assert M == acts.shape[2], f'{msg}: {M} slots, actions for {acts.shape[2]}'
     if kernel_tag is not None:
         assert kernel_tag in core.step_kernel_name, f'{msg}: dispatched {core.step_kernel_name}, expected {kernel_tag}'
-    ob = _oracle(scn, kind, E, seed, max_ues=M if mode == 'dyn' else None)
-    sched = orc.arrival_schedule(100, ARRIVAL) if mode == 'dyn' else None
+    ob = tc.oracle_batch(scn, kind, E, seed, max_ues=M if mode == 'dyn' else None)
+    sched = orc.arrival_schedule(100, tc.ARRIVAL) if mode == 'dyn' else None
     core.reset()
     o_reset = ob.reset()
     if mode == 'rollout':
@@ -171,7 +145,7 @@ def test_static_ues_at_the_threshold_circle(torch_cuda, fam, monkeypatch):
         sharing = (('mixed', 'rate-fair', 'resource-fair', 'proportional-fair') if ('wide' in name or 'tight' in name)
                    else ('mixed', 'resource-fair', 'max-cap', 'proportional-fair'))[c % 4]
         scn = _scenario(B, W, H, bs_pos, _specs([0] * U, ue_xy), sharing)
-        M = _slots(U, mode)
+        M = tc.slots(U, mode)
         rounds = []
         for s in range(S):
             a = np.zeros((E, M), dtype=np.uint8)
@@ -208,9 +182,9 @@ def test_moving_ues_cross_the_threshold_circle(torch_cuda, fam, monkeypatch):
         dummy = [(float(rng.uniform(0, W)), float(rng.uniform(0, H))) for _ in range(B)]
         scn0 = _scenario(B, W, H, dummy, _specs(vels))
         seed = 500 + c
-        M = _slots(U, mode)
-        ob = _oracle(scn0, kind, E, seed, max_ues=M if mode == 'dyn' else None)
-        sched = orc.arrival_schedule(100, ARRIVAL) if mode == 'dyn' else None
+        M = tc.slots(U, mode)
+        ob = tc.oracle_batch(scn0, kind, E, seed, max_ues=M if mode == 'dyn' else None)
+        sched = orc.arrival_schedule(100, tc.ARRIVAL) if mode == 'dyn' else None
         ob.reset()
         traj = [np.stack([o.state()['pos'] for o in ob.envs])]
         zero = np.zeros((E, M), dtype=np.uint8)
@@ -220,7 +194,7 @@ def test_moving_ues_cross_the_threshold_circle(torch_cuda, fam, monkeypatch):
                     o.set_event_counts(*sched[t])
             ob.step(zero, want_obs=False)
             traj.append(np.stack([o.state()['pos'] for o in ob.envs]))
-        traj = np.stack(traj)[:, :, :U]                 # (UE arrival / departure: the first U slots hold a UE at every step of ARRIVAL)
+        traj = np.stack(traj)[:, :, :U]                 # (UE arrival / departure: the first U slots hold a UE at every step of tc.ARRIVAL)
         bs_pos, act_small, nd = tc.moving_case(traj, rng, B, d_t)
         acts = np.zeros((T, E, M), dtype=np.uint8)
         acts[:, :, :act_small.shape[2]] = act_small

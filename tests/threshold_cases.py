@@ -159,3 +159,30 @@ def moving_case(positions, rng, B, d_t, t_lo=2, k_choices=(-2, -1, 0, 1, 2)):
             busy.add((t, e, u))
             n_dec += 1
     return bs, act, n_dec
+
+
+# ---------------------------------------------------------------------------------------------- what the GPU tests of the boundary share
+ARRIVAL = {1: 2, 3: -1, 5: 1, 8: -2}            # UE arrival / departure while the threshold decisions are taken (base.py:433-443)
+
+
+def slots(U, mode):
+    """UE slots per env: the list, or max_ues = the largest simultaneous count of the schedule (base.py:79-84)."""
+    if mode != 'dyn':
+        return U
+    n = peak = 0
+    for t in sorted(ARRIVAL):
+        n += ARRIVAL[t]
+        peak = max(peak, n)
+    return U + peak
+
+
+def oracle_batch(scn, kind, E, seed, max_ues=None):
+    from oracle import oracle as orc
+    init_xy = [(s['pos_x'], s['pos_y']) if s['pos_x'] != 'random' else (-1, -1) for s in scn.ue_specs]
+    envs = []
+    for e in range(E):
+        o = orc.OracleEnv(int(scn.width), int(scn.height), scn.bs_pos, scn.bs_sharing, [s['velocity'] for s in scn.ue_specs],
+                          kind=orc.MULTI if kind == 'multi' else orc.CENTRAL, init_xy=init_xy, max_ues=max_ues)
+        o.set_philox(seed, e)
+        envs.append(o)
+    return orc.OracleBatch(envs)
