@@ -174,6 +174,16 @@ ACCUM_SUMS = 8
 GROUP_ACCUM_EXPORTS = ['dcomp_learner_group_accumulate', 'dcomp_learner_group_accum_finish']
 
 
+# include/dcomp_gae_uid.h: advantages that follow a UE through the slots of a dynamic env by its uid word
+GAE_UID_EXPORTS = ['dcomp_gae_uid']
+
+
+class DcompGaeUidArgs(ctypes.Structure):
+    _fields_ = [('struct_size', ctypes.c_int32), ('num_steps', ctypes.c_int32), ('num_envs', ctypes.c_int32), ('num_slots', ctypes.c_int32),
+                ('max_shift', ctypes.c_int32), ('gamma', ctypes.c_float), ('lambda', ctypes.c_float)] + \
+               [(n, ctypes.c_void_p) for n in ('reward', 'vf', 'uid', 'uid_next', 'last_vf', 'end', 'advantages', 'value_targets', 'live')]
+
+
 class DcompPpoHyper(ctypes.Structure):
     _fields_ = [('struct_size', ctypes.c_int32), ('clip_param', ctypes.c_float), ('vf_clip_param', ctypes.c_float),
                 ('vf_loss_coeff', ctypes.c_float), ('entropy_coeff', ctypes.c_float), ('kl_coeff', ctypes.c_float)]
@@ -300,6 +310,10 @@ def load():
         L.dcomp_learner_group_accumulate.argtypes = [vp, ctypes.POINTER(DcompGroupBatch), ctypes.POINTER(DcompPpoHyper), vp, vp, vp]
         L.dcomp_learner_group_accum_finish.argtypes = [vp, vp, vp, ctypes.POINTER(DcompPpoHyper), _fp, _ip, vp, vp, vp]
         for name in GROUP_ACCUM_EXPORTS:
+            getattr(L, name)
+    if hasattr(L, 'dcomp_gae_uid') or not os.environ.get('DCOMP_LIB'):
+        L.dcomp_gae_uid.argtypes = [ctypes.POINTER(DcompGaeUidArgs), vp]
+        for name in GAE_UID_EXPORTS:
             getattr(L, name)
     for name in EXPORTS:
         getattr(L, name)

@@ -3,8 +3,8 @@
     python -m deepcomp_amd.build [--force] [--jobs N]
 
 One object per base-station count listed in csrc/dcomp_blist.h (all UE-group widths inside), compiled
-in parallel, plus the API object, the generic kernel's, the actor's (csrc/dcomp_actor.hip: actor, value function, GAE, per-UE policy sets) and the learner's
-(csrc/dcomp_learner.hip: PPO loss, backward pass, Adam); linked into deepcomp_amd/csrc/libdcomp_hip.so.  hipcc cross-compiles
+in parallel, plus the API object, the generic kernel's, the actor's (csrc/dcomp_actor.hip: actor, value function, GAE, per-UE policy sets), the learner's
+(csrc/dcomp_learner.hip: PPO loss, backward pass, Adam) and the per-UE advantage estimator's (csrc/dcomp_gae_uid.hip); linked into deepcomp_amd/csrc/libdcomp_hip.so.  hipcc cross-compiles
 for gfx950 without a GPU present.
 """
 import argparse
@@ -38,9 +38,9 @@ def _sources():
     return [os.path.join(CSRC, f) for f in ('dcomp_device.h', 'dcomp_wide.h', 'dcomp_dyn.h', 'dcomp_blist.h', 'dcomp_inst.hip', 'dcomp_api.hip', 'dcomp_fragment.h',
                                             'dcomp_big.h', 'dcomp_big.hip', 'dcomp_actor.hip', 'dcomp_actor_impl.h', 'dcomp_fcnet_plan.h', 'dcomp_learner.hip', 'dcomp_learner_tiles.inc',
                                             'dcomp_learner_reduce.inc', 'dcomp_learner_adam.inc', 'dcomp_learner_accumulate.inc', 'dcomp_learner_norm.inc',
-                                            'dcomp_learner_finish.inc')] + \
+                                            'dcomp_learner_finish.inc', 'dcomp_gae_uid.hip')] + \
         [os.path.join(os.path.dirname(HERE), 'include', f) for f in ('dcomp.h', 'dcomp_types.h', 'dcomp_learner.h', 'dcomp_learner_indexed.h', 'dcomp_policy_set.h',
-                                                                            'dcomp_learner_group.h', 'dcomp_learner_accum.h', 'dcomp_learner_group_accum.h')]
+                                                                            'dcomp_learner_group.h', 'dcomp_learner_accum.h', 'dcomp_learner_group_accum.h', 'dcomp_gae_uid.h')]
 
 
 def _dev_flags():
@@ -131,6 +131,8 @@ def build(force=False, jobs=None, extra_flags=()):
     tasks.append((o_actor, [hipcc] + CXXFLAGS + list(extra_flags) + ['-c', os.path.join(CSRC, 'dcomp_actor.hip'), '-o', o_actor]))
     o_learner = os.path.join(OBJ, 'dcomp_learner.o')    # the PPO learner on the actor's handle (shares csrc/dcomp_actor_impl.h with it)
     tasks.append((o_learner, [hipcc] + CXXFLAGS + list(extra_flags) + ['-c', os.path.join(CSRC, 'dcomp_learner.hip'), '-o', o_learner]))
+    o_gae_uid = os.path.join(OBJ, 'dcomp_gae_uid.o')    # advantages that follow a UE by its uid word (host helpers of csrc/dcomp_actor_impl.h only)
+    tasks.append((o_gae_uid, [hipcc] + CXXFLAGS + list(extra_flags) + ['-c', os.path.join(CSRC, 'dcomp_gae_uid.hip'), '-o', o_gae_uid]))
 
     def obj_stamp(t):
         """An object is rebuilt when its command line or one of ITS inputs changed: the per-station-count objects do not
@@ -140,11 +142,13 @@ def build(force=False, jobs=None, extra_flags=()):
         for f in _sources():
             if f.endswith(('dcomp_api.hip', 'dcomp_fragment.h')) and not t[0].endswith('dcomp_api.o'):
                 continue
-            if f.endswith(os.sep + 'dcomp.h') and not t[0].endswith(('dcomp_api.o', 'dcomp_actor.o', 'dcomp_learner.o')):
+            if f.endswith(os.sep + 'dcomp.h') and not t[0].endswith(('dcomp_api.o', 'dcomp_actor.o', 'dcomp_learner.o', 'dcomp_gae_uid.o')):
                 continue
             if f.endswith(('dcomp_actor.hip', 'dcomp_policy_set.h')) and not t[0].endswith('dcomp_actor.o'):
                 continue
-            if f.endswith(('dcomp_actor_impl.h', 'dcomp_fcnet_plan.h')) and not t[0].endswith(('dcomp_actor.o', 'dcomp_learner.o')):
+            if f.endswith(('dcomp_actor_impl.h', 'dcomp_fcnet_plan.h')) and not t[0].endswith(('dcomp_actor.o', 'dcomp_learner.o', 'dcomp_gae_uid.o')):
+                continue
+            if f.endswith(('dcomp_gae_uid.hip', 'dcomp_gae_uid.h')) and not t[0].endswith('dcomp_gae_uid.o'):
                 continue
             if f.endswith(('dcomp_learner.hip', 'dcomp_learner_tiles.inc', 'dcomp_learner_reduce.inc', 'dcomp_learner_adam.inc', 'dcomp_learner_accumulate.inc',
                            'dcomp_learner_norm.inc', 'dcomp_learner_finish.inc', 'dcomp_learner.h', 'dcomp_learner_indexed.h', 'dcomp_learner_group.h',
@@ -164,8 +168,11 @@ def build(force=False, jobs=None, extra_flags=()):
         with open(stamp, 'w') as f:
             f.write(want + '\n')
         return out
+    # compiled in reverse order (the link keeps the order above): a per-station-count object takes the longer the more stations it has --
+    # six minutes at 32, seconds at 1 -- and the generic kernel's four, so the long ones start first and the short ones fill the workers
+    # at the end, instead of the longest starting last and running alone
     with concurrent.futures.ThreadPoolExecutor(max_workers=jobs) as ex:
-        for out in ex.map(compile_one, tasks):
+        for out in ex.map(compile_one, tasks[::-1]):
             if out.strip():
                 sys.stderr.write(out)
     _run([hipcc, '--offload-arch=' + ARCH, '-shared', '-fPIC', '-o', LIB] + [t[0] for t in tasks] + ['-lpthread'])

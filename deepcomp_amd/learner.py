@@ -12,8 +12,9 @@ Supported: ``multi`` and ``central``, tanh and relu, every hidden width the acto
 (``vf_share_layers=False``, PPO's default); ``update`` takes the batch as observation rows or as the compact record
 (``collect(compact=True)``, multi), whose minibatches it picks through a row index (``grads_indexed``): from a compact batch no
 observation row is ever written.  The shared value function is refused (NotImplementedError), and so is the
-compact record by ``grads`` / ``evaluate``, which take a contiguous minibatch of rows; envs with UE arrival are refused by ``collect``
-already.  ``accumulate`` / ``accumulate_indexed`` / ``finish`` (include/dcomp_learner_accum.h) keep the unnormalised gradient as a running
+compact record by ``grads`` / ``evaluate``, which take a contiguous minibatch of rows.  Envs with UE arrival / departure: ``collect(..., by_ue=True)`` marks the rows that count
+(a slot is not one UE there) and ``update(batch, rows=sampler.live_rows(batch))`` trains on them; the learner itself needed no change.
+``accumulate`` / ``accumulate_indexed`` / ``finish`` (include/dcomp_learner_accum.h) keep the unnormalised gradient as a running
 sum in a buffer of the caller's: ``update(micro_rows=, grad_clip=)`` trains minibatches larger than the handle micro-batch by micro-batch and
 clips by the global norm, and deepcomp_amd.dp_learner sums the buffer across the ranks of a data-parallel learner.
 
@@ -767,7 +768,9 @@ class PPOLearner:
         the other rows are dropped before the split).  rows: an integer device tensor of distinct source rows of the flattened batch
         -- the learner then trains on exactly those rows: the advantages are standardised over them alone, the permutation runs over
         them only, and the result is that of update() on the batch gathered at rows, bit for bit (deepcomp_amd.policy_set hands each
-        per-UE policy the rows of its slots this way); not together with num_active.  rows are checked to be inside the batch and
+        per-UE policy the rows of its slots this way); not together with num_active.  A collect(..., by_ue=True) batch of an env with UE arrival / departure is trained this way:
+        rows=sampler.live_rows(batch), the rows whose UE acted and was still listed after the step -- every other row holds advantages
+        = value_targets = 0 and must stay out of the mean and the standardisation.  rows are checked to be inside the batch and
         distinct (one sort and one synchronisation; check_rows=False skips it for rows the caller built itself).  Returns the last iteration's mean statistics
         and the new kl_coeff.
 

@@ -8,6 +8,7 @@ this only shows where the time goes once the env runs at ~10^8-10^9 env-steps/s.
     python tools/closed_loop.py --collect 50 [--envs 65536] [--kind multi] [--compact] [--shared-value]
     python tools/closed_loop.py --train 3 [--train-steps 5] [--sgd-iters 2] [--minibatch ROWS] [--envs 65536] [--kind multi] [--compact]
                                 [--micro-rows ROWS] [--grad-clip NORM]
+    python tools/closed_loop.py --collect 50 | --train 3  --ue-arrival 10:4,30:-2,60:-3 [--envs 8192 --ues 12] [--compact]
     python tools/closed_loop.py --per-ue [--actor hip | --collect 50 | --train 3 [--grouped]] [--hidden 64] [--compact] [--envs 4096 --ues 128 --bs 32]
 
 --actor torch (default): the actor as torch ops (bf16 matmuls, Gumbel-max through torch.rand).  --actor hip: the same weights in
@@ -30,6 +31,12 @@ written anywhere in the loop; the unpack a rows-only learner would need first is
 --grad-clip NORM: update(grad_clip=NORM), RLlib's global-norm clip.  --micro-rows ROWS (a multiple of 2 048): the learner's handle is
 sized by ROWS instead of the minibatch and update(micro_rows=ROWS) accumulates a minibatch's gradient micro-batch by micro-batch; the
 time of one SGD iteration that way is printed and the comparisons that need a whole-minibatch handle are left out.
+
+--ue-arrival STEP:N,... (multi-agent, with --collect or --train): the env gets the reference's ue_arrival schedule -- N UEs arrive
+(N > 0) or depart (N < 0) in step STEP of every episode -- and has max_ues slots; collect runs with by_ue=True (advantages follow each UE
+through the slots by its uid word, include/dcomp_gae_uid.h) and update trains on rows=live_rows(batch).  --collect then times
+collect(by_ue=True) per step against the bare act + step_into loop on the same env (the torch GAE loop knows no shifting slots);
+--train prints the loop's statistics and the share of rows that count, and stops there.
 
 --per-ue (multi-agent): one policy network per UE (D3-CoMP) -- deepcomp_amd.policy_set.PerUEActor over U random-init members and, with
 --train, PerUELearner -- timed next to the shared-policy actor / learner on the same env, interleaved: the loop env step + actor
@@ -68,12 +75,16 @@ ap.add_argument('--micro-rows', type=int, default=0, help='--train: rows per mic
 ap.add_argument('--grad-clip', type=float, default=0.0, help='--train: global-norm gradient clip (RLlib grad_clip); 0: none')
 ap.add_argument('--hidden', type=int, default=256, help='hidden width of the fcnet (two layers)')
 ap.add_argument('--grouped', action='store_true', help='--per-ue --train: also time PerUELearner.update(grouped=True), interleaved with the sequential update and the shared learner')
+ap.add_argument('--ue-arrival', default='', metavar='STEP:N,...', help='--collect / --train, multi-agent: UEs arrive (N > 0) / depart (N < 0) in step STEP of every episode; collect(by_ue=True), update(rows=live_rows(batch))')
 ap.add_argument('--per-ue', action='store_true', help='one policy per UE (PerUEActor / PerUELearner) next to the shared policy; multi-agent')
 a = ap.parse_args()
 if a.per_ue and a.kind != 'multi':
     ap.error('--per-ue needs --kind multi')
 if a.collect or a.train or a.per_ue:
     a.actor = 'hip'
+arrival = {int(k): int(v) for k, v in (kv.split(':') for kv in a.ue_arrival.split(','))} if a.ue_arrival else None
+if arrival and (a.kind != 'multi' or a.per_ue or not (a.collect or a.train)):
+    ap.error('--ue-arrival needs --kind multi and --collect or --train, without --per-ue')
 if a.compact and (a.actor != 'hip' or a.kind != 'multi'):
     ap.error('--compact needs --actor hip and --kind multi')
 
@@ -82,7 +93,8 @@ E, U, B = a.envs, a.ues, a.bs
 scn = scenarios.grid_map(B, 'mixed').with_ues(num_slow=U)
 m, bs, ues = build_from_scenario(scn)
 multi = a.kind == 'multi'
-env = BatchedMobileEnv(m, bs, ues, a.kind, num_envs=E, seed=42, episode_length=100, rng='philox', rand_episodes=True, device=dev)
+env = BatchedMobileEnv(m, bs, ues, a.kind, num_envs=E, seed=42, episode_length=100, rng='philox', rand_episodes=True, device=dev, ue_arrival=arrival)
+U = env.U                                          # (UE slots: max_ues with --ue-arrival)
 dt = torch.bfloat16 if a.dtype == 'bf16' else torch.float32
 D = 4 * B + 1 if multi else U * (2 * B + 1)
 heads = 1 if multi else U
@@ -106,6 +118,8 @@ def collect_mode(T):
     gamma, lam = 0.99, 0.95
     host_v = FcnetActor.random_value_weights(a.kind, U, B, a.hidden, seed=0, shared=a.shared_value)
     hip.set_value(host_v, shared=a.shared_value)
+    if arrival:
+        return collect_dynamic(T, gamma, lam)
     trunk = host_v if not a.shared_value else host_w
     V1, V2 = (torch.from_numpy(trunk[n]).to(dev).to(dt) for n in ('w1', 'w2'))
     Vo = torch.from_numpy(host_v['wv']).to(dev).to(dt).view(-1, 1)
@@ -172,9 +186,56 @@ def collect_mode(T):
     env.check()
 
 
+def collect_dynamic(T, gamma, lam):
+    """--collect T --ue-arrival: collect(by_ue=True) per step against the bare act + step_into loop (rows) on the same env."""
+    from deepcomp_amd.sampler import buffers, collect
+    state = {'buf': None}
+    bare = buffers(env, hip, T, False)
+
+    def hip_batch():
+        state['buf'] = collect(env, hip, T, gamma, lam, compact=a.compact, out=state['buf'], by_ue=True)
+
+    def bare_loop():
+        obs, last = bare['obs'], bare['new_obs_last']
+        obs[0].copy_(env.obs)
+        for t in range(T):
+            hip.act(env, obs=obs[t], out=bare['actions'][t], logp=bare['action_logp'][t], vf=bare['vf_preds'][t])
+            nxt = obs[t + 1] if t + 1 < T else last
+            env.step_into(bare['actions'][t], nxt, bare['rewards'][t])
+            if env.time >= env.episode_length:
+                env.reset_into(nxt)
+        env.obs.copy_(last)
+
+    def timed(fn, n):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        for _ in range(n):
+            fn()
+        torch.cuda.synchronize()
+        return (time.perf_counter() - t0) / (n * T)
+
+    n = max(1, a.steps // T)
+    env.reset()
+    bare_loop()
+    hip_batch()
+    res = {'bare': [], 'hip': []}
+    for _ in range(3):
+        env.reset()
+        res['bare'].append(timed(bare_loop, n))
+        env.reset()
+        res['hip'].append(timed(hip_batch, n))
+    live = float(state['buf']['live'].float().mean())
+    print(f'{E} envs x {U} UE slots ({env.U0} initial, ue_arrival {arrival}) x {B} BS, actor 2x{a.hidden} tanh + value trunk, batches of T = {T}, {n} batches per timing')
+    for k, name in (('bare', 'act + step_into loop (rows, no advantages)'), ('hip', 'sampler.collect(by_ue=True)' + (' (compact record)' if a.compact else ''))):
+        ts = res[k]
+        print(f'{name:<46}: ' + ' / '.join(f'{t * 1e3:.3f}' for t in ts) + f' ms/step  (best {E / min(ts):.3e} env-steps/s)')
+    print(f'collect(by_ue=True) vs the bare loop: {min(res["hip"]) / min(res["bare"]):.2f} x the time; {live:.3f} of the rows of the last batch count')
+    env.check()
+
+
 def train_mode(iters):
     from deepcomp_amd.learner import PPOLearner, STATS
-    from deepcomp_amd.sampler import collect
+    from deepcomp_amd.sampler import collect, live_rows
     T = a.train_steps
     host_v = FcnetActor.random_value_weights(a.kind, U, B, a.hidden, seed=0)
     hip.set_value(host_v)
@@ -187,9 +248,14 @@ def train_mode(iters):
     print(f'{E} envs x {U} UE x {B} BS ({a.kind}), 2x{a.hidden} tanh + value trunk, batches of T = {T} ({T * rows} rows), {a.sgd_iters} SGD iterations, minibatches of {mb}'
           + (', compact record' if a.compact else ''))
     for it in range(iters):
-        buf = collect(env, hip, T, 0.99, 0.95, out=buf, dist_inputs=True, compact=a.compact)
-        st = learner.update(buf, num_sgd_iter=a.sgd_iters, minibatch_rows=mb, seed=it, **extra)
-        print(f'iter {it}: mean reward {float(buf["rewards"].mean()):+.4f}  ' + '  '.join(f'{n} {st[n]:+.5f}' for n in STATS) + f'  kl_coeff {st["kl_coeff"]:.3f}')
+        buf = collect(env, hip, T, 0.99, 0.95, out=buf, dist_inputs=True, compact=a.compact, by_ue=bool(arrival))
+        picked = live_rows(buf) if arrival else None
+        st = learner.update(buf, num_sgd_iter=a.sgd_iters, minibatch_rows=mb, seed=it, rows=picked, check_rows=False, **extra)
+        print(f'iter {it}: mean reward {float(buf["rewards"].mean()):+.4f}  ' + '  '.join(f'{n} {st[n]:+.5f}' for n in STATS) + f'  kl_coeff {st["kl_coeff"]:.3f}'
+              + (f'  rows that count {picked.numel()} of {T * rows}' if arrival else ''))
+    if arrival:                                                          # (the comparisons below take contiguous minibatches of a static env's batch)
+        env.check()
+        return
     if a.micro_rows:
         ts = []
         for _ in range(4):                                               # (the first: warm-up)
