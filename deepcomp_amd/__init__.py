@@ -15,7 +15,7 @@ def __getattr__(name):
     if name in ('BatchedMobileEnv', 'CentralRelNormEnv', 'MultiAgentMobileEnv', 'RelNormEnv', 'get_env_class'):
         from . import env
         return getattr(env, name)
-    if name in ('PerUEActor', 'PerUELearner', 'policy_set'):      # D3-CoMP: one policy network per UE
+    if name in ('PerUEActor', 'PerUELearner', 'PerIdActor', 'PerIdLearner', 'policy_set'):      # D3-CoMP: one policy network per UE (slot / UE id)
         import importlib
         mod = importlib.import_module('.policy_set', __name__)
         return mod if name == 'policy_set' else getattr(mod, name)

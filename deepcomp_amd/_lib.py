@@ -174,6 +174,10 @@ ACCUM_SUMS = 8
 GROUP_ACCUM_EXPORTS = ['dcomp_learner_group_accumulate', 'dcomp_learner_group_accum_finish']
 
 
+# include/dcomp_policy_set_uid.h: the set's launch keyed by UE id, for envs whose UE list changes during the episode
+SET_UID_EXPORTS = ['dcomp_policy_set_actions_uid']
+
+
 # include/dcomp_gae_uid.h: advantages that follow a UE through the slots of a dynamic env by its uid word
 GAE_UID_EXPORTS = ['dcomp_gae_uid']
 
@@ -314,6 +318,10 @@ def load():
     if hasattr(L, 'dcomp_gae_uid') or not os.environ.get('DCOMP_LIB'):
         L.dcomp_gae_uid.argtypes = [ctypes.POINTER(DcompGaeUidArgs), vp]
         for name in GAE_UID_EXPORTS:
+            getattr(L, name)
+    if hasattr(L, 'dcomp_policy_set_actions_uid') or not os.environ.get('DCOMP_LIB'):
+        L.dcomp_policy_set_actions_uid.argtypes = [vp, ctypes.POINTER(DcompActorRun), vp, vp, vp, vp, vp]
+        for name in SET_UID_EXPORTS:
             getattr(L, name)
     for name in EXPORTS:
         getattr(L, name)

@@ -10,7 +10,8 @@ the activations kept on chip, and out comes the uint8 action tensor ``env.step``
 
 ``multi``: one decision row per (env, UE slot), the weights shared across UEs (DD-CoMP), one categorical head of B + 1 actions.
 ``central``: one row per env, U heads (MultiDiscrete, central.py:28).  D3-CoMP's per-UE networks are a set over such actors, run in
-one launch: deepcomp_amd.policy_set.PerUEActor.  Training is deepcomp_amd.learner.PPOLearner, on this actor's handle.
+one launch: deepcomp_amd.policy_set.PerUEActor (a policy per UE slot) and PerIdActor (a policy per UE id, for envs whose UE list
+changes).  Training is deepcomp_amd.learner.PPOLearner, on this actor's handle.
 
 The value function of a PPO policy rides in the same launch once attached (``value_weights=`` / ``set_value``): RLlib's fcnet has it
 as a trunk of its own (``fc_value_1``, ``fc_value_2``, ``value_out``: PPO's default, vf_share_layers=False) or as ``value_out`` on
@@ -108,7 +109,8 @@ class _ActorLaunch:
         self._check(obs, dtype, E * per_env, 'obs')
         return E, (E * self.U if self.kind == _lib.MULTI else E)
 
-    def _launch(self, obs, compact, sample, seed, step, row_base, num_active, out, logits, logp, vf, policy):
+    def _checked_run(self, obs, compact, sample, seed, step, row_base, num_active, out, logits, logp, vf, policy):
+        """Every check of a launch's tensors, and its dcomp_actor_run: (envs, the action tensor, the run)."""
         E, rows = self._batch(obs, compact)
         if policy:
             if out is None:
@@ -126,6 +128,10 @@ class _ActorLaunch:
                                  self.U if num_active is None else int(num_active), 1 if sample else 0, int(step) & 0xFFFFFFFF,
                                  int(seed) & 0xFFFFFFFFFFFFFFFF, int(row_base),
                                  logits.data_ptr() if logits is not None else None, logp.data_ptr() if logp is not None else None)
+        return E, out, run
+
+    def _launch(self, obs, compact, sample, seed, step, row_base, num_active, out, logits, logp, vf, policy):
+        _, out, run = self._checked_run(obs, compact, sample, seed, step, row_base, num_active, out, logits, logp, vf, policy)
         with torch.cuda.device(self.device):
             if vf is None:
                 _lib.check(getattr(self._L, self._ACTIONS)(self._h, ctypes.byref(run), ctypes.c_void_p(obs.data_ptr()),

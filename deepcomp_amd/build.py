@@ -40,7 +40,8 @@ def _sources():
                                             'dcomp_learner_reduce.inc', 'dcomp_learner_adam.inc', 'dcomp_learner_accumulate.inc', 'dcomp_learner_norm.inc',
                                             'dcomp_learner_finish.inc', 'dcomp_gae_uid.hip')] + \
         [os.path.join(os.path.dirname(HERE), 'include', f) for f in ('dcomp.h', 'dcomp_types.h', 'dcomp_learner.h', 'dcomp_learner_indexed.h', 'dcomp_policy_set.h',
-                                                                            'dcomp_learner_group.h', 'dcomp_learner_accum.h', 'dcomp_learner_group_accum.h', 'dcomp_gae_uid.h')]
+                                                                            'dcomp_learner_group.h', 'dcomp_learner_accum.h', 'dcomp_learner_group_accum.h', 'dcomp_gae_uid.h',
+                                                                            'dcomp_policy_set_uid.h')]
 
 
 def _dev_flags():
@@ -144,7 +145,7 @@ def build(force=False, jobs=None, extra_flags=()):
                 continue
             if f.endswith(os.sep + 'dcomp.h') and not t[0].endswith(('dcomp_api.o', 'dcomp_actor.o', 'dcomp_learner.o', 'dcomp_gae_uid.o')):
                 continue
-            if f.endswith(('dcomp_actor.hip', 'dcomp_policy_set.h')) and not t[0].endswith('dcomp_actor.o'):
+            if f.endswith(('dcomp_actor.hip', 'dcomp_policy_set.h', 'dcomp_policy_set_uid.h')) and not t[0].endswith('dcomp_actor.o'):
                 continue
             if f.endswith(('dcomp_actor_impl.h', 'dcomp_fcnet_plan.h')) and not t[0].endswith(('dcomp_actor.o', 'dcomp_learner.o', 'dcomp_gae_uid.o')):
                 continue

@@ -34,7 +34,9 @@
 //
 // One policy per UE slot (include/dcomp_policy_set.h: D3-CoMP) is the same kernel with another tile map, instantiations of their own
 // (PER, see actor_kernel): a tile is 32 envs of one slot, its trunks come from the set's device table of pointers into the members'
-// images.  The set's entry points follow dcomp_actor_actions_v and share actor_launch.
+// images.  The set's entry points follow dcomp_actor_actions_v and share actor_launch.  One policy per UE ID
+// (include/dcomp_policy_set_uid.h), for envs whose UE list shifts, is a third tile map: a tile is 32 envs of one policy, and its
+// prologue finds the slot of the policy's UE in each env from the env's uid words.
 //
 // This file has the actor's own: the staging of observation rows and compact records (the fetch it hands to layer1), the ring that
 // streams the weights of layers 2 and 3, the row walk with its draws, and the entry points.  The pieces the learner's kernel runs
@@ -50,6 +52,7 @@
 #define DCOMP_BUILDING_LIBRARY 1
 #include "../../include/dcomp.h"
 #include "../../include/dcomp_policy_set.h"
+#include "../../include/dcomp_policy_set_uid.h"
 #include "dcomp_actor_impl.h"       // the forward-pass helpers, the fragment layout, Net and struct dcomp_actor, fail / HIP_TRY: shared with dcomp_learner.hip
 
 namespace dactor {
@@ -68,7 +71,15 @@ struct Params {
     // PER (a policy set, include/dcomp_policy_set.h) only, behind everything the other instantiations read:
     const Trunk *table;               // [U][2]: slot u's policy trunk, value trunk -- pointers into its member's images
     int32_t envs;                     // E; tiles = ceil(E / 32) * U
+    // BY_ID (a set keyed by UE id, include/dcomp_policy_set_uid.h) only: table is [P][2] in member order, tiles = ceil(E / 32) * P
+    int32_t members;                  // P
+    const uint16_t *uid;              // [E][U]: the env's uid words, the layout obs stands in
 };
+
+// the tile maps of actor_kernel (its PER parameter): one policy for every row; one per UE slot (include/dcomp_policy_set.h); one per UE id
+// (include/dcomp_policy_set_uid.h)
+constexpr int SHARED = 0, BY_SLOT = 1, BY_ID = 2;
+constexpr uint32_t ABSENT = 0xFFFFFFFFu;      // BY_ID: the entry of a tile row whose env does not list the tile's UE
 
 // entry i (wave-uniform) of a policy set's table.  The table is written once, before any launch: read through the constant address
 // space the twelve pointers are scalar loads into SGPRs, like the kernel arguments select_trunk picks from.
@@ -97,13 +108,20 @@ __device__ __forceinline__ void philox4x32_10(uint32_t c0, uint32_t c1, uint32_t
 
 
 // MT = hidden width / 32 (padded: 1, 2, 4 or 8); VF: 0 = no value, 1 = a value trunk of its own, 2 = value_out on the actor's h2
-// PER: one policy per UE slot.  A tile is 32 ENVS of one slot, tile id = env group * U + slot; lane r's decision row is
+// PER = BY_SLOT: one policy per UE slot.  A tile is 32 ENVS of one slot, tile id = env group * U + slot; lane r's decision row is
 // (32 g + r) U + slot, the address the shared launch has it at, and both sweeps' trunks come from the slot's table entry.
 // (Env-major: the U tiles of an env group run together, so their strided row reads and 1- and 4-byte stores meet in the same cache
 // lines while those are in L2.  Slot-major keeps one or two members' weights in flight instead of U and measured 1-14 % SLOWER,
 // profiles/r12_policy_set.txt: the weights are at most 340 KB per member and stay cache-resident either way.)  A row is one column of the B operand and depends on
 // no tile-mate, so its results are those of the shared launch with the same weights, bit for bit.
-template <int MT, bool RELU, int VF, bool PER = false>
+// PER = BY_ID: one policy per UE ID, on envs whose UE list shifts.  A tile is 32 envs of one POLICY, tile id = env group * P + policy
+// (env-major, as above).  Its prologue finds the slot at which the policy's UE stands in each of its envs: the 64 lanes read the
+// envs' uid rows (32 U contiguous 16-bit words, L2-resident across the P tiles of the group), the lane that meets id == policy + 1
+// leaves the slot in ri[row][3], preset to ABSENT.  Lane r's decision row is then (32 g + r) U + that slot -- or none: such a row is
+// computed on zeros and nothing is stored for it, like the rows beyond the batch; a tile without any returns after the scan.  The
+// tiles of policy 0 write, while they scan, the zeros of the slots no tile owns: dead ones and ids beyond P.  Every index comes
+// from a position inside the env's own row, whatever the words hold.
+template <int MT, bool RELU, int VF, int PER = SHARED>
 __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(2, 2))) void actor_kernel(const Params p)
 {
     extern __shared__ uint4 lds4[];
@@ -123,22 +141,62 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(2, 2))) v
     const float *rowsf = reinterpret_cast<const float *>(p.obs);
 
     for (int64_t tile = (int64_t)blockIdx.x * WAVES + wave; tile < p.tiles; tile += (int64_t)gridDim.x * WAVES) {
-        int pslot = 0, env0 = 0;                                                     // PER: the tile's UE slot and first env, wave-uniform
-        if constexpr (PER) {
+        int pslot = 0, env0 = 0;                                                     // PER: the tile's UE slot (BY_ID: policy) and first env, wave-uniform
+        if constexpr (PER == BY_SLOT) {
             const uint32_t id = __builtin_amdgcn_readfirstlane((uint32_t)tile);      // (tiles <= rows / 32 + U < 2^32)
             pslot = (int)(id % (uint32_t)U);
             env0 = TILE * (int)(id / (uint32_t)U);
         }
+        if constexpr (PER == BY_ID) {                                                // (P may exceed U: the tile count need not fit 32 bits)
+            const int64_t g = tile / p.members;
+            pslot = __builtin_amdgcn_readfirstlane((int)(tile - g * p.members));
+            env0 = __builtin_amdgcn_readfirstlane(TILE * (int)g);
+        }
         const int64_t row0 = tile * TILE;
-        auto row_of = [&](int rr) -> int64_t {                                       // the decision row of the tile's row rr
-            if constexpr (PER) return (int64_t)(env0 + rr) * U + pslot;
+        const int nrow = PER ? (p.envs - env0 < TILE ? p.envs - env0 : TILE) : (int)(p.rows - row0 < TILE ? p.rows - row0 : TILE);
+        if constexpr (PER == BY_ID) {
+            if (lane < TILE) ri[lane * 4 + 3] = ABSENT;
+            wave_fence();
+            const uint16_t *words = p.uid + (size_t)env0 * U;
+            const int nw = nrow * U;
+            bool found = false;
+            for (int i = lane; i < nw; i += 64) {
+                const uint32_t id = words[i] & 0x7FFFu;
+                const int rr = (int)((uint32_t)i / (uint32_t)U), s = i - rr * U;
+                if (id == (uint32_t)pslot + 1u) { ri[rr * 4 + 3] = (uint32_t)s; found = true; }
+                if (pslot == 0 && id - 1u >= (uint32_t)p.members) {                  // dead, or a UE beyond the set: no tile owns the row
+                    const size_t at = (size_t)(env0 + rr) * U + s;
+                    if (p.action) p.action[at] = 0;
+                    if (p.logp) p.logp[at] = 0.f;
+                    if (p.logits)
+                        for (int c = 0; c < n.N3; c++) p.logits[at * n.N3 + c] = 0.f;
+                    if (VF != 0) p.vf[at] = 0.f;
+                }
+            }
+            wave_fence();
+            if (!__any(found)) continue;                                             // no env of the tile lists the policy's UE
+        }
+        auto present = [&](int rr) -> bool {                                         // the tile's row rr is a decision row
+            if constexpr (PER == BY_ID) return rr < nrow && ri[rr * 4 + 3] != ABSENT;
+            else return rr < nrow;
+        };
+        auto row_of = [&](int rr) -> int64_t {                                       // the decision row of the tile's row rr (BY_ID: where present)
+            if constexpr (PER == BY_ID) return (int64_t)(env0 + rr) * U + (int)ri[rr * 4 + 3];
+            else if constexpr (PER == BY_SLOT) return (int64_t)(env0 + rr) * U + pslot;
             else return row0 + rr;
         };
-        const int nrow = PER ? (p.envs - env0 < TILE ? p.envs - env0 : TILE) : (int)(p.rows - row0 < TILE ? p.rows - row0 : TILE);
-        const int64_t myrow = row_of(r);                                             // the decision row on this lane
-        const bool have = r < nrow;
-        int slot = PER ? pslot : 0;                                                  // multi-agent: the row's UE slot
-        if (!PER && n.multi && have) slot = (int)(myrow % U);
+        int64_t myrow;                                                               // the decision row on this lane
+        bool have;
+        if constexpr (PER == BY_ID) {
+            have = present(r);
+            myrow = have ? row_of(r) : 0;
+        } else {
+            myrow = row_of(r);
+            have = r < nrow;
+        }
+        int slot = PER == BY_SLOT ? pslot : 0;                                       // multi-agent: the row's UE slot
+        if (PER == SHARED && n.multi && have) slot = (int)(myrow % U);
+        if (PER == BY_ID && have) slot = (int)ri[r * 4 + 3];
         if (p.compact) {
             if (lane < TILE) {
                 uint32_t lo = 0, hi = 0, listed = 0;
@@ -147,7 +205,8 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(2, 2))) v
                     const uint64_t off = (uint64_t)env * (uint64_t)env_words(U, B) + (uint64_t)slot * CW;
                     lo = (uint32_t)off; hi = (uint32_t)(off >> 32); listed = compact_listed(cwords, off, B);
                 }
-                ri[lane * 4 + 0] = lo; ri[lane * 4 + 1] = hi; ri[lane * 4 + 2] = listed; ri[lane * 4 + 3] = (uint32_t)slot;
+                ri[lane * 4 + 0] = lo; ri[lane * 4 + 1] = hi; ri[lane * 4 + 2] = listed;
+                ri[lane * 4 + 3] = PER == BY_ID && !have ? ABSENT : (uint32_t)slot;
             }
             wave_fence();
         }
@@ -166,7 +225,7 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(2, 2))) v
         layer1<MT>(acc, t.w1, n.K1p, xs, XS, lane, lane16, staged,
                    [&](int rr, int k) {
                        float v = 0.f;
-                       if (rr < nrow && k < K1) {
+                       if (present(rr) && k < K1) {
                            if (!p.compact) {
                                v = rowsf[(size_t)row_of(rr) * K1 + k];
                            } else {
@@ -267,7 +326,7 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(2, 2))) v
             if (p.logits) {
                 for (int i = lane; i < TILE * 32; i += 64) {
                     const int rr = i >> 5, c = i & 31;
-                    if (rr < nrow && c < ncol) p.logits[(size_t)row_of(rr) * N3 + 32 * nt + c] = lt[rr * LT + c];
+                    if (present(rr) && c < ncol) p.logits[(size_t)row_of(rr) * N3 + 32 * nt + c] = lt[rr * LT + c];
                 }
             }
             if (VF != 0) {
@@ -281,7 +340,7 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(2, 2))) v
 }
 
 typedef void (*kernel_fn)(const Params);
-template <int VF, bool PER = false> static kernel_fn pick_width(int mt, bool relu)
+template <int VF, int PER = SHARED> static kernel_fn pick_width(int mt, bool relu)
 {
     return pick_shape(mt, relu, [](auto s) -> kernel_fn { return actor_kernel<decltype(s)::MT, decltype(s)::RELU, VF, PER>; });
 }
@@ -291,7 +350,11 @@ static kernel_fn pick(int mt, bool relu, int vf)
 }
 static kernel_fn pick_set(int mt, bool relu, int vf)             // a policy set: no value, or trunks of their own
 {
-    return vf == 0 ? pick_width<0, true>(mt, relu) : pick_width<1, true>(mt, relu);
+    return vf == 0 ? pick_width<0, BY_SLOT>(mt, relu) : pick_width<1, BY_SLOT>(mt, relu);
+}
+static kernel_fn pick_set_uid(int mt, bool relu, int vf)         // a policy set keyed by UE id
+{
+    return vf == 0 ? pick_width<0, BY_ID>(mt, relu) : pick_width<1, BY_ID>(mt, relu);
 }
 
 // RLlib's compute_advantages(use_gae=True) as pinned f32 operations (include/dcomp.h: dcomp_gae): one lane per column walks t
@@ -426,13 +489,15 @@ extern "C" int dcomp_actor_destroy(dcomp_actor *a)
 struct dcomp_policy_set {
     std::vector<dcomp_actor *> members;
     dactor::Trunk *table;             // device [U][2]
-    int32_t value;                    // the members' value form when the table was written: 0 none, 1 a trunk of its own
+    dactor::Trunk *table_id;          // device [P][2], member order (include/dcomp_policy_set_uid.h): behind table, in its allocation
+    int32_t value;                  // the members' value form when the table was written: 0 none, 1 a trunk of its own
 };
 
 // dcomp_actor_actions (vf_call = false) and dcomp_actor_actions_v: every check on the host first, then ONE launch.
-// set: the same for a policy set, a = its first member (the shapes are equal across members)
+// set: the same for a policy set, a = its first member (the shapes are equal across members).  by_id: the set's launch keyed by UE
+// id (include/dcomp_policy_set_uid.h), one entry point for both forms: vf_call = vf != NULL, and its three checks of its own last
 static int actor_launch(const char *fn, bool vf_call, dcomp_actor *a, const dcomp_actor_run *r, const void *obs, uint8_t *action, float *vf, void *stream,
-                        const dcomp_policy_set *set = nullptr)
+                        const dcomp_policy_set *set = nullptr, bool by_id = false, const uint16_t *uid = nullptr)
 {
     using namespace dactor;
     if (!a || !r) return fail(DCOMP_EINVAL, "%s: handle and run must not be NULL", fn);
@@ -440,7 +505,11 @@ static int actor_launch(const char *fn, bool vf_call, dcomp_actor *a, const dcom
     if (r->obs_format != DCOMP_ACTOR_ROWS && r->obs_format != DCOMP_ACTOR_COMPACT) return fail(DCOMP_EINVAL, "%s: unknown obs_format %d", fn, r->obs_format);
     if (r->obs_format == DCOMP_ACTOR_COMPACT && !a->net.multi)
         return fail(DCOMP_EUNSUPPORTED, "%s: the compact record exists for multi-agent observations only", fn);
-    if (!vf_call) {
+    if (by_id) {
+        if (!obs) return fail(DCOMP_EINVAL, "%s: obs must not be NULL", fn);
+        if (!action && (r->logits || r->logp)) return fail(DCOMP_EINVAL, "%s: action == NULL is the value-only call: run.logits and run.logp must be NULL", fn);
+        if (vf && !set->value) return fail(DCOMP_EINVAL, "%s: the handle has no value function (dcomp_actor_set_value)", fn);
+    } else if (!vf_call) {
         if (!obs || !action) return fail(DCOMP_EINVAL, "%s: obs and action must not be NULL", fn);
     } else {
         if (!obs) return fail(DCOMP_EINVAL, "%s: obs must not be NULL", fn);
@@ -454,6 +523,12 @@ static int actor_launch(const char *fn, bool vf_call, dcomp_actor *a, const dcom
     if (r->row_base < 0 || r->row_base + rows > 0x100000000ll)
         return fail(DCOMP_EINVAL, "%s: decision rows %lld ... %lld do not fit the 32-bit draw counter word", fn, (long long)r->row_base,
                      (long long)(r->row_base + rows - 1));
+    if (by_id) {
+        if (!uid) return fail(DCOMP_EINVAL, "%s: uid must not be NULL", fn);
+        if (r->num_active != a->net.U)
+            return fail(DCOMP_EINVAL, "%s: num_active %d is not num_ue %d: the uid words say which slots are listed", fn, r->num_active, a->net.U);
+        if (!action && !vf) return fail(DCOMP_EINVAL, "%s: action and vf are both NULL: nothing to compute", fn);
+    }
     const int mode = vf_call ? (set ? set->value : a->value) : 0;      // (a set: the form its table was written for, 0 or 1)
     Params p;
     memset(&p, 0, sizeof(p));
@@ -474,8 +549,12 @@ static int actor_launch(const char *fn, bool vf_call, dcomp_actor *a, const dcom
         p.table = set->table; p.envs = r->num_envs;
         p.tiles = (int64_t)a->net.U * tiles_of(r->num_envs);
     }
+    if (by_id) {                                             // tiles of 32 envs per member, the member's trunks, the slot from the uid words
+        p.table = set->table_id; p.members = (int32_t)set->members.size(); p.uid = uid;
+        p.tiles = (int64_t)p.members * tiles_of(r->num_envs);
+    }
     const int grid = launch_blocks(p.tiles, a->max_blocks);
-    hipLaunchKernelGGL(set ? pick_set(pl.mt, a->relu != 0, mode) : pick(pl.mt, a->relu != 0, mode), dim3(grid), dim3(BLOCK), (size_t)pl.lds_per_wave * WAVES, static_cast<hipStream_t>(stream), p);
+    hipLaunchKernelGGL(by_id ? pick_set_uid(pl.mt, a->relu != 0, mode) : set ? pick_set(pl.mt, a->relu != 0, mode) : pick(pl.mt, a->relu != 0, mode), dim3(grid), dim3(BLOCK), (size_t)pl.lds_per_wave * WAVES, static_cast<hipStream_t>(stream), p);
     HIP_TRY(hipGetLastError());
     return DCOMP_OK;
 }
@@ -525,10 +604,13 @@ extern "C" int dcomp_policy_set_create(const dcomp_policy_set_cfg *cfg, dcomp_po
     if (int rc = check_device("dcomp_policy_set_create", "the members live", f->device)) return rc;
     // (without a value function the second entries are NULL; no launch reads them: set->value keeps the value sweep off, and a member
     // that gets a value function later makes every call on the set fail on the host, set_first)
-    std::vector<Trunk> host((size_t)2 * U);
+    std::vector<Trunk> host((size_t)2 * U + (size_t)2 * P);
     for (int u = 0; u < U; u++) {
         const dcomp_actor *m = cfg->members[cfg->slot_policy ? cfg->slot_policy[u] : u % P];
         host[2 * u] = m->net.pi; host[2 * u + 1] = m->net.vf;
+    }
+    for (int i = 0; i < P; i++) {                            // the table of the launch keyed by UE id: member i is the policy of id i + 1
+        host[2 * (U + i)] = cfg->members[i]->net.pi; host[2 * (U + i) + 1] = cfg->members[i]->net.vf;
     }
     dcomp_policy_set *s = new dcomp_policy_set();
     s->members.assign(cfg->members, cfg->members + P);
@@ -543,6 +625,7 @@ extern "C" int dcomp_policy_set_create(const dcomp_policy_set_cfg *cfg, dcomp_po
         delete s;
         return fail(DCOMP_EHIP, "dcomp_policy_set_create: %s", hipGetErrorString(e));
     }
+    s->table_id = s->table + (size_t)2 * U;
     *out = s;
     return DCOMP_OK;
 }
@@ -582,6 +665,14 @@ extern "C" int dcomp_policy_set_actions_v(dcomp_policy_set *s, const dcomp_actor
     dcomp_actor *a = nullptr;
     const int rc = set_first("dcomp_policy_set_actions_v", s, r, &a);
     return rc != DCOMP_OK ? rc : actor_launch("dcomp_policy_set_actions_v", true, a, r, obs, action, vf, stream, s);
+}
+
+extern "C" int dcomp_policy_set_actions_uid(dcomp_policy_set *s, const dcomp_actor_run *r, const void *obs, const uint16_t *uid, uint8_t *action, float *vf,
+                                            void *stream)
+{
+    dcomp_actor *a = nullptr;
+    const int rc = set_first("dcomp_policy_set_actions_uid", s, r, &a);
+    return rc != DCOMP_OK ? rc : actor_launch("dcomp_policy_set_actions_uid", vf != nullptr, a, r, obs, action, vf, stream, s, true, uid);
 }
 
 extern "C" int dcomp_actor_set_value(dcomp_actor *a, const dcomp_actor_value_cfg *cfg)

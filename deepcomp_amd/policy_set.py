@@ -24,13 +24,25 @@ Members are ``multi`` actors of one shape (UE slots, stations, hidden width, act
 all with a value trunk of their own; attach value functions BEFORE building the set -- its table holds the trunks the members have then,
 and once a member gets one afterwards every call on the set raises ValueError (build a new set).  Central members (one network by construction) and a shared value function are refused
 (NotImplementedError), and so is ``act`` on an env with UE arrival / departure: slots shift on departure, a slot is not one UE there.
+
+Envs with UE arrival / departure take the second kind of set, keyed by UE ID (include/dcomp_policy_set_uid.h; the reference keys its
+policy map by ue.id and builds a policy for every UE the episode will ever see, env.max_id here): ``PerIdActor(members)`` runs the
+row at (env, slot) through member id - 1, the id read from the env's uid word of that slot, and ``PerIdLearner`` trains member p on the
+counted rows of the UE with id p + 1 (``policy_rows_by_id``):
+
+    actor = PerIdActor([FcnetActor('multi', env.U, B, weights[p], value_weights=value_weights[p]) for p in range(env.max_id)])
+    learner = PerIdLearner(actor, lr=5e-5, max_rows=rows_per_policy_minibatch)
+    batch = collect(env, actor, num_steps=50, gamma=0.99, lam=0.95, dist_inputs=True, by_ue=True)
+    stats = learner.update(batch, num_sgd_iter=30, minibatch_rows=rows_per_policy_minibatch)
 """
 import ctypes
 
+import numpy as np
 import torch
 
 from . import _lib
 from .actor import FcnetActor, _ActorLaunch
+from .tape import uid_fields
 from .learner import INPUT, INPUTS, SUM, PPOLearner, close_out, field_pointers, fill, flatten_batch, minibatch_plan, sgd_epochs, standardize
 
 
@@ -76,12 +88,10 @@ def group_plan(n_of, minibatch_rows, max_rows_of, micro_rows=None, grad_clip=Non
     return accumulated, taken, rounds
 
 
-class PerUEActor(_ActorLaunch):
-    """A set of FcnetActors, one per UE slot (or per group of slots), running as one HIP kernel launch.  ``actions``, ``value`` and
-    ``act`` are FcnetActor's: same arguments, same checks, same [E, U] outputs."""
-    _ACTIONS, _ACTIONS_V = 'dcomp_policy_set_actions', 'dcomp_policy_set_actions_v'
+class _PolicySet(_ActorLaunch):
+    """What the two kinds of set share: the dcomp_policy_set handle over the members, and the members' weights."""
 
-    def __init__(self, actors, slot_policy=None):
+    def _create(self, actors, slot_policy):
         self._h = None
         actors = list(actors)
         if not actors or not all(isinstance(a, FcnetActor) for a in actors):
@@ -128,15 +138,27 @@ class PerUEActor(_ActorLaunch):
         set_value on a member since does not reach the set's table: every launch is then refused)."""
         return [m.value_weights for m in self.members] if self._has_value else None
 
+    @staticmethod
+    def _random_members(num_ue, num_bs, hidden, activation, seed, bias_std, device, num_policies, value):
+        return [FcnetActor('multi', num_ue, num_bs, FcnetActor.random_weights('multi', num_ue, num_bs, hidden, seed + p, bias_std), activation, device,
+                           value_weights=FcnetActor.random_value_weights('multi', num_ue, num_bs, hidden, seed + p, bias_std) if value else None)
+                for p in range(num_policies)]
+
+
+class PerUEActor(_PolicySet):
+    """A set of FcnetActors, one per UE slot (or per group of slots), running as one HIP kernel launch.  ``actions``, ``value`` and
+    ``act`` are FcnetActor's: same arguments, same checks, same [E, U] outputs."""
+    _ACTIONS, _ACTIONS_V = 'dcomp_policy_set_actions', 'dcomp_policy_set_actions_v'
+
+    def __init__(self, actors, slot_policy=None):
+        self._create(actors, slot_policy)
+
     @classmethod
     def random(cls, num_ue, num_bs, hidden=256, activation='tanh', seed=0, bias_std=0.0, device='cuda', num_policies=None, slot_policy=None,
                value=True):
         """Random-init members (policy p from seed + p, as FcnetActor.random_weights / random_value_weights) for tools and tests."""
         P = int(num_ue) if num_policies is None else int(num_policies)
-        members = [FcnetActor('multi', num_ue, num_bs, FcnetActor.random_weights('multi', num_ue, num_bs, hidden, seed + p, bias_std), activation, device,
-                              value_weights=FcnetActor.random_value_weights('multi', num_ue, num_bs, hidden, seed + p, bias_std) if value else None)
-                   for p in range(P)]
-        return cls(members, slot_policy)
+        return cls(cls._random_members(num_ue, num_bs, hidden, activation, seed, bias_std, device, P, value), slot_policy)
 
     def member_of(self, slot):
         return self.members[self.slot_policy[int(slot)]]
@@ -155,6 +177,111 @@ class PerUEActor(_ActorLaunch):
         return super().act(env, sample=sample, obs=obs, compact=compact, out=out, logp=logp, vf=vf, logits=logits)
 
 
+_STATIC_WORDS = {}
+
+
+def static_uid_words(num_envs, num_ue, device):
+    """The uid words of a static env, where slot s is UE s + 1 throughout: int16 [num_envs, num_ue], held once per device and width (a
+    prefix of the largest batch asked for so far)."""
+    key = (torch.device(device), int(num_ue))
+    held = _STATIC_WORDS.get(key)
+    if held is None or held.shape[0] < num_envs:
+        held = _STATIC_WORDS[key] = torch.arange(1, int(num_ue) + 1, dtype=torch.int16, device=device).repeat(int(num_envs), 1)
+    return held[:int(num_envs)]
+
+
+class PerIdActor(_PolicySet):
+    """A set of FcnetActors keyed by UE ID, running as one HIP kernel launch (include/dcomp_policy_set_uid.h): member p is the policy
+    of the UE with id p + 1, wherever that UE stands in an env's list.  The launch for envs with UE arrival / departure; on a static
+    env, where slot s is UE s + 1, it is PerUEActor with the identity map, bit for bit.  ``actions`` and ``value`` take the uid words
+    the observations stand in (``uid=``, int16 [E, U]: env.uid); ``act`` takes them from the env.  Slots whose word is 0 get action 0
+    and 0.0 in every other output.  Not a PerUEActor: what refuses a slot-keyed set keeps refusing exactly that."""
+
+    def __init__(self, actors):
+        self._create(actors, None)                               # (the handle's slot table plays no part in the launch by id)
+
+    @classmethod
+    def random(cls, num_ue, num_bs, num_policies, hidden=256, activation='tanh', seed=0, bias_std=0.0, device='cuda', value=True):
+        """Random-init members (policy p from seed + p, as PerUEActor.random) for tools and tests; num_policies: env.max_id."""
+        return cls(cls._random_members(num_ue, num_bs, hidden, activation, seed, bias_std, device, int(num_policies), value))
+
+    def member_of_id(self, ue_id):
+        """The member that decides for the UE with this 1-based id (the id field of its uid word)."""
+        if not 1 <= int(ue_id) <= self.num_policies:
+            raise ValueError(f"UE id {ue_id} outside 1 ... {self.num_policies}")
+        return self.members[int(ue_id) - 1]
+
+    def check_env(self, env):
+        """The set has a policy for every UE the env will ever list (the device's rule for ids beyond the set, zeros, is for C callers)."""
+        if env.kind != self.kind or env.U != self.U or env.B != self.B:
+            raise ValueError("the env's kind / UE slots / stations differ from the actor's")
+        if env.max_id > self.num_policies:
+            raise ValueError(f"the env lists UE ids up to {env.max_id} (env.max_id), the set has {self.num_policies} policies: build one member per id")
+
+    def uid_of(self, env):
+        """The env's uid words as the launch takes them: env.uid on a dynamic env, the constant words 1 ... U on a static one."""
+        return env.uid.view(env.E, env.U) if env.uid is not None else static_uid_words(env.E, env.U, self.device)
+
+    def actions(self, obs, *, uid, compact=False, sample=True, seed=0, step=0, row_base=0, out=None, logits=None, logp=None, vf=None):
+        """FcnetActor.actions with the row at (env, slot) going through member (uid[env, slot]'s id) - 1; uid: int16 [E, U]."""
+        return self._launch_uid(obs, uid, compact, sample, seed, step, row_base, out, logits, logp, vf, True)
+
+    def value(self, obs, *, uid, compact=False, out=None):
+        """FcnetActor.value, every row through the value trunk of its UE's member."""
+        E, rows = self._batch(obs, compact)
+        if out is None:
+            out = torch.empty(rows, dtype=torch.float32, device=self.device)
+        self._launch_uid(obs, uid, compact, False, 0, 0, 0, None, None, None, out, False)
+        return out
+
+    def _launch_uid(self, obs, uid, compact, sample, seed, step, row_base, out, logits, logp, vf, policy):
+        E, out, run = self._checked_run(obs, compact, sample, seed, step, row_base, None, out, logits, logp, vf, policy)
+        self._check(uid, torch.int16, E * self.U, 'uid')
+        with torch.cuda.device(self.device):
+            _lib.check(self._L.dcomp_policy_set_actions_uid(self._h, ctypes.byref(run), ctypes.c_void_p(obs.data_ptr()), ctypes.c_void_p(uid.data_ptr()),
+                                                            ctypes.c_void_p(out.data_ptr()) if policy else None,
+                                                            ctypes.c_void_p(vf.data_ptr()) if vf is not None else None, self._stream()))
+        return out
+
+    def act(self, env, sample=True, obs=None, compact=False, out=None, logp=None, vf=None, logits=None):
+        """FcnetActor.act with every UE's own policy, the UE known by the id in env.uid: draws keyed as there."""
+        self.check_env(env)
+        return self.actions(env.obs if obs is None else obs, uid=self.uid_of(env), compact=compact, sample=sample, seed=env.seed_value,
+                            step=env.time + max(env.episode, 0) * env.episode_length, row_base=env.env_id_base * self.U, out=out, logp=logp, vf=vf,
+                            logits=logits)
+
+
+def policy_rows_by_id_reference(batch, num_policies):
+    """The specification of policy_rows_by_id, in numpy: per policy p the ascending int64 array of the source rows t E U + e U + s of a
+    collect(..., by_ue=True) batch with live = 1 whose uid word holds id p + 1 (bit 15, "arrived during the episode", is not part of
+    the id).  batch: anything with 'uid' and 'live' of T E U elements each."""
+    ids, _ = uid_fields(np.asarray(torch.as_tensor(batch['uid']).cpu()).reshape(-1))
+    live = np.asarray(torch.as_tensor(batch['live']).cpu()).reshape(-1)
+    if ids.size != live.size:
+        raise ValueError(f"uid has {ids.size} words, live {live.size} rows")
+    rows = [[] for _ in range(int(num_policies))]
+    for s in range(live.size):
+        if live[s] and 1 <= ids[s] <= int(num_policies):
+            rows[int(ids[s]) - 1].append(s)
+    return [np.asarray(r, dtype=np.int64) for r in rows]
+
+
+def policy_rows_by_id(batch, num_policies):
+    """The row split of a collect(..., by_ue=True) batch by UE id: per policy p the ascending int64 tensor, on the batch's device, of
+    the source rows with live = 1 whose uid word holds id p + 1.  The tensors are disjoint and together are live_rows(batch) (every
+    id of a counted row being one of the set's: collect() holds env.max_id to that).  One stable sort by policy key and ONE host read,
+    of the P counts."""
+    P = int(num_policies)
+    ids, _ = uid_fields(batch['uid'].reshape(-1))
+    live = batch['live'].reshape(-1)
+    if ids.numel() != live.numel():
+        raise ValueError(f"uid has {ids.numel()} words, live {live.numel()} rows")
+    key = torch.where((live != 0) & (ids >= 1) & (ids <= P), ids - 1, torch.full_like(ids, P))      # P: a row of no policy
+    order = torch.sort(key, stable=True).indices
+    counts = torch.bincount(key, minlength=P + 1)[:P].tolist()
+    return list(torch.split(order[:sum(counts)], counts))
+
+
 class PerUELearner:
     """PPO for a PerUEActor: one PPOLearner per member, each with its own Adam state and its own kl_coeff -- RLlib likewise gives each
     policy its own batch, its own advantage standardisation and its own KL coefficient.  Every update lands in the member's handle,
@@ -168,9 +295,11 @@ class PerUELearner:
     policy, on both paths: grouped, the policies' accumulators are one [P, flat] and one [P, 8] tensor and a micro-batch round is one
     launch round (include/dcomp_learner_group_accum.h); with micro_rows the workspaces are sized by the micro-batch, P times over."""
 
+    _ACTOR = PerUEActor
+
     def __init__(self, actor, **ppo_kwargs):
-        if not isinstance(actor, PerUEActor):
-            raise ValueError("actor must be a PerUEActor")
+        if not isinstance(actor, self._ACTOR):
+            raise ValueError(f"actor must be a {self._ACTOR.__name__}")
         self.actor, self.device = actor, actor.device
         if len({id(m) for m in actor.members}) != len(actor.members):
             raise ValueError("the same FcnetActor is a member twice: two learners would train one handle with two Adam states -- list it once and "
@@ -195,6 +324,10 @@ class PerUELearner:
             self._split = {num_rows: policy_rows(num_rows, a.U, a.slot_policy, a.num_policies, self.device)}
         return self._split[num_rows]
 
+    def _batch_rows(self, batch):
+        """Per policy the source rows of the batch it trains on."""
+        return self.rows_of(int(batch['actions'].numel()))
+
     def update(self, batch, num_sgd_iter=30, minibatch_rows=None, seed=0, grouped=False, micro_rows=None, grad_clip=None):
         """PPO's SGD phase on one collect(env, per_ue_actor, ..., dist_inputs=True) batch, rows or compact record: policy p's
         PPOLearner.update on the source rows whose UE slot maps to p (rows=), with seed + p.  Returns one statistics dict per policy
@@ -213,12 +346,12 @@ class PerUELearner:
         dcomp_learner_group_accumulate per micro-batch round (a policy whose minibatch is exhausted sits it out), one
         dcomp_learner_group_accum_finish and one dcomp_learner_group_apply: the sequential update with the same arguments, bit for
         bit."""
-        rows = self.rows_of(int(batch['actions'].numel()))
+        rows = self._batch_rows(batch)
         if grouped:
             return self._update_grouped(batch, rows, int(num_sgd_iter), minibatch_rows, int(seed), micro_rows, grad_clip)
         return [ln.update(batch, num_sgd_iter=num_sgd_iter, minibatch_rows=minibatch_rows, seed=int(seed) + p, rows=rows[p], check_rows=False,
                           micro_rows=micro_rows, grad_clip=grad_clip)
-                if rows[p].numel() else None                     # (check_rows: policy_rows() built them, distinct and in range)
+                if rows[p].numel() else None                     # (check_rows: _batch_rows() built them, distinct and in range)
                 for p, ln in enumerate(self.learners)]
 
     def _group_handle(self):
@@ -407,4 +540,23 @@ class PerUELearner:
             ln.load_state_dict(st)
 
 
-__all__ = ['PerUEActor', 'PerUELearner', 'policy_rows', 'default_slot_policy', 'group_plan']
+class PerIdLearner(PerUELearner):
+    """PPO for a PerIdActor: PerUELearner with the policies' rows picked by UE ID.  ``update`` takes a collect(env, per_id_actor, ...,
+    dist_inputs=True, by_ue=True) batch and trains member p on the counted rows (live = 1) of the UE with id p + 1
+    (policy_rows_by_id: one sort and one host read per update).  Everything behind the rows is PerUELearner's: sequential and
+    grouped=True, micro_rows=, grad_clip=, every policy's own standardisation, seed + p, None for a policy without rows -- a UE
+    that was never listed in the batch -- whose state stays untouched.  Data-parallel training of an id-keyed set is not supported."""
+    _ACTOR = PerIdActor
+
+    def rows_of(self, num_rows):
+        raise NotImplementedError("an id-keyed set has no row split by batch size (its rows depend on the batch's uid words: policy_rows_by_id), and "
+                                  "data-parallel training of an id-keyed set is not supported")
+
+    def _batch_rows(self, batch):
+        if 'uid' not in batch or 'live' not in batch:
+            raise ValueError("the batch has no uid / live: collect it with by_ue=True")
+        return policy_rows_by_id(batch, self.actor.num_policies)
+
+
+__all__ = ['PerUEActor', 'PerUELearner', 'PerIdActor', 'PerIdLearner', 'policy_rows', 'policy_rows_by_id', 'policy_rows_by_id_reference',
+           'default_slot_policy', 'group_plan']

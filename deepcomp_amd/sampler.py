@@ -218,15 +218,19 @@ def collect(env, actor, num_steps, gamma=0.99, lam=1.0, sample=True, compact=Fal
     before its first action; rows that do not count hold advantages = value_targets = 0.  Train on the counted rows:
     PPOLearner.update(batch, rows=live_rows(batch)).  On a static env uid and uid_next hold 1 ... U and the batch is the plain
     collector's, bit for bit, with live all ones.  Not with central envs (a row is an env there, and the learner's num_active is one
-    number per batch) and not with per-UE policy sets (their learner picks rows by slot, and a slot is not one UE here)."""
+    number per batch) and not with per-UE policy sets keyed by slot (their learner picks rows by slot, and a slot is not one UE here).  A
+    set keyed by UE id (deepcomp_amd.policy_set.PerIdActor, which needs by_ue=True and one member per id up to env.max_id) is the
+    per-UE set of such envs: every row goes through the policy of the id in its uid word, the bootstrap too, with the words after the
+    last step; PerIdLearner.update trains each policy on its UE's counted rows."""
     T = int(num_steps)
     if T < 1:
         raise ValueError("num_steps must be >= 1")
     if env.dynamic and not by_ue:
         raise NotImplementedError("envs with UE arrival / departure: slots shift on departure, a column is not one UE's trajectory; "
                                   "by_ue=True follows each UE through the slots (multi-agent envs)")
+    from .policy_set import PerIdActor, PerUEActor
+    by_id = isinstance(actor, PerIdActor)
     if by_ue:
-        from .policy_set import PerUEActor
         if env.kind != _lib.MULTI:
             raise NotImplementedError("by_ue=True with a central env: its rows are envs, not UEs, and the learner takes one num_active per batch "
                                       "while the number of listed UEs changes from step to step")
@@ -234,6 +238,10 @@ def collect(env, actor, num_steps, gamma=0.99, lam=1.0, sample=True, compact=Fal
             raise NotImplementedError("by_ue=True with a per-UE policy set: its policies belong to slots, and a slot is not one UE where the list shifts")
     if env.kind != actor.kind or env.U != actor.U or env.B != actor.B:
         raise ValueError("the env's kind / UE slots / stations differ from the actor's")
+    if by_id:
+        if not by_ue:
+            raise ValueError("a policy set keyed by UE id needs by_ue=True: its learner picks every policy's rows by the recorded uid words")
+        actor.check_env(env)
     if actor.value_weights is None:
         raise ValueError("the actor has no value function (set_value)")
     if compact and env.kind != _lib.MULTI:
@@ -275,7 +283,9 @@ def collect(env, actor, num_steps, gamma=0.99, lam=1.0, sample=True, compact=Fal
         if done:                                     # the horizon: what the step wrote is discarded, the new episode's first observation takes its place
             b['dones'][t].fill_(1)
             reset_into(nxt)
-    if not done:
+    if not done and by_id:                             # the words after the last step: the layout `last` stands in
+        actor.value(last, uid=actor.uid_of(env), compact=compact, out=b['last_vf'])
+    elif not done:
         actor.value(last, compact=compact, out=b['last_vf'])
     if by_ue:
         gae_uid(b['rewards'], b['vf_preds'], b['uid'], b['uid_next'], None if done else b['last_vf'], b['dones'], gamma, lam,

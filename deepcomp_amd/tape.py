@@ -12,9 +12,14 @@ from . import rng as _rng
 
 def uid_fields(words):
     """uid words (dcomp_state.uid, int16 / uint16 array of any shape) -> (id, born): the UE's 1-based id among the initial UEs or
-    among the arrived ones, and whether it arrived during the episode."""
+    among the arrived ones, and whether it arrived during the episode.  A tensor of such words (anything with .long() that is not a
+    numpy array) stays a tensor on its device: the two fields as an int64 and a bool tensor."""
+    id_bits, born_bit = 0x7FFF, 0x8000
+    if not isinstance(words, np.ndarray) and hasattr(words, 'long'):
+        words = words.long()                               # (int16 words: the sign extension is masked away)
+        return words & id_bits, (words & born_bit) != 0
     words = np.asarray(words).astype(np.uint16)
-    return (words & 0x7FFF).astype(np.int64), (words & 0x8000) != 0
+    return (words & id_bits).astype(np.int64), (words & born_bit) != 0
 
 
 def ue_lists(uid, num_ue):

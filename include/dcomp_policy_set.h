@@ -18,7 +18,10 @@
  * call.  dcomp_policy_set_create checks in this order: what needs no dereference of a member (NULL cfg / out / members: DCOMP_EINVAL;
  * struct_size: DCOMP_EABI; num_policies outside 1 ... DCOMP_MAX_UE, a NULL member: DCOMP_EINVAL); that the members agree (DCOMP_EINVAL);
  * forms that agree but are not supported -- DCOMP_CENTRAL members (one network by construction), a shared value function
- * (dcomp_actor_value_cfg.shared = 1) -- DCOMP_EUNSUPPORTED; the range of slot_policy (DCOMP_EINVAL). */
+ * (dcomp_actor_value_cfg.shared = 1) -- DCOMP_EUNSUPPORTED; the range of slot_policy (DCOMP_EINVAL).
+ *
+ * Envs whose UE list changes during the episode (dcomp_step_dyn) shift their slots when a UE leaves, so a slot is not one UE there:
+ * dcomp_policy_set_uid.h has the launch on this handle that picks a row's member by the UE id in the env's uid word instead. */
 #ifndef DCOMP_POLICY_SET_H
 #define DCOMP_POLICY_SET_H
 

@@ -38,6 +38,10 @@ through the slots by its uid word, include/dcomp_gae_uid.h) and update trains on
 collect(by_ue=True) per step against the bare act + step_into loop on the same env (the torch GAE loop knows no shifting slots);
 --train prints the loop's statistics and the share of rows that count, and stops there.
 
+--per-ue --ue-arrival STEP:N,...: the per-UE set of an env with arrival and departure is keyed by UE ID (deepcomp_amd.policy_set.PerIdActor,
+one random-init member per id the schedule ever lists): --train N (default 3) iterations of collect(by_ue=True) -> PerIdLearner.update
+(--grouped: in grouped launch rounds), with the rows that count, the policies that had rows and the two phases' wall times.
+
 --per-ue (multi-agent): one policy network per UE (D3-CoMP) -- deepcomp_amd.policy_set.PerUEActor over U random-init members and, with
 --train, PerUELearner -- timed next to the shared-policy actor / learner on the same env, interleaved: the loop env step + actor
 (--actor hip), sampler.collect (--collect T), or collect + update with the time of one SGD iteration (--train ITERS; --minibatch is
@@ -83,8 +87,8 @@ if a.per_ue and a.kind != 'multi':
 if a.collect or a.train or a.per_ue:
     a.actor = 'hip'
 arrival = {int(k): int(v) for k, v in (kv.split(':') for kv in a.ue_arrival.split(','))} if a.ue_arrival else None
-if arrival and (a.kind != 'multi' or a.per_ue or not (a.collect or a.train)):
-    ap.error('--ue-arrival needs --kind multi and --collect or --train, without --per-ue')
+if arrival and (a.kind != 'multi' or not (a.collect or a.train or a.per_ue)):
+    ap.error('--ue-arrival needs --kind multi and --collect, --train or --per-ue')
 if a.compact and (a.actor != 'hip' or a.kind != 'multi'):
     ap.error('--compact needs --actor hip and --kind multi')
 
@@ -463,6 +467,40 @@ def per_ue_mode():
     env.check()
 
 
+def per_id_mode(iters):
+    """--per-ue --ue-arrival: a set keyed by UE id, one member per id the schedule ever lists: collect(by_ue=True) -> PerIdLearner.update."""
+    from deepcomp_amd.policy_set import PerIdActor, PerIdLearner
+    from deepcomp_amd.sampler import collect
+    T = a.train_steps
+    P = env.max_id
+    pset = PerIdActor.random(U, B, P, hidden=a.hidden, seed=0, device=dev)
+    mb = a.minibatch or E * T
+    extra = dict(micro_rows=a.micro_rows or None, grad_clip=a.grad_clip or None)
+    learner = PerIdLearner(pset, lr=5e-5, max_rows=a.micro_rows or mb)
+    print(f'{E} envs x {U} UE slots ({env.U0} initial, ue_arrival {arrival}, ids up to {P}) x {B} BS, {P} policies 2x{a.hidden} tanh + value trunk, '
+          f'batches of T = {T} ({T * E * U} rows), {a.sgd_iters} SGD iterations, minibatches of {mb} per policy' + (', grouped' if a.grouped else '')
+          + (', compact record' if a.compact else ''))
+    env.reset()
+    buf = None
+    for it in range(iters):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        buf = collect(env, pset, T, 0.99, 0.95, out=buf, dist_inputs=True, compact=a.compact, by_ue=True)
+        torch.cuda.synchronize()
+        t1 = time.perf_counter()
+        stats = learner.update(buf, num_sgd_iter=a.sgd_iters, minibatch_rows=mb, seed=it, grouped=a.grouped, **extra)
+        torch.cuda.synchronize()
+        t2 = time.perf_counter()
+        trained = [s for s in stats if s is not None]
+        print(f'iter {it}: mean reward {float(buf["rewards"].mean()):+.4f}  rows that count {int(buf["live"].sum())} of {T * E * U}  policies trained {len(trained)} of {P}  '
+              f'total_loss {sum(s["total_loss"] for s in trained) / len(trained):+.5f}  kl {sum(s["kl"] for s in trained) / len(trained):+.5f} (mean over policies)  '
+              f'collect {(t1 - t0) * 1e3:.1f} ms  update {(t2 - t1) * 1e3:.1f} ms')
+    env.check()
+
+
+if a.per_ue and arrival:
+    per_id_mode(a.train or 3)
+    sys.exit(0)
 if a.per_ue:
     per_ue_mode()
     sys.exit(0)

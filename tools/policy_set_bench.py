@@ -11,20 +11,35 @@ three interleaved timings each:
   (ii) what per-UE networks cost without the set: per slot a strided copy of the slot's rows into E / U whole envs, the member's own
        launch, and three strided copies back (actions, logp, vf)
 and one check that the set's outputs at slot 1 are its member's own, bit for bit.  profiles/r12_policy_set.txt sections 3 and 3b are
-this output; DCOMP_LIB=<another build> times that library instead (a tools/ab/ab_lib.py variant, e.g. another tile order)."""
+this output; DCOMP_LIB=<another build> times that library instead (a tools/ab/ab_lib.py variant, e.g. another tile order).
+
+    python tools/policy_set_bench.py --by-id [--shapes 65536x32x10x256,4096x260x10x64] [--layouts static,dynamic] [--repeats 7] [--launches 30]
+
+The set keyed by UE id (PerIdActor, include/dcomp_policy_set_uid.h) instead.  Per shape E x U x B x hidden, on real envs (reset and three
+steps of random actions), actions + logp + vf, sampled, observation rows; each figure the MEDIAN of --repeats interleaved timings (at
+least 5) with their spread:
+  static   a static env of U UEs, P = U members: the launch by id (the words 1 ... U) against the slot-keyed launch of a PerUEActor over
+           the SAME members on the same observations -- what the scan of the uid words and the slot read from LDS cost
+  dynamic  an env with UE arrival and departure of the same U slots (U - 2 initial UEs, {1: 2, 2: -1, 3: -2, 5: 1}), P = env.max_id
+           members: the launch by id against the shared-policy launch of member 0 on the same observations
+and one check per layout that the launch by id writes its members' bits.  profiles/r23_policy_set_uid.txt is this output."""
 import argparse
 import sys
 
 sys.path.insert(0, '.')
 import torch
 
-from deepcomp_amd.policy_set import PerUEActor
+from deepcomp_amd.policy_set import PerIdActor, PerUEActor
+from deepcomp_amd.tape import uid_fields
 
 ap = argparse.ArgumentParser()
 ap.add_argument('--shapes', default='65536x32x10x256,4096x128x32x64,4096x128x32x256', help='comma-separated E x U x B x hidden; E must be a multiple of U')
 ap.add_argument('--launches', type=int, default=30)
 ap.add_argument('--no-per-slot', action='store_true', help='skip (ii)')
 ap.add_argument('--out', default='', help='also write the lines to this file')
+ap.add_argument('--by-id', action='store_true', help='the set keyed by UE id against the slot-keyed set (static env) and the shared policy (dynamic env)')
+ap.add_argument('--layouts', default='static,dynamic', help='--by-id: which of the two comparisons')
+ap.add_argument('--repeats', type=int, default=7, help='--by-id: interleaved timings per figure (at least 5)')
 a = ap.parse_args()
 dev = torch.device('cuda', 0)
 log = open(a.out, 'w') if a.out else None
@@ -49,6 +64,63 @@ def timed(fn, n):
     torch.cuda.synchronize()
     return e0.elapsed_time(e1) / n
 
+
+def by_id_env(E, U0, B, ue_arrival):
+    from deepcomp_amd import scenarios
+    from deepcomp_amd.entities import build_from_scenario
+    from deepcomp_amd.env import BatchedMobileEnv
+    m, bs, ues = build_from_scenario(scenarios.grid_map(B, 'mixed').with_ues(num_slow=U0))
+    env = BatchedMobileEnv(m, bs, ues, 'multi', num_envs=E, seed=42, episode_length=100, rng='philox', rand_episodes=True, ue_arrival=ue_arrival, device=dev)
+    env.reset()
+    g = torch.Generator(device=dev).manual_seed(3)
+    for _ in range(3):
+        env.step(torch.randint(0, B + 1, (E, env.U), generator=g, device=dev, dtype=torch.uint8))
+    return env
+
+
+def by_id_lines(shape):
+    E, U, B, H = (int(x) for x in shape.split('x'))
+    repeats = max(5, a.repeats)
+    for layout in a.layouts.split(','):
+        env = by_id_env(E, U if layout == 'static' else U - 2, B, None if layout == 'static' else {1: 2, 2: -1, 3: -2, 5: 1})
+        assert env.U == U
+        members = PerIdActor._random_members(U, B, H, 'tanh', 0, 0.0, dev, env.max_id, True)
+        by_id = PerIdActor(members)
+        other = PerUEActor(members) if layout == 'static' else members[0]
+        obs, uid, rows = env.obs, by_id.uid_of(env), E * U
+        out = torch.zeros((E, U), dtype=torch.uint8, device=dev)
+        logp, vf = torch.zeros((rows, 1), device=dev), torch.zeros(rows, device=dev)
+        variants = [('by_id', 'dcomp_policy_set_actions_uid', lambda i: by_id.actions(obs, uid=uid, sample=True, seed=1, step=i, out=out, logp=logp, vf=vf)),
+                    ('other', 'dcomp_policy_set_actions_v (slot-keyed, same members)' if layout == 'static' else 'dcomp_actor_actions_v (shared policy, member 0)',
+                     lambda i: other.actions(obs, sample=True, seed=1, step=i, out=out, logp=logp, vf=vf))]
+        res = {k: [] for k, _, _ in variants}
+        for _ in range(repeats):
+            for k, _, fn in variants:
+                res[k].append(timed(fn, a.launches))
+        med = {k: sorted(v)[len(v) // 2] for k, v in res.items()}
+        listed = int((uid != 0).sum())
+        say(f'{layout}: {E} x {U} x {B} multi, 2x{H} tanh + value trunk, actions + logp + vf, sampled, rows obs; {env.max_id} members, '
+            f'{listed} of {rows} slots listed; median of {repeats} x {a.launches} launches [min .. max]')
+        for k, name, _ in variants:
+            say(f'   {name:<56}: {med[k] * 1e3:9.1f} us  [{min(res[k]) * 1e3:.1f} .. {max(res[k]) * 1e3:.1f}]')
+        say(f'   by id / {"slot-keyed" if layout == "static" else "shared"} = {med["by_id"] / med["other"]:.3f} x')
+        got = torch.zeros_like(out), torch.zeros_like(logp), torch.zeros_like(vf)
+        by_id.actions(obs, uid=uid, sample=True, seed=1, step=0, out=got[0], logp=got[1], vf=got[2])
+        ids = uid_fields(uid.reshape(-1))[0]
+        ue = int(ids[1])                                         # the UE at slot 1 of env 0: its member's own launch, at its rows
+        members[ue - 1].actions(obs, sample=True, seed=1, step=0, out=out, logp=logp, vf=vf)
+        at = torch.nonzero(ids == ue).reshape(-1)
+        same = all(torch.equal(x.reshape(rows)[at], y.reshape(rows)[at]) for x, y in zip(got, (out, logp, vf)))
+        say(f'   the rows of UE {ue} ({at.numel()}) equal its member\'s own launch: {bool(same)}')
+        del by_id, other, members, env
+
+
+if a.by_id:
+    for shape in (a.shapes if a.shapes != ap.get_default('shapes') else '65536x32x10x256').split(','):
+        by_id_lines(shape)
+    if log:
+        log.close()
+    sys.exit(0)
 
 for shape in a.shapes.split(','):
     E, U, B, H = (int(x) for x in shape.split('x'))
